@@ -17,6 +17,11 @@ Two scaling modes:
 worker processes itself (before anything touches a GPU) and prints rank 0's JSON line.  Under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` it is a worker right away.
 
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else it can
+measure: the per-kernel roofline blocks and the replay roof, the time to a 1-spp frame, with N > 1 the C4 strong-scaling
+frame, the CPU baseline and the one-process device group.  `--dump-outputs DIR` writes the film of the last timed step
+as DIR/film.npy (float32; the inputs are the same on every run with the same arguments).
+
 One JSON line on rank 0 (see DESIGN.md section 8 for the definition of every field)."""
 import argparse
 import datetime
@@ -32,6 +37,19 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_MAX_BYTES = 60 << 20  # --dump-outputs writes at most this much
+
+
+def film_output(film):
+    """what --dump-outputs writes for a [H][W][5] film: all of it up to DUMP_MAX_BYTES (1024 x 1024: 20 MB), above that a
+    fixed, seeded sample of its pixels (rows of the [H*W][5] view in pixel order, the same pixels on every run)"""
+    import numpy as np
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.nbytes <= DUMP_MAX_BYTES:
+        return film
+    px = film.reshape(-1, film.shape[-1])
+    k = DUMP_MAX_BYTES // px[0].nbytes
+    return px[np.sort(np.random.RandomState(0x5EED).choice(px.shape[0], k, replace=False))]
 
 
 def kernel_source_hash():
@@ -275,6 +293,9 @@ def main():
     ap.add_argument("--no-group", action="store_true", help="skip the one-process device-group timing")
     ap.add_argument("--group", action="store_true", help="time the one-process device group with one GPU too (default: only with --gpus > 1)")
     ap.add_argument("--dump-group-film", default="", help="the group child writes its reduced film to this .npy file")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline figure: roofline blocks and replay roof, "
+                    "time to a 1-spp frame, the C4 frame with N > 1, the CPU baseline, the device group (the --no-* options still apply)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes the film of the last timed step as DIR/film.npy (float32)")
     args = ap.parse_args()
 
     if args.group_child > 0:
@@ -373,30 +394,31 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # --- untimed: warmup, one counting step (algorithmic work of the traversal kernels), and KT steps with a HIP-event
-    # pair around every launch on the library's streams: the per-kernel durations of the roofline blocks.  The timed
-    # steps below run WITHOUT those events (about 130 event pairs per frame are not part of the hot path).
+    # --- untimed: warmup; with --full also one counting step (algorithmic work of the traversal kernels), and KT steps
+    # with a HIP-event pair around every launch on the library's streams: the per-kernel durations of the roofline blocks.
+    # The timed steps below run WITHOUT those events (about 130 event pairs per frame are not part of the hot path).
     it.set_options(max_paths=args.max_paths, count_traversal=False, time_kernels=False)
     for _ in range(args.warmup):
         step()
-    it.set_options(max_paths=args.max_paths, count_traversal=True, time_kernels=False)
-    step()
-    torch.cuda.synchronize()
-    counts = it.stats()
-    bytes_per_step = algorithmic_bytes(counts)
-    it.set_options(max_paths=args.max_paths, count_traversal=False, time_kernels=True)
-    trace_ms = trace_first_ms = trace_shadow_ms = 0.0
-    trace_launches = 0
-    shade_ms = 0.0
-    kt_steps = 2
-    for _ in range(kt_steps):
+    if args.full:
+        it.set_options(max_paths=args.max_paths, count_traversal=True, time_kernels=False)
         step()
-        st = it.stats()                     # per-launch HIP-event durations on the library's streams
-        trace_ms += st["trace_ms"]; shade_ms += st["shade_ms"]; trace_launches += st["trace_launches"]
-        trace_first_ms += st["trace_first_ms"]; trace_shadow_ms += st["trace_shadow_ms"]
-    trace_ms /= kt_steps; shade_ms /= kt_steps; trace_launches /= kt_steps      # per step from here on
-    trace_first_ms /= kt_steps; trace_shadow_ms /= kt_steps
-    it.set_options(max_paths=args.max_paths, count_traversal=False, time_kernels=False)
+        torch.cuda.synchronize()
+        counts = it.stats()
+        bytes_per_step = algorithmic_bytes(counts)
+        it.set_options(max_paths=args.max_paths, count_traversal=False, time_kernels=True)
+        trace_ms = trace_first_ms = trace_shadow_ms = 0.0
+        trace_launches = 0
+        shade_ms = 0.0
+        kt_steps = 2
+        for _ in range(kt_steps):
+            step()
+            st = it.stats()                     # per-launch HIP-event durations on the library's streams
+            trace_ms += st["trace_ms"]; shade_ms += st["shade_ms"]; trace_launches += st["trace_launches"]
+            trace_first_ms += st["trace_first_ms"]; trace_shadow_ms += st["trace_shadow_ms"]
+        trace_ms /= kt_steps; shade_ms /= kt_steps; trace_launches /= kt_steps      # per step from here on
+        trace_first_ms /= kt_steps; trace_shadow_ms /= kt_steps
+        it.set_options(max_paths=args.max_paths, count_traversal=False, time_kernels=False)
 
     # --- timed region: exactly K steps between barriers ---
     fence()
@@ -421,13 +443,16 @@ def main():
         reduce_ms = [float(e[1].item()) for e in every]
     if args.dump_film and rank == 0:
         np.save(args.dump_film, film.cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "film.npy"), film_output(film.cpu().numpy()))
 
     # --- the traversal kernels against replays of their own request streams: samples of the frame's own rays, one per class
-    # of launch (untimed; rank 0).  Deep rays first: the camera class generates the last pass's camera rays again. ---
+    # of launch (untimed; rank 0, --full).  Deep rays first: the camera class generates the last pass's camera rays again. ---
     replay_raw = {}
     replay_note = None
     r_stride = 1
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             avail = min(W * H * spp_total // world, 72 << 20)    # paths of one pass
             r_stride = 8 if avail >= (32 << 20) else 1
@@ -444,9 +469,9 @@ def main():
         except Exception as e:
             replay_note = "%s: %s" % (type(e).__name__, e)
 
-    # --- time to a 1-spp frame (second half of BASELINE.json's metric), untimed region ---
+    # --- time to a 1-spp frame (second half of BASELINE.json's metric), untimed region, --full ---
     one_spp_ms = None
-    if not args.no_1spp:
+    if args.full and not args.no_1spp:
         it.preprocess(scene, cam, sampler="ldsampler", sampleCount=1, seed=0x5EED)
         it.set_tiles(32, rank, world)
         it.set_options(max_paths=args.max_paths, count_traversal=False, time_kernels=False)
@@ -459,9 +484,9 @@ def main():
         one_spp_ms = best
 
     # --- BASELINE.json configs[3] next to the weak line: with N > 1 GPUs the same scene at 4096 spp per FRAME (strong
-    # scaling: every GPU renders its tiles at 4096 spp, one film reduce per frame), timed like the steps above ---
+    # scaling: every GPU renders its tiles at 4096 spp, one film reduce per frame), timed like the steps above, --full ---
     c4 = None
-    if world > 1 and not strong and not args.no_c4:
+    if args.full and world > 1 and not strong and not args.no_c4:
         it.preprocess(scene, cam, sampler="ldsampler", sampleCount=args.c4_spp, seed=0x5EED)
         it.set_tiles(32, rank, world)
         it.set_options(max_paths=args.max_paths, count_traversal=False, time_kernels=False)
@@ -480,86 +505,8 @@ def main():
               "steps": n_c4, "warmup": 1, "ms_per_step": c4_elapsed / n_c4 * 1e3, "spp_total": args.c4_spp}
 
     if rank == 0:
-        # HBM traffic of the traversal launches from a separate PMC pass of the same frame (profiles/); only a
-        # record taken with exactly these kernel sources counts
-        traffic = None
-        fabric_rec = None
-        l2 = {"l2_hit_rate": None, "l2_miss_per_ray": None}
-        traffic_note = "no PMC record for these kernel sources (tools/profile_round.sh writes profiles/*_traffic.json)"
-        try:
-            cands = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_traffic.json"))
-            for f in reversed(cands):
-                tj = json.load(open(os.path.join(ROOT, "profiles", f)))
-                if tj.get("kernel_source_hash") == kernel_source_hash() and world == 1 and not strong \
-                        and tj["workload"] == {"grid": args.grid, "res": args.res, "spp": args.spp}:
-                    traffic = tj["hbm_bytes_per_launch"]; traffic_note = "profiles/" + f
-                    fabric_rec = tj
-                    l2 = {"l2_hit_rate": tj.get("l2_hit_rate"), "l2_miss_per_ray": tj.get("l2_miss_per_ray")}
-                    break
-        except Exception:
-            pass
         total_samples = W * H * spp_total * args.steps
         value = total_samples / elapsed / 1e6
-        achieved = bytes_per_step / (trace_ms * 1e-3) / 1e9 if trace_ms > 0 else 0.0
-        rays = counts["rays_closest"] + counts["rays_shadow"]
-        triad = pkg.hbm_triad_gbs(device)
-        gather = pkg.gather_roof(device, 4)
-        req_per_step = issued_requests(counts)
-        replay = {"kernel": "k_trace (closest-hit and any-hit launches, by class)",
-                  "what": "each class of traversal launch against a replay of its own request stream (mtsgpu_replay_roof: the same lines in "
-                          "the same per-ray order, one 16-byte load each, eight independent requests in flight per lane, no arithmetic, "
-                          "grid and LDS footprint of the closest-hit kernel).  A throughput test of the memory system on these lines, "
-                          "not a bound: other issue orders may be faster.  Not replayed: what moves in queue order (queue ids, rays, "
-                          "binned ids and hits, shadow rays), stack spills, the extra chunks of sphere primitives",
-                  "issued_requests_per_ray": req_per_step / max(rays, 1),
-                  "lds_served_requests_per_ray": (counts["req_pair_lds"] + counts["req_node_lds"]) / max(rays, 1),
-                  "issued_breakdown_per_ray": {"pairs": counts["req_pair_global"] / max(rays, 1), "pop_nodes": counts["req_node_global"] / max(rays, 1),
-                                               "record_heads": counts["req_head"] / max(rays, 1), "record_tails": counts["req_tail"] / max(rays, 1),
-                                               "stack_spills": counts["req_spill"] / max(rays, 1)},
-                  "random_gather_4MiB_G_per_s": gather / 1e9 if gather else None,
-                  "note": replay_note}
-        if replay_raw:
-            samples = {"camera": "camera rays of the last pass, generated again, every %dth; closest-hit kernel in plain 64-ray batches",
-                       "deep": "the last ray of every %dth path of the frame just rendered; closest-hit kernel with material binning",
-                       "shadow": "every %dth slot of the shadow queue as the frame left it; any-hit kernel"}
-            class_ms = {"camera": trace_first_ms, "shadow": trace_shadow_ms, "deep": trace_ms - trace_first_ms - trace_shadow_ms}
-            classes = {}
-            replay_ms_per_step = 0.0
-            complete = True
-            for kind, rr in replay_raw.items():
-                if "error" in rr:
-                    classes[kind] = {"error": rr["error"], "launches_ms_per_step": class_ms[kind]}
-                    complete = False
-                    continue
-                ratio = rr["replay_ms"] / rr["product_ms"]
-                classes[kind] = {"sample": ("%d rays: " % rr["rays"]) + samples[kind] % r_stride,
-                                 "sample_requests_per_ray": rr["requests"] / rr["rays"], "sample_truncated_rays": rr["truncated_rays"],
-                                 "product_ms": rr["product_ms"], "replay_ms": rr["replay_ms"], "replay_ratio": ratio,
-                                 "product_G_requests_per_s": rr["requests"] / (rr["product_ms"] * 1e-3) / 1e9,
-                                 "replay_G_requests_per_s": rr["requests"] / (rr["replay_ms"] * 1e-3) / 1e9,
-                                 "launches_ms_per_step": class_ms[kind],
-                                 "launches": {"camera": "the closest-hit launch of every pass's first bounce", "shadow": "all any-hit launches",
-                                              "deep": "all other closest-hit launches"}[kind]}
-                replay_ms_per_step += class_ms[kind] * ratio
-            replay.update({"classes": classes, "unit": "G lane-requests/s", "trace_ms_per_step": trace_ms,
-                           # sum over the frame's launches of (launch time x the replay ratio measured on its class's sample)
-                           "replay_ms_per_step": replay_ms_per_step if complete else None,
-                           "replay_ratio": replay_ms_per_step / trace_ms if complete and trace_ms > 0 else None})
-        # what crosses the fabric (L2 misses, 128-byte lines; calibrated: profiles/r06a_fetch_size_calibration.txt) during the
-        # traversal launches, against the rate the chip sustains for random 128-byte lines that live in the Infinity Cache
-        fabric = None
-        if fabric_rec and trace_ms > 0:
-            fb = fabric_rec.get("fabric_bytes_per_frame")
-            ceil = (fabric_rec.get("random_line_rate_G_per_s") or {}).get("k_sustained_150MB")
-            if fb:
-                lines = fb / 128.0 / (trace_ms * 1e-3) / 1e9
-                fabric = {"bytes_per_step": fb, "tb_per_s": fb / (trace_ms * 1e-3) / 1e12, "G_lines_per_s": lines,
-                          "random_line_ceiling_G_per_s": ceil, "frac_of_ceiling": lines / ceil if ceil else None,
-                          "read_requests_per_ray": (fabric_rec.get("fabric_read_requests_per_frame") or 0) / max(rays, 1) or None,
-                          "what": "bytes between the L2s and the Infinity Cache / HBM per step (2 x FETCH_SIZE + WRITE_SIZE, the x2 measured) over the traversal "
-                                  "launches' time; ceiling = sustained random 16-byte gathers, eight in flight per lane, on distinct lines of a 150 MB footprint (tools/micro/gather_calib.hip k_sustained)"}
-        sh_bytes = shade_algorithmic_bytes(counts)
-        sh_achieved = sh_bytes / (shade_ms * 1e-3) / 1e9 if shade_ms > 0 else 0.0
         out = {
             "metric": "Msamples/s", "value": value, "unit": "Msamples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -582,39 +529,120 @@ def main():
             # per rank: ms per step of its own frame (film clear + all kernels), and of the film reduce that follows
             # (it includes the wait for the slowest rank; on rank 0 also the receive)
             "rank_ms": rank_ms, "reduce_ms": reduce_ms,
-            "c4_strong": c4,
-            "time_to_1spp_frame_ms": one_spp_ms,
-            "avg_path_length": counts.get("avg_path_length"),
-            "roofline": {
-                "kernel": "k_trace (closest-hit + shadow kd-tree traversal)",
-                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
-                "l2_hit_rate": l2["l2_hit_rate"], "l2_miss_per_ray": l2["l2_miss_per_ray"],     # TCC_HIT / TCC_MISS of the same record
-                "fabric": fabric,
-                "peak_measured_triad": triad, "frac_of_triad": achieved / triad if triad else None,
-                "algorithmic_bytes_per_launch": bytes_per_step / max(counts["trace_launches"], 1),
-                "algorithmic_bytes_per_step": bytes_per_step, "bytes_per_ray": bytes_per_step / max(rays, 1),
-                "rays_per_step": rays, "launches_per_step": counts["trace_launches"],
-                "avg_launch_ms": trace_ms / max(trace_launches, 1), "trace_ms_per_step": trace_ms,
-                "kernel_times_from": "%d untimed steps with HIP events around every launch, right before the timed steps" % kt_steps,
-                "shade_ms_per_step": shade_ms,
-                "n_inner_per_ray": counts["n_inner"] / max(rays, 1), "n_leaf_per_ray": counts["n_leaf"] / max(rays, 1),
-                "n_idx_per_ray": counts["n_idx"] / max(rays, 1), "n_tri_tested_per_ray": counts["n_tri_tested"] / max(rays, 1),
-            },
-            "roofline_requests": replay,
-            "roofline_shade": {
-                "kernel": "k_shade (one Li iteration per path: emitter hit, MIS, RR, NEE sample, BSDF sample); ms_per_step brackets the k_shade launches only",
-                "bound": "hbm", "achieved": sh_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": sh_achieved / HBM_PEAK_GBS,
-                "algorithmic_bytes_per_step": sh_bytes, "ms_per_step": shade_ms,
-            },
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(pkg, sd, args.res, args.spp, sd.max_depth)
+        if args.full:
+            # HBM traffic of the traversal launches from a separate PMC pass of the same frame (profiles/); only a
+            # record taken with exactly these kernel sources counts
+            traffic = None
+            fabric_rec = None
+            l2 = {"l2_hit_rate": None, "l2_miss_per_ray": None}
+            traffic_note = "no PMC record for these kernel sources (tools/profile_round.sh writes profiles/*_traffic.json)"
+            try:
+                cands = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_traffic.json"))
+                for f in reversed(cands):
+                    tj = json.load(open(os.path.join(ROOT, "profiles", f)))
+                    if tj.get("kernel_source_hash") == kernel_source_hash() and world == 1 and not strong \
+                            and tj["workload"] == {"grid": args.grid, "res": args.res, "spp": args.spp}:
+                        traffic = tj["hbm_bytes_per_launch"]; traffic_note = "profiles/" + f
+                        fabric_rec = tj
+                        l2 = {"l2_hit_rate": tj.get("l2_hit_rate"), "l2_miss_per_ray": tj.get("l2_miss_per_ray")}
+                        break
+            except Exception:
+                pass
+            achieved = bytes_per_step / (trace_ms * 1e-3) / 1e9 if trace_ms > 0 else 0.0
+            rays = counts["rays_closest"] + counts["rays_shadow"]
+            triad = pkg.hbm_triad_gbs(device)
+            gather = pkg.gather_roof(device, 4)
+            req_per_step = issued_requests(counts)
+            replay = {"kernel": "k_trace (closest-hit and any-hit launches, by class)",
+                      "what": "each class of traversal launch against a replay of its own request stream (mtsgpu_replay_roof: the same lines in "
+                              "the same per-ray order, one 16-byte load each, eight independent requests in flight per lane, no arithmetic, "
+                              "grid and LDS footprint of the closest-hit kernel).  A throughput test of the memory system on these lines, "
+                              "not a bound: other issue orders may be faster.  Not replayed: what moves in queue order (queue ids, rays, "
+                              "binned ids and hits, shadow rays), stack spills, the extra chunks of sphere primitives",
+                      "issued_requests_per_ray": req_per_step / max(rays, 1),
+                      "lds_served_requests_per_ray": (counts["req_pair_lds"] + counts["req_node_lds"]) / max(rays, 1),
+                      "issued_breakdown_per_ray": {"pairs": counts["req_pair_global"] / max(rays, 1), "pop_nodes": counts["req_node_global"] / max(rays, 1),
+                                                   "record_heads": counts["req_head"] / max(rays, 1), "record_tails": counts["req_tail"] / max(rays, 1),
+                                                   "stack_spills": counts["req_spill"] / max(rays, 1)},
+                      "random_gather_4MiB_G_per_s": gather / 1e9 if gather else None,
+                      "note": replay_note}
+            if replay_raw:
+                samples = {"camera": "camera rays of the last pass, generated again, every %dth; closest-hit kernel in plain 64-ray batches",
+                           "deep": "the last ray of every %dth path of the frame just rendered; closest-hit kernel with material binning",
+                           "shadow": "every %dth slot of the shadow queue as the frame left it; any-hit kernel"}
+                class_ms = {"camera": trace_first_ms, "shadow": trace_shadow_ms, "deep": trace_ms - trace_first_ms - trace_shadow_ms}
+                classes = {}
+                replay_ms_per_step = 0.0
+                complete = True
+                for kind, rr in replay_raw.items():
+                    if "error" in rr:
+                        classes[kind] = {"error": rr["error"], "launches_ms_per_step": class_ms[kind]}
+                        complete = False
+                        continue
+                    ratio = rr["replay_ms"] / rr["product_ms"]
+                    classes[kind] = {"sample": ("%d rays: " % rr["rays"]) + samples[kind] % r_stride,
+                                     "sample_requests_per_ray": rr["requests"] / rr["rays"], "sample_truncated_rays": rr["truncated_rays"],
+                                     "product_ms": rr["product_ms"], "replay_ms": rr["replay_ms"], "replay_ratio": ratio,
+                                     "product_G_requests_per_s": rr["requests"] / (rr["product_ms"] * 1e-3) / 1e9,
+                                     "replay_G_requests_per_s": rr["requests"] / (rr["replay_ms"] * 1e-3) / 1e9,
+                                     "launches_ms_per_step": class_ms[kind],
+                                     "launches": {"camera": "the closest-hit launch of every pass's first bounce", "shadow": "all any-hit launches",
+                                                  "deep": "all other closest-hit launches"}[kind]}
+                    replay_ms_per_step += class_ms[kind] * ratio
+                replay.update({"classes": classes, "unit": "G lane-requests/s", "trace_ms_per_step": trace_ms,
+                               # sum over the frame's launches of (launch time x the replay ratio measured on its class's sample)
+                               "replay_ms_per_step": replay_ms_per_step if complete else None,
+                               "replay_ratio": replay_ms_per_step / trace_ms if complete and trace_ms > 0 else None})
+            # what crosses the fabric (L2 misses, 128-byte lines; calibrated: profiles/r06a_fetch_size_calibration.txt) during the
+            # traversal launches, against the rate the chip sustains for random 128-byte lines that live in the Infinity Cache
+            fabric = None
+            if fabric_rec and trace_ms > 0:
+                fb = fabric_rec.get("fabric_bytes_per_frame")
+                ceil = (fabric_rec.get("random_line_rate_G_per_s") or {}).get("k_sustained_150MB")
+                if fb:
+                    lines = fb / 128.0 / (trace_ms * 1e-3) / 1e9
+                    fabric = {"bytes_per_step": fb, "tb_per_s": fb / (trace_ms * 1e-3) / 1e12, "G_lines_per_s": lines,
+                              "random_line_ceiling_G_per_s": ceil, "frac_of_ceiling": lines / ceil if ceil else None,
+                              "read_requests_per_ray": (fabric_rec.get("fabric_read_requests_per_frame") or 0) / max(rays, 1) or None,
+                              "what": "bytes between the L2s and the Infinity Cache / HBM per step (2 x FETCH_SIZE + WRITE_SIZE, the x2 measured) over the traversal "
+                                      "launches' time; ceiling = sustained random 16-byte gathers, eight in flight per lane, on distinct lines of a 150 MB footprint (tools/micro/gather_calib.hip k_sustained)"}
+            sh_bytes = shade_algorithmic_bytes(counts)
+            sh_achieved = sh_bytes / (shade_ms * 1e-3) / 1e9 if shade_ms > 0 else 0.0
+            out.update({
+                "c4_strong": c4,
+                "time_to_1spp_frame_ms": one_spp_ms,
+                "avg_path_length": counts.get("avg_path_length"),
+                "roofline": {
+                    "kernel": "k_trace (closest-hit + shadow kd-tree traversal)",
+                    "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
+                    "l2_hit_rate": l2["l2_hit_rate"], "l2_miss_per_ray": l2["l2_miss_per_ray"],     # TCC_HIT / TCC_MISS of the same record
+                    "fabric": fabric,
+                    "peak_measured_triad": triad, "frac_of_triad": achieved / triad if triad else None,
+                    "algorithmic_bytes_per_launch": bytes_per_step / max(counts["trace_launches"], 1),
+                    "algorithmic_bytes_per_step": bytes_per_step, "bytes_per_ray": bytes_per_step / max(rays, 1),
+                    "rays_per_step": rays, "launches_per_step": counts["trace_launches"],
+                    "avg_launch_ms": trace_ms / max(trace_launches, 1), "trace_ms_per_step": trace_ms,
+                    "kernel_times_from": "%d untimed steps with HIP events around every launch, right before the timed steps" % kt_steps,
+                    "shade_ms_per_step": shade_ms,
+                    "n_inner_per_ray": counts["n_inner"] / max(rays, 1), "n_leaf_per_ray": counts["n_leaf"] / max(rays, 1),
+                    "n_idx_per_ray": counts["n_idx"] / max(rays, 1), "n_tri_tested_per_ray": counts["n_tri_tested"] / max(rays, 1),
+                },
+                "roofline_requests": replay,
+                "roofline_shade": {
+                    "kernel": "k_shade (one Li iteration per path: emitter hit, MIS, RR, NEE sample, BSDF sample); ms_per_step brackets the k_shade launches only",
+                    "bound": "hbm", "achieved": sh_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": sh_achieved / HBM_PEAK_GBS,
+                    "algorithmic_bytes_per_step": sh_bytes, "ms_per_step": shade_ms,
+                },
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(pkg, sd, args.res, args.spp, sd.max_depth)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if (world > 1 or args.group) and not args.no_group:
+        if args.full and (world > 1 or args.group) and not args.no_group:
             # every rank is done (the others exit now): the form the Mitsuba plugin uses, all GPUs behind one process.
             # With one GPU it is the same frame once more (--group asks for it anyway)
             out["group"] = run_group_child(args, world)

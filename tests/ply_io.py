@@ -1,10 +1,13 @@
 """Test helper: reader for the binary little-endian PLY meshes the reference's tests use (data/tests/bunny.ply,
-loaded there through the `ply` shape plugin, src/tests/test_kd.cpp:86-91): float x/y/z vertices, triangle lists."""
+loaded there through the `ply` shape plugin, src/tests/test_kd.cpp:86-91): float x/y/z vertices, triangle lists.
+A path ending in .gz is read through gzip (tests/golden/bunny.ply.gz keeps the fixture under the size limit)."""
+import gzip
+
 import numpy as np
 
 
 def read(path):
-    data = open(path, "rb").read()
+    data = (gzip.open if path.endswith(".gz") else open)(path, "rb").read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
     header = data[:end].decode("ascii").split("\n")
     assert header[0] == "ply" and header[1].startswith("format binary_little_endian")

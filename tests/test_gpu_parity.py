@@ -21,12 +21,20 @@ SCENES = {
 }
 
 
+_bunny_dir = []
+
+
 def _bunny_serialized():
+    import atexit
+    import shutil
     import tempfile
     import ply_io
     import serialized_io as sio
-    path = os.path.join(tempfile.gettempdir(), "mtsgpu_test_bunny.serialized")
-    pos, tri = ply_io.read(os.path.join(os.path.dirname(__file__), "golden", "bunny.ply"))
+    if not _bunny_dir:                  # a directory of this process's own: another user's file cannot stand in the way
+        _bunny_dir.append(tempfile.mkdtemp(prefix="mtsgpu_test_"))
+        atexit.register(shutil.rmtree, _bunny_dir[0], True)
+    path = os.path.join(_bunny_dir[0], "bunny.serialized")
+    pos, tri = ply_io.read(os.path.join(os.path.dirname(__file__), "golden", "bunny.ply.gz"))
     plane = dict(positions=np.array([[-1, 0.033, -1], [1, 0.033, -1], [1, 0.033, 1], [-1, 0.033, 1]], dtype=np.float64),
                  triangles=np.array([[0, 2, 1], [0, 3, 2]]), face_normals=True)
     sio.write(path, [dict(positions=pos.astype(np.float64), triangles=tri), plane], double=True)
@@ -354,9 +362,9 @@ def test_orthographic_camera(gpu_lib, mts, orc):
 
 def test_bunny_benchmark_rays(gpu_lib, mts, orc):
     """the reference's own traversal benchmark (src/tests/test_kd.cpp:85-130): chords of the test's sphere through the
-    kd-tree of data/tests/bunny.ply (tests/golden/bunny.ply), rays drawn exactly as the test draws them"""
+    kd-tree of data/tests/bunny.ply (tests/golden/bunny.ply.gz), rays drawn exactly as the test draws them"""
     import ply_io
-    pos, tri = ply_io.read(os.path.join(os.path.dirname(__file__), "golden", "bunny.ply"))
+    pos, tri = ply_io.read(os.path.join(os.path.dirname(__file__), "golden", "bunny.ply.gz"))
     assert pos.shape == (35947, 3) and tri.shape == (69451, 3)
     sd = mts.scenes.SceneDescription("bunny")
     sd.add_mesh(pos, tri, bsdf=sd.lambertian(0.5), face_normals=False, name="bunny")

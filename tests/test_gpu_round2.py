@@ -257,7 +257,7 @@ def test_bench_world2_branch_on_one_gpu(gpu_lib, mts, orc, tmp_path):
     for mode, extra, spp_total in (("weak", ["--spp", "4"], 8), ("strong", ["--spp-total", "16"], 16)):
         out = str(tmp_path / ("film_%s.npy" % mode))
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--devices", "0,0", "--res", "96", "--grid", "24",
-               "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-1spp", "--host-kd", "--c4-spp", "64", "--c4-steps", "1", "--dump-film", out] + extra
+               "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-1spp", "--host-kd", "--c4-spp", "64", "--c4-steps", "1", "--dump-film", out] + extra
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
         assert r.returncode == 0, r.stderr.decode()[-2000:]
         line = [l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1]

@@ -77,7 +77,7 @@ def test_bench_line_carries_the_group_form_and_the_replay_roof(gpu_lib, mts, tmp
     fresh child process after the ranks have finished) with a film equal to the unsharded render bit for bit, the
     replay roof with frac <= 1, and a CPU baseline that says what an ungated host would extrapolate to"""
     out = str(tmp_path / "group.npy")
-    rec = _bench(["--res", "256", "--grid", "48", "--spp", "16", "--steps", "1", "--warmup", "1", "--host-kd",
+    rec = _bench(["--res", "256", "--grid", "48", "--spp", "16", "--steps", "1", "--warmup", "1", "--full", "--host-kd",
                   "--no-1spp", "--no-cpu-baseline", "--group", "--dump-group-film", out])
     g = rec["group"]
     assert "error" not in g, g
@@ -102,6 +102,27 @@ def test_bench_line_carries_the_group_form_and_the_replay_roof(gpu_lib, mts, tmp
     assert np.array_equal(np.load(out).view(np.uint32), it.film().view(np.uint32))
 
 
+def test_plain_bench_line_and_dumped_outputs(gpu_lib, mts, tmp_path):
+    """bench.py without --full: exactly --steps timed steps, the headline fields and nothing measured beyond them; the
+    film that --dump-outputs writes after the timed steps equals the unsharded render bit for bit"""
+    import os
+    d = tmp_path / "outputs"
+    rec = _bench(["--res", "96", "--grid", "24", "--spp", "4", "--steps", "2", "--warmup", "0", "--host-kd", "--dump-outputs", str(d)])
+    assert rec["metric"] == rec["unit"] == "Msamples/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["value"] > 0
+    assert abs(rec["value"] - 96 * 96 * 4 / (rec["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * rec["value"]
+    for moved in ("roofline", "roofline_requests", "roofline_shade", "c4_strong", "time_to_1spp_frame_ms", "cpu_baseline", "group"):
+        assert moved not in rec, moved
+    assert sorted(os.listdir(str(d))) == ["film.npy"]
+    dumped = np.load(str(d / "film.npy"))
+    assert dumped.dtype == np.float32 and dumped.shape == (96, 96, 5)
+    sd = mts.scenes.cornell_c3(grid=24, sphere_subdiv=5)
+    it = mts.MIPathTracer(maxDepth=sd.max_depth, rrDepth=sd.rr_depth)
+    it.preprocess(mts.Scene(sd), mts.PerspectiveCamera.for_description(sd, 96, 96), sampler="ldsampler", sampleCount=4, seed=0x5EED)
+    assert it.render()
+    assert np.array_equal(dumped.view(np.uint32), it.film().view(np.uint32))
+
+
 def test_bench_over_two_gpus_uses_the_nccl_backend(gpu_lib, mts, tmp_path):
     """`bench.py --gpus 2` as the driver starts it (no --devices): the ranks form an RCCL process group, rank 0's reduced film
     equals the unsharded render, and the group child renders the same film through mtsgpu_group_render over both GPUs.
@@ -110,7 +131,7 @@ def test_bench_over_two_gpus_uses_the_nccl_backend(gpu_lib, mts, tmp_path):
     if torch.cuda.device_count() < 2:
         pytest.skip("one GPU visible: the nccl branch of bench.py needs two")
     out, gout = str(tmp_path / "film.npy"), str(tmp_path / "group.npy")
-    rec = _bench(["--gpus", "2", "--res", "128", "--grid", "24", "--spp", "4", "--steps", "1", "--warmup", "0", "--host-kd",
+    rec = _bench(["--gpus", "2", "--res", "128", "--grid", "24", "--spp", "4", "--steps", "1", "--warmup", "0", "--full", "--host-kd",
                   "--no-1spp", "--no-cpu-baseline", "--c4-spp", "64", "--c4-steps", "1", "--dump-film", out, "--dump-group-film", gout])
     assert rec["n_gpus"] == 2 and len(rec["rank_ms"]) == 2
     assert rec["rccl_ranks"] == 2 and "rccl" in rec["reduce_kind"]           # RCCL's first collective summed one per rank

@@ -178,17 +178,35 @@ def test_bench_helpers():
     assert bench.algorithmic_bytes(st) == 8 * 100 + 8 * 20 + 52 * 30 + 48 * 15
 
 
+def test_bench_dump_outputs_stay_bounded_and_fixed(monkeypatch):
+    """bench.py --dump-outputs: a film within the cap is written whole in float32; a larger one as a seeded sample of its
+    pixels that is the same on every run and stays within the cap"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    film = np.random.RandomState(3).rand(32, 48, 5).astype(np.float32)
+    whole = bench.film_output(film)
+    assert whole.dtype == np.float32 and np.array_equal(whole, film)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2000)
+    a, b = bench.film_output(film), bench.film_output(film.copy())
+    assert a.dtype == np.float32 and a.shape == (100, 5) and a.nbytes <= 2000
+    assert np.array_equal(a, b)
+    px = film.reshape(-1, 5)
+    rows = [int(np.flatnonzero((px == r).all(axis=1))[0]) for r in a]
+    assert rows == sorted(set(rows))                   # distinct pixels, in pixel order
+
+
 def test_serialized_mesh_loader(mts, tmp_path):
     """mtsgpu_load_serialized == TriMesh::TriMesh(Stream *, int) (src/librender/trimesh.cpp:156-236): on files written
-    by an independent Python implementation of the format (tests/serialized_io.py) and, where the reference checkout
-    is present (not on the GPU box), on its own data/blender/mitsuba/matpreview/matpreview.serialized, whose counts
+    by an independent Python implementation of the format (tests/serialized_io.py) and on the reference's own
+    data/blender/mitsuba/matpreview/matpreview.serialized (kept as tests/golden/matpreview.serialized), whose counts
     and hashes are recorded here"""
     import hashlib
     import os
     import serialized_io as sio
-    path = "/root/reference/data/blender/mitsuba/matpreview/matpreview.serialized"
+    path = os.path.join(ROOT, "tests", "golden", "matpreview.serialized")
     golden = {0: (2078, 3936, "ebdc487819cb"), 1: (7529, 14288, "f67fc789ac10"), 2: (25, 32, "7aa5b07f5656")}
-    for i in range(3 if os.path.exists(path) else 0):
+    for i in range(3):
         assert sio.shape_count(open(path, "rb").read()) == 3
         ref = sio.read(path, i)
         m = mts.load_serialized(path, i)

@@ -12,7 +12,7 @@ import _pkgload
 import ply_io
 pkg = _pkgload.load()
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
-pos, tri = ply_io.read(os.path.join(ROOT, "tests", "golden", "bunny.ply"))
+pos, tri = ply_io.read(os.path.join(ROOT, "tests", "golden", "bunny.ply.gz"))
 sd = pkg.scenes.SceneDescription("bunny")
 sd.add_mesh(pos, tri, bsdf=sd.lambertian(0.5), face_normals=False, name="bunny")
 sd.point_light((0.0, 0.5, 0.5), 1.0)       # a scene needs a luminaire (scene.cpp:310-318)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MTSGPU_ABI_VERSION 6
+#define MTSGPU_ABI_VERSION 7
 
 enum {
 	MTSGPU_OK = 0,
@@ -213,8 +213,8 @@ typedef struct mtsgpu_stats {
 	uint64_t path_length_sum;
 	/* closest-hit launches repeated with static ray dealing because a material-queue segment overflowed */
 	uint64_t bin_overflow_retries;
-	/* time during which at least one traversal launch was running (the shadow rays of a bounce run next to the
-	 * closest-hit launch of the following one when `overlap` is on: trace_ms then counts that time twice) */
+	/* time during which at least one traversal launch was running (device-driven bounces trace the shadow rays of a bounce
+	 * next to the closest-hit launch of the following one: trace_ms then counts that time twice) */
 	double trace_union_ms;
 	/* vector-memory requests the traversal kernels ISSUED (lane level; only filled when counting is on): 16-byte sibling
 	 * pairs fetched from global memory / served by the LDS copy of the top of the tree, single 8-byte nodes (two per pop)
@@ -225,9 +225,6 @@ typedef struct mtsgpu_stats {
 	/* parts of trace_ms: the closest-hit launch of the first bounce of every pass (camera rays), and all any-hit launches;
 	 * the remaining closest-hit launches are trace_ms - trace_first_ms - trace_shadow_ms */
 	double trace_first_ms, trace_shadow_ms;
-	/* closest-hit rays traced a second time, with the mailbox, because two primitives tied in t on them (the mailbox-free
-	 * closest-hit kernel of host-driven bounces lists them instead of binning them; sahkdtree3.h:130-144, :278-283) */
-	uint64_t rays_redone;
 } mtsgpu_stats;
 
 typedef struct mtsgpu_ctx mtsgpu_ctx;
@@ -287,8 +284,6 @@ int  mtsgpu_set_options(mtsgpu_ctx *ctx, uint64_t max_paths, int count_traversal
  *   sync_free (-1 rule, 0 off, 1 on)          bounce loop without host round trips (device-side counts); the rule
  *                                             turns it on for passes of at most 8 Mi paths
  *   chunk (1..1024, default 8)                bounces enqueued between two looks at the queue size (sync_free)
- *   overlap (0/1)                             host-driven loop: shadow rays of bounce b on a second stream, next to
- *                                             the closest-hit launch of bounce b + 1
  *   test_retry (0/1)                          treat every first closest-hit launch as overflowed (exercises the retry) */
 int  mtsgpu_set_tuning(mtsgpu_ctx *ctx, const char *key, long value);
 
@@ -346,13 +341,6 @@ const char *mtsgpu_group_reduce_note(const mtsgpu_group *g);
 /* mtsgpu_set_tuning on every member.  One key belongs to the group itself and exists for tests: "rccl_fail" != 0 makes
  * the next collectives report a failure, which exercises the fall-back to the ordered sum. */
 int  mtsgpu_group_set_tuning(mtsgpu_group *g, const char *key, long value);
-
-/* Test hook of the traversal kernels' record-tail filter: 1 when mtsgpu_upload_scene would flag a leaf entry with this TriAccel
- * (12 dwords, include/mitsuba/render/triaccel.h:34-48) in a leaf with this box, i.e. when TriAccel::rayIntersect
- * (triaccel.h:141-158), evaluated in binary32, provably rejects EVERY projected point (o_u + t d_u, o_v + t d_v) that lies beyond
- * the box by more than `margin` on the triangle's u or v axis -- k_trace then does not fetch the record's tail for such a
- * candidate (its margin is 2^-16 of the scene's largest coordinate).  No GPU needed. */
-int  mtsgpu_tail_filter_flag(const uint32_t *triaccel12, const float *box_min, const float *box_max, float margin);
 
 /* HBM triad a[i] = b[i] + s * c[i] over three arrays of `bytes` each on `device` (float4 lanes, best of `iters`
  * launches): the practical bandwidth roof next to the 8 TB/s specification.  GB/s in *gbs. */

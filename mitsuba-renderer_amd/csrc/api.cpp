@@ -6,8 +6,6 @@
 #include "devmath.h"
 #include "ctx.h"
 #include <algorithm>
-#include <functional>
-#include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -143,7 +141,6 @@ int ensurePaths(mtsgpu_ctx *c, size_t cap) {
 	rc |= devAlloc(c, &c->queueA, cap, o); rc |= devAlloc(c, &c->queueB, cap, o);
 	for (int k = 0; k < 2; ++k) { rc |= devAlloc(c, &c->rayqA[k], cap, o); rc |= devAlloc(c, &c->rayqB[k], cap, o); }
 	rc |= devAlloc(c, &c->q.shadow, cap, o);
-	rc |= devAlloc(c, &c->q.redo, cap, o);          // closest-hit rays on which two primitives tied (k_trace TIE): traced again with the mailbox
 	rc |= devAlloc(c, &c->counterSets, (size_t) kCounterSets * kNumCounters * kCounterStride, o);
 	rc |= devAlloc(c, &c->viewsDev, kNumBins, o);
 	rc |= devAlloc(c, &c->devStats, kNumDevStats, o);
@@ -278,10 +275,7 @@ int readCounters(mtsgpu_ctx *c) {
 // Closest-hit launch over queue[0..n) with the material sort, then the per-bin segment sizes (one blocking read of the
 // counters).  A shard segment that overflowed (possible only with dynamically claimed batches, see ensurePaths) makes
 // the launch run again with static dealing: tracing a ray twice writes the same hit twice.
-// pairWith (knob "merged"): the any-hit queue of the previous bounce rides in the same launch (k_trace_pair)
-struct PairedShadow { const DQueues *q; uint32_t n; bool coherent; };
-int traceAndBin(mtsgpu_ctx *c, const uint32_t *queue, uint32_t n, bool coherent, BinView *views, const std::function<int()> &afterLaunch = nullptr,
-                const PairedShadow *pairWith = nullptr) {
+int traceAndBin(mtsgpu_ctx *c, const uint32_t *queue, uint32_t n, bool coherent, BinView *views) {
 	hipStream_t s = c->stream;
 	const size_t counterBytes = kNumCounters * kCounterStride * sizeof(uint32_t);
 	for (int attempt = 0; attempt < 2; ++attempt) {
@@ -289,35 +283,11 @@ int traceAndBin(mtsgpu_ctx *c, const uint32_t *queue, uint32_t n, bool coherent,
 		c->q.force_static = attempt ? 1u : 0u;
 		hipEvent_t *ev = c->timeKernels ? nextTraceEvents(c, coherent ? 1 : 0) : nullptr;
 		if (ev) HIPCHK(c, hipEventRecord(ev[0], s));
-		// the closest-hit kernel without the mailbox (k_trace TIE, one more level of the tree in LDS); rays on which two primitives
-		// tied come back in q.redo and go through the kernel with the mailbox
-		const bool tie = tuningOr(c, "mailbox_free", 0) != 0 && !c->countTraversal && !(pairWith && attempt == 0);
-		if (pairWith && attempt == 0 && !c->countTraversal)
-			launch_trace_pair(s, c->dsc, c->paths, c->q, queue, n, coherent, *pairWith->q, pairWith->q->shadow, pairWith->n, pairWith->coherent);
-		else
-			launch_trace(s, 0, c->countTraversal && attempt == 0, true, c->dsc, c->paths, c->q, queue, n, coherent, nullptr, tie);
+		launch_trace(s, 0, c->countTraversal && attempt == 0, true, c->dsc, c->paths, c->q, queue, n, coherent);
 		if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
 		HIPCHK(c, hipGetLastError());
 		c->stats.trace_launches++;
-		if (attempt == 0 && afterLaunch) { const int rc2 = afterLaunch(); if (rc2) { c->q.force_static = 0; return rc2; } }
 		int rc = readCounters(c); if (rc) { c->q.force_static = 0; return rc; }
-		if (tie) {
-			const uint32_t nRedo = c->hostCounters[kRedoWord];
-			if (nRedo > n) { c->q.force_static = 0; return fail(c, MTSGPU_EHIP, "internal: redo list longer than the queue"); }
-			if (nRedo) {
-				// their rays come from the path records (the list is not in queue order); statically dealt: no segment can overflow
-				DPaths viaRecords = c->paths; viaRecords.rq_o = viaRecords.rq_d = nullptr;
-				c->q.force_static = 1;
-				hipEvent_t *ev2 = c->timeKernels ? nextTraceEvents(c, 0) : nullptr;
-				if (ev2) HIPCHK(c, hipEventRecord(ev2[0], s));
-				launch_trace(s, 0, false, true, c->dsc, viaRecords, c->q, c->q.redo, nRedo, false);
-				if (ev2) HIPCHK(c, hipEventRecord(ev2[1], s));
-				HIPCHK(c, hipGetLastError());
-				c->stats.trace_launches++;
-				c->stats.rays_redone += nRedo;
-				rc = readCounters(c); if (rc) { c->q.force_static = 0; return rc; }
-			}
-		}
 		c->q.force_static = 0;
 		bool overflow = false;
 		for (int b = 0; b < kNumBins; ++b) {
@@ -527,47 +497,16 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 		if (sf == 1 || (sf < 0 && nPaths <= (8u << 20)))
 			return runBouncesDevice(c, cfg, nPaths, cancel);
 	}
-	// Two chip-filling persistent grids next to each other.  overlap = 1 (round 5, profiles/r05k_*): the any-hit launch of bounce b
-	// first, the closest-hit launch of bounce b + 1 behind it on the other stream -- a third SLOWER, because the workgroups of the
-	// larger footprint (80 VGPRs, 52 KB) do not pack into the holes the smaller ones (64 VGPRs, 36 KB) leave.  overlap = 2
-	// (round 6): the other way round -- the closest-hit launch of bounce b + 1 goes first and takes the whole chip, the any-hit
-	// launch of bounce b is enqueued behind it on the second stream and its workgroups move in where closest-hit workgroups
-	// leave, i.e. into the 0.3-0.7 ms at the end of that launch in which its longest rays finish alone.  Legal either way: the
-	// any-hit kernel only parks direct-light terms, the shading of bounce b + 1 waits for both.
-	const long overlap = tuningOr(c, "overlap", 0);
-	// merged = 1: the held-back any-hit queue rides in the next closest-hit LAUNCH (k_trace_pair: one footprint, no second stream)
-	const bool merged = tuningOr(c, "merged", 0) != 0 && !overlap && !c->countTraversal;
+	// Host-driven bounces, all on c->stream: stream order puts the shadow rays of bounce b before the shading of bounce
+	// b + 1, which adds to Li after them (path.cpp:124 before :80)
 	uint32_t nQ = nPaths;
 	uint32_t *cur = c->queueA, *nxt = c->queueB;
 	bool first = true;       // camera rays and their shadow rays are coherent: plain 64-ray batches win there
-	hipStream_t s = c->stream, s2 = overlap ? c->stream2 : c->stream;
+	hipStream_t s = c->stream;
 	const size_t setBytes = (size_t) kNumCounters * kCounterStride * sizeof(uint32_t);
-	bool shadowPending = false;
-	int b = 0;
 	RayQueuesOff rqOff{ c };
 	c->q.nee_parked = tuningOr(c, "nee_parked", 1) != 0 ? 1u : 0u;
-	if (overlap && !c->q.nee_parked) return fail(c, MTSGPU_EINVAL, "overlap needs nee_parked");
-	// the any-hit launch of a bounce: at once, or (overlap = 2) held back until the next closest-hit launch has been enqueued
-	struct Deferred { bool pending = false; DQueues q; uint32_t n = 0; bool coherent = false; int bounce = 0; } held;
-	auto launchShadow = [&](const DQueues &q2, uint32_t nShadow, bool coherent, int bounce) -> int {
-		hipEvent_t *ev2 = c->timeKernels ? nextTraceEvents(c, 2) : nullptr;
-		if (ev2) HIPCHK(c, hipEventRecord(ev2[0], s2));
-		launch_trace(s2, 1, c->countTraversal, false, c->dsc, c->paths, q2, q2.shadow, nShadow, coherent);
-		if (ev2) HIPCHK(c, hipEventRecord(ev2[1], s2));
-		HIPCHK(c, hipGetLastError());
-		if (overlap) HIPCHK(c, hipEventRecord(c->evShadow[bounce & 1], s2));
-		return 0;
-	};
-	auto flushHeld = [&]() -> int {
-		if (!held.pending) return 0;
-		held.pending = false;
-		if (const long us = tuningOr(c, "overlap_delay_us", 0)) {      // experiment: let the closest-hit grid take its slots first
-			const auto t0 = std::chrono::steady_clock::now();
-			while (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() < us) { }
-		}
-		return launchShadow(held.q, held.n, held.coherent, held.bounce);
-	};
-	for (; nQ > 0; ++b) {
+	for (int b = 0; nQ > 0; ++b) {
 		if (cancel && *cancel)
 			return fail(c, MTSGPU_ECANCEL, "render cancelled");
 		// the counter set of this bounce; its last users (bounce b - 2) are done: the shading of bounce b - 1 waited for them
@@ -575,20 +514,10 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 		HIPCHK(c, hipMemsetAsync(c->q.counters, 0, setBytes, s));
 		c->q.next = nxt;
 		rayQueues(c, cur, nxt);
-		// closest hit + material sort (and, behind it, the any-hit launch of the previous bounce that was held back)
+		// closest hit + material sort
 		BinView views[kNumBins];
-		int rc;
-		if (merged && held.pending) {
-			const PairedShadow pair{ &held.q, held.n, held.coherent };
-			held.pending = false;
-			rc = traceAndBin(c, cur, nQ, first, views, nullptr, &pair);
-		} else {
-			rc = traceAndBin(c, cur, nQ, first, views, flushHeld);
-		}
-		if (rc) return rc;
+		int rc = traceAndBin(c, cur, nQ, first, views); if (rc) return rc;
 		c->stats.rays_closest += nQ;
-		// the shading of this bounce adds to Li after the shadow rays of the previous one have (path.cpp:124 before :80)
-		if (shadowPending && overlap) HIPCHK(c, hipStreamWaitEvent(s, c->evShadow[(b - 1) & 1], 0));
 		// shade, one launch per BSDF type
 		hipEvent_t *sev = c->timeKernels ? nextEventPair(c, c->shadeEvents, c->shadeEvUsed) : nullptr;
 		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
@@ -602,18 +531,15 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 		if (nShadow) {
 			DQueues q2 = c->q; q2.spill = c->spillShadow;
 			c->lastPass.shadowMax = std::max(c->lastPass.shadowMax, nShadow);
-			if ((overlap == 2 || merged) && nNext > 0) {
-				held.pending = true; held.q = q2; held.n = nShadow; held.coherent = first; held.bounce = b;
-			} else {
-				rc = launchShadow(q2, nShadow, first, b); if (rc) return rc;
-			}
-			shadowPending = true;
+			hipEvent_t *ev2 = c->timeKernels ? nextTraceEvents(c, 2) : nullptr;
+			if (ev2) HIPCHK(c, hipEventRecord(ev2[0], s));
+			launch_trace(s, 1, c->countTraversal, false, c->dsc, c->paths, q2, q2.shadow, nShadow, first);
+			if (ev2) HIPCHK(c, hipEventRecord(ev2[1], s));
+			HIPCHK(c, hipGetLastError());
 			c->stats.rays_shadow += nShadow; c->stats.trace_launches++;
-		} else {
-			shadowPending = false;
 		}
-		if (getenv("MTSGPU_DEBUG") && !overlap) {
-			HIPCHK(c, hipStreamSynchronize(s)); HIPCHK(c, hipStreamSynchronize(s2));
+		if (getenv("MTSGPU_DEBUG")) {
+			HIPCHK(c, hipStreamSynchronize(s));
 			float a = 0, b2 = 0, c2 = 0;
 			if (c->timeKernels) {
 				const size_t ti = c->traceEvUsed - (nShadow ? 2 : 1);
@@ -628,127 +554,8 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 		nQ = nNext;
 		first = false;
 	}
-	{ const int rc = flushHeld(); if (rc) return rc; }
-	if (shadowPending && overlap) HIPCHK(c, hipStreamWaitEvent(s, c->evShadow[(b - 1) & 1], 0));
 	c->q.counters = c->counterSets;
 	return 0;
-}
-
-// ---- exact record-tail filter of k_trace: per leaf entry, one flag ----------------------------------------------------------
-// TriAccel::rayIntersect (triaccel.h:141-158) first computes the plane distance t from the record's head, then
-//     hu = o_u + t d_u - a_u,  hv = o_v + t d_v - a_v,  u = hv b_nu + hu b_nv,  v = hu c_nu + hv c_nv,  accept iff u >= 0 && v >= 0 && u + v <= 1
-// from its tail.  k_trace may skip the tail -- two 16-byte requests -- of a candidate exactly when that test is CERTAIN to fail.  It
-// knows the face through which the ray leaves the leaf it is visiting (axis, plane, side: the current exit point of the traversal,
-// sahkdtree3.h:233,248-249) and the point p = o + t d in the arithmetic of the reference; what it cannot know without the tail is
-// whether the triangle reaches beyond that face.  The flag says: for EVERY pair of binary32 values (p_u, p_v) with p_u beyond the
-// leaf's box on the u axis (either side), or p_v beyond it on the v axis, the expressions above -- evaluated in binary32 in the
-// reference's order, each operation rounded -- fail the test.  Proof per half-plane, here for p_u > hi_u:
-//   * hu = fl(p_u - a_u) >= fl(hi_u - a_u) =: h (rounding is monotone); the flag needs h > 0.
-//   * with U = hv b_nu + hu b_nv and V = hu c_nu + hv c_nv in exact arithmetic, the computed u, v differ from U, V by at most
-//     E_u = g (|hv b_nu| + |hu b_nv|) + e and E_v likewise (two roundings per term: g = 2^-22 covers 2 ulp, e the subnormal range),
-//     and fl(u + v) <= 1 needs u + v <= 1 + 2^-24.  So the test fails whenever U < -E_u, or V < -E_v, or U + V - E_u - E_v > 1 + 2^-22.
-//   * all three conditions are stable under (hu, hv) -> lambda (hu, hv), lambda >= 1 (U, V and the g-part of E scale with lambda),
-//     and every point of the half-plane hu >= h is lambda (h, w) for some real w: it suffices that for every real w one of the three
-//     holds at (h, w).  On w >= 0 and on w <= 0 each condition is "an affine function of w is positive": the maximum of three
-//     affine functions is convex, its minimum over a half-line lies at the end point or where two of them cross.
-// The bounds are evaluated in binary64 (products of two binary32 values are exact there) with g doubled for its own rounding.
-// Nothing here depends on where the triangle's vertices are: a flag that is set is a statement about the record's numbers alone.
-bool rejectsOnHalfLine(const double m[3], const double c[3]) {
-	// max_i (m_i z + c_i) > 0 for all z >= 0 ?
-	auto value = [&](double z) { double v = -INFINITY; for (int i = 0; i < 3; ++i) v = std::max(v, m[i] * z + c[i]); return v; };
-	if (!(value(0.0) > 0.0)) return false;
-	// far out: some function must grow, or a constant one must stay positive
-	double mmax = std::max(m[0], std::max(m[1], m[2]));
-	if (!(mmax >= 0.0)) return false;
-	if (mmax == 0.0) {
-		double cbest = -INFINITY;
-		for (int i = 0; i < 3; ++i) if (m[i] == 0.0) cbest = std::max(cbest, c[i]);
-		if (!(cbest > 0.0)) return false;
-	}
-	for (int i = 0; i < 3; ++i)
-		for (int j = i + 1; j < 3; ++j) {
-			if (m[i] == m[j]) continue;
-			const double z = (c[j] - c[i]) / (m[i] - m[j]);
-			if (!(z > 0.0) || !std::isfinite(z)) continue;
-			// the crossing point itself is rounded: look at it and at its neighbours
-			for (double zz : { z, z * (1.0 - 1e-12), z * (1.0 + 1e-12) })
-				if (!(value(zz) > 0.0)) return false;
-		}
-	return true;
-}
-// the half-plane {fixed coordinate beyond h (same sign as h), other coordinate w free}: U = af h' + aw w, V = bf h' + bw w
-bool rejectsBeyond(double af, double aw, double bf, double bw, double h) {
-	if (!(h != 0.0) || !std::isfinite(h) || !std::isfinite(af) || !std::isfinite(aw) || !std::isfinite(bf) || !std::isfinite(bw)) return false;
-	const double g = 0x1p-21, e = 0x1p-140;
-	for (int side = 0; side < 2; ++side) {              // w >= 0, then w = -z <= 0
-		const double aW = side ? -aw : aw, bW = side ? -bw : bw;
-		const double m[3] = { -aW - g * std::fabs(aW), -bW - g * std::fabs(bW), aW + bW - g * (std::fabs(aW) + std::fabs(bW)) };
-		const double c[3] = { -af * h - g * std::fabs(af * h) - e, -bf * h - g * std::fabs(bf * h) - e,
-		                      (af + bf) * h - g * (std::fabs(af * h) + std::fabs(bf * h)) - 1.0 - 0x1p-21 - 2 * e };
-		if (!rejectsOnHalfLine(m, c)) return false;
-	}
-	return true;
-}
-// The SAH builder puts its planes on the bounds of the (clipped) triangles, so most triangles TOUCH faces of their leaf, and for
-// a point one ulp beyond a touched face nothing can be proven (u + v may round to exactly 1).  The kernel therefore only skips a
-// tail when the point lies beyond the face by more than a margin mu (one scene-wide binary32 constant, DTraceScene::tail_margin):
-// it tests fl(p - plane) > mu, which implies p - plane > mu in exact arithmetic (rounding is monotone), and the plane is the
-// leaf's own bound or lies beyond it.  The proof is made for the half-planes beyond lo - mu / hi + mu.
-// rec: the 12 dwords of a TriAccel (triaccel.h:34-48); lo / hi: the leaf's box
-float roundedTowardZero(double x) {
-	float f = (float) x;
-	if (std::fabs((double) f) > std::fabs(x)) f = std::nextafterf(f, 0.0f);
-	return f;
-}
-bool tailFilterFlag(const uint32_t *rec, const float lo[3], const float hi[3], float margin) {
-	const uint32_t k = rec[0];
-	if (k > 2u || !(margin >= 0.0f) || !std::isfinite(margin)) return false;
-	float f[12]; std::memcpy(f, rec, 48);
-	const float a_u = f[4], a_v = f[5];
-	const double b_nu = f[6], b_nv = f[7], c_nu = f[8], c_nv = f[9];
-	const int ku = (int) ((k + 1u) % 3u), kv = (int) ((k + 2u) % 3u);          // triaccel.h:104-137
-	// hu = fl(p_u - a_u) with p_u > hi_u + mu: hu >= fl(hi_u + mu - a_u) >= that value rounded toward zero (binary64 holds the sum of
-	// three binary32 values to 2^-53, far inside the step to the next binary32 value toward zero); likewise below lo - mu
-	const float hUhi = roundedTowardZero(((double) hi[ku] + margin - a_u) * (1.0 - 0x1p-50)), hUlo = roundedTowardZero(((double) lo[ku] - margin - a_u) * (1.0 - 0x1p-50));
-	const float hVhi = roundedTowardZero(((double) hi[kv] + margin - a_v) * (1.0 - 0x1p-50)), hVlo = roundedTowardZero(((double) lo[kv] - margin - a_v) * (1.0 - 0x1p-50));
-	if (!(hUhi > 0.0f) || !(hUlo < 0.0f) || !(hVhi > 0.0f) || !(hVlo < 0.0f)) return false;
-	// fixed hu: U = hv b_nu + hu b_nv -> af = b_nv, aw = b_nu; V = hu c_nu + hv c_nv -> bf = c_nu, bw = c_nv
-	if (!rejectsBeyond(b_nv, b_nu, c_nu, c_nv, hUhi) || !rejectsBeyond(b_nv, b_nu, c_nu, c_nv, hUlo)) return false;
-	// fixed hv: af = b_nu, aw = b_nv; bf = c_nv, bw = c_nu
-	return rejectsBeyond(b_nu, b_nv, c_nv, c_nu, hVhi) && rejectsBeyond(b_nu, b_nv, c_nv, c_nu, hVlo);
-}
-// one flag per entry of the index list: the leaves' boxes come from walking the tree with the scene's box (gkdtree.h:1170-1176)
-// the margin of a scene: 2^-16 of its largest coordinate (some tens of ulps there; rays whose plane point lies closer to a face
-// than this are not filtered, everything else about the filter is independent of the choice)
-float tailFilterMargin(const mtsgpu_scene *sc) {
-	float m = 0.0f;
-	for (int a = 0; a < 3; ++a) m = std::max(m, std::max(std::fabs(sc->aabb_min[a]), std::fabs(sc->aabb_max[a])));
-	m *= 0x1p-16f;
-	return (std::isfinite(m) && m > 0.0f) ? m : 0x1p-100f;
-}
-void tailFilterFlags(const mtsgpu_scene *sc, float margin, std::vector<uint8_t> &flags) {
-	flags.assign(sc->n_indices, 0);
-	struct Item { uint32_t node; float lo[3], hi[3]; };
-	std::vector<Item> stack;
-	Item root; root.node = 0;
-	for (int a = 0; a < 3; ++a) { root.lo[a] = sc->aabb_min[a]; root.hi[a] = sc->aabb_max[a]; }
-	stack.push_back(root);
-	while (!stack.empty()) {
-		const Item it = stack.back(); stack.pop_back();
-		const uint32_t a = sc->kd_nodes[2 * (size_t) it.node], b = sc->kd_nodes[2 * (size_t) it.node + 1];
-		if (a & 0x80000000u) {
-			for (uint32_t e = a & 0x7FFFFFFFu; e < b; ++e)
-				flags[e] = tailFilterFlag(sc->triaccel + 12 * (size_t) sc->kd_indices[e], it.lo, it.hi, margin) ? 1 : 0;
-			continue;
-		}
-		const int axis = (int) (a & 3u);
-		float split; std::memcpy(&split, &b, 4);
-		const uint32_t left = it.node + ((a & 0x3FFFFFFCu) >> 2);
-		Item l = it, r = it;
-		l.node = left; l.hi[axis] = split;
-		r.node = left + 1; r.lo[axis] = split;
-		stack.push_back(r); stack.push_back(l);
-	}
 }
 
 int checkReady(mtsgpu_ctx *c) {
@@ -1015,16 +822,11 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 	c->haveScene = false;
 	DScene d{};
 	int rc = 0;
-	// entryOld[e]: which entry of the index list the device's leaf-record slot e holds.  The identity, unless the experiment knob
-	// MTSGPU_LEAF_ORDER=1 lays the leaves' runs out in the order of their nodes in the device tree (treelet order) instead of the
-	// builder's index-list order (profiles/r06h_*); leafFirst[i]: first slot of the leaf with (old) node index i
-	std::vector<uint32_t> entryOld(sc->n_indices), leafFirst;
-	for (uint32_t e = 0; e < sc->n_indices; ++e) entryOld[e] = e;
-	const bool leafReorder = getenv("MTSGPU_LEAF_ORDER") && atoi(getenv("MTSGPU_LEAF_ORDER")) == 1;
 	{
 		// Device node order.  The first trace_top_nodes() slots hold the root and the sibling pairs below it in
-		// breadth-first order: k_trace keeps that prefix in LDS.  After it, 128-byte lines (16 nodes) are filled with
-		// breadth-first pieces of subtrees ("treelets") so that one L1 miss serves several consecutive traversal steps.
+		// breadth-first order: k_trace keeps the first half of that prefix in LDS (kernels.h: kTopNodes).  After it,
+		// 128-byte lines (16 nodes) are filled with breadth-first pieces of subtrees ("treelets") so that one L1 miss
+		// serves several consecutive traversal steps.
 		// The KDNode encoding is unchanged (siblings adjacent, relative offset to the left child,
 		// gkdtree.h:442-470); only where a node lives changes, which traversal results do not depend on.
 		const uint32_t N = sc->n_nodes;
@@ -1055,26 +857,9 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 		if (total >= (1u << 29)) return fail(c, MTSGPU_EINVAL, "kd-tree too large");      // absolute child indices; k_trace's stack words keep node index * 2 below bit 30
 		std::vector<uint32_t> dev(2 * (size_t) total, 0u);
 		dev[2] = 0x80000000u; dev[3] = 0u;           // padding slot: empty leaf, never referenced
-		if (leafReorder) {
-			std::vector<std::pair<uint32_t, uint32_t>> leaves;      // (device node index, old node index)
-			uint64_t covered = 0;
-			for (uint32_t i = 0; i < N; ++i)
-				if (isLeaf(i)) { leaves.emplace_back(newIndex[i], i); covered += sc->kd_nodes[2 * (size_t) i + 1] - (sc->kd_nodes[2 * (size_t) i] & 0x7FFFFFFFu); }
-			if (covered == sc->n_indices) {           // every entry belongs to exactly one leaf (what the builders produce)
-				std::sort(leaves.begin(), leaves.end());
-				leafFirst.assign(N, 0u);
-				uint32_t at = 0;
-				for (const auto &lf : leaves) {
-					const uint32_t first = sc->kd_nodes[2 * (size_t) lf.second] & 0x7FFFFFFFu, end = sc->kd_nodes[2 * (size_t) lf.second + 1];
-					leafFirst[lf.second] = at;
-					for (uint32_t e = first; e < end; ++e) entryOld[at++] = e;
-				}
-			}
-		}
 		for (uint32_t i = 0; i < N; ++i) {
-			uint32_t a = sc->kd_nodes[2 * (size_t) i], b = sc->kd_nodes[2 * (size_t) i + 1];
+			const uint32_t a = sc->kd_nodes[2 * (size_t) i], b = sc->kd_nodes[2 * (size_t) i + 1];
 			uint32_t *o = &dev[2 * (size_t) newIndex[i]];
-			if ((a & 0x80000000u) && !leafFirst.empty()) { const uint32_t n = b - (a & 0x7FFFFFFFu); a = 0x80000000u | leafFirst[i]; b = leafFirst[i] + n; }
 			if (a & 0x80000000u) { o[0] = a; o[1] = b; }
 			else { o[0] = (a & 3u) | (newIndex[leftOf(i)] << 2); o[1] = b; }     // absolute left-child index (< 2^29)
 		}
@@ -1086,21 +871,15 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 		// (Shape::isOccluder, shape.h:324)
 		const size_t LS = 4 * (size_t) kLeafStride;                 // dwords per record slot
 		std::vector<uint32_t> ta(LS * ((size_t) sc->n_indices + 1), 0u);
-		std::vector<uint8_t> tailFlags;
-		d.tail_margin = tailFilterMargin(sc);
-		if (trace_tail_filter()) tailFilterFlags(sc, d.tail_margin, tailFlags);      // experiment builds only (trace.hip: MG_TAIL_FILTER)
-		else tailFlags.assign(sc->n_indices, 0);
-		for (uint32_t slot = 0; slot < sc->n_indices; ++slot) {
-			const uint32_t e = entryOld[slot];
+		for (uint32_t e = 0; e < sc->n_indices; ++e) {
 			const uint32_t prim = sc->kd_indices[e];
-			uint32_t *dst = &ta[LS * (size_t) slot];
+			uint32_t *dst = &ta[LS * (size_t) e];
 			std::memcpy(dst, sc->triaccel + 12 * (size_t) prim, 48);
 			// dword 0 = k<<30 | non-occluder<<29 | primitive id (the head of the record decides everything
 			// up to the plane distance); dword 10 stays the shape index
 			if (prim >= (1u << 28)) return fail(c, MTSGPU_EINVAL, "more than 2^28 primitives");
 			const bool isShape = dst[0] == MTSGPU_KNOTRIANGLE;
-			// bit 28: the record's tail may be skipped for candidates beyond the leaf's box on a projection axis (tailFilterFlag)
-			dst[0] = (std::min(dst[0], 3u) << 30) | (sc->shape_bsdf[dst[10]] < 0 ? 0x20000000u : 0u) | (tailFlags[e] ? 0x10000000u : 0u) | prim;
+			dst[0] = (std::min(dst[0], 3u) << 30) | (sc->shape_bsdf[dst[10]] < 0 ? 0x20000000u : 0u) | prim;
 			dst[11] = 0;
 			if ((dst[0] >> 30) == 3u) {
 				// k == 3: a degenerate triangle (dword 1 = 0) or a non-triangle shape (dword 1 = shape type,
@@ -1114,10 +893,6 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 			}
 		}
 		rc |= upload(c, (const uint32_t **) &d.leaf_ta, ta.data(), ta.size());
-		if (getenv("MTSGPU_DEBUG")) {
-			size_t nf = 0; for (uint8_t f : tailFlags) nf += f;
-			fprintf(stderr, "[mtsgpu] record-tail filter: %zu of %u leaf entries flagged (%.3f)\n", nf, sc->n_indices, sc->n_indices ? (double) nf / sc->n_indices : 0.0);
-		}
 		// per-primitive position / normal records for the shading kernels
 		const size_t TS = 4 * (size_t) kTriStride;                    // floats per record (one 128-byte line)
 		std::vector<float> triRec(TS * ((size_t) sc->n_tris + 1), 0.0f);
@@ -1316,7 +1091,7 @@ int mtsgpu_set_tuning(mtsgpu_ctx *c, const char *key, long value) {
 	if (!c || !key) return fail(c, MTSGPU_EINVAL, "null argument");
 	struct Knob { const char *key; long lo, hi; };
 	static const Knob knobs[] = { { "refill_min", 1, 64 }, { "desc_min", 1, 64 }, { "leaf_min", 1, 64 }, { "batch", 0, 64 },
-	                              { "dyn_div", 0, 1 << 20 }, { "test_retry", 0, 1 }, { "sync_free", -1, 1 }, { "overlap", 0, 2 }, { "overlap_delay_us", 0, 100000 }, { "merged", 0, 1 }, { "mailbox_free", 0, 1 }, { "chunk", 1, 1024 }, { "blocks_per_cu", 0, (long) kTraceBlocksPerCuMax }, { "plain_below", 0, 1 << 30 }, { "dyn_min_rounds", 0, 1 << 20 }, { "shade_fused", 0, 1 }, { "ray_queues", 0, 1 }, { "nee_parked", 0, 1 } };
+	                              { "dyn_div", 0, 1 << 20 }, { "test_retry", 0, 1 }, { "sync_free", -1, 1 }, { "chunk", 1, 1024 }, { "blocks_per_cu", 0, (long) kTraceBlocksPerCuMax }, { "plain_below", 0, 1 << 30 }, { "dyn_min_rounds", 0, 1 << 20 }, { "shade_fused", 0, 1 }, { "ray_queues", 0, 1 }, { "nee_parked", 0, 1 } };
 	for (const Knob &k : knobs)
 		if (std::strcmp(k.key, key) == 0) {
 			if (value < k.lo || value > k.hi) return fail(c, MTSGPU_EINVAL, "tuning knob %s: %ld outside [%ld, %ld]", key, value, k.lo, k.hi);
@@ -1822,11 +1597,6 @@ int mtsgpu_li_samples(mtsgpu_ctx *c, const uint32_t *pix_samples, uint32_t n, fl
 
 // --- host-side flattening ------------------------------------------------------
 struct mtsgpu_flat_scene { FlatScene fs; };
-
-int mtsgpu_tail_filter_flag(const uint32_t *triaccel12, const float *box_min, const float *box_max, float margin) {
-	if (!triaccel12 || !box_min || !box_max) return 0;
-	return tailFilterFlag(triaccel12, box_min, box_max, margin) ? 1 : 0;
-}
 
 int mtsgpu_flatten(const mtsgpu_scene_desc *desc, const mtsgpu_kd_params *kd, mtsgpu_flat_scene **out) {
 	if (!desc || !out) return fail(nullptr, MTSGPU_EINVAL, "null argument");

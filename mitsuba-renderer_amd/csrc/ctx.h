@@ -12,8 +12,9 @@ struct mtsgpu_ctx {
 	uint32_t nCUs = 256;                   // hipDeviceProp_t::multiProcessorCount
 	hipStream_t stream = nullptr;
 	bool ownStream = false;
-	// second stream: the shadow rays of bounce b are traced on it while `stream` already traces the closest hits of
-	// bounce b + 1 (both only depend on the shading of bounce b); evShade / evShadow order the two
+	// second stream of device-driven bounces (runBouncesDevice): the shadow rays of bounce b are traced on it while `stream`
+	// already traces the closest hits of bounce b + 1 (both only depend on the shading of bounce b); evShade / evShadow order
+	// the two
 	hipStream_t stream2 = nullptr;
 	hipEvent_t evShade[2] = { nullptr, nullptr }, evShadow[2] = { nullptr, nullptr }, evCount = nullptr;
 	std::string error;

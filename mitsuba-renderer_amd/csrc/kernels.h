@@ -39,13 +39,10 @@ constexpr int kStackLDS = MG_STACK_LDS;       // stack levels kept in LDS (deepe
 // levels that every other ray visits too, and a vector-memory request costs the CU ~0.5-1 ns per lane where an LDS
 // read costs ~0.05 (profiles/r02_ta_gather_microbench.txt).  0 switches the cache off.
 constexpr uint32_t kTopPairs = MG_TOP_PAIRS;
-// The closest-hit kernel of host-driven bounces runs WITHOUT the hashed mailbox (trace.hip: TIE) and spends the 16 KB on one more
-// level of the tree: 2 048 sibling pairs.  The breadth-first prefix of the device tree covers the larger of the two copies.
-#ifndef MG_TOP_PAIRS_TIE
-#define MG_TOP_PAIRS_TIE (2 * MG_TOP_PAIRS)
-#endif
-constexpr uint32_t kTopPairsTie = MG_TOP_PAIRS_TIE;
-constexpr uint32_t kTopPairsMax = kTopPairsTie > kTopPairs ? kTopPairsTie : kTopPairs;
+// Device nodes laid out breadth-first before the treelets start (mtsgpu_upload_scene): twice the LDS copy, 4 096 in the product.
+// Kept apart from kTopPairs because it decides where every node sits in memory: the traversal was measured with this layout.
+constexpr uint32_t kTopNodes = 4 * kTopPairs;
+static_assert(kTopNodes >= 2 * kTopPairs && (kTopPairs != 1024 || kTopNodes == 4096), "the LDS copy lies inside the breadth-first prefix");
 constexpr int kSpillLevels = 50 - kStackLDS;      // LDS + spill levels = MTS_KD_MAXDEPTH (48, gkdtree.h:35) + 2
 static_assert(kStackLDS >= 1 && kStackLDS + kSpillLevels >= 48 + 2, "the traversal stack must hold every tree the reference can build");
 constexpr uint32_t kSentinel = 0xFFFFFFFFu;
@@ -60,13 +57,13 @@ constexpr int kLumStride = 32;        // MTSGPU_LUM_NPARAMS
 constexpr int kCounterStride = 32;    // one 128-byte line per queue counter (atomics on one line serialise)
 constexpr int kBsdfNParams = 16;      // MTSGPU_BSDF_NPARAMS
 constexpr int kBinShards = 16;        // the closest-hit kernel appends to bins[b] through 16 independent segments
-constexpr int kNumCounters = kNumBins * kBinShards + 5;   // bins x shards, next, shadow, dynamic heads of the two traversal launches, redo list
+constexpr int kNumCounters = kNumBins * kBinShards + 4;   // bins x shards, next, shadow, dynamic heads of the two traversal launches
 // Two sets of counters, used by alternate bounces: the shadow rays of bounce b are traced (second stream) while the
 // closest-hit launch of bounce b + 1 already fills the next set
 constexpr int kCounterSets = 2;
-constexpr int kCntNext = kNumBins * kBinShards, kCntShadow = kCntNext + 1, kCntDynClosest = kCntNext + 2, kCntDynShadow = kCntNext + 3, kCntRedo = kCntNext + 4;
+constexpr int kCntNext = kNumBins * kBinShards, kCntShadow = kCntNext + 1, kCntDynClosest = kCntNext + 2, kCntDynShadow = kCntNext + 3;
 // word offsets of the two queue counters of k_shade inside a counter set (one 128-byte line each)
-constexpr int kNextWord = kCntNext * kCounterStride, kShadowWord = kCntShadow * kCounterStride, kRedoWord = kCntRedo * kCounterStride;
+constexpr int kNextWord = kCntNext * kCounterStride, kShadowWord = kCntShadow * kCounterStride;
 #ifndef MG_SHADE_BLOCK
 #define MG_SHADE_BLOCK 1024     // 512: two atomics-bound milliseconds more per 64-spp frame (one reservation per workgroup)
 #endif
@@ -112,7 +109,6 @@ struct DScene {
 	int32_t background_lum;
 	uint32_t n_lums, n_nodes, n_tris, n_shapes;
 	float aabb_min[3], aabb_max[3];
-	float tail_margin;            // record-tail filter of k_trace (api.cpp: tailFilterFlag): how far beyond a leaf's face a plane point must lie
 };
 
 // What k_trace needs of the scene (a kernel argument: the fewer scalar registers it pins, the fewer get spilled)
@@ -122,11 +118,10 @@ struct DTraceScene {
 	const uint32_t *shape_bin;
 	uint32_t has_shapes;
 	float aabb_min[3], aabb_max[3];
-	float tail_margin;
 };
 inline DTraceScene trace_scene(const DScene &sc) {
 	DTraceScene t;
-	t.nodes = sc.nodes; t.leaf_ta = sc.leaf_ta; t.shape_bin = sc.shape_bin; t.has_shapes = sc.has_shapes; t.tail_margin = sc.tail_margin;
+	t.nodes = sc.nodes; t.leaf_ta = sc.leaf_ta; t.shape_bin = sc.shape_bin; t.has_shapes = sc.has_shapes;
 	for (int i = 0; i < 3; ++i) { t.aabb_min[i] = sc.aabb_min[i]; t.aabb_max[i] = sc.aabb_max[i]; }
 	return t;
 }
@@ -222,10 +217,6 @@ struct DQueues {
 	__host__ __device__ uint32_t *bin(int b) const { return bins_base + (size_t) b * bin_stride; }
 	uint32_t *next;               // paths that continue (input of the next closest-hit launch)
 	uint32_t *shadow;             // paths with a pending shadow ray
-	// closest-hit launches without the mailbox (trace.hip: TIE): the path ids of rays on which two primitives tied in t -- the one
-	// case in which the mailbox decides the result (sahkdtree3.h:130-144, :278-283); they are not binned but traced again by the
-	// kernel with the mailbox.  Count in counters[kCntRedo]
-	uint32_t *redo;
 	uint32_t *counters;           // the counter set of this bounce, [i * kCounterStride]: i = b * kBinShards + shard for the bins, then kCnt*
 	// counting builds (u64 x kNumTraceCounts): n_inner, n_leaf, n_idx, n_tri_tested, the lane slots of the three loops and of
 	// the batches, then the vector-memory requests the kernel ISSUED: sibling pairs from global memory / from the LDS copy,
@@ -336,13 +327,8 @@ void launch_generate(hipStream_t s, const DScene &sc, const DPaths &ps, const DC
 // mode 2: any-hit over ps.ray_* (writes ps.hit.w = occluded) -- test/benchmark API
 // n_dev == NULL: n rays, grid sized for them.  n_dev != NULL: the count is read from device memory by the kernel and n
 // is only its upper bound (device-driven bounces: the host never learns the queue sizes)
-// tie: (mode 0 with bin, no counting) the mailbox-free kernel that lists tied rays in q.redo instead of binning them
 void launch_trace(hipStream_t s, int mode, bool count, bool bin, const DScene &sc, const DPaths &ps,
-                  const DQueues &q, const uint32_t *queue, uint32_t n, bool coherent, const uint32_t *n_dev = nullptr, bool tie = false);
-// one launch for the closest-hit queue of a bounce (mode 0 with the material sort) and, behind it in the same waves, the any-hit
-// queue of the bounce before (mode 1); host-sized grids only
-void launch_trace_pair(hipStream_t s, const DScene &sc, const DPaths &ps, const DQueues &qc, const uint32_t *queue_c, uint32_t n_c, bool coherent_c,
-                       const DQueues &qs, const uint32_t *queue_s, uint32_t n_s, bool coherent_s);
+                  const DQueues &q, const uint32_t *queue, uint32_t n, bool coherent, const uint32_t *n_dev = nullptr);
 // prefix[s] = number of entries of the bin in segments < s (prefix[kBinShards] = total)
 struct BinView { uint32_t prefix[kBinShards + 1]; };
 // views_dev == NULL: the bin has view.prefix[kBinShards] entries.  Otherwise the view is views_dev[bin] (written by
@@ -389,8 +375,7 @@ void launch_add_blocks(hipStream_t s, const DConfig &cfg, const TileMeta *tiles,
 void launch_fill_u32(hipStream_t s, uint32_t *p, uint32_t v, size_t n);
 void launch_iota(hipStream_t s, uint32_t *p, uint32_t n);
 size_t trace_spill_levels();
-int trace_tail_filter();          // MG_TAIL_FILTER of the build: scene upload computes the per-entry flags only when the kernels use them
-uint32_t trace_top_nodes();       // device nodes k_trace copies into LDS: the breadth-first top of the tree
+uint32_t trace_top_nodes();       // kTopNodes: the breadth-first top of the device tree, which holds the part k_trace copies into LDS
 size_t trace_stack_levels();      // depth of the traversal stack (LDS + spill levels)
 
 } // namespace mg

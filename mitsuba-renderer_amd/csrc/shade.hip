@@ -1089,11 +1089,6 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 
 }
 
-#ifndef MG_SHADE_ALL_SLOTS
-#define MG_SHADE_ALL_SLOTS 1      // whole 128-byte lines in both directions; 0 (only the slots needed: 7 read, 6 written, 3 of the
-                                  // triangle) was measured at 66 ms instead of 44 ms per frame: partial lines cost a read-modify-write
-#endif
-
 #ifndef MG_SHADE_WAVES
 #define MG_SHADE_WAVES 0
 #endif
@@ -1150,8 +1145,9 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	for (int r = 0; r < 8; ++r) {
 		const uint32_t src = grp + 8u * r;
 		const uint32_t sid = (uint32_t) __shfl((int) id, (int) src);
-		// slot 7 (the raster position) is only read by the film kernels
-		if (((actMask >> src) & 1ull) && (MG_SHADE_ALL_SLOTS || sub != 7u)) rows[shade_row_index(src, sub)] = ld_stream<4>(&ps.base[(size_t) sid * kPathSlots + sub]);
+		// whole 128-byte lines in both directions, slot 7 (the raster position, only read by the film kernels) included: only
+		// the slots needed (7 read, 6 written, 3 of the triangle) cost 66 ms instead of 44 ms per frame (partial-line writes)
+		if ((actMask >> src) & 1ull) rows[shade_row_index(src, sub)] = ld_stream<4>(&ps.base[(size_t) sid * kPathSlots + sub]);
 	}
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	bool continues = false, wantShadow = false;
@@ -1191,7 +1187,7 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 		for (int r = 0; r < 4; ++r) {
 			const uint32_t src = grp4 + 16u * r;
 			const uint32_t sprim = (uint32_t) __shfl((int) prim, (int) src);
-			if (((validMask >> src) & 1ull) && (MG_SHADE_ALL_SLOTS || sub4 != 3u)) rows[shade_row_index(src, slotOf)] = sc.tri_pos[(size_t) sprim * kTriStride + sub4];
+			if ((validMask >> src) & 1ull) rows[shade_row_index(src, slotOf)] = sc.tri_pos[(size_t) sprim * kTriStride + sub4];
 		}
 	}
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
@@ -1202,9 +1198,9 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	for (int r = 0; r < 8; ++r) {
 		const uint32_t src = grp + 8u * r;
 		const uint32_t sid = (uint32_t) __shfl((int) id, (int) src);
-		// the raster position (slot 7) does not change here; slot 2 does when direct-light terms are parked in it (the term this
+		// whole lines again: slot 7 does not change here; slot 2 does when direct-light terms are parked in it (the term this
 		// shading added has to go: every later reader would add it again), otherwise it holds the hit, unchanged
-		if (((actMask >> src) & 1ull) && (MG_SHADE_ALL_SLOTS || ((sub != 2u || q.nee_parked) && sub != 7u))) st_stream<4>(&ps.base[(size_t) sid * kPathSlots + sub], rows[shade_row_index(src, sub)]);
+		if ((actMask >> src) & 1ull) st_stream<4>(&ps.base[(size_t) sid * kPathSlots + sub], rows[shade_row_index(src, sub)]);
 	}
 
 	// stream compaction: survivors -> next closest-hit queue, shadow rays -> shadow queue.

@@ -18,33 +18,16 @@ namespace mg {
 // (sahkdtree3.h:130-144) is kept (LDS) because it decides equal-t ties.
 // ===========================================================================
 
-// MG_TAIL_FILTER: the exact record-tail filter (api.cpp: tailFilterFlag).  The stack words then carry the split axis of their node
-// in bits 30-31 (node index * 2 + side stays below bit 30), so that the leaf loop knows through which face the ray leaves the
-// leaf -- axis, plane, side -- without fetching anything.  Exact (bit-identical results: the GPU suite and the film A/B ran on it),
-// it removes a quarter of the tail requests of a C3 frame -- and is NEUTRAL in time (profiles/r06g_exp_trace_exact_tail_filter.txt:
-// the skipped tails are L1 hits on their head's line, the test costs six vector instructions per candidate), so the product is
-// built without it.
-#ifndef MG_TAIL_FILTER
-#define MG_TAIL_FILTER 0
-#endif
 // How many lanes below this one have their bit set in a wave mask (ranks of the material sort, of the refill).  The hardware counts
 // them (v_mbcnt_lo / _hi); the portable form popcount(mask & ((1 << lane) - 1)) keeps a 64-bit per-lane mask and its complement alive
 // across the whole kernel -- four VGPRs in a kernel that sits on its register ceiling, which the compiler paid for with 20 bytes of
 // scratch reloaded at every retirement (round 6: 79 VGPRs / 20 B -> 79 / 0 B closest-hit, 63 -> 61 VGPRs any-hit).
-#ifndef MG_RANK_MBCNT
-#define MG_RANK_MBCNT 1
-#endif
-__device__ __forceinline__ uint32_t lanes_below(uint64_t mask, uint32_t lane) {
-	if (MG_RANK_MBCNT) return __builtin_amdgcn_mbcnt_hi((uint32_t) (mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mask, 0u));
-	return (uint32_t) __popcll(mask & ((1ull << lane) - 1ull));
+__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
+	return __builtin_amdgcn_mbcnt_hi((uint32_t) (mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mask, 0u));
 }
-#ifndef MG_EXP_EXTRA_MISS
-#define MG_EXP_EXTRA_MISS 0
-#endif
 size_t trace_spill_levels() { return kSpillLevels; }      // in dwords per thread
-int trace_tail_filter() { return MG_TAIL_FILTER; }          // 0: the kernels were built without the record-tail filter (the default), 1: both kernels, 2: any-hit only
 size_t trace_stack_levels() { return kStackLDS + kSpillLevels; }
-uint32_t trace_top_nodes() { return 2u * kTopPairsMax; }
+uint32_t trace_top_nodes() { return kTopNodes; }
 
 // Persistent waves: the grid is sized to fill the chip once and every wave walks its own 64-ray
 // batches of the queue with a private cursor (no work-queue atomic: a single head word saturates at
@@ -60,7 +43,7 @@ uint32_t trace_top_nodes() { return 2u * kTopPairsMax; }
 __device__ __forceinline__ const uint4 *leaf_head(const DTraceScene &sc, uint32_t e) { return &sc.leaf_ta[kLeafStride * (size_t) e]; }
 __device__ __forceinline__ const uint4 *leaf_tail(const DTraceScene &sc, uint32_t e, uint32_t half) { return &sc.leaf_ta[kLeafStride * (size_t) e + 1 + half]; }
 
-template <int MODE, bool COUNT, bool BIN, bool TIE = false>
+template <int MODE, bool COUNT, bool BIN>
 __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &ps, const DQueues &q, const TracePlan &plan,
                                            const uint32_t *queue, uint32_t n, const uint32_t first, const uint32_t stride,
                                            uint32_t (*s_stack)[kTraceBlock], uint32_t (*s_mbox)[kTraceBlock], const uint4 *s_top) {
@@ -74,14 +57,13 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 			rec_n++;
 		}
 	};
-	constexpr uint32_t kTop = TIE ? kTopPairsTie : kTopPairs;      // sibling pairs of the LDS copy this instantiation was given
 	auto load_node = [&](uint32_t i) -> uint2 {
-		if (kTop && i < 2u * kTop) { if (COUNT) l_node++; return reinterpret_cast<const uint2 *>(s_top)[i]; }
+		if (kTopPairs && i < 2u * kTopPairs) { if (COUNT) l_node++; return reinterpret_cast<const uint2 *>(s_top)[i]; }
 		if (COUNT) { g_node++; rec_add(kReqNode, i); }
 		return sc.nodes[i];
 	};
 	auto load_pair = [&](uint32_t left) -> uint4 {
-		if (kTop && left < 2u * kTop) { if (COUNT) l_pair++; return s_top[left >> 1]; }
+		if (kTopPairs && left < 2u * kTopPairs) { if (COUNT) l_pair++; return s_top[left >> 1]; }
 		if (COUNT) { g_pair++; rec_add(kReqPair, left >> 1); }
 		return reinterpret_cast<const uint4 *>(sc.nodes)[left >> 1];
 	};
@@ -89,13 +71,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 	// closest-hit rays keep it.  For any-hit rays it only saves repeated tests of a primitive that spans several leaves --
 	// the answer is a disjunction over the same primitives either way -- and its 8 dwords per lane are better spent on
 	// the LDS copy of the tree: the shadow kernels run without it (counting builds keep it: the oracle counts with it).
-	// TIE: closest-hit rays WITHOUT the mailbox.  Skipping a primitive that was tested before only saves work -- its test gives the
-	// same answer again (rejected: the interval has only shrunk; accepted before and still the best: t == maxt is accepted again and
-	// changes nothing) -- EXCEPT when two different primitives tie in t: then the later test wins and which tests run depends on the
-	// mailbox's eight hashed slots.  Such a ray (an accepted hit with t == best_t on another primitive) is flagged, listed in q.redo
-	// instead of being binned, and traced again by the kernel with the mailbox; everything else is bit-identical by the argument above.
-	static_assert(!TIE || (MODE == 0 && BIN && !COUNT), "the mailbox-free form exists for binned closest-hit launches");
-	constexpr bool kMbox = (MODE == 0 && !TIE) || COUNT;
+	constexpr bool kMbox = MODE == 0 || COUNT;
 	const uint32_t tid = threadIdx.x;
 	const uint32_t gtid = blockIdx.x * kTraceBlock + tid;     // spill slot of this lane
 	const uint32_t lane = lane_id();
@@ -167,12 +143,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 					if (BIN) {
 						bin = kNumBins - 1;
 						if (found) {
-							bin = (int) sc.shape_bin[TIE ? (best_shape & 0x7FFFFFFFu) : best_shape];      // BSDF type of the hit shape, or the terminal bin (one lookup)
-						}
-						if (TIE && (best_shape & 0x80000000u)) {
-							// two primitives tied on this ray: the mailbox decides (rare: coincident geometry, hits on shared edges)
-							q.redo[atomicAdd(&q.counters[kCntRedo * kCounterStride], 1u)] = id;
-							bin = -1;
+							bin = (int) sc.shape_bin[best_shape];      // BSDF type of the hit shape, or the terminal bin (one lookup)
 						}
 					}
 				}
@@ -184,7 +155,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 					for (int b = 0; b < kNumBins; ++b) {
 						const uint64_t m = __builtin_amdgcn_ballot_w64(bin == b);
 						if (lane == (uint32_t) b) cnt = (uint32_t) __popcll(m);
-						if (bin == b) rank = lanes_below(m, lane);
+						if (bin == b) rank = lanes_below(m);
 					}
 					uint32_t base = 0;
 					if (lane < (uint32_t) kNumBins && cnt != 0u)
@@ -223,7 +194,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 				break;          // nlive == 0 and nothing left: the wave is finished
 
 			// ---- refill: idle lane number r takes ray r of the current chunk ----
-			const uint32_t r = lanes_below(~liveMask & limitMask, lane);
+			const uint32_t r = lanes_below(~liveMask & limitMask);
 			const bool take = !has && lane < B && r < remaining;
 			const uint32_t taken = (B - nlive < remaining) ? B - nlive : remaining;
 			const uint32_t my = sup_base + r;
@@ -333,7 +304,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 						++sp;
 						const uint32_t farRight = A ? 1u : 0u;
 						const float distToSplit = (split - sel3(ox, oy, oz, axis)) * sel3(rx, ry, rz, axis);
-						ex_ref = (cur << 1) | farRight | (MG_TAIL_FILTER ? ((uint32_t) axis << 30) : 0u);
+						ex_ref = (cur << 1) | farRight;
 						ex_t = distToSplit;
 						const float px = ox + distToSplit * dx, py = oy + distToSplit * dy, pz = oz + distToSplit * dz;
 						exx = (axis == 0) ? split : px; exy = (axis == 1) ? split : py; exz = (axis == 2) ? split : pz;   // selects, not branches
@@ -352,32 +323,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 				if (COUNT && e_cont == kNoPrim) c_leaf++;      // a resumed leaf was counted already
 				MG_WSLOT(w_outer);
 				bool hitShadow = false, more = false;
-#if MG_EXP_EXTRA_MISS
-				// sensitivity probe (profiles/r06n_*): ONE more 16-byte request per leaf visit whose line is not in the L2 -- a pseudo-random
-				// line of the path records, inside a 128 MB window (1: served by the Infinity Cache) or anywhere in 8 GB of them (2: from HBM);
-				// the value is not used
-				if (e_cont == kNoPrim) {
-					uint32_t hsh = (id * 0x9E3779B9u) ^ (nd.x * 0x85EBCA6Bu); hsh ^= hsh >> 15; hsh *= 0x2C1B3C6Du; hsh ^= hsh >> 12;
-					const uint32_t lines = MG_EXP_EXTRA_MISS == 1 ? (1u << 20) : (1u << 26);
-					// 3: the same request to a line that IS in the L2 (the first 256 KB of the node array): what the request itself costs
-					const float4 probe = MG_EXP_EXTRA_MISS == 3 ? reinterpret_cast<const float4 *>(sc.nodes)[(hsh & 0x3FFFu) * 1u] : ps.base[(size_t) (hsh & (lines - 1u)) * 8u];
-					if (__float_as_uint(probe.x) == 0xDEADBEEFu && __float_as_uint(probe.w) == 0x12345u) best_u = 0.0f;
-				}
-#endif
 				{
-#if MG_TAIL_FILTER
-					// The face through which the ray leaves this leaf: the plane of the current exit point (sahkdtree3.h:233,248-249) on its
-					// axis; the leaf lies below the plane when the exit point's far child is the right one.  Kept with the sign that turns
-					// "beyond the face" into "greater than": fO + t fD is the plane point's coordinate on that axis -- the very expression
-					// o_u + t d_u (or o_v + t d_v) of triaccel.h:151-152 when the axis is one of the triangle's projection axes, negated
-					// exactly when the leaf lies above the plane -- and fS the plane.  The end of the ray itself is no face (fS = inf).
-					const uint32_t fAxisHi = ex_ref & 0xC0000000u;            // the axis where the records keep k; 3 for the sentinel
-					const int fAxis = (int) (ex_ref >> 30);
-					const uint32_t fFlip = (ex_ref & 1u) ? 0u : 0x80000000u;
-					const float fO = __uint_as_float(__float_as_uint(sel3(ox, oy, oz, fAxis)) ^ fFlip);
-					const float fD = __uint_as_float(__float_as_uint(sel3(dx, dy, dz, fAxis)) ^ fFlip);
-					const float fS = ex_ref == kSentinel ? MG_INF : __uint_as_float(__float_as_uint(sel3(exx, exy, exz, fAxis)) ^ fFlip);
-#endif
 					uint32_t e = (e_cont != kNoPrim) ? e_cont : (nd.x & 0x7FFFFFFFu);     // resume an interrupted leaf
 					const uint32_t last = nd.y;
 					// record = 3 x 16 B: A = (k<<30 | non-occluder<<29 | prim, n_u, n_v, n_d), B = (a_u, a_v, b_nu, b_nv),
@@ -417,10 +363,9 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 							} else {
 								float ts;
 								if (sphere_intersect(ctr, rad, V3(ox, oy, oz), V3(dx, dy, dz), mint, maxt, ts)) {
-									const uint32_t tied = TIE ? ((ts == best_t && prim != best_prim) ? 0x80000000u : (best_shape & 0x80000000u)) : 0u;
 									maxt = ts;
 									best_t = ts; best_u = 0.0f; best_v = 0.0f; best_prim = prim;
-									best_shape = leaf_tail(sc, e, 1)->z | tied;
+									best_shape = leaf_tail(sc, e, 1)->z;
 								}
 							}
 						}
@@ -430,14 +375,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 						const float d_u = k0 ? dy : (k1 ? dz : dx), d_v = k0 ? dz : (k1 ? dx : dy), d_k = k0 ? dx : (k1 ? dy : dz);
 						const float recip = 1.0f / (d_u * n_u + d_v * n_v + d_k);
 						const float t = (n_d - o_u * n_u - o_v * n_v - o_k) * recip;
-#if MG_TAIL_FILTER
-						// flagged entry (api.cpp: tailFilterFlag), exit axis one of the triangle's projection axes (not its k), plane point
-						// beyond the face by more than the margin: TriAccel::rayIntersect is certain to reject, the tail is not fetched
-						const bool beyond = (MG_TAIL_FILTER == 1 || MODE != 0) && (A.x & 0x10000000u) && ((A.x ^ fAxisHi) & 0xC0000000u) != 0u && (fO + t * fD) - fS > sc.tail_margin;
-						if (ok && !(t < mint || t > maxt) && !beyond) {
-#else
 						if (ok && !(t < mint || t > maxt)) {
-#endif
 							const uint4 B = ld_stream<2>(leaf_tail(sc, e, 0));
 							const uint4 C = ld_stream<2>(leaf_tail(sc, e, 1));         // c_nu, c_nv, shape index, -
 							if (COUNT) { g_tail += 2u; rec_add(kReqLeaf, kLeafStride * e + 1u); rec_add(kReqLeaf, kLeafStride * e + 2u); }
@@ -451,9 +389,8 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 							const float v = hu * c_nu + hv * c_nv;
 							if (u >= 0 && v >= 0 && u + v <= 1.0f) {
 								if (MODE != 0) hitShadow = true;
-								const uint32_t tied = TIE ? ((t == best_t && prim != best_prim) ? 0x80000000u : (best_shape & 0x80000000u)) : 0u;
 								maxt = t;      // a later hit with equal t replaces this one (t > maxt rejects)
-								best_t = t; best_u = u; best_v = v; best_prim = prim; best_shape = C.z | tied;
+								best_t = t; best_u = u; best_v = v; best_prim = prim; best_shape = C.z;
 							}
 						}
 						if (kMbox) *mslot = prim;         // (re)writing an entry that is already there changes nothing
@@ -485,7 +422,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 							ex_node = kNullNode; ex_ref = kSentinel;
 						} else {
 							// the exit point is a function of (parent node, ray): rebuilt with the reference's formulas (sahkdtree3.h:233,248-249)
-							const uint2 pn = load_node(MG_TAIL_FILTER ? ((ref & 0x3FFFFFFFu) >> 1) : (ref >> 1));
+							const uint2 pn = load_node(ref >> 1);
 							const int axis = (int) (pn.x & 3u);
 							const float split = __uint_as_float(pn.y);
 							ex_node = (pn.x >> 2) + (ref & 1u);
@@ -519,13 +456,12 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 	}
 }
 
-template <int MODE, bool COUNT, bool BIN, bool TIE = false>
+template <int MODE, bool COUNT, bool BIN>
 __global__ __launch_bounds__(kTraceBlock, trace_waves_per_simd(MODE)) void k_trace(DTraceScene sc, DPaths ps, DQueues q,
                                                           const uint32_t *queue, uint32_t n_host, const uint32_t *n_dev) {
-	constexpr uint32_t kTop = TIE ? kTopPairsTie : kTopPairs;
 	__shared__ uint32_t s_stack[kStackLDS][kTraceBlock];
-	__shared__ uint32_t s_mbox[((MODE == 0 && !TIE) || COUNT) ? 8 : 1][kTraceBlock];
-	__shared__ uint4 s_top[kTop ? kTop : 1];
+	__shared__ uint32_t s_mbox[(MODE == 0 || COUNT) ? 8 : 1][kTraceBlock];
+	__shared__ uint4 s_top[kTopPairs ? kTopPairs : 1];
 	// the number of rays: known to the host, or left in device memory by the kernel that filled the queue
 	const uint32_t n = n_dev ? (uint32_t) __builtin_amdgcn_readfirstlane((int) *n_dev) : n_host;
 	const TracePlan plan = trace_plan(n, MODE, q);
@@ -537,35 +473,12 @@ __global__ __launch_bounds__(kTraceBlock, trace_waves_per_simd(MODE)) void k_tra
 	}
 	const uint32_t first = (blockIdx.x * (kTraceBlock / 64u) + (threadIdx.x >> 6)) * plan.batch;
 	const uint32_t stride = plan.blocks * (kTraceBlock / 64u) * plan.batch;      // queue entries per round of the grid
-	if (kTop) {
-		// the device tree is padded to at least 2 * kTopPairsMax nodes (mtsgpu_upload_scene)
-		for (uint32_t t = threadIdx.x; t < kTop; t += kTraceBlock) s_top[t] = reinterpret_cast<const uint4 *>(sc.nodes)[t];
-		__syncthreads();
-	}
-	trace_body<MODE, COUNT, BIN, TIE>(sc, ps, q, plan, queue, n, first, stride, s_stack, s_mbox, s_top);
-}
-
-// ONE persistent launch per bounce (host-driven bounces, knob "merged"): its waves drain the closest-hit
-// queue of bounce b + 1 and then the any-hit queue of bounce b -- legal because the any-hit kernel only parks direct-light
-// terms, so neither queue depends on the other -- so that the waves that run out of closest-hit rays go on with shadow rays
-// instead of idling through the 0.3-0.7 ms in which the launch's longest rays finish alone.  One footprint: the closest-hit
-// kernel's (80 VGPRs, 52 KB of LDS, 3 workgroups per CU), which the any-hit phase then runs at too (6 waves per SIMD
-// instead of 8, no mailbox).  Each phase deals its queue exactly as the separate launches do (own plan, own counter set).
-__global__ __launch_bounds__(kTraceBlock, trace_waves_per_simd(0)) void k_trace_pair(DTraceScene sc, DPaths ps, DQueues qc, DQueues qs,
-                                                                                    const uint32_t *queue_c, uint32_t n_c, const uint32_t *queue_s, uint32_t n_s) {
-	__shared__ uint32_t s_stack[kStackLDS][kTraceBlock];
-	__shared__ uint32_t s_mbox[8][kTraceBlock];
-	__shared__ uint4 s_top[kTopPairs ? kTopPairs : 1];
-	const TracePlan plan_c = trace_plan(n_c, 0, qc), plan_s = trace_plan(n_s, 1, qs);
 	if (kTopPairs) {
+		// the device tree is padded to at least kTopNodes nodes (mtsgpu_upload_scene)
 		for (uint32_t t = threadIdx.x; t < kTopPairs; t += kTraceBlock) s_top[t] = reinterpret_cast<const uint4 *>(sc.nodes)[t];
 		__syncthreads();
 	}
-	const uint32_t wave = blockIdx.x * (kTraceBlock / 64u) + (threadIdx.x >> 6);
-	if (blockIdx.x < plan_c.blocks)
-		trace_body<0, false, true>(sc, ps, qc, plan_c, queue_c, n_c, wave * plan_c.batch, plan_c.blocks * (kTraceBlock / 64u) * plan_c.batch, s_stack, s_mbox, s_top);
-	if (blockIdx.x < plan_s.blocks)
-		trace_body<1, false, false>(sc, ps, qs, plan_s, queue_s, n_s, wave * plan_s.batch, plan_s.blocks * (kTraceBlock / 64u) * plan_s.batch, s_stack, s_mbox, s_top);
+	trace_body<MODE, COUNT, BIN>(sc, ps, q, plan, queue, n, first, stride, s_stack, s_mbox, s_top);
 }
 
 // Device-driven bounces: the per-bin views k_shade needs, from the shard counters the closest-hit launch left in `cur`
@@ -592,7 +505,7 @@ __global__ __launch_bounds__(256) void k_prep(const uint32_t *cur, uint32_t *nex
 	}
 }
 
-template <int MODE, bool COUNT, bool BIN, bool TIE = false>
+template <int MODE, bool COUNT, bool BIN>
 static void launch_trace_t(hipStream_t s, const DScene &sc, const DPaths &ps, const DQueues &q, const uint32_t *queue, uint32_t n,
                            const uint32_t *n_dev) {
 	// persistent grid: enough workgroups to fill every CU, never more than there are rays (trace_plan); when only the
@@ -606,36 +519,24 @@ static void launch_trace_t(hipStream_t s, const DScene &sc, const DPaths &ps, co
 		blocks = std::min<unsigned>(blocks_for(n, minBatch * (kTraceBlock / 64)), q.n_cus * perCu);
 	}
 	if (!blocks) return;
-	hipLaunchKernelGGL((k_trace<MODE, COUNT, BIN, TIE>), dim3(blocks), dim3(kTraceBlock), 0, s, trace_scene(sc), ps, q, queue, n, n_dev);
+	hipLaunchKernelGGL((k_trace<MODE, COUNT, BIN>), dim3(blocks), dim3(kTraceBlock), 0, s, trace_scene(sc), ps, q, queue, n, n_dev);
 }
 
 void launch_trace(hipStream_t s, int mode, bool count, bool bin, const DScene &sc, const DPaths &ps,
-                  const DQueues &q, const uint32_t *queue, uint32_t n, bool coherent, const uint32_t *n_dev, bool tie) {
+                  const DQueues &q, const uint32_t *queue, uint32_t n, bool coherent, const uint32_t *n_dev) {
 	if (!n) return;
 	DQueues qq = q;
 	qq.coherent = coherent ? 1u : 0u;
 	if (n_dev)
 		qq.force_static = 1u;        // no dynamically claimed batches: the material-queue segments cannot overflow then
 	if (mode == 0) {
-		if (bin) { if (count) launch_trace_t<0, true, true>(s, sc, ps, qq, queue, n, n_dev); else if (tie) launch_trace_t<0, false, true, true>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<0, false, true>(s, sc, ps, qq, queue, n, n_dev); }
+		if (bin) { if (count) launch_trace_t<0, true, true>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<0, false, true>(s, sc, ps, qq, queue, n, n_dev); }
 		else     { if (count) launch_trace_t<0, true, false>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<0, false, false>(s, sc, ps, qq, queue, n, n_dev); }
 	} else if (mode == 1) {
 		if (count) launch_trace_t<1, true, false>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<1, false, false>(s, sc, ps, qq, queue, n, n_dev);
 	} else {
 		if (count) launch_trace_t<2, true, false>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<2, false, false>(s, sc, ps, qq, queue, n, n_dev);
 	}
-}
-
-void launch_trace_pair(hipStream_t s, const DScene &sc, const DPaths &ps, const DQueues &qc, const uint32_t *queue_c, uint32_t n_c, bool coherent_c,
-                       const DQueues &qs, const uint32_t *queue_s, uint32_t n_s, bool coherent_s) {
-	DQueues a = qc, b = qs;
-	a.coherent = coherent_c ? 1u : 0u; b.coherent = coherent_s ? 1u : 0u;
-	// the any-hit phase lives in the closest-hit kernel's footprint: 3 workgroups per CU
-	const uint32_t perCu = trace_blocks_per_cu(0);
-	if (!b.tune_blocks_per_cu || b.tune_blocks_per_cu > perCu) b.tune_blocks_per_cu = perCu;
-	const unsigned blocks = std::max(trace_plan(n_c, 0, a).blocks, trace_plan(n_s, 1, b).blocks);
-	if (!blocks) return;
-	hipLaunchKernelGGL(k_trace_pair, dim3(blocks), dim3(kTraceBlock), 0, s, trace_scene(sc), ps, a, b, queue_c, n_c, queue_s, n_s);
 }
 
 void launch_prep(hipStream_t s, const uint32_t *cur, uint32_t *next_set, BinView *views_dev, uint32_t bin_seg_cap,

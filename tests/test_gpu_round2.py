@@ -298,8 +298,9 @@ def test_overflow_retry_and_tuning_knobs_do_not_change_results(gpu_lib, mts, orc
         it.clear_film(); assert it.render()
         assert it.stats()["bin_overflow_retries"] == 0
         assert np.array_equal(it.film().view(np.uint32), ref.view(np.uint32)), knobs
-    with pytest.raises(mts.MtsGpuError):
-        it.set_tuning(no_such_knob=1)
+    for knob in ("no_such_knob", "mailbox_free", "merged", "overlap", "overlap_delay_us"):     # the last four: removed experiments
+        with pytest.raises(mts.MtsGpuError):
+            it.set_tuning(**{knob: 1})
 
 
 def test_malformed_trees_are_refused(gpu_lib, mts):

@@ -77,53 +77,26 @@ def test_group_rccl_reduce_equals_the_ordered_sum_on_eight_gpus(gpu_lib, mts):
     assert one.render() and np.array_equal(one.film().view(np.uint32), a.view(np.uint32))
 
 
-def test_exact_tail_filter_variant_matches_the_oracle(gpu_lib, mts, orc, tmp_path):
-    """the record-tail filter build of the traversal kernels (tools/build_variant.sh tf -DMG_TAIL_FILTER=1; not the product:
-    it is time-neutral, profiles/r06g_*) skips a quarter of the record tails and must change nothing: the film of a child
-    process that loads the variant equals the oracle's bit for bit.  Skipped when the variant library has not been built"""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "mitsuba-renderer_amd", "libmtsgpu_tf.so")
-    if not os.path.exists(lib):
-        pytest.skip("libmtsgpu_tf.so not built")
-    out = str(tmp_path / "film.npy")
-    code = ("import sys, numpy as np; sys.path.insert(0, %r); import _pkgload; pkg = _pkgload.load(); "
-            "sd = pkg.scenes.cornell_c5(sphere_subdiv=3); it = pkg.MIPathTracer(maxDepth=12); "
-            "it.preprocess(pkg.Scene(sd), pkg.PerspectiveCamera.for_description(sd, 96, 96), sampler='ldsampler', sampleCount=16, seed=11); "
-            "assert it.render(); assert pkg.lib().mtsgpu_source_hash; np.save(%r, it.film())") % (root, out)
-    env = dict(os.environ, MTSGPU_LIB=lib)
-    r = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    sd = mts.scenes.cornell_c5(sphere_subdiv=3)
-    oscene = orc.FlatScene(sd)                              # kept alive: the oracle's scene lives as long as this object
-    ofilm, _ = orc.render(oscene.scene, orc.make_camera(sd, 96, 96),
-                          orc.render_params(12, sampler=mts.abi.SAMPLER_LD_KEYED, spp=16, seed=11))
-    assert np.array_equal(np.load(out).view(np.uint32), ofilm.view(np.uint32))
-
-
-def test_traversal_launch_orders_do_not_change_the_film(gpu_lib, mts, orc):
-    """host-driven bounces with the any-hit launch of a bounce in front of / behind the next closest-hit launch on a second
-    stream (overlap = 1 / 2) and inside it (merged = 1: k_trace_pair, one launch per bounce; also when that launch is repeated
-    with static dealing): the any-hit kernel only parks direct-light terms, so every order gives the oracle's film"""
+def test_host_driven_bounces_match_the_oracle_with_retry_and_ragged_passes(gpu_lib, mts, orc):
+    """host-driven bounces (one stream: the any-hit launch of a bounce before the shading of the next one), also when every
+    first closest-hit launch is repeated with static dealing and when the frame takes ragged passes: the oracle's film"""
     sd, scene, oscene, cam, ocam, it, op = _setup(mts, orc, "c5_small", W=48, H=40, sampler="ldsampler", spp=16, max_depth=8)
     ofilm, _ = orc.render(oscene.scene, ocam, op)
-    for knobs in (dict(sync_free=0), dict(sync_free=0, overlap=1), dict(sync_free=0, overlap=2), dict(sync_free=0, overlap=2, overlap_delay_us=20),
-                  dict(sync_free=0, overlap=0, merged=1), dict(sync_free=0, merged=1, test_retry=1)):
+    for knobs in (dict(sync_free=0), dict(sync_free=0, test_retry=1)):
         it.set_tuning(**knobs)
         it.clear_film(); assert it.render()
         assert np.array_equal(it.film().view(np.uint32), ofilm.view(np.uint32)), knobs
-    it.set_tuning(sync_free=0, merged=1, test_retry=0)
+    it.set_tuning(sync_free=0, test_retry=0)
     it.set_options(max_paths=16 * 500)                     # ragged passes
     it.clear_film(); assert it.render()
     assert np.array_equal(it.film().view(np.uint32), ofilm.view(np.uint32))
 
 
-def test_closest_hit_without_the_mailbox_hands_ties_back(gpu_lib, mts, orc):
-    """host-driven bounces trace closest hits WITHOUT the hashed mailbox (one more level of the tree in its LDS instead); the one
-    case in which the mailbox decides a result -- two primitives tied in t: the later test wins, and which tests run depends on
-    the mailbox (sahkdtree3.h:130-144, :278-283) -- is detected per ray and traced again by the kernel with the mailbox.  A box whose
-    every wall exists twice, with different reflectances, makes every hit a tie: the film equals the oracle's bit for bit, with the
-    knob on and off, and the statistics show the rays that went back"""
+def test_tied_walls_match_the_oracle(gpu_lib, mts, orc):
+    """the one case in which the hashed mailbox decides a closest hit: two primitives tied in t -- the later test wins, and which
+    tests run depends on the mailbox (sahkdtree3.h:130-144, :278-283).  A box whose every wall exists twice, with different
+    reflectances, makes every hit a tie: the film equals the oracle's bit for bit with host-driven bounces (also with the retry
+    of the closest-hit launch) and with device-driven ones"""
     S = mts.scenes
     sd = S.SceneDescription("tied_walls")
     a, b = sd.lambertian(0.7, 0.2, 0.2), sd.lambertian(0.2, 0.7, 0.2)
@@ -141,18 +114,12 @@ def test_closest_hit_without_the_mailbox_hands_ties_back(gpu_lib, mts, orc):
     ofilm, _ = orc.render(oscene.scene, ocam, orc.render_params(6, sampler=mts.abi.SAMPLER_LD_KEYED, spp=spp, seed=5))
     it = mts.MIPathTracer(maxDepth=6)
     it.preprocess(scene, cam, sampler="ldsampler", sampleCount=spp, seed=5)
-    redone = {}
-    for knobs in (dict(sync_free=0, mailbox_free=1), dict(sync_free=0, mailbox_free=0), dict(sync_free=0, mailbox_free=1, test_retry=1),
-                  dict(sync_free=1, mailbox_free=1, test_retry=0)):
+    for knobs in (dict(sync_free=0), dict(sync_free=0, test_retry=1), dict(sync_free=1, test_retry=0)):
         it.set_tuning(**knobs)
         it.clear_film(); assert it.render()
         assert np.array_equal(it.film().view(np.uint32), ofilm.view(np.uint32)), knobs
-        redone[tuple(sorted(knobs.items()))] = it.stats()["rays_redone"]
-    vals = list(redone.values())
-    assert vals[0] > 0.3 * it.stats()["rays_closest"] and vals[1] == 0 and vals[3] == 0, redone      # device-driven bounces keep the mailbox
-    # an ordinary scene hands back next to nothing
+    # an ordinary scene
     sd2, scene2, oscene2, cam2, ocam2, it2, op2 = _setup(mts, orc, "c5_small", W=48, H=40, sampler="ldsampler", spp=16, max_depth=8)
-    it2.set_tuning(sync_free=0, mailbox_free=1)
+    it2.set_tuning(sync_free=0)
     assert it2.render()
     assert np.array_equal(it2.film().view(np.uint32), orc.render(oscene2.scene, ocam2, op2)[0].view(np.uint32))
-    assert it2.stats()["rays_redone"] < 1e-3 * it2.stats()["rays_closest"]

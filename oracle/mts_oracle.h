@@ -13,6 +13,14 @@
  *             Random == MT19937-64 against the published known answers
  *             (10000th output of seed 5489 = 9981545732273789042) and the
  *             values the survey measured from the reference.
+ *   binary64: f, pdf and sample(bRec, pdf, s) of every BSDF plugin and the
+ *             twosided wrapper, fresnel / fresnelConductor, and the radiance of
+ *             the point, spot, directional and collimated luminaires, against a
+ *             second, independent restatement in binary64 (tests/ref64.py),
+ *             within a stated multiple of 2^-23 times a conditioning factor,
+ *             exact zeros included (tests/test_closed_forms.py; the device in
+ *             tests/test_gpu_closed_forms.py).  Independent of this code, but
+ *             still a reading of the reference, not its output.
  *   unpinned: everything else ("parity unpinned").  The reference cannot be
  *             built in this image: every translation unit includes
  *             include/mitsuba/core/util.h:22 -> <boost/static_assert.hpp>

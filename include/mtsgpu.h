@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MTSGPU_ABI_VERSION 7
+#define MTSGPU_ABI_VERSION 8
 
 enum {
 	MTSGPU_OK = 0,
@@ -39,7 +39,7 @@ enum {
 	MTSGPU_ESTATE = -5    /* call sequence error (e.g. render before upload)    */
 };
 
-/* BSDF plugins on the path (src/bsdfs/{lambertian,dielectric,roughmetal,microfacet}.cpp) */
+/* BSDF plugins on the path (the plugins of src/bsdfs) */
 enum {
 	MTSGPU_BSDF_LAMBERTIAN = 0, /* params: [0..2] reflectance                                  */
 	MTSGPU_BSDF_DIELECTRIC = 1, /* params: [0] intIOR [1] extIOR [2..4] specRefl [5..7] specTrans */
@@ -55,11 +55,22 @@ enum {
 	                                       [3] extIOR [4..6] specularReflectance [7..9] specularTransmittance
 	                                       (src/bsdfs/roughglass.cpp)                                              */
 	MTSGPU_BSDF_DIFFTRANS = 7,  /* params: [0..2] transmittance                          (src/bsdfs/difftrans.cpp)  */
-	MTSGPU_BSDF_NTYPES = 8,
+	MTSGPU_BSDF_WARD = 8,       /* params: [0] model type (0 ward, 1 ward-duer, 2 balanced) [1] alphaX [2] alphaY [3] kd [4] ks
+	                                       [5] specularSamplingWeight [6] diffuseSamplingWeight [7..9] diffuseRefl
+	                                       [10..12] specRefl (values after Ward::configure, src/bsdfs/ward.cpp:118-136).
+	                                       alphaX != alphaY needs a tangent frame: accepted on spheres (dpdu / dpdv,
+	                                       sphere.cpp:136-178), refused on triangle meshes, which carry no texture
+	                                       coordinates here (as trimesh.cpp:547-556 refuses them)                      */
+	MTSGPU_BSDF_COMPOSITE = 9,  /* params: [0] child count n, 1..MTSGPU_COMPOSITE_MAX [1..n] weights (>= 0)
+	                                       [1+n..2n] the children's indices into the scene's BSDF table, stored as floats
+	                                       (exact below 2^24).  Children are non-delta entries of any other type, each
+	                                       with or without MTSGPU_BSDF_TWOSIDED      (src/bsdfs/composite.cpp)         */
+	MTSGPU_BSDF_NTYPES = 10,
 	/* OR-ed into bsdf_type: the BSDF is wrapped in a `twosided` adapter (src/bsdfs/twosided.cpp) */
 	MTSGPU_BSDF_TWOSIDED = 0x100
 };
 #define MTSGPU_BSDF_NPARAMS 16
+#define MTSGPU_COMPOSITE_MAX 7   /* children of a composite: 1 + 2 * 7 of the 16 slots */
 
 /* Luminaire plugins on the path (src/luminaires/{area,constant}.cpp) */
 enum {
@@ -402,6 +413,11 @@ int  mtsgpu_random_values(mtsgpu_ctx *ctx, int op, uint64_t seed, uint64_t arg, 
  * procedure of the reference (src/tests/test_chisquare.cpp:299-420 with the BSDFs of data/tests/test_bsdf.xml) runs
  * against these values, i.e. against the code k_shade executes, with no CPU restatement in between. */
 int  mtsgpu_bsdf_eval(mtsgpu_ctx *ctx, uint32_t bsdf_type, const float *params, int op, uint32_t n, const float *queries, float *out);
+/* The same operations, query and output layout for entry `index` of a BSDF table types[n_bsdfs], params[n_bsdfs][16] (what
+ * mtsgpu_scene carries; checked as mtsgpu_upload_scene checks it).  A composite reaches its children through the table, so
+ * mtsgpu_bsdf_eval returns MTSGPU_EINVAL for MTSGPU_BSDF_COMPOSITE and this call evaluates it. */
+int  mtsgpu_bsdf_eval_table(mtsgpu_ctx *ctx, uint32_t n_bsdfs, const uint32_t *types, const float *params, uint32_t index, int op,
+                            uint32_t n, const float *queries, float *out);
 /* MIPathTracer::Li for explicit camera samples: in [n][3] u32 = pixel x, y, sample index;
  * out [n][8] f32 = Li rgb, alpha, raster x, raster y, depth, unused */
 int  mtsgpu_li_samples(mtsgpu_ctx *ctx, const uint32_t *pix_samples, uint32_t n, float *out);

@@ -14,14 +14,15 @@
  *
  * What of a Mitsuba scene reaches the GPU (everything else stops with an error message that names the class):
  *   shapes      every TriMesh (obj, ply, serialized, ...: TriMesh accessors), `sphere`
- *   BSDFs       lambertian, dielectric, roughmetal, microfacet, mirror, phong, roughglass, difftrans, twosided(any of them);
+ *   BSDFs       lambertian, dielectric, roughmetal, microfacet, mirror, phong, roughglass, difftrans, ward (anisotropic on
+ *               spheres only), twosided(any of them), composite(up to 7 of the non-delta ones, each with or without twosided);
  *               constant reflectances only (textures need uv partials and a MIPMap lookup per hit: out of scope)
  *   luminaires  area (on meshes and spheres), constant, point, spot (no projection texture), directional, collimated, envmap
  *   cameras     perspective (pinhole and thin lens), orthographic
  *   samplers    independent, ldsampler, stratified (keyed forms), halton, hammersley
  *   films       any (the result goes back as ImageBlocks); reconstruction filter = the film's own TabulatedFilter
- * Private members that block more: Texture2D bitmaps (BitmapTexture::m_mipmap has no accessor), `ward` and `composite`
- * BSDFs and every shape other than TriMesh / Sphere (not implemented by the library, not blocked by access), media and
+ * Private members that block more: Texture2D bitmaps (BitmapTexture::m_mipmap has no accessor); every shape
+ * other than TriMesh / Sphere (not implemented by the library, not blocked by access), media and
  * subsurface integrators (path.cpp ignores media, :31-34).
  */
 #ifndef MTSGPU_GPUCOMMON_H
@@ -357,16 +358,13 @@ private:
 		if (!bsdf) return -1;
 		std::map<const BSDF *, int>::const_iterator it = bsdfIndex.find(bsdf);
 		if (it != bsdfIndex.end()) return it->second;
-		const int index = (int) bsdfType.size();
-		bsdfIndex[bsdf] = index;
-		bsdfParams.insert(bsdfParams.end(), MTSGPU_BSDF_NPARAMS, 0.0f);
-		bsdfType.push_back(0);
+		/* one entry, or for a composite its children first and then the composite itself, whose block points at them */
 		ref<MemoryStream> st = serializedBSDF(bsdf);
 		std::string err;
-		uint32_t type = 0;
-		if (!mtsgpu_stream::parseBSDF<Float>(st->getData(), st->getSize(), &type, &bsdfParams[(size_t) MTSGPU_BSDF_NPARAMS * index], &err))
+		const int index = mtsgpu_stream::parseBSDFTable<Float>(st->getData(), st->getSize(), bsdfType, bsdfParams, &err);
+		if (index < 0)
 			SLog(EError, "gpupath: %s", err.c_str());
-		bsdfType[index] = type;
+		bsdfIndex[bsdf] = index;
 		return index;
 	}
 };

@@ -21,6 +21,7 @@
 #include <map>
 #include <set>
 #include <string>
+#include <vector>
 #include <stdint.h>
 
 namespace mtsgpu_stream {
@@ -42,6 +43,7 @@ public:
 
 	uint32_t readUInt() { uint32_t v = 0; raw(&v, 4); return v; }                      /* stream.cpp:275-281 */
 	int32_t readInt() { int32_t v = 0; raw(&v, 4); return v; }
+	uint64_t readSize() { uint64_t v = 0; raw(&v, 8); return v; }                       /* stream.h:267: readULong */
 	bool readBool() { uint8_t v = 0; raw(&v, 1); return v != 0; }                     /* stream.h:279 */
 	FloatT readFloat() { FloatT v = 0; raw(&v, sizeof(FloatT)); return v; }
 	std::string readString() {                                                        /* stream.cpp:391-402 */
@@ -118,9 +120,14 @@ public:
 		skipReference();
 		return r.readFloat();
 	}
-	/* the nested BRDF of a `twosided` adapter: positions the reader on its fields */
+	/* the nested BRDF of a `twosided` adapter or of a composite: positions the reader on its fields */
 	void enterNestedBSDF() {
-		if (!openObject(m_className)) { r.fail("twosided BRDF without a nested BRDF"); return; }
+		const std::string outer = m_className;
+		if (!r.ok()) return;
+		if (!openObject(m_className)) {
+			r.fail(outer == "TwoSidedBRDF" ? "twosided BRDF without a nested BRDF" : outer + ": a nested BSDF is missing or was written before (shared instances are not supported)");
+			return;
+		}
 		skipReference(); r.readString();
 	}
 	ByteReader<FloatT> r;
@@ -142,15 +149,8 @@ private:
 	std::string m_className;
 };
 
-/* One BSDF instance -> its type word (MTSGPU_BSDF_* | MTSGPU_BSDF_TWOSIDED) and parameter block P[MTSGPU_BSDF_NPARAMS]
- * (zeroed by the caller).  Returns false with `err` set for classes and textures that are not on this path. */
-template <typename FloatT> inline bool parseBSDF(const uint8_t *data, size_t size, uint32_t *type, float *P, std::string *err) {
-	BSDFStream<FloatT> rd(data, size);
-	uint32_t flags = 0;
-	if (rd.className() == "TwoSidedBRDF") {                                  /* twosided.cpp:52-56: the nested BRDF follows */
-		flags |= MTSGPU_BSDF_TWOSIDED;
-		rd.enterNestedBSDF();
-	}
+/* The fields of the class the reader stands on (after BSDF::serialize's own), for every class with ONE parameter block */
+template <typename FloatT> inline void parseBSDFFields(BSDFStream<FloatT> &rd, uint32_t flags, uint32_t *type, float *P) {
 	const std::string cls = rd.className();
 	if (cls == "Lambertian") {                                               /* lambertian.cpp:137-141 */
 		*type = MTSGPU_BSDF_LAMBERTIAN | flags;
@@ -188,12 +188,88 @@ template <typename FloatT> inline bool parseBSDF(const uint8_t *data, size_t siz
 	} else if (cls == "DiffuseTransmitter") {                                /* difftrans.cpp:142-146 */
 		*type = MTSGPU_BSDF_DIFFTRANS | flags;
 		rd.readConstantTexture("transmittance", P);
+	} else if (cls == "Ward") {                                              /* ward.cpp:299-311 (values after configure()) */
+		*type = MTSGPU_BSDF_WARD | flags;
+		const uint32_t model = rd.r.readUInt();                              /* EWard 0, EWardDuer 1, EBalanced 2 (:45-52) = the ABI's codes */
+		if (model > 2 && rd.r.ok()) rd.r.fail("Ward: unknown model type");
+		P[0] = (float) model;
+		rd.readConstantTexture("diffuseReflectance", P + 7);
+		rd.readConstantTexture("specularReflectance", P + 10);
+		for (int k = 1; k <= 6; ++k) P[k] = (float) rd.r.readFloat();        /* alphaX, alphaY, kd, ks, specular / diffuse sampling weight */
 	} else {
 		rd.r.fail("BSDF class " + cls + " is not on this path (lambertian, dielectric, roughmetal, microfacet, mirror, phong, "
-		          "roughglass, difftrans and the twosided adapter are)");
+		          "roughglass, difftrans, ward, composite and the twosided adapter are)");
 	}
-	if (!rd.r.ok()) { if (err) *err = rd.r.error(); return false; }
+}
+
+/* One BSDF instance -> its type word (MTSGPU_BSDF_* | MTSGPU_BSDF_TWOSIDED) and parameter block P[MTSGPU_BSDF_NPARAMS]
+ * (zeroed by the caller).  Returns false with `err` set for classes and textures that are not on this path, and for a
+ * Composite, which is more than one block: parseBSDFTable reads those. */
+template <typename FloatT> inline bool parseBSDF(const uint8_t *data, size_t size, uint32_t *type, float *P, std::string *err) {
+	BSDFStream<FloatT> rd(data, size);
+	uint32_t flags = 0;
+	if (rd.className() == "TwoSidedBRDF") {                                  /* twosided.cpp:52-56: the nested BRDF follows */
+		flags |= MTSGPU_BSDF_TWOSIDED;
+		rd.enterNestedBSDF();
+	}
+	if (rd.className() == "Composite") rd.r.fail("a Composite BSDF fills several table entries: read it with parseBSDFTable");
+	else parseBSDFFields(rd, flags, type, P);
+	if (!rd.r.ok()) { if (err) *err = rd.r.error() + " (while reading a " + rd.className() + ")"; return false; }
 	return true;
+}
+
+/* One BSDF instance -> entries appended to a BSDF table (types[i], params[16 i ..]); returns the index of the instance's
+ * own entry, or -1 with `err` set.  Every class but Composite appends one entry.  Composite::serialize (composite.cpp:81-89)
+ * writes the child count (a size_t: 64 bits, stream.h:180) and then, per child, its weight and the nested BSDF instance;
+ * the children are appended first, in their order, then the composite with the block of include/mtsgpu.h: [0] n,
+ * [1..n] weights, [1+n..2n] the children's table indices as floats.  What the device cannot run is refused here with the
+ * reason: more than MTSGPU_COMPOSITE_MAX children or none, a negative weight (composite.cpp:45-46), a nested composite, a
+ * delta child (dielectric, mirror), a child instance that was written before (a bare id: its fields are not in reach). */
+template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t size, std::vector<uint32_t> &types, std::vector<float> &params,
+                                                     std::string *err) {
+	BSDFStream<FloatT> rd(data, size);
+	const size_t first = types.size();
+	uint32_t flags = 0;
+	if (rd.className() == "TwoSidedBRDF") { flags |= MTSGPU_BSDF_TWOSIDED; rd.enterNestedBSDF(); }
+	int own = -1;
+	if (rd.className() != "Composite") {
+		types.push_back(0); params.insert(params.end(), MTSGPU_BSDF_NPARAMS, 0.0f);
+		parseBSDFFields(rd, flags, &types.back(), &params[params.size() - MTSGPU_BSDF_NPARAMS]);
+		own = (int) types.size() - 1;
+	} else {
+		const uint64_t n = rd.r.readSize();
+		if (rd.r.ok() && (n < 1 || n > MTSGPU_COMPOSITE_MAX))
+			rd.r.fail("a Composite with " + std::to_string((unsigned long long) n) + " children: between 1 and " + std::to_string(MTSGPU_COMPOSITE_MAX) + " are supported");
+		float block[MTSGPU_BSDF_NPARAMS] = { 0 };
+		block[0] = (float) n;
+		for (uint64_t i = 0; i < n && rd.r.ok(); ++i) {
+			const float w = (float) rd.r.readFloat();
+			if (rd.r.ok() && !(w >= 0.0f)) rd.r.fail("Composite: invalid BRDF weight (composite.cpp:45-46)");
+			block[1 + i] = w;
+			rd.enterNestedBSDF();                                            /* fails on NULL and on an instance written before */
+			uint32_t childFlags = 0;
+			if (rd.r.ok() && rd.className() == "TwoSidedBRDF") { childFlags |= MTSGPU_BSDF_TWOSIDED; rd.enterNestedBSDF(); }
+			if (!rd.r.ok()) break;
+			if (rd.className() == "Composite") { rd.r.fail("Composite: nested composites are not supported"); break; }
+			if (rd.className() == "Dielectric" || rd.className() == "Mirror") {
+				rd.r.fail("Composite: child " + rd.className() + " is a delta BSDF (a composite would need fDelta / pdfDelta): not supported"); break;
+			}
+			types.push_back(0); params.insert(params.end(), MTSGPU_BSDF_NPARAMS, 0.0f);
+			parseBSDFFields(rd, childFlags, &types.back(), &params[params.size() - MTSGPU_BSDF_NPARAMS]);
+			block[1 + n + i] = (float) (types.size() - 1);
+		}
+		if (rd.r.ok()) {
+			types.push_back(MTSGPU_BSDF_COMPOSITE | flags);
+			params.insert(params.end(), block, block + MTSGPU_BSDF_NPARAMS);
+			own = (int) types.size() - 1;
+		}
+	}
+	if (!rd.r.ok()) {
+		types.resize(first); params.resize(first * MTSGPU_BSDF_NPARAMS);
+		if (err) *err = rd.r.error() + " (while reading a " + rd.className() + ")";
+		return -1;
+	}
+	return own;
 }
 
 /* ------------------------------------------------------------------------------------------------------------------

@@ -32,7 +32,7 @@ EXPORTS = [
     "mtsgpu_make_camera_crop", "mtsgpu_hbm_triad", "mtsgpu_sampler_values", "mtsgpu_random_values", "mtsgpu_set_tuning", "mtsgpu_gather_roof",
     "mtsgpu_create_multi", "mtsgpu_group_destroy", "mtsgpu_group_size", "mtsgpu_group_ctx", "mtsgpu_group_last_error",
     "mtsgpu_group_upload_scene", "mtsgpu_group_set_camera", "mtsgpu_group_set_integrator", "mtsgpu_group_set_sampler",
-    "mtsgpu_group_set_rfilter", "mtsgpu_group_render", "mtsgpu_group_last_reduce_kind", "mtsgpu_group_rccl_ranks", "mtsgpu_group_reduce_note", "mtsgpu_bsdf_eval", "mtsgpu_replay_roof", "mtsgpu_group_set_tuning",
+    "mtsgpu_group_set_rfilter", "mtsgpu_group_render", "mtsgpu_group_last_reduce_kind", "mtsgpu_group_rccl_ranks", "mtsgpu_group_reduce_note", "mtsgpu_bsdf_eval", "mtsgpu_bsdf_eval_table", "mtsgpu_replay_roof", "mtsgpu_group_set_tuning",
 ]
 
 
@@ -162,6 +162,7 @@ def lib():
     L.mtsgpu_sampler_values.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, f32p]
     L.mtsgpu_random_values.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.mtsgpu_bsdf_eval.argtypes = [vp, C.c_uint32, f32p, C.c_int, C.c_uint32, f32p, f32p]
+    L.mtsgpu_bsdf_eval_table.argtypes = [vp, C.c_uint32, u32p, f32p, C.c_uint32, C.c_int, C.c_uint32, f32p, f32p]
     L.mtsgpu_hbm_triad.argtypes = [C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
     L.mtsgpu_replay_roof.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_double)]
     L.mtsgpu_create_multi.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
@@ -437,6 +438,21 @@ class MIPathTracer:
         out = np.zeros((n, 8), dtype=np.float32)
         self._chk(lib().mtsgpu_bsdf_eval(self._ctx, int(bsdf_type), abi.ptr(P, abi.f32p), int(op), n, abi.ptr(q, abi.f32p),
                                          abi.ptr(out, abi.f32p)), "bsdf_eval")
+        return out
+
+    def bsdf_eval_table(self, types, params, index, op, wi, aux):
+        """the same read-out for entry `index` of a BSDF table (mtsgpu_bsdf_eval_table): types [n_bsdfs], params
+        [n_bsdfs][16] as a scene description holds them; a composite reads its children there"""
+        aux = np.atleast_2d(np.asarray(aux, dtype=np.float32))
+        n = aux.shape[0]
+        q = np.zeros((n, 6), dtype=np.float32)
+        q[:, :3] = np.asarray(wi, dtype=np.float32).reshape(-1, 3)
+        q[:, 3:3 + aux.shape[1]] = aux
+        T = np.ascontiguousarray(types, dtype=np.uint32).reshape(-1)
+        P = np.ascontiguousarray(params, dtype=np.float32).reshape(len(T), abi.BSDF_NPARAMS)
+        out = np.zeros((n, 8), dtype=np.float32)
+        self._chk(lib().mtsgpu_bsdf_eval_table(self._ctx, len(T), abi.ptr(T, abi.u32p), abi.ptr(P, abi.f32p), int(index), int(op), n,
+                                               abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)), "bsdf_eval_table")
         return out
 
     def li_samples(self, pix_samples):

@@ -5,9 +5,11 @@ against the sizes the C compiler reports (mtsgpu_abi_sizeof)."""
 import ctypes as C
 import numpy as np
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 BSDF_LAMBERTIAN, BSDF_DIELECTRIC, BSDF_ROUGHMETAL, BSDF_MICROFACET, BSDF_MIRROR, BSDF_PHONG, BSDF_ROUGHGLASS, BSDF_DIFFTRANS = 0, 1, 2, 3, 4, 5, 6, 7
+BSDF_WARD, BSDF_COMPOSITE, BSDF_NTYPES = 8, 9, 10
 BSDF_TWOSIDED = 0x100
+COMPOSITE_MAX = 7
 BSDF_NPARAMS = 16
 LUM_AREA, LUM_CONSTANT, LUM_POINT, LUM_DIRECTIONAL, LUM_SPOT, LUM_ENVMAP, LUM_COLLIMATED = 0, 1, 2, 3, 4, 5, 6
 LUM_NPARAMS = 32

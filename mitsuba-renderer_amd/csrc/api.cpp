@@ -98,9 +98,9 @@ bool samplerHasTables(const mtsgpu_ctx *c) {
 	return c->samplerKind == MTSGPU_SAMPLER_LD_KEYED || c->samplerKind == MTSGPU_SAMPLER_STRATIFIED_KEYED;
 }
 
-// Device bytes ensurePaths() allocates per path of a pass: the 128-byte record, the shadow ray (3 x 16), the nine material
+// Device bytes ensurePaths() allocates per path of a pass: the 128-byte record, the shadow ray (3 x 16), the eleven material
 // bins sized for the all-in-one-bin case with a quarter of headroom (id 4 + hit 16 bytes per entry), the two next queues
-// (id 4 + ray 32 bytes each) and the shadow queue's ids -- about 480 bytes, 34 GB for the default pass of 72 M paths.
+// (id 4 + ray 32 bytes each) and the shadow queue's ids -- about 530 bytes, 38 GB for the default pass of 72 M paths.
 constexpr size_t kBytesPerPath = kPathSlots * 16 + 3 * 16 + (size_t) (kNumBins * (4 + 16) * 5 / 4) + 2 * (4 + 32) + 4 + 4;
 // Paths per pass when the caller set none (mtsgpu_set_options max_paths == 0): 72 M, or what 60 % of the free device memory
 // holds if that is less (the sampler tables, the film and the scene of a later upload need room too)
@@ -439,7 +439,12 @@ int runBouncesDevice(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatil
 			rc = timed(c->shadeEvents, c->shadeEvUsed, s1, 0); if (rc) return rc;
 			launch_prep(s1, set, prev, c->viewsDev, c->q.bin_seg_cap, c->devStats);
 			if (cfg.dr_mode == 0 && tuningOr(c, "shade_fused", 1) != 0) {
-				launch_shade_all(s1, c->dsc, c->paths, cfg, c->q, c->viewsDev, c->binMask & ((1u << kNumBins) - 1u), upper);
+				launch_shade_all(s1, c->dsc, c->paths, cfg, c->q, c->viewsDev, c->binMask & kShadeAllBins, upper);
+				// the bins the fused kernel leaves out (the composite), one launch each, only when the scene has them
+				BinView none{};
+				for (int bin = 0; bin < kNumBins; ++bin)
+					if (c->binMask & ~kShadeAllBins & (1u << bin))
+						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper);
 			} else {
 				BinView none{};
 				for (int bin = 0; bin < kNumBins; ++bin)
@@ -791,8 +796,14 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 	if (sc->shape_tri_offset[sc->n_shapes] != sc->n_tris) return fail(c, MTSGPU_EINVAL, "shape_tri_offset does not cover all triangles");
 	for (uint32_t t = 0; t < sc->n_tris; ++t)
 		if (sc->triaccel[12 * (size_t) t + 10] >= sc->n_shapes) return fail(c, MTSGPU_EINVAL, "TriAccel %u: shape index out of range", t);
-	for (uint32_t b = 0; b < sc->n_bsdfs; ++b)
-		if ((sc->bsdf_type[b] & ~(uint32_t) MTSGPU_BSDF_TWOSIDED) >= MTSGPU_BSDF_NTYPES) return fail(c, MTSGPU_EINVAL, "BSDF %u: unknown type", b);
+	{
+		const std::string why = checkBsdfTable(sc->n_bsdfs, sc->bsdf_type, sc->bsdf_params);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+		// an anisotropic BSDF needs a tangent frame: spheres have one (dpdu / dpdv), triangle meshes carry no texture coordinates
+		for (uint32_t s = 0; s < sc->n_shapes; ++s)
+			if (sc->shape_bsdf[s] >= 0 && !shapeHasTangentFrame(shapeType(s)) && bsdfIsAnisotropic(sc->bsdf_type, sc->bsdf_params, (uint32_t) sc->shape_bsdf[s]))
+				return fail(c, MTSGPU_EINVAL, "%s", anisotropicOnMeshMessage(s).c_str());
+	}
 	for (uint32_t l = 0; l < sc->n_lums; ++l) {
 		if (sc->lum_type[l] == MTSGPU_LUM_AREA) {
 			const int32_t s = sc->lum_shape[l];
@@ -1518,6 +1529,8 @@ int mtsgpu_bsdf_eval(mtsgpu_ctx *c, uint32_t bsdf_type, const float *params, int
 	if (!c || !params || !queries || !out) return fail(c, MTSGPU_EINVAL, "null argument");
 	if ((bsdf_type & 0xFFu) >= (uint32_t) MTSGPU_BSDF_NTYPES || (bsdf_type & ~(0xFFu | (uint32_t) MTSGPU_BSDF_TWOSIDED)) || op < 0 || op > 2)
 		return fail(c, MTSGPU_EINVAL, "bad BSDF type or operation");
+	if ((bsdf_type & 0xFFu) == (uint32_t) MTSGPU_BSDF_COMPOSITE)
+		return fail(c, MTSGPU_EINVAL, "a composite needs its children: use mtsgpu_bsdf_eval_table");
 	if (n == 0) return 0;
 	if (n > (1u << 24)) return fail(c, MTSGPU_EINVAL, "at most 2^24 query records per call");
 	HIPCHK(c, hipSetDevice(c->device));
@@ -1532,6 +1545,39 @@ int mtsgpu_bsdf_eval(mtsgpu_ctx *c, uint32_t bsdf_type, const float *params, int
 	if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, (size_t) n * 8 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
 	(void) hipFree(dQ); if (dOut) (void) hipFree(dOut);
+	if (e != hipSuccess) return fail(c, MTSGPU_EHIP, "BSDF read-out failed: %s", hipGetErrorString(e));
+	return 0;
+}
+
+int mtsgpu_bsdf_eval_table(mtsgpu_ctx *c, uint32_t n_bsdfs, const uint32_t *types, const float *params, uint32_t index, int op,
+                           uint32_t n, const float *queries, float *out) {
+	if (!c || !types || !params || !queries || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (index >= n_bsdfs || n_bsdfs > (1u << 24) || op < 0 || op > 2) return fail(c, MTSGPU_EINVAL, "bad BSDF index or operation");
+	const std::string why = checkBsdfTable(n_bsdfs, types, params);
+	if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+	if (n == 0) return 0;
+	if (n > (1u << 24)) return fail(c, MTSGPU_EINVAL, "at most 2^24 query records per call");
+	HIPCHK(c, hipSetDevice(c->device));
+	float *dQ = nullptr, *dOut = nullptr, *dP = nullptr;
+	uint32_t *dT = nullptr;
+	const size_t pBytes = (size_t) n_bsdfs * MTSGPU_BSDF_NPARAMS * sizeof(float), tBytes = (size_t) n_bsdfs * sizeof(uint32_t);
+	hipError_t e = hipMalloc((void **) &dQ, (size_t) n * 6 * sizeof(float));
+	if (e == hipSuccess) e = hipMalloc((void **) &dOut, (size_t) n * 8 * sizeof(float));
+	if (e == hipSuccess) e = hipMalloc((void **) &dP, pBytes);
+	if (e == hipSuccess) e = hipMalloc((void **) &dT, tBytes);
+	if (e == hipSuccess) e = hipMemcpyAsync(dQ, queries, (size_t) n * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(dP, params, pBytes, hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(dT, types, tBytes, hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) {
+		launch_bsdf_eval_table(c->stream, dT, dP, index, op, n, dQ, dOut);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, (size_t) n * 8 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (dQ) (void) hipFree(dQ);
+	if (dOut) (void) hipFree(dOut);
+	if (dP) (void) hipFree(dP);
+	if (dT) (void) hipFree(dT);
 	if (e != hipSuccess) return fail(c, MTSGPU_EHIP, "BSDF read-out failed: %s", hipGetErrorString(e));
 	return 0;
 }

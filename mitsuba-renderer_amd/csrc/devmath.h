@@ -87,6 +87,8 @@ HD void sincos_d(double x, double &s, double &c) {
 HD void dsincos(float x, float &s, float &c) { double sd, cd; sincos_d((double) x, sd, cd); s = (float) sd; c = (float) cd; }
 HD float dsin(float x) { float s, c; dsincos(x, s, c); return s; }
 HD float dcos(float x) { float s, c; dsincos(x, s, c); return c; }
+// std::tan (ward.cpp:223-224): the binary64 sine over the binary64 cosine of the same reduction, one rounding
+HD float dtan(float x) { if (x != x) return x; double s, c; sincos_d((double) x, s, c); return (float) (s / c); }
 
 HD float dexp(float x) {
 	const double LOG2E = 1.44269504088896338700e+00;
@@ -212,6 +214,7 @@ HD float datan2(float y, float x) {
 }
 
 HD float dpow4(float x) { double d = (double) x * (double) x; return (float) (d * d); }
+HD float dpow3(float x) { double d = (double) x; return (float) ((d * d) * d); }      // std::pow(x, 3) (ward.cpp:193)
 
 // binary64 exp / log (same reductions and polynomials as dexp / dlog) for pow
 HD double exp_d(double xd) {

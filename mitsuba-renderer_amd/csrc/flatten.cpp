@@ -96,6 +96,10 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 	fs.bsdfType.assign(d.bsdf_type, d.bsdf_type + d.n_bsdfs); fs.bsdfType.push_back(0);
 	fs.bsdfParams.assign(d.bsdf_params, d.bsdf_params + (size_t) MTSGPU_BSDF_NPARAMS * d.n_bsdfs);
 	fs.bsdfParams.resize(fs.bsdfParams.size() + MTSGPU_BSDF_NPARAMS, 0.0f);
+	{
+		const std::string why = checkBsdfTable(d.n_bsdfs, d.bsdf_type, d.bsdf_params);
+		if (!why.empty()) throw std::runtime_error("flatten: " + why);
+	}
 	fs.lumType.assign(d.lum_type, d.lum_type + nLums); fs.lumType.push_back(0);
 	fs.lumParams.assign(d.lum_params, d.lum_params + (size_t) MTSGPU_LUM_NPARAMS * nLums);
 	fs.lumParams.resize(fs.lumParams.size() + MTSGPU_LUM_NPARAMS, 0.0f);
@@ -113,6 +117,8 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 			throw std::runtime_error("flatten: mesh references a missing BSDF/luminaire");
 		fs.shapeTriOffset[s] = tbase;
 		fs.shapeBsdf[s] = m.bsdf;
+		if (m.bsdf >= 0 && !shapeHasTangentFrame((uint32_t) m.shape_type) && bsdfIsAnisotropic(d.bsdf_type, d.bsdf_params, (uint32_t) m.bsdf))
+			throw std::runtime_error("flatten: " + anisotropicOnMeshMessage(s));
 		fs.shapeLum[s] = m.lum;
 		if (m.lum >= 0) {
 			if (fs.lumShape[m.lum] >= 0 || fs.lumType[m.lum] != MTSGPU_LUM_AREA)

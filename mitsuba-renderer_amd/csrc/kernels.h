@@ -5,7 +5,7 @@
 
 namespace mg {
 
-constexpr int kNumBsdfTypes = 8;      // lambertian, dielectric, roughmetal, microfacet, mirror, phong, roughglass, difftrans
+constexpr int kNumBsdfTypes = 10;     // lambertian, dielectric, roughmetal, microfacet, mirror, phong, roughglass, difftrans, ward, composite
 constexpr int kNumBins = kNumBsdfTypes + 1;   // + "terminal" (miss / no BSDF)
 // Threads per traversal workgroup and resident workgroups per CU.  Round 3: 512 threads, 3 workgroups for closest-hit rays
 // (24 waves per CU, up to 80 VGPRs) and 4 for shadow rays (32 waves, 64 VGPRs), instead of 7 / 8 workgroups of 256: the
@@ -57,6 +57,9 @@ constexpr int kLumStride = 32;        // MTSGPU_LUM_NPARAMS
 constexpr int kCounterStride = 32;    // one 128-byte line per queue counter (atomics on one line serialise)
 constexpr int kBsdfNParams = 16;      // MTSGPU_BSDF_NPARAMS
 constexpr int kBinShards = 16;        // the closest-hit kernel appends to bins[b] through 16 independent segments
+// The bins k_shade_all shades.  The composite (bin 9) loops over its children and switches on their type: inside the fused
+// kernel that loop would raise the registers of every bin, so device-driven frames launch k_shade<9> next to it.
+constexpr uint32_t kShadeAllBins = ((1u << kNumBins) - 1u) & ~(1u << 9);
 constexpr int kNumCounters = kNumBins * kBinShards + 4;   // bins x shards, next, shadow, dynamic heads of the two traversal launches
 // Two sets of counters, used by alternate bounces: the shadow rays of bounce b are traced (second stream) while the
 // closest-hit launch of bounce b + 1 already fills the next set
@@ -206,7 +209,7 @@ struct DConfig {
 
 struct DQueues {
 	// per-material queues written by the closest-hit kernel: bin b = bins_base + b * bin_stride, kBinShards segments of
-	// bin_seg_cap entries each (one base pointer instead of nine keeps the kernels' scalar registers free)
+	// bin_seg_cap entries each (one base pointer instead of one per bin keeps the kernels' scalar registers free)
 	uint32_t *bins_base;
 	uint32_t bin_stride;
 	uint32_t bin_seg_cap;
@@ -319,6 +322,9 @@ size_t random_state_bytes();
 void launch_sampler_values(hipStream_t s, const DConfig &cfg, uint32_t pixel_key, uint32_t j, uint32_t n, int two_d, float *out);
 // BSDF::f (op 0), pdf (1), sample(bRec, pdf, sample) (2) for n query records [n][6] of one parameter block; out [n][8]
 void launch_bsdf_eval(hipStream_t s, uint32_t type, const float *params, int op, uint32_t n, const float *queries, float *out);
+// the same for entry `index` of a BSDF table in device memory, types[n_bsdfs] / params[n_bsdfs][16] (a composite reads its children there)
+void launch_bsdf_eval_table(hipStream_t s, const uint32_t *types, const float *params, uint32_t index, int op, uint32_t n,
+                            const float *queries, float *out);
 void launch_generate(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                      const uint32_t *pixel_list, uint32_t n_slots, const uint32_t *explicit_samples,
                      uint32_t n_paths, uint32_t *queue);

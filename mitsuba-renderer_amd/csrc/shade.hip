@@ -801,6 +801,74 @@ template <> struct Bsdf<7> {
 	}
 };
 
+// Ward (src/bsdfs/ward.cpp:142-285), parameters after Ward::configure (:118-136), through BSDF::sample(bRec, pdf, s)
+// (bsdf.cpp:37-48).  wi / wo are in the local frame, so alphaX != alphaY needs nothing here: the tangent comes from the shape.
+// P: [0] model type (0 ward, 1 ward-duer, 2 balanced) [1] alphaX [2] alphaY [3] kd [4] ks [5] specularSamplingWeight
+//    [6] diffuseSamplingWeight [7..9] diffuseReflectance [10..12] specularReflectance
+template <> struct Bsdf<8> {
+	static __device__ __forceinline__ V3 f(const float *P, V3 wi, V3 wo) {
+		if (wi.z <= 0 || wo.z <= 0) return V3(0, 0, 0);
+		const float alphaX = P[1], alphaY = P[2];
+		const V3 H = wi + wo;
+		const int model = (int) P[0];
+		float factor1;
+		if (model == 0) factor1 = 1.0f / (4.0f * kPi * alphaX * alphaY * sqrtf(wi.z * wo.z));
+		else if (model == 1) factor1 = 1.0f / (4.0f * kPi * alphaX * alphaY * wi.z * wo.z);
+		else factor1 = dot(H, H) / (kPi * alphaX * alphaY * dpow4(H.z));
+		const float factor2 = H.x / alphaX, factor3 = H.y / alphaY;
+		const float exponent = -(factor2 * factor2 + factor3 * factor3) / (H.z * H.z);
+		const float specRef = factor1 * dexp(exponent) * P[4];
+		V3 r(0, 0, 0);
+		if (specRef > 1e-10f) r = V3(0.0f + P[10] * specRef, 0.0f + P[11] * specRef, 0.0f + P[12] * specRef);
+		const float dk = kInvPi * P[3];
+		r.x += P[7] * dk; r.y += P[8] * dk; r.z += P[9] * dk;
+		return r;
+	}
+	static __device__ __forceinline__ float pdf_spec(const float *P, V3 wi, V3 wo) {       // pdfSpec (:190-199)
+		const float alphaX = P[1], alphaY = P[2];
+		const V3 H = normalize(wi + wo);
+		const float factor1 = 1.0f / (4.0f * kPi * alphaX * alphaY * dot(H, wi) * dpow3(H.z));
+		const float factor2 = H.x / alphaX, factor3 = H.y / alphaY;
+		const float exponent = -(factor2 * factor2 + factor3 * factor3) / (H.z * H.z);
+		return factor1 * dexp(exponent);
+	}
+	static __device__ __forceinline__ float pdf(const float *P, V3 wi, V3 wo) {
+		if (wi.z <= 0 || wo.z <= 0) return 0.0f;
+		return P[5] * pdf_spec(P, wi, wo) + P[6] * (wo.z * kInvPi);
+	}
+	static __device__ __forceinline__ V3 sample(const float *P, V3 wi, float sx, float sy, V3 &wo, float &pdfv, uint32_t &st) {
+		pdfv = 0; st = 0; wo = V3(0, 0, 0);
+		if (wi.z <= 0) return V3(0, 0, 0);
+		V3 qv(0, 0, 0);
+		if (sx <= P[5]) {
+			sx = sx / P[5];
+			const float alphaX = P[1], alphaY = P[2];                  // sampleSpecular (:222-246)
+			float phiH = datan(alphaY / alphaX * dtan(2.0f * kPi * sy));
+			if (sy > 0.5f) phiH += kPi;
+			const float cosPhiH = dcos(phiH);
+			const float sinPhiH = sqrtf(smax(0.0f, 1.0f - cosPhiH * cosPhiH));
+			const float thetaH = datan(sqrtf(smax(0.0f, -dlog(sx) / ((cosPhiH * cosPhiH) / (alphaX * alphaX) + (sinPhiH * sinPhiH) / (alphaY * alphaY)))));
+			float sth, cth, sph, cph;
+			dsincos(thetaH, sth, cth); dsincos(phiH, sph, cph);
+			const V3 H(sth * cph, sth * sph, cth);                      // sphericalDirection (util.cpp:543-550)
+			const float k = 2.0f * dot(wi, H);
+			wo = V3(H.x * k - wi.x, H.y * k - wi.y, H.z * k - wi.z);
+			st = T_GLOSSY_REFL;
+			if (wo.z <= 0.0f) return V3(0, 0, 0);
+			qv = f(P, wi, wo) * (1.0f / pdf(P, wi, wo));
+		} else {
+			sx = (sx - P[5]) / P[6];
+			wo = squareToHemispherePSA(sx, sy);                        // sampleLambertian (:252-257)
+			st = T_DIFFUSE_REFL;
+			qv = f(P, wi, wo) * (1.0f / pdf(P, wi, wo));
+		}
+		if (isZero(qv)) return V3(0, 0, 0);
+		pdfv = pdf(P, wi, wo);
+		return f(P, wi, wo);
+	}
+};
+
+// (type 9, the composite, needs the BSDF table: BsdfT<9> below)
 // "terminal" bin: never evaluated
 template <> struct Bsdf<kNumBsdfTypes> {
 	static __device__ __forceinline__ V3 f(const float *, V3, V3) { return V3(0, 0, 0); }
@@ -810,20 +878,125 @@ template <> struct Bsdf<kNumBsdfTypes> {
 	}
 };
 
+// The scene's BSDF table (DScene::bsdf_type / bsdf_params): what a composite reaches its children through
+struct BsdfTable { const uint32_t *type; const float *params; };
+
+// One interface for all types: every plugin but the composite ignores the table
+template <int BT> struct BsdfT {
+	static __device__ __forceinline__ V3 f(const BsdfTable &, const float *P, V3 wi, V3 wo) { return Bsdf<BT>::f(P, wi, wo); }
+	static __device__ __forceinline__ float pdf(const BsdfTable &, const float *P, V3 wi, V3 wo) { return Bsdf<BT>::pdf(P, wi, wo); }
+	static __device__ __forceinline__ V3 sample(const BsdfTable &, const float *P, V3 wi, float sx, float sy, V3 &wo, float &pdf, uint32_t &st) {
+		return Bsdf<BT>::sample(P, wi, sx, sy, wo, pdf, st);
+	}
+};
+
+// f and / or pdf of one child of a composite, with the child's own twosided adapter (twosided.cpp:80-98).  Children are
+// non-delta entries of the table (mtsgpu_upload_scene checks it); anything else evaluates to zero.
+template <bool WF, bool WP>
+__device__ __forceinline__ void child_eval(uint32_t type, const float *P, V3 wi, V3 wo, V3 &f, float &pdf) {
+	if ((type & 0x100u) && wi.z < 0) { wi.z *= -1; wo.z *= -1; }
+	f = V3(0, 0, 0); pdf = 0.0f;
+	#define MG_CHILD(BT) case BT: if (WF) f = Bsdf<BT>::f(P, wi, wo); if (WP) pdf = Bsdf<BT>::pdf(P, wi, wo); break
+	switch (type & 0xFFu) {
+		MG_CHILD(0); MG_CHILD(2); MG_CHILD(3); MG_CHILD(5); MG_CHILD(6); MG_CHILD(7); MG_CHILD(8);
+		default: break;
+	}
+	#undef MG_CHILD
+}
+// sample(bRec, sample) of one child (the two-argument form composite.cpp:216 calls): the returned spectrum is zero exactly
+// when that form's is (it returns f / pdf of what the three-argument form returns), the adapter flips wo back when it is
+// not (twosided.cpp:100-113)
+__device__ __forceinline__ V3 child_sample(uint32_t type, const float *P, V3 wi, float sx, float sy, V3 &wo, uint32_t &st) {
+	bool flipped = false;
+	if ((type & 0x100u) && wi.z < 0) { wi.z *= -1; flipped = true; }
+	V3 r(0, 0, 0); float pdf = 0.0f;
+	wo = V3(0, 0, 0); st = 0;
+	#define MG_CHILD(BT) case BT: r = Bsdf<BT>::sample(P, wi, sx, sy, wo, pdf, st); break
+	switch (type & 0xFFu) {
+		MG_CHILD(0); MG_CHILD(2); MG_CHILD(3); MG_CHILD(5); MG_CHILD(6); MG_CHILD(7); MG_CHILD(8);
+		default: break;
+	}
+	#undef MG_CHILD
+	if (flipped && !isZero(r)) wo.z *= -1;
+	return r;
+}
+
+// Composite (src/bsdfs/composite.cpp:144-229), bRec.component == -1.
+// P: [0] child count n (1..MTSGPU_COMPOSITE_MAX = 7) [1..n] weights [1+n..2n] the children's indices into the BSDF table, as floats
+template <> struct BsdfT<9> {
+	// m_pdf.getOriginalSum(): the last knot of the running sum (pdf.h:84-87)
+	static __device__ __forceinline__ float weight_sum(const float *P, int n) {
+		float sum = 0.0f;
+		for (int i = 0; i < n; ++i) sum = sum + P[1 + i];
+		return sum;
+	}
+	// f = sum of w_i f_i (:144-159), pdf = sum of m_pdf[i] pdf_i (:178-193), children in table order
+	template <bool WF, bool WP>
+	static __device__ __forceinline__ void eval(const BsdfTable &tab, const float *P, V3 wi, V3 wo, V3 &f, float &pdf) {
+		const int n = (int) P[0];
+		const float sum = weight_sum(P, n);
+		f = V3(0, 0, 0); pdf = 0.0f;
+		#pragma unroll 1
+		for (int i = 0; i < n; ++i) {
+			const uint32_t c = (uint32_t) P[1 + n + i];
+			const float w = P[1 + i];
+			V3 cf; float cp;
+			child_eval<WF, WP>(tab.type[c], tab.params + kBsdfNParams * (size_t) c, wi, wo, cf, cp);
+			if (WF) { f.x += cf.x * w; f.y += cf.y * w; f.z += cf.z * w; }
+			if (WP) pdf += cp * (w / sum);                          // m_pdf[i] after DiscretePDF::build (pdf.h:88-91)
+		}
+	}
+	static __device__ __forceinline__ V3 f(const BsdfTable &tab, const float *P, V3 wi, V3 wo) {
+		V3 fv; float pv; eval<true, false>(tab, P, wi, wo, fv, pv); return fv;
+	}
+	static __device__ __forceinline__ float pdf(const BsdfTable &tab, const float *P, V3 wi, V3 wo) {
+		V3 fv; float pv; eval<false, true>(tab, P, wi, wo, fv, pv); return pv;
+	}
+	// sample(bRec, pdf, sample) (:212-229): sampleReuse picks the child, its sample() the direction, then pdf and f of the WHOLE
+	static __device__ __forceinline__ V3 sample(const BsdfTable &tab, const float *P, V3 wi, float sx, float sy, V3 &wo, float &pdfv, uint32_t &st) {
+		pdfv = 0; st = 0; wo = V3(0, 0, 0);
+		const int n = (int) P[0];
+		const float sum = weight_sum(P, n);
+		// DiscretePDF::sample (pdf.h:102-107): std::lower_bound over the n + 1 knots m_cdf[i] = (w_0 + .. + w_(i-1)) / sum, m_cdf[n] = 1
+		int it = n + 1;
+		float acc = 0.0f;
+		for (int i = 0; i <= n; ++i) {
+			const float knot = (i == n) ? 1.0f : acc / sum;
+			if (it > n && !(knot < sx)) it = i;
+			if (i < n) acc = acc + P[1 + i];
+		}
+		int entry = it - 1;
+		if (entry < 0) entry = 0;
+		if (entry > n - 1) entry = n - 1;
+		// sampleReuse (pdf.h:128-133)
+		float lo = 0.0f;
+		for (int i = 0; i < entry; ++i) lo = lo + P[1 + i];
+		const float hi = (entry + 1 == n) ? 1.0f : (lo + P[1 + entry]) / sum;
+		lo = lo / sum;
+		sx = (sx - lo) / (hi - lo);
+		const uint32_t c = (uint32_t) P[1 + n + entry];
+		const V3 r = child_sample(tab.type[c], tab.params + kBsdfNParams * (size_t) c, wi, sx, sy, wo, st);
+		if (isZero(r)) { wo = V3(0, 0, 0); st = 0; return V3(0, 0, 0); }      // sampling failed (:218-219)
+		V3 fv;
+		eval<true, true>(tab, P, wi, wo, fv, pdfv);
+		return fv;
+	}
+};
+
 // TwoSidedBRDF adapter (src/bsdfs/twosided.cpp:80-130) around any BSDF whose type carries MTSGPU_BSDF_TWOSIDED
 template <int BT> struct Bsdf2 {
-	static __device__ __forceinline__ V3 f(bool two, const float *P, V3 wi, V3 wo) {
+	static __device__ __forceinline__ V3 f(const BsdfTable &tab, bool two, const float *P, V3 wi, V3 wo) {
 		if (two && wi.z < 0) { wi.z *= -1; wo.z *= -1; }
-		return Bsdf<BT>::f(P, wi, wo);
+		return BsdfT<BT>::f(tab, P, wi, wo);
 	}
-	static __device__ __forceinline__ float pdf(bool two, const float *P, V3 wi, V3 wo) {
+	static __device__ __forceinline__ float pdf(const BsdfTable &tab, bool two, const float *P, V3 wi, V3 wo) {
 		if (two && wi.z < 0) { wi.z *= -1; wo.z *= -1; }
-		return Bsdf<BT>::pdf(P, wi, wo);
+		return BsdfT<BT>::pdf(tab, P, wi, wo);
 	}
-	static __device__ __forceinline__ V3 sample(bool two, const float *P, V3 wi, float sx, float sy, V3 &wo, float &pdf, uint32_t &st) {
+	static __device__ __forceinline__ V3 sample(const BsdfTable &tab, bool two, const float *P, V3 wi, float sx, float sy, V3 &wo, float &pdf, uint32_t &st) {
 		bool flipped = false;
 		if (two && wi.z < 0) { wi.z *= -1; flipped = true; }
-		const V3 result = Bsdf<BT>::sample(P, wi, sx, sy, wo, pdf, st);
+		const V3 result = BsdfT<BT>::sample(tab, P, wi, sx, sy, wo, pdf, st);
 		if (flipped && !isZero(result) && pdf != 0) wo.z *= -1;
 		return result;
 	}
@@ -833,16 +1006,16 @@ template <int BT> struct Bsdf2 {
 // src/tests/test_chisquare.cpp:299-420 runs against exactly the code k_shade runs.  One query record per thread:
 // wi = q[i][0..2]; op 0 / 1: wo = q[i][3..5]; op 2: sample = q[i][3..4].
 template <int BT>
-__device__ __forceinline__ void bsdf_eval_one(bool two, const float *P, int op, const float *q, float *o) {
+__device__ __forceinline__ void bsdf_eval_one(const BsdfTable &tab, bool two, const float *P, int op, const float *q, float *o) {
 	const V3 wi(q[0], q[1], q[2]);
 	if (op == 0) {
-		const V3 f = Bsdf2<BT>::f(two, P, wi, V3(q[3], q[4], q[5]));
+		const V3 f = Bsdf2<BT>::f(tab, two, P, wi, V3(q[3], q[4], q[5]));
 		o[0] = f.x; o[1] = f.y; o[2] = f.z;
 	} else if (op == 1) {
-		o[0] = Bsdf2<BT>::pdf(two, P, wi, V3(q[3], q[4], q[5]));
+		o[0] = Bsdf2<BT>::pdf(tab, two, P, wi, V3(q[3], q[4], q[5]));
 	} else {
 		V3 wo; float pdf; uint32_t st;
-		const V3 f = Bsdf2<BT>::sample(two, P, wi, q[3], q[4], wo, pdf, st);
+		const V3 f = Bsdf2<BT>::sample(tab, two, P, wi, q[3], q[4], wo, pdf, st);
 		o[0] = wo.x; o[1] = wo.y; o[2] = wo.z; o[3] = pdf; o[4] = f.x; o[5] = f.y; o[6] = f.z; o[7] = __uint_as_float(st);
 	}
 }
@@ -853,15 +1026,41 @@ __global__ void k_bsdf_eval(uint32_t type, BsdfParams params, int op, uint32_t n
 	const bool two = (type & 0x100u) != 0;
 	const float *P = params.v, *q = queries + 6 * (size_t) i;
 	float o[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+	const BsdfTable tab{ nullptr, nullptr };       // a single block has no table: the host refuses the composite here
 	switch (type & 0xFFu) {
-		case 0: bsdf_eval_one<0>(two, P, op, q, o); break;
-		case 1: bsdf_eval_one<1>(two, P, op, q, o); break;
-		case 2: bsdf_eval_one<2>(two, P, op, q, o); break;
-		case 3: bsdf_eval_one<3>(two, P, op, q, o); break;
-		case 4: bsdf_eval_one<4>(two, P, op, q, o); break;
-		case 5: bsdf_eval_one<5>(two, P, op, q, o); break;
-		case 6: bsdf_eval_one<6>(two, P, op, q, o); break;
-		default: bsdf_eval_one<7>(two, P, op, q, o); break;
+		case 0: bsdf_eval_one<0>(tab, two, P, op, q, o); break;
+		case 1: bsdf_eval_one<1>(tab, two, P, op, q, o); break;
+		case 2: bsdf_eval_one<2>(tab, two, P, op, q, o); break;
+		case 3: bsdf_eval_one<3>(tab, two, P, op, q, o); break;
+		case 4: bsdf_eval_one<4>(tab, two, P, op, q, o); break;
+		case 5: bsdf_eval_one<5>(tab, two, P, op, q, o); break;
+		case 6: bsdf_eval_one<6>(tab, two, P, op, q, o); break;
+		case 7: bsdf_eval_one<7>(tab, two, P, op, q, o); break;
+		default: bsdf_eval_one<8>(tab, two, P, op, q, o); break;
+	}
+	#pragma unroll
+	for (int k = 0; k < 8; ++k) out[8 * (size_t) i + k] = o[k];
+}
+// The same read-out for entry `index` of a BSDF table in device memory (mtsgpu_bsdf_eval_table): what a composite needs
+__global__ void k_bsdf_eval_table(const uint32_t *types, const float *params, uint32_t index, int op, uint32_t n, const float *queries, float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t type = types[index];
+	const bool two = (type & 0x100u) != 0;
+	const float *P = params + kBsdfNParams * (size_t) index, *q = queries + 6 * (size_t) i;
+	float o[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+	const BsdfTable tab{ types, params };
+	switch (type & 0xFFu) {
+		case 0: bsdf_eval_one<0>(tab, two, P, op, q, o); break;
+		case 1: bsdf_eval_one<1>(tab, two, P, op, q, o); break;
+		case 2: bsdf_eval_one<2>(tab, two, P, op, q, o); break;
+		case 3: bsdf_eval_one<3>(tab, two, P, op, q, o); break;
+		case 4: bsdf_eval_one<4>(tab, two, P, op, q, o); break;
+		case 5: bsdf_eval_one<5>(tab, two, P, op, q, o); break;
+		case 6: bsdf_eval_one<6>(tab, two, P, op, q, o); break;
+		case 7: bsdf_eval_one<7>(tab, two, P, op, q, o); break;
+		case 8: bsdf_eval_one<8>(tab, two, P, op, q, o); break;
+		default: bsdf_eval_one<9>(tab, two, P, op, q, o); break;
 	}
 	#pragma unroll
 	for (int k = 0; k < 8; ++k) out[8 * (size_t) i + k] = o[k];
@@ -1006,6 +1205,7 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			const int bsdfIdx = sc.shape_bsdf[its.shape];
 			const float *BP = sc.bsdf_params + 16 * (size_t) bsdfIdx;
 			const bool twoSided = (sc.bsdf_type[bsdfIdx] & 0x100u) != 0;
+			const BsdfTable tab{ sc.bsdf_type, sc.bsdf_params };
 			if (shapeLum >= 0 && (flags & F_EMITTED) && !(skipToNee || skipToBsdf)) {
 				// Li += pathThroughput * its.Le(-ray.d) (path.cpp:80-81, area.cpp:62-66)
 				const float *LP = sc.lum_params + kLumStride * (size_t) shapeLum;
@@ -1030,12 +1230,12 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				if ((!direct || cfg.n_lum > 0) && sample_luminaire(sc, its.p, s0, s1, lRec)) {
 					const V3 wo = -lRec.d;
 					const V3 woL(dot(wo, its.shS), dot(wo, its.shT), dot(wo, its.shN));
-					V3 bsdfVal = Bsdf2<BT>::f(twoSided, BP, its.wi, woL) * fabsf(woL.z);
+					V3 bsdfVal = Bsdf2<BT>::f(tab, twoSided, BP, its.wi, woL) * fabsf(woL.z);
 					const float woDotGeoN = dot(its.geoN, wo);
 					if (!isZero(bsdfVal) && (!strict || woDotGeoN * woL.z > 0)) {
 						// isIntersectable() || isBackgroundLuminaire() (path.cpp:118-120): 0 for delta luminaires
 						const uint32_t lt = sc.lum_type[lRec.lum];      // area, constant and envmap luminaires can be hit by BSDF samples
-						const float bsdfPdf = (lt <= 1u || lt == 5u) ? Bsdf2<BT>::pdf(twoSided, BP, its.wi, woL) : 0.0f;
+						const float bsdfPdf = (lt <= 1u || lt == 5u) ? Bsdf2<BT>::pdf(tab, twoSided, BP, its.wi, woL) : 0.0f;
 						const float weight = direct ? mi_weight(lRec.pdf * cfg.frac_lum, bsdfPdf * cfg.frac_bsdf) * cfg.weight_lum
 						                            : mi_weight(lRec.pdf, bsdfPdf);          // direct.cpp:143-145
 						// added to Li by k_trace<shadow> iff the segment is unoccluded
@@ -1060,7 +1260,7 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			if (direct && cfg.n_bsdf <= 0)
 				break;                                      // the sample is drawn even when it is not used (direct.cpp:156-161)
 			V3 woL; float bsdfPdf; uint32_t sampledType;
-			V3 bsdfVal = Bsdf2<BT>::sample(twoSided, BP, its.wi, s0, s1, woL, bsdfPdf, sampledType);
+			V3 bsdfVal = Bsdf2<BT>::sample(tab, twoSided, BP, its.wi, s0, s1, woL, bsdfPdf, sampledType);
 			if (!isZero(bsdfVal))
 				bsdfVal = bsdfVal * fabsf(woL.z);          // sampleCos (bsdf.h:273-279)
 			if (isZero(bsdfVal))
@@ -1272,6 +1472,8 @@ __global__ MG_SHADE_BOUNDS void k_shade_all(DScene sc, DPaths ps, DConfig cfg, D
 		case 5: shade_block<5, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
 		case 6: shade_block<6, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
 		case 7: shade_block<7, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		case 8: shade_block<8, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		case 9: return;      // the composite's loop over its children is launched on its own (kShadeAllBins)
 		default: shade_block<kNumBsdfTypes, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
 	}
 }
@@ -1280,6 +1482,11 @@ void launch_bsdf_eval(hipStream_t s, uint32_t type, const float *params, int op,
 	BsdfParams p;
 	for (int k = 0; k < kBsdfNParams; ++k) p.v[k] = params[k];
 	if (n) hipLaunchKernelGGL(k_bsdf_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, type, p, op, n, queries, out);
+}
+
+void launch_bsdf_eval_table(hipStream_t s, const uint32_t *types, const float *params, uint32_t index, int op, uint32_t n,
+                            const float *queries, float *out) {
+	if (n) hipLaunchKernelGGL(k_bsdf_eval_table, dim3(blocks_for(n, 256)), dim3(256), 0, s, types, params, index, op, n, queries, out);
 }
 
 void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, const DConfig &cfg,
@@ -1299,6 +1506,8 @@ void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, co
 		case 5: MG_SHADE(5); break;
 		case 6: MG_SHADE(6); break;
 		case 7: MG_SHADE(7); break;
+		case 8: MG_SHADE(8); break;
+		case 9: MG_SHADE(9); break;
 		default: MG_SHADE(kNumBsdfTypes); break;
 	}
 	#undef MG_SHADE
@@ -1306,6 +1515,7 @@ void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, co
 
 void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,
                       const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound) {
+	bin_mask &= kShadeAllBins;
 	if (!n_bound || !bin_mask) return;
 	// every bin rounds its size up to whole workgroups
 	const unsigned blocks = blocks_for(n_bound, kShadeBlock) + (unsigned) __builtin_popcount(bin_mask);

@@ -93,6 +93,34 @@ class SceneDescription:
     def difftrans(self, t=0.5):
         return self.add_bsdf(abi.BSDF_DIFFTRANS, [t, t, t])
 
+    def ward(self, alpha_x=0.1, alpha_y=0.1, rd=0.5, rs=0.2, kd=1.0, ks=1.0, model="balanced", specular_sampling_weight=-1.0,
+             verify_energy_conservation=True):
+        """parameter block as the constructor and Ward::configure() leave it (src/bsdfs/ward.cpp:54-88, :118-136), float32
+        arithmetic; rd / rs: a grey level or an RGB triple"""
+        m = {"ward": 0, "ward-duer": 1, "balanced": 2}[model]
+        rd = np.broadcast_to(np.asarray(rd, dtype=np.float32), (3,)); rs = np.broadcast_to(np.asarray(rs, dtype=np.float32), (3,))
+        kd, ks = F(kd), F(ks)
+        if verify_energy_conservation and kd * rd.max() + ks * rs.max() > F(1.0):
+            norm = F(1) / (kd * rd.max() + ks * rs.max())
+            kd, ks = kd * norm, ks * norm
+        ssw = F(specular_sampling_weight)
+        if ssw == F(-1):
+            avg_d = (rd[0] + rd[1] + rd[2]) * F(1.0 / 3) * kd          # Spectrum::average() * m_kd
+            avg_s = (rs[0] + rs[1] + rs[2]) * F(1.0 / 3) * ks
+            ssw = avg_s / (avg_d + avg_s)
+        dsw = F(1.0) - ssw
+        return self.add_bsdf(abi.BSDF_WARD, [m, alpha_x, alpha_y, kd, ks, ssw, dsw, rd[0], rd[1], rd[2], rs[0], rs[1], rs[2]])
+
+    def composite(self, weights, children):
+        """<bsdf type="composite"> (src/bsdfs/composite.cpp): weights and the indices of blocks added before.  Block:
+        [0] n, [1..n] weights, [1+n..2n] child indices as floats (include/mtsgpu.h); the flattener checks it"""
+        weights = [float(w) for w in weights]; children = [int(c) for c in children]
+        if len(weights) != len(children):
+            raise ValueError("BSDF count mismatch: %d bsdfs, but specified %d weights" % (len(children), len(weights)))   # composite.cpp:98-100
+        if 1 + 2 * len(weights) > abi.BSDF_NPARAMS:
+            raise ValueError("a composite holds at most %d children" % abi.COMPOSITE_MAX)
+        return self.add_bsdf(abi.BSDF_COMPOSITE, [len(weights)] + weights + children)
+
     def twosided(self, bsdf):
         """wrap an existing BSDF block in the `twosided` adapter (src/bsdfs/twosided.cpp)"""
         self.bsdf_type[bsdf] |= abi.BSDF_TWOSIDED

@@ -85,11 +85,17 @@ enum {
 	                            3x3 (row major) [19] beamWidth (rad)           (src/luminaires/spot.cpp:33-118) */
 	MTSGPU_LUM_COLLIMATED = 6, /* [0..2] intensity [3] radius [4..15] world->luminaire 3x4 (row major, affine)
 	                            [16..27] luminaire->world 3x4              (src/luminaires/collimated.cpp) */
+	MTSGPU_LUM_SKY = 7,      /* [0] skyScale [1] turbidity [2] clipBelowHorizon (0/1) [3..5] bsphere centre [6] radius = the
+	                            scene's bounding sphere x 1.01, no camera expansion (sky.cpp:221-227) [7..15] world->luminaire
+	                            3x3 (row major) [16] thetaS [17] phiS [18..22] aConst..eConst: what the object holds after
+	                            serialize() and preprocess(); what configure() derives is mtsgpu_sky_configure().  Always
+	                            the background luminaire, at most one per scene          (src/luminaires/sky.cpp) */
 	MTSGPU_LUM_ENVMAP = 5    /* [0] intensityScale [3..5] bsphere centre [6] radius (envmap.cpp:112-126)
 	                            [7..15] world->luminaire 3x3 [16..24] luminaire->world 3x3 (row major); the image and
 	                            its sampling density are the env_* arrays of the scene   (src/luminaires/envmap.cpp) */
 };
 #define MTSGPU_LUM_NPARAMS 32
+#define MTSGPU_SKY_NDERIVED 24   /* floats mtsgpu_sky_configure() writes */
 
 /* Sampler kinds.  *_KEYED are the per-(pixel,sample)-keyed forms of the two
  * reference samplers (src/samplers/{independent,ldsampler}.cpp): identical
@@ -418,6 +424,21 @@ int  mtsgpu_bsdf_eval(mtsgpu_ctx *ctx, uint32_t bsdf_type, const float *params, 
  * mtsgpu_bsdf_eval returns MTSGPU_EINVAL for MTSGPU_BSDF_COMPOSITE and this call evaluates it. */
 int  mtsgpu_bsdf_eval_table(mtsgpu_ctx *ctx, uint32_t n_bsdfs, const uint32_t *types, const float *params, uint32_t index, int op,
                             uint32_t n, const float *queries, float *out);
+/* SkyLuminaire::configure() (sky.cpp:139-179) for one MTSGPU_LUM_SKY block: derived[MTSGPU_SKY_NDERIVED] = [0] zenith x
+ * [1] zenith y [2] zenith Y [3..7] Perez coefficients of x [8..12] of y [13..17] of Y [18..20] the Perez denominators of
+ * x, y, Y (sky.cpp:458-461) [21] sin(thetaS) [22] cos(thetaS).  Host only: needs no device and no context.  The library
+ * derives the same array when a scene with a sky is uploaded and keeps it in device memory next to the scene. */
+int  mtsgpu_sky_configure(const float *block, float *derived);
+/* The luminaire plugins as the device runs them, for n query records of ONE parameter block[MTSGPU_LUM_NPARAMS].
+ * queries [n][6], out [n][12]:
+ *   op 0  Le(direction)        queries = direction.xyz (world)      out = Le.rgb
+ *   op 1  sample(p, lRec, s)   queries = p.xyz, s.x, s.y, -         out = lRec.d.xyz, pdf, value.rgb (not divided by the
+ *                                                                         pdf), -, lRec.sRec.p.xyz (end of the shadow ray)
+ *   op 2  pdf(p, lRec)         queries = p.xyz, lRec.d.xyz          out = pdf
+ * Serves MTSGPU_LUM_SKY (checked as mtsgpu_upload_scene checks it); MTSGPU_EINVAL for every other type.  A test hook
+ * like mtsgpu_bsdf_eval: ops 0 and 1 call the device functions k_shade calls (sky_le, sky_sample), op 2 returns the constant
+ * pdf_luminaire uses. */
+int  mtsgpu_lum_eval(mtsgpu_ctx *ctx, uint32_t lum_type, const float *block, int op, uint32_t n, const float *queries, float *out);
 /* MIPathTracer::Li for explicit camera samples: in [n][3] u32 = pixel x, y, sample index;
  * out [n][8] f32 = Li rgb, alpha, raster x, raster y, depth, unused */
 int  mtsgpu_li_samples(mtsgpu_ctx *ctx, const uint32_t *pix_samples, uint32_t n, float *out);

@@ -179,9 +179,19 @@ struct FlatScene {
 				if (sc.background_lum >= 0) SLog(EError, "gpupath: more than one background luminaire");
 				sc.background_lum = (int32_t) l;
 				readEnvMap(lum, P);
+			} else if (cls == "SkyLuminaire") {
+				lumType.push_back(MTSGPU_LUM_SKY);
+				if (sc.background_lum >= 0) SLog(EError, "gpupath: more than one background luminaire");
+				sc.background_lum = (int32_t) l;
+				ref<MemoryStream> st = serializedDetached(lum);                     /* sky.cpp:121-133 */
+				if (!mtsgpu_stream::parseSky<Float>(st->getData(), st->getSize(), P, &err)) SLog(EError, "gpupath: %s", err.c_str());
+				/* SkyLuminaire::preprocess (sky.cpp:221-227): the scene's bounding sphere x 1.01f, not grown to hold the camera */
+				BSphere bs = scene->getBSphere();
+				bs.radius *= 1.01f;
+				P[3] = (float) bs.center.x; P[4] = (float) bs.center.y; P[5] = (float) bs.center.z; P[6] = (float) bs.radius;
 			} else {
-				SLog(EError, "gpupath: luminaire class %s is not on this path (area, constant, point, spot, directional, collimated "
-					"and envmap are)", cls.c_str());
+				SLog(EError, "gpupath: luminaire class %s is not on this path (area, constant, point, spot, directional, collimated, "
+					"envmap and sky are)", cls.c_str());
 			}
 		}
 

@@ -1,6 +1,6 @@
 /*
  * streamparse.h -- the field-order logic of the reference-side binding (integration/gpucommon.h), free of Mitsuba's headers:
- * it takes the bytes `InstanceManager::serialize` produced for a BSDF, a delta / environment luminaire or a sphere and fills
+ * it takes the bytes `InstanceManager::serialize` produced for a BSDF, a delta / environment / sky luminaire or a sphere and fills
  * the parameter blocks of include/mtsgpu.h.  gpucommon.h produces the bytes (MemoryStream) and calls in here; the CPU tests
  * (tests/test_stream_parsers.py) produce them with an independent writer that follows each class's serialize() and compare
  * the blocks with what the library's own flattener builds for the same scene description, bit for bit.
@@ -362,6 +362,23 @@ template <typename FloatT> inline bool parseEnvMapHeader(const uint8_t *data, si
 	*exrSize = r.readUInt();
 	*exrOffset = r.pos();
 	if (r.ok() && r.pos() + *exrSize > r.size()) r.fail("the environment map's bitmap is truncated");
+	if (!r.ok()) { if (err) *err = r.error(); return false; }
+	return true;
+}
+
+/* SkyLuminaire (sky.cpp:121-133): Luminaire::serialize's fields, then skyScale, turbidity, thetaS, phiS, aConst .. eConst and
+ * clipBelowHorizon (a bool: one byte).  Fills [0..2] and [7..22] of the block; the bounding sphere [3..6] is not serialized
+ * (preprocess() takes it from the scene, sky.cpp:221-227) and is the caller's.  What configure() derives from these
+ * (:139-179) is mtsgpu_sky_configure(). */
+template <typename FloatT> inline bool parseSky(const uint8_t *data, size_t size, float *P, std::string *err) {
+	ByteReader<FloatT> r(data, size);
+	openDetached(r, "SkyLuminaire");
+	const Xform<FloatT> w2l = readLuminaireBase(r);                          /* m_worldToLuminaire lives in the base class */
+	P[0] = (float) r.readFloat(); P[1] = (float) r.readFloat();              /* m_skyScale, m_turbidity */
+	P[16] = (float) r.readFloat(); P[17] = (float) r.readFloat();            /* m_thetaS, m_phiS */
+	for (int k = 0; k < 5; ++k) P[18 + k] = (float) r.readFloat();           /* m_aConst .. m_eConst */
+	P[2] = r.readBool() ? 1.0f : 0.0f;                                       /* m_clipBelowHorizon */
+	copy3x3(P + 7, w2l.fwd);
 	if (!r.ok()) { if (err) *err = r.error(); return false; }
 	return true;
 }

@@ -33,6 +33,7 @@ EXPORTS = [
     "mtsgpu_create_multi", "mtsgpu_group_destroy", "mtsgpu_group_size", "mtsgpu_group_ctx", "mtsgpu_group_last_error",
     "mtsgpu_group_upload_scene", "mtsgpu_group_set_camera", "mtsgpu_group_set_integrator", "mtsgpu_group_set_sampler",
     "mtsgpu_group_set_rfilter", "mtsgpu_group_render", "mtsgpu_group_last_reduce_kind", "mtsgpu_group_rccl_ranks", "mtsgpu_group_reduce_note", "mtsgpu_bsdf_eval", "mtsgpu_bsdf_eval_table", "mtsgpu_replay_roof", "mtsgpu_group_set_tuning",
+    "mtsgpu_sky_configure", "mtsgpu_lum_eval",
 ]
 
 
@@ -163,6 +164,8 @@ def lib():
     L.mtsgpu_random_values.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.mtsgpu_bsdf_eval.argtypes = [vp, C.c_uint32, f32p, C.c_int, C.c_uint32, f32p, f32p]
     L.mtsgpu_bsdf_eval_table.argtypes = [vp, C.c_uint32, u32p, f32p, C.c_uint32, C.c_int, C.c_uint32, f32p, f32p]
+    L.mtsgpu_sky_configure.argtypes = [f32p, f32p]
+    L.mtsgpu_lum_eval.argtypes = [vp, C.c_uint32, f32p, C.c_int, C.c_uint32, f32p, f32p]
     L.mtsgpu_hbm_triad.argtypes = [C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
     L.mtsgpu_replay_roof.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_double)]
     L.mtsgpu_create_multi.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
@@ -455,6 +458,23 @@ class MIPathTracer:
                                                abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)), "bsdf_eval_table")
         return out
 
+    def lum_eval(self, lum_type, block, op, a, b=None):
+        """the luminaire plugins on the device for n query records (mtsgpu_lum_eval; the sky): op 0 Le(a = direction
+        [n][3]); op 1 sample(a = p [n][3], b = the 2D sample [n][2]); op 2 pdf(a = p, b = lRec.d).  Returns [n][12]:
+        Le.rgb | d.xyz, pdf, value.rgb, -, end point of the shadow ray xyz | pdf"""
+        a = np.atleast_2d(np.asarray(a, dtype=np.float32))
+        n = a.shape[0]
+        q = np.zeros((n, 6), dtype=np.float32)
+        q[:, :3] = a
+        if b is not None:
+            b = np.atleast_2d(np.asarray(b, dtype=np.float32))
+            q[:, 3:3 + b.shape[1]] = b
+        P = np.zeros(abi.LUM_NPARAMS, dtype=np.float32); P[:len(block)] = block
+        out = np.zeros((n, 12), dtype=np.float32)
+        self._chk(lib().mtsgpu_lum_eval(self._ctx, int(lum_type), abi.ptr(P, abi.f32p), int(op), n, abi.ptr(q, abi.f32p),
+                                        abi.ptr(out, abi.f32p)), "lum_eval")
+        return out
+
     def li_samples(self, pix_samples):
         ps = np.ascontiguousarray(pix_samples, dtype=np.uint32).reshape(-1, 3)
         out = np.zeros((ps.shape[0], 8), dtype=np.float32)
@@ -569,6 +589,16 @@ class DeviceGroup:
             self.close()
         except Exception:
             pass
+
+
+def sky_configure(block):
+    """SkyLuminaire::configure() for one LUM_SKY block (mtsgpu_sky_configure, host only): zenith x / y / Y, the 3 x 5 Perez
+    coefficients (x, y, Y), their three denominators, sin and cos of thetaS"""
+    P = np.zeros(abi.LUM_NPARAMS, dtype=np.float32); P[:len(block)] = block
+    out = np.zeros(abi.SKY_NDERIVED, dtype=np.float32)
+    if lib().mtsgpu_sky_configure(abi.ptr(P, abi.f32p), abi.ptr(out, abi.f32p)) != 0:
+        raise MtsGpuError("mtsgpu_sky_configure: %s" % lib().mtsgpu_last_error(None).decode())
+    return out
 
 
 def hbm_triad_gbs(device=0, gib=1.0, iters=5):

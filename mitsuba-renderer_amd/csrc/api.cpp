@@ -804,6 +804,7 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 			if (sc->shape_bsdf[s] >= 0 && !shapeHasTangentFrame(shapeType(s)) && bsdfIsAnisotropic(sc->bsdf_type, sc->bsdf_params, (uint32_t) sc->shape_bsdf[s]))
 				return fail(c, MTSGPU_EINVAL, "%s", anisotropicOnMeshMessage(s).c_str());
 	}
+	float skyDerived[MTSGPU_SKY_NDERIVED] = { 0 };      // SkyLuminaire::configure() of the background sky, filled by its check
 	for (uint32_t l = 0; l < sc->n_lums; ++l) {
 		if (sc->lum_type[l] == MTSGPU_LUM_AREA) {
 			const int32_t s = sc->lum_shape[l];
@@ -823,6 +824,9 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 				if (!(sc->env_cdf[i] <= sc->env_cdf[i + 1]) || !(sc->env_pdf[i] >= 0.0f)) return fail(c, MTSGPU_EINVAL, "luminaire %u: the environment map's CDF is not monotone", l);
 			const float *LP = sc->lum_params + (size_t) MTSGPU_LUM_NPARAMS * l;
 			for (int i = 0; i < 25; ++i) if (!std::isfinite(LP[i])) return fail(c, MTSGPU_EINVAL, "luminaire %u: non-finite parameter", l);
+		} else if (sc->lum_type[l] == MTSGPU_LUM_SKY) {
+			const std::string why = checkSkyLuminaire(l, sc->lum_params + (size_t) MTSGPU_LUM_NPARAMS * l, sc->background_lum, skyDerived);
+			if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
 		} else if (sc->lum_type[l] > MTSGPU_LUM_COLLIMATED) {
 			return fail(c, MTSGPU_EINVAL, "luminaire %u: unknown type", l);
 		}
@@ -965,6 +969,10 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 		rc |= upload(c, &d.env_cdf, sc->env_cdf, np + 1);
 		d.env_width = sc->env_width; d.env_height = sc->env_height;
 		d.env_pdf_width = sc->env_pdf_width; d.env_pdf_height = sc->env_pdf_height;
+	}
+	if (sc->background_lum >= 0 && sc->lum_type[sc->background_lum] == MTSGPU_LUM_SKY) {
+		// what SkyLuminaire::configure() derives (sky.cpp:139-179), once per scene
+		rc |= upload(c, (const float **) &d.sky, (const float *) skyDerived, (size_t) MTSGPU_SKY_NDERIVED);
 	}
 	if (rc) { freeAll(c->sceneAllocs); return rc; }
 	d.lum_sel_sum = sc->lum_sel_sum; d.background_lum = sc->background_lum;
@@ -1579,6 +1587,45 @@ int mtsgpu_bsdf_eval_table(mtsgpu_ctx *c, uint32_t n_bsdfs, const uint32_t *type
 	if (dP) (void) hipFree(dP);
 	if (dT) (void) hipFree(dT);
 	if (e != hipSuccess) return fail(c, MTSGPU_EHIP, "BSDF read-out failed: %s", hipGetErrorString(e));
+	return 0;
+}
+
+int mtsgpu_sky_configure(const float *block, float *derived) {
+	if (!block || !derived) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	skyConfigure(block, derived);
+	return 0;
+}
+
+int mtsgpu_lum_eval(mtsgpu_ctx *c, uint32_t lum_type, const float *block, int op, uint32_t n, const float *queries, float *out) {
+	if (!c || !block || !queries || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (lum_type != (uint32_t) MTSGPU_LUM_SKY) return fail(c, MTSGPU_EINVAL, "luminaire type %u is not served by this read-out (sky only)", lum_type);
+	if (op < 0 || op > 2) return fail(c, MTSGPU_EINVAL, "bad luminaire operation");
+	float host[MTSGPU_LUM_NPARAMS + MTSGPU_SKY_NDERIVED];
+	{
+		const std::string why = checkSkyLuminaire(0, block, 0, host + MTSGPU_LUM_NPARAMS);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+	}
+	if (n == 0) return 0;
+	if (n > (1u << 24)) return fail(c, MTSGPU_EINVAL, "at most 2^24 query records per call");
+	HIPCHK(c, hipSetDevice(c->device));
+	std::memcpy(host, block, sizeof(float) * MTSGPU_LUM_NPARAMS);
+	float *dQ = nullptr, *dOut = nullptr, *dB = nullptr;
+	hipError_t e = hipMalloc((void **) &dQ, (size_t) n * 6 * sizeof(float));
+	if (e == hipSuccess) e = hipMalloc((void **) &dOut, (size_t) n * 12 * sizeof(float));
+	if (e == hipSuccess) e = hipMalloc((void **) &dB, sizeof(host));
+	if (e == hipSuccess) e = hipMemcpyAsync(dQ, queries, (size_t) n * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(dB, host, sizeof(host), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);       // `host` lives on this stack
+	if (e == hipSuccess) {
+		launch_sky_eval(c->stream, dB, op, n, dQ, dOut);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, (size_t) n * 12 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (dQ) (void) hipFree(dQ);
+	if (dOut) (void) hipFree(dOut);
+	if (dB) (void) hipFree(dB);
+	if (e != hipSuccess) return fail(c, MTSGPU_EHIP, "luminaire read-out failed: %s", hipGetErrorString(e));
 	return 0;
 }
 

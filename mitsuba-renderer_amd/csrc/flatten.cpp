@@ -242,6 +242,15 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 				throw std::runtime_error("flatten: more than one background luminaire");
 			buildEnvMap(d, P, fs);
 			background = (int32_t) l;
+		} else if (fs.lumType[l] == MTSGPU_LUM_SKY) {
+			// SkyLuminaire::preprocess (src/luminaires/sky.cpp:221-227): the scene's bounding sphere, enlarged; unlike the
+			// constant luminaire's it does not grow to hold the camera
+			float br = radius;
+			br *= 1.01f;
+			P[3] = center.x; P[4] = center.y; P[5] = center.z; P[6] = br;
+			if (background >= 0)
+				throw std::runtime_error("flatten: more than one background luminaire");
+			background = (int32_t) l;
 		} else if (fs.lumType[l] == MTSGPU_LUM_POINT || fs.lumType[l] == MTSGPU_LUM_COLLIMATED) {
 			// nothing to derive (point.cpp:28-33)
 		} else if (fs.lumType[l] == MTSGPU_LUM_DIRECTIONAL) {
@@ -254,6 +263,13 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 			throw std::runtime_error("flatten: unknown luminaire type");
 		}
 	}
+	// the check mtsgpu_upload_scene makes too: a sky is the background (a constant luminaire listed after it would have taken
+	// its place), its parameters are finite and its divisions have non-zero divisors
+	for (uint32_t l = 0; l < nLums; ++l)
+		if (fs.lumType[l] == MTSGPU_LUM_SKY) {
+			const std::string why = checkSkyLuminaire(l, &fs.lumParams[(size_t) MTSGPU_LUM_NPARAMS * l], background);
+			if (!why.empty()) throw std::runtime_error("flatten: " + why);
+		}
 	// Scene::initialize: luminaire selection PDF, weight getSamplingWeight() = 1 (scene.cpp:320-330)
 	float selSum = 0.0f;
 	if (nLums > 0) {

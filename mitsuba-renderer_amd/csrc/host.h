@@ -1,6 +1,8 @@
 // host.h -- host-side pieces of libmtsgpu shared between translation units.
 #pragma once
 #include "../../include/mtsgpu.h"
+#include "devmath.h"
+#include <cmath>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -82,6 +84,74 @@ inline std::string anisotropicOnMeshMessage(uint32_t shape) {
 	return "shape " + std::to_string(shape) + ": computeTangentSpace(): texture coordinates are required to generate tangent vectors. "
 	       "If you want to render with an anisotropic material, please make sure that all associated shapes have valid texture "
 	       "coordinates (triangle meshes have none here: an anisotropic Ward BSDF needs a sphere)";
+}
+
+// SkyLuminaire::configure() (src/luminaires/sky.cpp:139-179) and the parts of getDistribution() that depend on the
+// parameters alone (:458-461), from a MTSGPU_LUM_SKY block: derived[MTSGPU_SKY_NDERIVED] =
+//   [0] zenithX [1] zenithY [2] zenithL [3..7] perezX [8..12] perezY [13..17] perezL [18..20] the Perez denominators of
+//   x, y, L [21] sin(thetaS) [22] cos(thetaS) (getAngleBetween, :431-432).
+// Types as the reference's single-precision build: double literals promote each expression to binary64, every store into a Float member rounds to
+// binary32.  The denominators and [21], [22] use the elementary functions of devmath.h in the operation order of
+// getDistribution / getAngleBetween, so the kernels that read them see the bits they would have computed themselves.
+inline void skyConfigure(const float *LP, float *derived) {
+	const float turbidity = LP[1], thetaS = LP[16];
+	const float k[5] = { LP[18], LP[19], LP[20], LP[21], LP[22] };
+	const float theta2 = thetaS * thetaS;
+	const float theta3 = theta2 * thetaS;
+	const float turb2 = turbidity * turbidity;
+	derived[0] = (float) (
+		(+0.00165 * theta3 - 0.00374 * theta2 + 0.00208 * thetaS + 0) * turb2 +
+		(-0.02902 * theta3 + 0.06377 * theta2 - 0.03202 * thetaS + 0.00394) * turbidity +
+		(+0.11693 * theta3 - 0.21196 * theta2 + 0.06052 * thetaS + 0.25885));
+	derived[1] = (float) (
+		(+0.00275 * theta3 - 0.00610 * theta2 + 0.00316 * thetaS + 0) * turb2 +
+		(-0.04214 * theta3 + 0.08970 * theta2 - 0.04153 * thetaS + 0.00515) * turbidity +
+		(+0.15346 * theta3 - 0.26756 * theta2 + 0.06669 * thetaS + 0.26688));
+	const float chi = (float) ((4.0 / 9.0 - turbidity / 120.0) * (kPi - 2 * thetaS));      // M_PI is a binary32 literal (constants.h:45-46)
+	double sChi, cChi;
+	sincos_d((double) chi, sChi, cChi);      // tan(chi): the binary64 sine over the binary64 cosine
+	derived[2] = (float) ((4.0453 * turbidity - 4.9710) * (sChi / cChi) - 0.2155 * turbidity + 2.4192);
+	float *perezX = derived + 3, *perezY = derived + 8, *perezL = derived + 13;
+	perezL[0] = (float) (( 0.17872 * turbidity - 1.46303) * k[0]);
+	perezL[1] = (float) ((-0.35540 * turbidity + 0.42749) * k[1]);
+	perezL[2] = (float) ((-0.02266 * turbidity + 5.32505) * k[2]);
+	perezL[3] = (float) (( 0.12064 * turbidity - 2.57705) * k[3]);
+	perezL[4] = (float) ((-0.06696 * turbidity + 0.37027) * k[4]);
+	perezX[0] = (float) ((-0.01925 * turbidity - 0.25922) * k[0]);
+	perezX[1] = (float) ((-0.06651 * turbidity + 0.00081) * k[1]);
+	perezX[2] = (float) ((-0.00041 * turbidity + 0.21247) * k[2]);
+	perezX[3] = (float) ((-0.06409 * turbidity - 0.89887) * k[3]);
+	perezX[4] = (float) ((-0.00325 * turbidity + 0.04517) * k[4]);
+	perezY[0] = (float) ((-0.01669 * turbidity - 0.26078) * k[0]);
+	perezY[1] = (float) ((-0.09495 * turbidity + 0.00921) * k[1]);
+	perezY[2] = (float) ((-0.00792 * turbidity + 0.21023) * k[2]);
+	perezY[3] = (float) ((-0.04405 * turbidity - 1.65369) * k[3]);
+	perezY[4] = (float) ((-0.01092 * turbidity + 0.05291) * k[4]);
+	float sinThetaS, cosThetaS;
+	dsincos(thetaS, sinThetaS, cosThetaS);
+	for (int i = 0; i < 3; ++i) {
+		const float *lam = derived + 3 + 5 * i;
+		derived[18 + i] = (1 + lam[0] * dexp(lam[1])) * (1 + lam[2] * dexp(lam[3] * thetaS) + lam[4] * cosThetaS * cosThetaS);
+	}
+	derived[21] = sinThetaS; derived[22] = cosThetaS;
+	derived[23] = 0.0f;
+}
+// What the kernels require of a sky luminaire (the flattener and mtsgpu_upload_scene both ask here): it is the scene's
+// background luminaire, its parameters are finite, its bounding sphere has a positive radius, and the two divisions of
+// getSkySpectralRadiance / getDistribution (Y / y, num / den; sky.cpp:463,484) have non-zero divisors.  Returns the reason,
+// or an empty string; derivedOut (MTSGPU_SKY_NDERIVED floats, optional) receives what skyConfigure derived on the way.
+inline std::string checkSkyLuminaire(uint32_t l, const float *LP, int32_t background_lum, float *derivedOut = nullptr) {
+	const std::string who = "luminaire " + std::to_string(l) + ": ";
+	if ((int32_t) l != background_lum) return who + "the sky must be the background luminaire";
+	for (int i = 0; i <= 22; ++i) if (!std::isfinite(LP[i])) return who + "non-finite sky parameter";
+	if (!(LP[6] > 0.0f)) return who + "the sky's bounding sphere needs a positive radius";
+	float own[MTSGPU_SKY_NDERIVED];
+	float *derived = derivedOut ? derivedOut : own;
+	skyConfigure(LP, derived);
+	for (int i = 0; i < MTSGPU_SKY_NDERIVED; ++i) if (!std::isfinite(derived[i])) return who + "non-finite derived sky quantity (sky.cpp:139-179)";
+	if (derived[1] == 0.0f) return who + "the sky's zenith y is zero (Y / y, sky.cpp:484)";
+	for (int i = 0; i < 3; ++i) if (derived[18 + i] == 0.0f) return who + "a Perez denominator of the sky is zero (sky.cpp:463)";
+	return std::string();
 }
 
 void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs);

@@ -112,6 +112,9 @@ struct DScene {
 	int32_t background_lum;
 	uint32_t n_lums, n_nodes, n_tris, n_shapes;
 	float aabb_min[3], aabb_max[3];
+	// SkyLuminaire::configure() of the background luminaire (skyConfigure, host.h: MTSGPU_SKY_NDERIVED floats), NULL when the
+	// background is not a sky: the shading launches pick their sky instantiations by it
+	const float *sky;
 };
 
 // What k_trace needs of the scene (a kernel argument: the fewer scalar registers it pins, the fewer get spilled)
@@ -325,6 +328,9 @@ void launch_bsdf_eval(hipStream_t s, uint32_t type, const float *params, int op,
 // the same for entry `index` of a BSDF table in device memory, types[n_bsdfs] / params[n_bsdfs][16] (a composite reads its children there)
 void launch_bsdf_eval_table(hipStream_t s, const uint32_t *types, const float *params, uint32_t index, int op, uint32_t n,
                             const float *queries, float *out);
+// the sky luminaire (mtsgpu_lum_eval): Le (op 0), sample (1), pdf (2) for n query records [n][6]; block = the parameter
+// block followed by its derived array, in device memory; out [n][12]
+void launch_sky_eval(hipStream_t s, const float *block, int op, uint32_t n, const float *queries, float *out);
 void launch_generate(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                      const uint32_t *pixel_list, uint32_t n_slots, const uint32_t *explicit_samples,
                      uint32_t n_paths, uint32_t *queue);

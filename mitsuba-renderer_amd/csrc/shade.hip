@@ -161,8 +161,71 @@ __device__ __forceinline__ float env_pdf(const DScene &sc, const float *LP, V3 l
 	return pdf / (psx * psy * sinTheta);
 }
 
+// ---- SkyLuminaire (src/luminaires/sky.cpp): the Preetham / Perez daylight model ----
+// getDistribution (sky.cpp:451-464) with the terms all three calls share passed in: cos(theta_fin), gamma, cos(gamma);
+// lam = five Perez coefficients, den = their denominator (a function of the parameters alone, derived on the host)
+__device__ __forceinline__ float sky_distribution(const float *lam, float den, float cosThetaFin, float gamma, float cosGamma) {
+	const float num = (1 + lam[0] * dexp(lam[1] / cosThetaFin)) * (1 + lam[2] * dexp(lam[3] * gamma) + lam[4] * cosGamma * cosGamma);
+	return num / den;
+}
+// Le(direction) (sky.cpp:235-267, getSkySpectralRadiance :469-495, getAngleBetween :429-439); LP = the luminaire's
+// parameter block, SD = what SkyLuminaire::configure() derives from it (skyConfigure, host.h).  Both are wave-uniform.
+__device__ __forceinline__ V3 sky_le(const float *LP, const float *SD, V3 dir) {
+	const float *M = LP + 7;
+	V3 d = normalize(V3(M[0] * dir.x + M[1] * dir.y + M[2] * dir.z, M[3] * dir.x + M[4] * dir.y + M[5] * dir.z, M[6] * dir.x + M[7] * dir.y + M[8] * dir.z));
+	if (LP[2] != 0.0f && d.z < 0.0f)
+		return V3(0.0f, 0.0f, 0.0f);
+	if (d.z < 0.001f)
+		d = normalize(V3(d.x, d.y, 0.001f));
+	// toSphericalCoordinates (util.cpp:618-626)
+	const float theta = dacos(d.z);
+	float phi = datan2(d.y, d.x);
+	if (phi < 0) phi += 2 * kPi;                          // M_PI is a binary32 literal here (constants.h:45-46)
+	const float thetaFin = smin(theta, (kPi * 0.5f) - 0.001f);
+	// getAngleBetween(theta, phi, thetaS, phiS)
+	float sinTheta, cosTheta;
+	dsincos(theta, sinTheta, cosTheta);
+	const float cospsi = sinTheta * SD[21] * dcos(LP[17] - phi) + cosTheta * SD[22];
+	float gamma;
+	if (cospsi > 1.0f) gamma = 0.0f;
+	else if (cospsi < -1.0f) gamma = kPi;
+	else gamma = dacos(cospsi);
+	const float cosGamma = dcos(gamma), cosThetaFin = dcos(thetaFin);
+	const float x = SD[0] * sky_distribution(SD + 3, SD[18], cosThetaFin, gamma, cosGamma);
+	const float y = SD[1] * sky_distribution(SD + 8, SD[19], cosThetaFin, gamma, cosGamma);
+	const float Y = SD[2] * sky_distribution(SD + 13, SD[20], cosThetaFin, gamma, cosGamma);
+	// xyY -> XYZ
+	const float yFrac = Y / y;
+	const float X = yFrac * x;
+	const float z = smax(0.0f, 1.0f - x - y);
+	const float Z = yFrac * z;
+	// Spectrum::fromXYZ, RGB (spectrum.cpp:94-98), clampNegative (spectrum.h:331-334), L *= m_skyScale
+	const float r = 3.240479f * X + -1.537150f * Y + -0.498535f * Z;
+	const float g = -0.969256f * X + 1.875991f * Y + 0.041556f * Z;
+	const float b = 0.055648f * X + -0.204043f * Y + 1.057311f * Z;
+	return V3(smax(0.0f, r) * LP[0], smax(0.0f, g) * LP[0], smax(0.0f, b) * LP[0]);
+}
+// SkyLuminaire::sample + sampleDirection (sky.cpp:277-281, :415-421): a uniform direction, pdf 1 / (4 pi), value Le(-d), the
+// shadow ray ends at p - d * (2 radius); no bounding-sphere test, no normal.  Used by sample_luminaire and by the read-out hook.
+__device__ __forceinline__ void sky_sample(const float *LP, const float *SD, V3 p, float sx, float sy, V3 &d, float &pdf, V3 &value, V3 &end) {
+	d = squareToSphere(sx, sy);
+	const float k = 2 * LP[6];
+	pdf = 1.0f / (4 * kPi);
+	value = sky_le(LP, SD, -d);
+	end = V3(p.x - d.x * k, p.y - d.y * k, p.z - d.z * k);
+}
+// the radiance of the background luminaire along a ray that left the scene: constant.cpp:65-67, envmap.cpp:147-153, sky
+template <bool SKY>
+__device__ __forceinline__ V3 background_le(const DScene &sc, V3 rayD) {
+	const float *LP = sc.lum_params + kLumStride * (size_t) sc.background_lum;
+	if (SKY) return sky_le(LP, sc.sky, normalize(rayD));
+	return (sc.lum_type[sc.background_lum] == 5u) ? env_le(sc, LP, normalize(rayD)) : V3(LP[0], LP[1], LP[2]);
+}
+
 // Scene::sampleLuminaire without the visibility test (scene.cpp:396-415):
 // returns true when a shadow ray has to be traced; value is already divided by pdf.
+// SKY: the instantiation for scenes whose background luminaire is a sky (the only one that carries its code)
+template <bool SKY>
 __device__ __forceinline__ bool sample_luminaire(const DScene &sc, V3 p, float s0, float s1, LRec &lRec) {
 	float sx = s0, sy = s1;
 	const int l = dpdf_sample_reuse(sc.lum_sel_cdf, sc.n_lums, sx);
@@ -309,6 +372,9 @@ __device__ __forceinline__ bool sample_luminaire(const DScene &sc, V3 p, float s
 			lRec.pdf = 1.0f;
 			lRec.value = V3(LP[0], LP[1], LP[2]);
 		}
+	} else if (SKY && sc.lum_type[l] == 7u) {
+		sky_sample(LP, sc.sky, p, sx, sy, lRec.d, lRec.pdf, lRec.value, lRec.p);
+		lRec.n = V3(0, 0, 0);
 	} else if (sc.lum_type[l] == 3u) {
 		// DirectionalLuminaire::sample (directional.cpp:84-91)
 		const V3 dir(LP[3], LP[4], LP[5]);
@@ -370,7 +436,7 @@ __device__ __forceinline__ float pdf_luminaire(const DScene &sc, V3 p, int lum, 
 	} else if (sc.lum_type[lum] == 5u) {
 		pdf = env_pdf(sc, sc.lum_params + kLumStride * (size_t) lum, ld);
 	} else {
-		pdf = 1.0f / (4 * kPi);
+		pdf = 1.0f / (4 * kPi);      // ConstantLuminaire::pdf (constant.cpp:89-91), SkyLuminaire::pdf (sky.cpp:288-292)
 	}
 	return pdf * fraction;
 }
@@ -1066,6 +1132,30 @@ __global__ void k_bsdf_eval_table(const uint32_t *types, const float *params, ui
 	for (int k = 0; k < 8; ++k) out[8 * (size_t) i + k] = o[k];
 }
 
+// The sky luminaire read out for n query records (mtsgpu_lum_eval): block = its parameters followed by the derived array
+// (kLumStride + MTSGPU_SKY_NDERIVED floats in device memory); queries [n][6], out [n][12]
+__global__ void k_sky_eval(const float *block, int op, uint32_t n, const float *queries, float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float *LP = block, *SD = block + kLumStride, *q = queries + 6 * (size_t) i;
+	float o[12] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	if (op == 0) {
+		const V3 le = sky_le(LP, SD, V3(q[0], q[1], q[2]));
+		o[0] = le.x; o[1] = le.y; o[2] = le.z;
+	} else if (op == 1) {
+		// the call sample_luminaire<true> makes; the value is reported before that function divides it by the pdf
+		V3 d, le, end; float pdf;
+		sky_sample(LP, SD, V3(q[0], q[1], q[2]), q[3], q[4], d, pdf, le, end);
+		o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = pdf;
+		o[4] = le.x; o[5] = le.y; o[6] = le.z;
+		o[8] = end.x; o[9] = end.y; o[10] = end.z;
+	} else {
+		o[0] = 1.0f / (4 * kPi);      // sky.cpp:288-292
+	}
+	#pragma unroll
+	for (int k = 0; k < 12; ++k) out[12 * (size_t) i + k] = o[k];
+}
+
 __device__ __forceinline__ float mi_weight(float pdfA, float pdfB) {     // path.cpp:218-222
 	pdfA *= pdfA;
 	pdfB *= pdfB;
@@ -1098,7 +1188,7 @@ struct ShadeRow {
 };
 __device__ __forceinline__ uint32_t shade_row_index(uint32_t lane, uint32_t k) { return lane * kRowStride + (MG_SHADE_PACKED ? (k ^ (lane & 7u)) : k); }
 
-template <int BT, bool ROUNDS>
+template <int BT, bool ROUNDS, bool SKY>
 __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, const DConfig &cfg, const uint32_t id,
                                            const float4 ro, const float4 rd, const uint4 h, const float4 T4, const float4 L4,
                                            const ShadeRow row, bool &continues, bool &wantShadow, V3 &neeV, V3 &shO, V3 &shD) {
@@ -1157,9 +1247,8 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 					}
 				} else {
 					if (sc.background_lum >= 0) {
-						const float *LP = sc.lum_params + kLumStride * (size_t) sc.background_lum;
 						llum = sc.background_lum;
-						lvalue = (sc.lum_type[llum] == 5u) ? env_le(sc, LP, normalize(rayD)) : V3(LP[0], LP[1], LP[2]);
+						lvalue = background_le<SKY>(sc, rayD);
 						hitLuminaire = true;
 					} else {
 						if (!direct) depth++;
@@ -1194,8 +1283,7 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			if (!valid) {
 				if (skipToNee || skipToBsdf) break;
 				if ((flags & F_EMITTED) && sc.background_lum >= 0) {
-					const float *LP = sc.lum_params + kLumStride * (size_t) sc.background_lum;
-					const V3 le = (sc.lum_type[sc.background_lum] == 5u) ? env_le(sc, LP, normalize(rayD)) : V3(LP[0], LP[1], LP[2]);
+					const V3 le = background_le<SKY>(sc, rayD);
 					Li.x += thr.x * le.x; Li.y += thr.y * le.y; Li.z += thr.z * le.z;
 				}
 				break;
@@ -1227,15 +1315,15 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				if (ROUNDS && direct && cfg.n_lum > 1) sampler_array2d(cfg, smp, misc_zw.y, 0, (uint32_t) cfg.dr_index, s0, s1);   // direct.cpp:122-123
 				else sampler_next2d(cfg, smp, s0, s1);
 				LRec lRec;
-				if ((!direct || cfg.n_lum > 0) && sample_luminaire(sc, its.p, s0, s1, lRec)) {
+				if ((!direct || cfg.n_lum > 0) && sample_luminaire<SKY>(sc, its.p, s0, s1, lRec)) {
 					const V3 wo = -lRec.d;
 					const V3 woL(dot(wo, its.shS), dot(wo, its.shT), dot(wo, its.shN));
 					V3 bsdfVal = Bsdf2<BT>::f(tab, twoSided, BP, its.wi, woL) * fabsf(woL.z);
 					const float woDotGeoN = dot(its.geoN, wo);
 					if (!isZero(bsdfVal) && (!strict || woDotGeoN * woL.z > 0)) {
 						// isIntersectable() || isBackgroundLuminaire() (path.cpp:118-120): 0 for delta luminaires
-						const uint32_t lt = sc.lum_type[lRec.lum];      // area, constant and envmap luminaires can be hit by BSDF samples
-						const float bsdfPdf = (lt <= 1u || lt == 5u) ? Bsdf2<BT>::pdf(tab, twoSided, BP, its.wi, woL) : 0.0f;
+						const uint32_t lt = sc.lum_type[lRec.lum];      // area, constant, envmap and sky luminaires can be hit by BSDF samples
+						const float bsdfPdf = (lt <= 1u || lt == 5u || (SKY && lt == 7u)) ? Bsdf2<BT>::pdf(tab, twoSided, BP, its.wi, woL) : 0.0f;
 						const float weight = direct ? mi_weight(lRec.pdf * cfg.frac_lum, bsdfPdf * cfg.frac_bsdf) * cfg.weight_lum
 						                            : mi_weight(lRec.pdf, bsdfPdf);          // direct.cpp:143-145
 						// added to Li by k_trace<shadow> iff the segment is unoccluded
@@ -1305,7 +1393,7 @@ struct ShadeShared {
 };
 // One workgroup of k_shade: the paths block * kShadeBlock .. of the material queue whose segment sizes are `prefix`
 // (prefix[kBinShards] entries in kBinShards segments of bin_ids)
-template <int BT, bool ROUNDS>
+template <int BT, bool ROUNDS, bool SKY>
 __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const uint32_t *prefix,
                                             const uint32_t *bin_ids, const uint32_t block, ShadeShared &sh) {
 	uint32_t (&s_cnt)[2][kShadeBlock / 64] = sh.cnt;
@@ -1392,7 +1480,7 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	}
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	if (active)
-		shade_path<BT, ROUNDS>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD);
+		shade_path<BT, ROUNDS, SKY>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD);
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	#pragma unroll
 	for (int r = 0; r < 8; ++r) {
@@ -1439,18 +1527,21 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	}
 }
 
-template <int BT, bool ROUNDS>
+template <int BT, bool ROUNDS, bool SKY>
 __global__ MG_SHADE_BOUNDS void k_shade(DScene sc, DPaths ps, DConfig cfg, DQueues q, BinView view_host,
                                                        const BinView *views_dev, const uint32_t *bin_ids) {
 	__shared__ ShadeShared sh;
 	// the bin's segment sizes: a kernel argument when the host read the counters back, otherwise what k_prep wrote
-	shade_block<BT, ROUNDS>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh);
+	shade_block<BT, ROUNDS, SKY>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh);
 }
 
 // All material queues of a bounce in ONE launch (device-driven bounces): the workgroups are dealt to the bins in bin order,
 // ceil(size / kShadeBlock) each, the sizes read from what k_prep left in device memory.  A frame of few paths is a chain of
 // short launches, and a launch of k_shade -- 1024 threads and 148 KB of LDS per workgroup -- costs 10-20 us even when
 // nearly all of its worst-case grid exits at once: one launch per bounce instead of one per BSDF type present.
+// SKY: the launch for scenes whose background is a sky (launch_shade_all picks it): every other scene runs the instantiation
+// without that code, whose registers are what they were before the sky existed
+template <bool SKY>
 __global__ MG_SHADE_BOUNDS void k_shade_all(DScene sc, DPaths ps, DConfig cfg, DQueues q, const BinView *views_dev, uint32_t bin_mask) {
 	__shared__ ShadeShared sh;
 	uint32_t block = blockIdx.x;
@@ -1464,17 +1555,17 @@ __global__ MG_SHADE_BOUNDS void k_shade_all(DScene sc, DPaths ps, DConfig cfg, D
 	if (bin < 0) return;
 	const uint32_t *prefix = views_dev[bin].prefix, *ids = q.bin(bin);
 	switch (bin) {
-		case 0: shade_block<0, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 1: shade_block<1, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 2: shade_block<2, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 3: shade_block<3, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 4: shade_block<4, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 5: shade_block<5, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 6: shade_block<6, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 7: shade_block<7, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 8: shade_block<8, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		case 0: shade_block<0, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		case 1: shade_block<1, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		case 2: shade_block<2, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		case 3: shade_block<3, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		case 4: shade_block<4, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		case 5: shade_block<5, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		case 6: shade_block<6, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		case 7: shade_block<7, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		case 8: shade_block<8, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
 		case 9: return;      // the composite's loop over its children is launched on its own (kShadeAllBins)
-		default: shade_block<kNumBsdfTypes, false>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		default: shade_block<kNumBsdfTypes, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
 	}
 }
 
@@ -1489,14 +1580,22 @@ void launch_bsdf_eval_table(hipStream_t s, const uint32_t *types, const float *p
 	if (n) hipLaunchKernelGGL(k_bsdf_eval_table, dim3(blocks_for(n, 256)), dim3(256), 0, s, types, params, index, op, n, queries, out);
 }
 
+void launch_sky_eval(hipStream_t s, const float *block, int op, uint32_t n, const float *queries, float *out) {
+	if (n) hipLaunchKernelGGL(k_sky_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, block, op, n, queries, out);
+}
+
 void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                   const DQueues &q, const BinView &view, const BinView *views_dev, uint32_t n_bound, const uint32_t *bin_ids) {
 	const uint32_t n = views_dev ? n_bound : view.prefix[kBinShards];
 	if (!n) return;
 	if (!bin_ids) bin_ids = q.bin(bin);
 	const dim3 g(blocks_for(n, kShadeBlock)), b(kShadeBlock);
-	#define MG_SHADE(BT) do { if (cfg.dr_mode != 0) hipLaunchKernelGGL((k_shade<BT, true>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids); \
-	                          else hipLaunchKernelGGL((k_shade<BT, false>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids); } while (0)
+	// a scene whose background is a sky carries its derived block (DScene::sky) and runs the sky instantiations
+	const bool sky = sc.sky != nullptr;
+	#define MG_SHADE(BT) do { if (cfg.dr_mode != 0) { if (sky) hipLaunchKernelGGL((k_shade<BT, true, true>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids); \
+	                                                  else hipLaunchKernelGGL((k_shade<BT, true, false>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids); } \
+	                          else if (sky) hipLaunchKernelGGL((k_shade<BT, false, true>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids); \
+	                          else hipLaunchKernelGGL((k_shade<BT, false, false>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids); } while (0)
 	switch (bin) {
 		case 0: MG_SHADE(0); break;
 		case 1: MG_SHADE(1); break;
@@ -1519,7 +1618,8 @@ void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const D
 	if (!n_bound || !bin_mask) return;
 	// every bin rounds its size up to whole workgroups
 	const unsigned blocks = blocks_for(n_bound, kShadeBlock) + (unsigned) __builtin_popcount(bin_mask);
-	hipLaunchKernelGGL(k_shade_all, dim3(blocks), dim3(kShadeBlock), 0, s, sc, ps, cfg, q, views_dev, bin_mask);
+	if (sc.sky) hipLaunchKernelGGL(k_shade_all<true>, dim3(blocks), dim3(kShadeBlock), 0, s, sc, ps, cfg, q, views_dev, bin_mask);
+	else hipLaunchKernelGGL(k_shade_all<false>, dim3(blocks), dim3(kShadeBlock), 0, s, sc, ps, cfg, q, views_dev, bin_mask);
 }
 
 } // namespace mg

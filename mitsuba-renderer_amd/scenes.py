@@ -179,6 +179,41 @@ class SceneDescription:
         assert self.env_bitmap.ndim == 3 and self.env_bitmap.shape[2] == 3
         return l
 
+    def sky(self, sun_direction=None, latitude=None, longitude=None, standard_meridian=None, julian_day=None, time_of_day=None,
+            turbidity=2.0, sky_scale=1.0, a=1.0, b=1.0, c=1.0, d=1.0, e=1.0, clip_below_horizon=True, to_world=None):
+        """<luminaire type="sky"> as its constructor leaves it (src/luminaires/sky.cpp:47-103), float32 arithmetic: the sun
+        is placed EITHER by a direction (+x south, +y east, +z up) OR by latitude, longitude, standardMeridian, julianDay and
+        timeOfDay, all five; with neither, the defaults of the reference apply.  to_world: 3x3 rotation (row major).  The
+        block holds world->luminaire = inverse(rotate(x, -90 deg) * toWorld), thetaS and phiS; the flattener adds the
+        bounding sphere."""
+        loc = [latitude, longitude, standard_meridian, julian_day, time_of_day]
+        has_dir, has_some, has_all = sun_direction is not None, any(v is not None for v in loc), all(v is not None for v in loc)
+        if not (has_dir or has_some):
+            has_some = has_all = True
+        elif has_dir and has_some:
+            raise ValueError("Please decide for either positioning the sun by a direction vector or by some location and time information.")
+        elif has_some and not has_all:
+            raise ValueError("Please give all required parameters for specifing the sun's position by location and time information. "
+                             "At least one is missing.")
+        if has_dir:
+            theta_s, phi_s = sky_sun_from_direction(sun_direction)
+        else:
+            dflt = [51.050891, 13.694458, 0, 200, 22.00]
+            theta_s, phi_s = sky_sun_from_location(*[dv if v is None else v for v, dv in zip(loc, dflt)])
+        # Transform::rotate(Vector(1, 0, 0), -90) (transform.cpp:72-98) * toWorld, and its inverse (a rotation: the transpose)
+        ang = F(-90.0) * (F(np.pi) / F(180.0))                 # degToRad
+        sn, cs = F(np.sin(ang)), F(np.cos(ang))
+        rot = np.array([[1, 0, 0], [0, cs, -sn], [0, sn, cs]], dtype=np.float32)
+        tw = np.eye(3, dtype=np.float32) if to_world is None else np.asarray(to_world, dtype=np.float32).reshape(3, 3)
+        l2w = (rot.astype(np.float64) @ tw.astype(np.float64)).astype(np.float32)
+        w2l = np.linalg.inv(l2w.astype(np.float64)).astype(np.float32)
+        l = self.add_lum(abi.LUM_SKY, [sky_scale, turbidity, 1.0 if clip_below_horizon else 0.0])
+        P = self.lum_params[l]
+        P[7:16] = w2l.ravel()
+        P[16], P[17] = theta_s, phi_s
+        P[18:23] = np.asarray([a, b, c, d, e], dtype=np.float32)
+        return l
+
     def add_lum(self, ltype, intensity):
         p = np.zeros(abi.LUM_NPARAMS, dtype=np.float32)
         p[:3] = np.asarray(intensity, dtype=np.float32)
@@ -239,6 +274,42 @@ class SceneDescription:
             keep.append(self.env_bitmap)
         keep += [meshes, bt, bp, lt, lp]
         return d, keep
+
+
+# ---------------------------------------------------------------------------
+# the sun of the sky luminaire
+# ---------------------------------------------------------------------------
+def sky_sun_from_direction(sun_direction):
+    """SkyLuminaire::configureSunPosition(const Vector &) (sky.cpp:214-219): toSphericalCoordinates of the normalised
+    direction (util.cpp:618-626) -> (thetaS, phiS) as float32"""
+    v = np.asarray(sun_direction, dtype=np.float32)
+    v = v * (F(1) / np.sqrt((v * v).sum(dtype=np.float32), dtype=np.float32))
+    theta = F(np.arccos(np.float64(np.clip(v[2], -1, 1))))
+    phi = F(np.arctan2(np.float64(v[1]), np.float64(v[0])))
+    if phi < 0:
+        phi = phi + F(2) * F(np.pi)                          # M_PI is a float literal in the single-precision build (constants.h:45-46)
+    return theta, phi
+
+
+def sky_sun_from_location(lat, lon, std_mrd, jul_day, time_of_day):
+    """SkyLuminaire::configureSunPosition(lat, lon, int stdMrd, int julDay, timeOfDay) (sky.cpp:186-208, IES Lighting
+    Handbook p. 361): standardMeridian and julianDay are truncated to int by the call; M_PI is a float, double literals
+    promote their expression to double, every const Float rounds to float32"""
+    D = np.float64
+    lat, lon, time_of_day = F(lat), F(lon), F(time_of_day)
+    std_mrd, jul_day = int(F(std_mrd)), int(F(jul_day))
+    pi = F(np.pi)
+    solar_time = F(D(time_of_day)
+                   + (0.170 * np.sin(4.0 * D(pi) * (jul_day - 80.0) / 373.0) - 0.129 * np.sin(2.0 * D(pi) * (jul_day - 8.0) / 355.0))
+                   + D(F(std_mrd) - lon) / 15.0)
+    decl = F(0.4093 * D(np.sin(F(2) * pi * F(jul_day - 81) / F(368))))
+    rlat = lat * (pi / F(180.0))                             # degToRad
+    hour = D(pi * solar_time) / 12.0
+    altitude = F(np.arcsin(D(np.sin(rlat) * np.sin(decl)) - D(np.cos(rlat) * np.cos(decl)) * np.cos(hour)))
+    opp = F(D(-np.cos(decl)) * np.sin(hour))
+    adj = F(-(D(np.cos(rlat) * np.sin(decl)) + D(np.sin(rlat) * np.cos(decl)) * np.cos(hour)))
+    azimuth = F(np.arctan2(opp, adj))
+    return F(D(pi) / 2.0 - D(altitude)), F(-azimuth)
 
 
 # ---------------------------------------------------------------------------

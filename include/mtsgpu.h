@@ -301,7 +301,8 @@ int  mtsgpu_set_options(mtsgpu_ctx *ctx, uint64_t max_paths, int count_traversal
  *   sync_free (-1 rule, 0 off, 1 on)          bounce loop without host round trips (device-side counts); the rule
  *                                             turns it on for passes of at most 8 Mi paths
  *   chunk (1..1024, default 8)                bounces enqueued between two looks at the queue size (sync_free)
- *   test_retry (0/1)                          treat every first closest-hit launch as overflowed (exercises the retry) */
+ *   test_retry (0/1)                          treat every first closest-hit launch as overflowed (exercises the retry)
+ *   stats_wave (-1 rule, 0 lane, 1 wave)      form of the variance kernel of the test-case mode (below) */
 int  mtsgpu_set_tuning(mtsgpu_ctx *ctx, const char *key, long value);
 
 /* --- the hot path (replaces SampleIntegrator::render, integrator.cpp:87-120) */
@@ -311,6 +312,27 @@ int  mtsgpu_sync(mtsgpu_ctx *ctx);
 int  mtsgpu_read_film(mtsgpu_ctx *ctx, float *rgbaw);
 int  mtsgpu_clear_film(mtsgpu_ctx *ctx);
 int  mtsgpu_get_stats(mtsgpu_ctx *ctx, mtsgpu_stats *out);
+
+/* --- test-case mode (`mitsuba -t`): per-pixel variance next to the film ---------------------------------------
+ * What an ImageBlock with statistics collects (renderproc.cpp:44-50): SampleIntegrator::renderBlock runs Knuth's online
+ * recurrence over the Li values of a pixel's sampleCount camera samples, in sample order, in binary32 per channel
+ * (integrator.cpp:171-202):
+ *     delta = spec - mean;  mean += delta * (1 / (float) (j + 1));  msq += delta * (spec - mean)
+ * over EVERY sample -- also one ImageBlock::putSample rejects as invalid -- and keeps the last setVariance of a pixel:
+ *     variance = msq * (1 / (float) (sampleCount - 1)),  nSamples = sampleCount.
+ * With sampleCount == 1 that reciprocal is +inf and the stored variance is 0 * inf = NaN, as in the reference.  Pixels
+ * this context does not render (tiles of other parts) keep variance 0, nSamples 0.  The film sums do not change.
+ * The reference collects statistics with the box filter only (renderjob.cpp:96-99, mfilm.cpp:145): mtsgpu_render with
+ * the mode on and a wider filter fails with MTSGPU_EINVAL and leaves the context usable.  mtsgpu_clear_film clears the
+ * statistics too.  MFilm::develop's .m file and TestSupervisor::analyze's t-test live in the Python package (testmode.py).
+ * Tuning key `stats_wave` (-1 rule, 0 one lane per pixel, 1 one wave per pixel) picks the form of the variance kernel. */
+int  mtsgpu_set_film_statistics(mtsgpu_ctx *ctx, int on);
+/* host copies of the variance [H][W][3] f32 and the sample counts [H][W] u32 (crop-window coordinates, like the film);
+ * MTSGPU_ESTATE while the mode is off */
+int  mtsgpu_read_film_statistics(mtsgpu_ctx *ctx, float *var3, uint32_t *nsamp);
+/* which form of the variance kernel the last pass of the last mtsgpu_render ran: 0 lane per pixel, 1 wave per pixel,
+ * -1 none (mode off, nothing rendered) */
+int  mtsgpu_film_statistics_form(const mtsgpu_ctx *ctx);
 
 /* --- several GPUs in one process -------------------------------------------------------------------------
  * A group owns one ctx per entry of devs[] (entries may repeat: two ctx on one GPU is how the single-GPU test box
@@ -358,6 +380,11 @@ const char *mtsgpu_group_reduce_note(const mtsgpu_group *g);
 /* mtsgpu_set_tuning on every member.  One key belongs to the group itself and exists for tests: "rccl_fail" != 0 makes
  * the next collectives report a failure, which exercises the fall-back to the ordered sum. */
 int  mtsgpu_group_set_tuning(mtsgpu_group *g, const char *key, long value);
+/* mtsgpu_set_film_statistics on every member.  With the box filter every pixel belongs to exactly one member: after
+ * mtsgpu_group_render member 0 holds the statistics of all members, copied pixel by pixel in member order (peer copies
+ * like the ordered film sum; the u32 counts never pass through the f32 collective, and the film reduce is unchanged);
+ * mtsgpu_read_film_statistics(mtsgpu_group_ctx(g, 0)) returns them. */
+int  mtsgpu_group_set_film_statistics(mtsgpu_group *g, int on);
 
 /* HBM triad a[i] = b[i] + s * c[i] over three arrays of `bytes` each on `device` (float4 lanes, best of `iters`
  * launches): the practical bandwidth roof next to the 8 TB/s specification.  GB/s in *gbs. */

@@ -51,7 +51,8 @@ namespace {
 /* ImageBlock keeps its alpha channel protected and has no setter (include/mitsuba/render/imageblock.h:277-297) */
 class FilmBlock : public ImageBlock {
 public:
-	FilmBlock(const Vector2i &maxSize) : ImageBlock(maxSize, 0, true, true, false, false) { }   /* imageblock.h:64-66 */
+	/* statistics: per-pixel variance and sample count, the test-case mode (renderproc.cpp:44-50) */
+	FilmBlock(const Vector2i &maxSize, bool statistics = false) : ImageBlock(maxSize, 0, true, true, false, statistics) { }   /* imageblock.h:64-66 */
 	inline void setAlpha(size_t idx, Float a) { alpha[idx] = a; }
 };
 
@@ -489,6 +490,13 @@ struct GPURenderDriver {
 		for (int i = 0; i < mtsgpu_group_size(group); ++i)
 			check(mtsgpu_set_film_edges(mtsgpu_group_ctx(group, i), film->hasHighQualityEdges() ? 1 : 0), mtsgpu_group_ctx(group, i));   /* film.h:75 */
 
+		/* --- test-case mode (`mitsuba -t`): a scene that asks for a t-test gets blocks with statistics
+		 *     (renderproc.cpp:44-50); the device then runs the variance recurrence of SampleIntegrator::renderBlock
+		 *     (integrator.cpp:171-202).  Like the reference, only with the box filter (renderjob.cpp:96-99): the library
+		 *     refuses the render otherwise. --- */
+		const bool statistics = scene->getTestType() == Scene::ETTest;                            /* scene.h:434 */
+		check(mtsgpu_group_set_film_statistics(group, statistics ? 1 : 0));
+
 		/* --- render: tiles sharded over the GPUs, films summed on GPU 0 (renderproc.cpp:123-130 in one collective) --- */
 		cancelFlag = 0;
 		const int bs = scene->getBlockSize();                                                     /* scene.h:543 */
@@ -507,8 +515,13 @@ struct GPURenderDriver {
 		 *     The sums of the crop window go out as border-less blocks: the filter has been applied already. --- */
 		std::vector<float> rgbaw((size_t) cam.width * cam.height * 5);
 		check(mtsgpu_read_film(mtsgpu_group_ctx(group, 0), &rgbaw[0]), mtsgpu_group_ctx(group, 0));
+		std::vector<float> var3; std::vector<uint32_t> nsamp;
+		if (statistics) {
+			var3.resize((size_t) cam.width * cam.height * 3); nsamp.resize((size_t) cam.width * cam.height);
+			check(mtsgpu_read_film_statistics(mtsgpu_group_ctx(group, 0), &var3[0], &nsamp[0]), mtsgpu_group_ctx(group, 0));
+		}
 		for (int y0 = 0; y0 < cam.height; y0 += bs) for (int x0 = 0; x0 < cam.width; x0 += bs) {
-			ref<FilmBlock> block = new FilmBlock(Vector2i(bs, bs));
+			ref<FilmBlock> block = new FilmBlock(Vector2i(bs, bs), statistics);
 			block->setOffset(Point2i(x0 + cropOffset.x, y0 + cropOffset.y));                     /* imageblock.h:261 */
 			block->setSize(Vector2i(std::min(bs, cam.width - x0), std::min(bs, cam.height - y0)));
 			block->clear();
@@ -517,6 +530,13 @@ struct GPURenderDriver {
 				const float *p = &rgbaw[5 * ((size_t) (y0 + y) * cam.width + (x0 + x))];
 				Spectrum s; s.fromLinearRGB(p[0], p[1], p[2]);
 				block->setPixel(idx, s); block->setAlpha(idx, p[3]); block->setWeight(idx, p[4]);   /* spectrum, alpha, weight sums */
+				if (statistics) {
+					/* before putImageBlock, so that MFilm takes its statistics branch (mfilm.cpp:144-170); setVariance takes
+					 * raster coordinates and subtracts the block's offset itself (imageblock.h:247-252) */
+					const size_t fp = (size_t) (y0 + y) * cam.width + (x0 + x);
+					Spectrum v; v.fromLinearRGB(var3[3 * fp], var3[3 * fp + 1], var3[3 * fp + 2]);
+					block->setVariance(x0 + x + cropOffset.x, y0 + y + cropOffset.y, v, nsamp[fp]);
+				}
 			}
 			film->putImageBlock(block);                                                           /* renderproc.cpp:126 */
 			queue->signalWorkEnd(job, block);                                                     /* renderproc.cpp:128 */

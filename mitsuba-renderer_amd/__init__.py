@@ -16,7 +16,8 @@ import subprocess
 
 import numpy as np
 
-from . import abi, scenes, filmreduce  # noqa: F401
+from . import abi, scenes, filmreduce, testmode  # noqa: F401
+from .testmode import write_mfile, analyze  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MTSGPU_LIB selects an experiment build (tools/build_variant.sh); the product is libmtsgpu.so next to this file
@@ -34,6 +35,7 @@ EXPORTS = [
     "mtsgpu_group_upload_scene", "mtsgpu_group_set_camera", "mtsgpu_group_set_integrator", "mtsgpu_group_set_sampler",
     "mtsgpu_group_set_rfilter", "mtsgpu_group_render", "mtsgpu_group_last_reduce_kind", "mtsgpu_group_rccl_ranks", "mtsgpu_group_reduce_note", "mtsgpu_bsdf_eval", "mtsgpu_bsdf_eval_table", "mtsgpu_replay_roof", "mtsgpu_group_set_tuning",
     "mtsgpu_sky_configure", "mtsgpu_lum_eval",
+    "mtsgpu_set_film_statistics", "mtsgpu_read_film_statistics", "mtsgpu_film_statistics_form", "mtsgpu_group_set_film_statistics",
 ]
 
 
@@ -183,6 +185,10 @@ def lib():
     L.mtsgpu_group_rccl_ranks.argtypes = [vp]
     L.mtsgpu_group_reduce_note.argtypes = [vp]; L.mtsgpu_group_reduce_note.restype = C.c_char_p
     L.mtsgpu_group_set_tuning.argtypes = [vp, C.c_char_p, C.c_long]
+    L.mtsgpu_set_film_statistics.argtypes = [vp, C.c_int]
+    L.mtsgpu_read_film_statistics.argtypes = [vp, f32p, u32p]
+    L.mtsgpu_film_statistics_form.argtypes = [vp]
+    L.mtsgpu_group_set_film_statistics.argtypes = [vp, C.c_int]
     _lib = L
     return L
 
@@ -389,6 +395,24 @@ class MIPathTracer:
         self._chk(lib().mtsgpu_get_stats(self._ctx, C.byref(st)), "get_stats")
         return st.as_dict()
 
+    # --- test-case mode (`mitsuba -t`, testmode.py) -----------------------------
+    def set_film_statistics(self, on=True):
+        """ImageBlocks with statistics (renderproc.cpp:44-50): render() also runs the per-pixel variance recurrence of
+        SampleIntegrator::renderBlock (integrator.cpp:171-202).  Box filter only, as in the reference."""
+        self._chk(lib().mtsgpu_set_film_statistics(self._ctx, int(bool(on))), "set_film_statistics")
+
+    def film_statistics(self):
+        """(variance [H][W][3] float32, nSamples [H][W] uint32) of the last render; pixels not rendered hold 0, 0"""
+        cam = self.camera.c if hasattr(self.camera, "c") else self.camera
+        var = np.zeros((cam.height, cam.width, 3), dtype=np.float32)
+        n = np.zeros((cam.height, cam.width), dtype=np.uint32)
+        self._chk(lib().mtsgpu_read_film_statistics(self._ctx, abi.ptr(var, abi.f32p), abi.ptr(n, abi.u32p)), "read_film_statistics")
+        return var, n
+
+    def film_statistics_form(self):
+        """the form of the variance kernel the last pass ran: "lane", "wave" or None"""
+        return {0: "lane", 1: "wave"}.get(lib().mtsgpu_film_statistics_form(self._ctx))
+
     # --- kernels exposed for parity tests --------------------------------------
     def trace_rays(self, rays, shadow=False):
         r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
@@ -573,6 +597,18 @@ class DeviceGroup:
         if rc != 0:
             raise MtsGpuError("read_film: %s" % lib().mtsgpu_last_error(self.member(0)).decode())
         return out
+
+    def set_film_statistics(self, on=True):
+        """test-case mode on every member; member 0 holds the merged statistics after render()"""
+        self._chk(lib().mtsgpu_group_set_film_statistics(self._g, int(bool(on))), "group_set_film_statistics")
+
+    def film_statistics(self):
+        var = np.zeros((self.camera.c.height, self.camera.c.width, 3), dtype=np.float32)
+        n = np.zeros((self.camera.c.height, self.camera.c.width), dtype=np.uint32)
+        rc = lib().mtsgpu_read_film_statistics(self.member(0), abi.ptr(var, abi.f32p), abi.ptr(n, abi.u32p))
+        if rc != 0:
+            raise MtsGpuError("read_film_statistics: %s (code %d)" % (lib().mtsgpu_last_error(self.member(0)).decode(), rc))
+        return var, n
 
     def member_stats(self, i):
         st = abi.Stats()

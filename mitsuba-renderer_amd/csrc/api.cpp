@@ -109,7 +109,9 @@ uint64_t defaultMaxPaths(mtsgpu_ctx *c) {
 	size_t freeB = 0, totalB = 0;
 	if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
 		// what this context already holds for its passes is free for the next one
-		const uint64_t avail = (uint64_t) freeB + (uint64_t) c->pathCap * kBytesPerPath;
+		uint64_t avail = (uint64_t) freeB + (uint64_t) c->pathCap * kBytesPerPath;
+		// test-case mode: 16 bytes of statistics per film pixel (variance 3 x f32, count u32), if not allocated yet
+		if (c->filmStats && !c->statVar) avail -= std::min<uint64_t>(avail, 16ull * (uint64_t) c->cam.width * (uint64_t) c->cam.height);
 		paths = std::min<uint64_t>(paths, std::max<uint64_t>(1ull << 16, avail * 6 / 10 / kBytesPerPath));
 	}
 	return paths;
@@ -702,6 +704,8 @@ void mtsgpu_destroy(mtsgpu_ctx *c) {
 	if (c->pathLen) (void) hipFree(c->pathLen);
 	if (c->explicitSamples) (void) hipFree(c->explicitSamples);
 	if (c->filtValues) (void) hipFree(c->filtValues);
+	if (c->statVar) (void) hipFree(c->statVar);
+	if (c->statN) (void) hipFree(c->statN);
 	if (c->tileMeta) (void) hipFree(c->tileMeta);
 	if (c->blocks) (void) hipFree(c->blocks);
 	if (c->hostCounters) (void) hipHostFree(c->hostCounters);
@@ -1110,7 +1114,7 @@ int mtsgpu_set_tuning(mtsgpu_ctx *c, const char *key, long value) {
 	if (!c || !key) return fail(c, MTSGPU_EINVAL, "null argument");
 	struct Knob { const char *key; long lo, hi; };
 	static const Knob knobs[] = { { "refill_min", 1, 64 }, { "desc_min", 1, 64 }, { "leaf_min", 1, 64 }, { "batch", 0, 64 },
-	                              { "dyn_div", 0, 1 << 20 }, { "test_retry", 0, 1 }, { "sync_free", -1, 1 }, { "chunk", 1, 1024 }, { "blocks_per_cu", 0, (long) kTraceBlocksPerCuMax }, { "plain_below", 0, 1 << 30 }, { "dyn_min_rounds", 0, 1 << 20 }, { "shade_fused", 0, 1 }, { "ray_queues", 0, 1 }, { "nee_parked", 0, 1 } };
+	                              { "dyn_div", 0, 1 << 20 }, { "test_retry", 0, 1 }, { "sync_free", -1, 1 }, { "chunk", 1, 1024 }, { "blocks_per_cu", 0, (long) kTraceBlocksPerCuMax }, { "plain_below", 0, 1 << 30 }, { "dyn_min_rounds", 0, 1 << 20 }, { "shade_fused", 0, 1 }, { "ray_queues", 0, 1 }, { "nee_parked", 0, 1 }, { "stats_wave", -1, 1 } };
 	for (const Knob &k : knobs)
 		if (std::strcmp(k.key, key) == 0) {
 			if (value < k.lo || value > k.hi) return fail(c, MTSGPU_EINVAL, "tuning knob %s: %ld outside [%ld, %ld]", key, value, k.lo, k.hi);
@@ -1139,10 +1143,59 @@ static int ensureFilm(mtsgpu_ctx *c) {
 	return 0;
 }
 
+// the statistics buffers of the test-case mode, zeroed when (re)allocated: sized like the film, owned by the context
+static void freeFilmStats(mtsgpu_ctx *c) {
+	if (c->statVar) (void) hipFree(c->statVar);
+	if (c->statN) (void) hipFree(c->statN);
+	c->statVar = nullptr; c->statN = nullptr; c->statPixels = 0;
+}
+static int ensureFilmStats(mtsgpu_ctx *c) {
+	const size_t px = (size_t) c->cam.width * c->cam.height;
+	if (c->statVar && c->statN && c->statPixels == px) return 0;
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	freeFilmStats(c);
+	HIPCHK(c, hipMalloc((void **) &c->statVar, px * 3 * sizeof(float)));
+	HIPCHK(c, hipMalloc((void **) &c->statN, px * sizeof(uint32_t)));
+	HIPCHK(c, hipMemset(c->statVar, 0, px * 3 * sizeof(float)));
+	HIPCHK(c, hipMemset(c->statN, 0, px * sizeof(uint32_t)));
+	c->statPixels = px;
+	return 0;
+}
+
+int mtsgpu_set_film_statistics(mtsgpu_ctx *c, int on) {
+	if (!c) return fail(nullptr, MTSGPU_EINVAL, "null context");
+	HIPCHK(c, hipSetDevice(c->device));
+	c->filmStats = on != 0;
+	c->statsForm = -1;
+	if (!c->filmStats) {
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		freeFilmStats(c);
+	}
+	return 0;
+}
+
+int mtsgpu_film_statistics_form(const mtsgpu_ctx *c) { return c ? c->statsForm : -1; }
+
+int mtsgpu_read_film_statistics(mtsgpu_ctx *c, float *var3, uint32_t *nsamp) {
+	int rc = checkReady(c); if (rc) return rc;
+	if (!c->filmStats) return fail(c, MTSGPU_ESTATE, "film statistics are off (mtsgpu_set_film_statistics)");
+	if (!var3 || !nsamp) return fail(c, MTSGPU_EINVAL, "null output");
+	rc = ensureFilmStats(c); if (rc) return rc;
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	HIPCHK(c, hipMemcpy(var3, c->statVar, c->statPixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+	HIPCHK(c, hipMemcpy(nsamp, c->statN, c->statPixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+
 int mtsgpu_clear_film(mtsgpu_ctx *c) {
 	int rc = checkReady(c); if (rc) return rc;
 	rc = ensureFilm(c); if (rc) return rc;
 	HIPCHK(c, hipMemsetAsync(c->film, 0, (size_t) c->cam.width * c->cam.height * 5 * sizeof(float), c->stream));
+	if (c->filmStats) {
+		rc = ensureFilmStats(c); if (rc) return rc;
+		HIPCHK(c, hipMemsetAsync(c->statVar, 0, c->statPixels * 3 * sizeof(float), c->stream));
+		HIPCHK(c, hipMemsetAsync(c->statN, 0, c->statPixels * sizeof(uint32_t), c->stream));
+	}
 	return 0;
 }
 
@@ -1154,7 +1207,13 @@ int mtsgpu_sync(mtsgpu_ctx *c) {
 
 int mtsgpu_render(mtsgpu_ctx *c, volatile const int *cancel) {
 	int rc = checkReady(c); if (rc) return rc;
+	// refused before anything is touched: the context stays as it was
+	if (c->filmStats && c->filtBorder > 0)
+		return fail(c, MTSGPU_EINVAL, "film statistics need the box filter: the reference collects them only with a reconstruction "
+		            "filter no wider than a pixel (renderjob.cpp:96-99, mfilm.cpp:145); this filter has a border of %d", c->filtBorder);
 	rc = ensureFilm(c); if (rc) return rc;
+	c->statsForm = -1;
+	if (c->filmStats) { rc = ensureFilmStats(c); if (rc) return rc; }      // before defaultMaxPaths() asks for the free memory
 	const int W = c->cam.width, H = c->cam.height, bs = c->blockSize;
 	const uint32_t spp = effectiveSpp(c);
 	// ImageBlock work units (imageproc.cpp:43-78) owned by this context: tile (tx, ty) -> part morton(tx, ty) % n_parts
@@ -1269,6 +1328,12 @@ int mtsgpu_render(mtsgpu_ctx *c, volatile const int *cancel) {
 			launch_path_lengths(c->stream, c->paths, nPaths, c->pathLen);
 		} else {
 			launch_accumulate(c->stream, c->paths, cfg, nSlots, spp, c->film, c->pathLen);
+			if (c->filmStats) {
+				const long form = tuningOr(c, "stats_wave", -1);
+				const bool wave = form < 0 ? variance_wave_rule(nSlots, spp) : form != 0;
+				launch_variance(c->stream, wave, c->paths, cfg, c->pixelList + base, nSlots, spp, c->statVar, c->statN);
+				c->statsForm = wave ? 1 : 0;
+			}
 		}
 		HIPCHK(c, hipGetLastError());
 		c->stats.camera_samples += nPaths;

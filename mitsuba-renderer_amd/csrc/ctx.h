@@ -41,6 +41,11 @@ struct mtsgpu_ctx {
 	bool hqEdges = false;
 	int integrator = 0, nLumSamples = 1, nBsdfSamples = 1;
 	float *filtValues = nullptr;           // device [16][16]
+	// test-case mode (mtsgpu_set_film_statistics): per-pixel variance [H][W][3] and sample count [H][W], allocated only while
+	// the mode is on; statsForm = the form of the variance kernel the last pass ran (0 lane, 1 wave, -1 none)
+	bool filmStats = false;
+	float *statVar = nullptr; uint32_t *statN = nullptr; size_t statPixels = 0;
+	int statsForm = -1;
 	mg::TileMeta *tileMeta = nullptr; size_t tileMetaCap = 0;
 	float *blocks = nullptr; size_t blocksCap = 0;
 

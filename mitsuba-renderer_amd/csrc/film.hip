@@ -280,6 +280,78 @@ __global__ __launch_bounds__(256) void k_accumulate_wave(DPaths ps, DConfig cfg,
 	}
 }
 
+// ===========================================================================
+// K7c: test-case mode -- the per-pixel variance an ImageBlock with statistics holds (renderproc.cpp:44-50).
+// SampleIntegrator::renderBlock (integrator.cpp:171-202) runs Knuth's online recurrence over the Li values of a pixel,
+// sample after sample, in binary32 per channel, and every sample overwrites the pixel's setVariance: the last one stays,
+//     variance = meanSqr / (Float) (spp - 1),  nSamples = spp.
+// Spectrum::operator/(Float) multiplies by the reciprocal (spectrum.h:229-241).  The recurrence takes EVERY sample, also
+// one that putSample rejects (Spectrum::isValid).  spp == 1: the reciprocal is +inf and the variance 0 * inf = NaN, as in
+// the reference.  A pass holds all samples of its pixels (id = slot * spp + j), so there is no state across passes.
+// Kernels of their own: the film kernels above stay what they are when the mode is off, and the film keeps its bits.
+// ===========================================================================
+struct KnuthVar {
+	float m0 = 0, m1 = 0, m2 = 0, q0 = 0, q1 = 0, q2 = 0;       // mean, meanSqr
+	__device__ __forceinline__ void add(float x, float y, float z, float inv) {
+		const float d0 = x - m0, d1 = y - m1, d2 = z - m2;
+		m0 = m0 + d0 * inv; m1 = m1 + d1 * inv; m2 = m2 + d2 * inv;
+		q0 = q0 + d0 * (x - m0); q1 = q1 + d1 * (y - m1); q2 = q2 + d2 * (z - m2);
+	}
+	// block->setVariance(offset.x, offset.y, ...) -> Film::putImageBlock (imageblock.h:247-252, mfilm.cpp:144-170)
+	__device__ __forceinline__ void store(const DConfig &cfg, uint32_t key, uint32_t spp, float *var, uint32_t *nsamp) const {
+		const int fx = (int) (key % (uint32_t) cfg.pix_w) + cfg.pix_off - cfg.crop_x, fy = (int) (key / (uint32_t) cfg.pix_w) + cfg.pix_off - cfg.crop_y;
+		if (fx < 0 || fx >= cfg.width || fy < 0 || fy >= cfg.height) return;
+		const float inv = 1.0f / (float) (spp - 1u);
+		const size_t p = (size_t) fy * cfg.width + fx;
+		var[3 * p] = q0 * inv; var[3 * p + 1] = q1 * inv; var[3 * p + 2] = q2 * inv;
+		nsamp[p] = spp;
+	}
+};
+
+// one lane per pixel
+__global__ __launch_bounds__(256) void k_variance(DPaths ps, DConfig cfg, const uint32_t *pixel_keys, uint32_t n_slots, uint32_t spp,
+                                                 float *var, uint32_t *nsamp) {
+	const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+	if (slot >= n_slots) return;
+	KnuthVar k;
+	for (uint32_t j = 0; j < spp; ++j) {
+		const size_t id = (size_t) slot * spp + j;
+		const float4 L = settled_Li(ps.Li(id), ps.slot(id, 2));
+		k.add(L.x, L.y, L.z, 1.0f / (float) (j + 1u));
+	}
+	k.store(cfg, pixel_keys[slot], spp, var, nsamp);
+}
+
+// One wave per pixel, for the passes k_accumulate_wave exists for (few pixels, many samples: a lane per pixel chains spp
+// dependent round trips on a handful of waves).  The 64 lanes load 64 consecutive records -- a stream -- and work out their own
+// sample's 1 / (j + 1); the recurrence then advances in lane = sample order on wave-uniform values, four readlanes a sample.
+__global__ __launch_bounds__(256) void k_variance_wave(DPaths ps, DConfig cfg, const uint32_t *pixel_keys, uint32_t n_slots, uint32_t spp,
+                                                      float *var, uint32_t *nsamp) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t slot = blockIdx.x * 4u + (threadIdx.x >> 6);
+	if (slot >= n_slots) return;             // whole waves
+	KnuthVar k;                              // uniform
+	for (uint32_t j0 = 0; j0 < spp; j0 += 64u) {
+		const uint32_t j = j0 + lane;
+		const size_t id = (size_t) slot * spp + (j < spp ? j : spp - 1u);
+		const float4 L = settled_Li(ps.Li(id), ps.slot(id, 2));
+		const float inv = 1.0f / (float) (j + 1u);
+		const uint32_t cnt = min(64u, spp - j0);
+		for (uint32_t l = 0; l < cnt; ++l)
+			k.add(bcast(L.x, l), bcast(L.y, l), bcast(L.z, l), bcast(inv, l));
+	}
+	if (lane == 0) k.store(cfg, pixel_keys[slot], spp, var, nsamp);
+}
+
+__global__ void k_merge_statistics(float *dst_var, uint32_t *dst_nsamp, const float *src_var, const uint32_t *src_nsamp, size_t n) {
+	const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t ns = src_nsamp[i];
+	if (ns == 0u) return;                    // not rendered by src
+	dst_nsamp[i] = ns;
+	dst_var[3 * i] = src_var[3 * i]; dst_var[3 * i + 1] = src_var[3 * i + 1]; dst_var[3 * i + 2] = src_var[3 * i + 2];
+}
+
 // the avgPathLength statistic for passes that do not run k_accumulate (filters wider than a pixel)
 __global__ void k_path_lengths(DPaths ps, uint32_t n_paths, unsigned long long *path_len) {
 	const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
@@ -395,6 +467,19 @@ void launch_accumulate(hipStream_t s, const DPaths &ps, const DConfig &cfg, uint
 		hipLaunchKernelGGL(k_accumulate_wave, dim3(blocks_for(n_slots, 4)), dim3(256), 0, s, ps, cfg, n_slots, spp_per_slot, film, path_len);
 	else
 		hipLaunchKernelGGL(k_accumulate, dim3(blocks_for(n_slots, 256)), dim3(256), 0, s, ps, cfg, n_slots, spp_per_slot, film, path_len);
+}
+// the rule of launch_accumulate, one place for both
+bool variance_wave_rule(uint32_t n_slots, uint32_t spp_per_slot) { return spp_per_slot >= 256u && n_slots <= (1u << 15); }
+void launch_variance(hipStream_t s, bool wave, const DPaths &ps, const DConfig &cfg, const uint32_t *pixel_keys, uint32_t n_slots,
+                     uint32_t spp_per_slot, float *var, uint32_t *nsamp) {
+	if (!n_slots) return;
+	if (wave)
+		hipLaunchKernelGGL(k_variance_wave, dim3(blocks_for(n_slots, 4)), dim3(256), 0, s, ps, cfg, pixel_keys, n_slots, spp_per_slot, var, nsamp);
+	else
+		hipLaunchKernelGGL(k_variance, dim3(blocks_for(n_slots, 256)), dim3(256), 0, s, ps, cfg, pixel_keys, n_slots, spp_per_slot, var, nsamp);
+}
+void launch_merge_statistics(hipStream_t s, float *dst_var, uint32_t *dst_nsamp, const float *src_var, const uint32_t *src_nsamp, size_t n_pixels) {
+	if (n_pixels) hipLaunchKernelGGL(k_merge_statistics, dim3(blocks_for(n_pixels, 256)), dim3(256), 0, s, dst_var, dst_nsamp, src_var, src_nsamp, n_pixels);
 }
 void launch_path_lengths(hipStream_t s, const DPaths &ps, uint32_t n_paths, unsigned long long *path_len) {
 	if (n_paths) hipLaunchKernelGGL(k_path_lengths, dim3(blocks_for(n_paths, 256)), dim3(256), 0, s, ps, n_paths, path_len);

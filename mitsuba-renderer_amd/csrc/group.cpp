@@ -339,6 +339,29 @@ int mtsgpu_group_render(mtsgpu_group *g, int block_size, int ordered_reduce, vol
 		return mtsgpu_render(c, cancel);          // returns with the member's stream idle
 	});
 	if (rc) return rc;
+	// test-case mode: member 0 collects the statistics of the pixels the others rendered, in member order.  Plain copies on
+	// member 0's GPU (a peer's buffers travel into the staging buffer first, like its film in the ordered sum below): the
+	// u32 counts never pass through the f32 collective, and the film reduce that follows is what it was.
+	if (n > 1 && g->members[0]->filmStats) {
+		mtsgpu_ctx *root = g->members[0];
+		const size_t px = root->statPixels;
+		for (int i = 1; i < n; ++i)
+			if (!g->members[i]->filmStats || g->members[i]->statPixels != px || !g->members[i]->statVar)
+				return gfail(g, MTSGPU_ESTATE, "member %d has no film statistics of the size of member 0's", i);
+		GHIP(g, hipSetDevice(g->devices[0]));
+		for (int i = 1; i < n; ++i) {
+			const float *sv = g->members[i]->statVar; const uint32_t *sn = g->members[i]->statN;
+			if (g->devices[i] != g->devices[0]) {
+				if (int r = ensureStaging(g, px * 5)) return r;
+				GHIP(g, hipMemcpyPeerAsync(g->staging, g->devices[0], sv, g->devices[i], px * 3 * sizeof(float), root->stream));
+				GHIP(g, hipMemcpyPeerAsync(g->staging + px * 3, g->devices[0], sn, g->devices[i], px * sizeof(uint32_t), root->stream));
+				sv = g->staging; sn = reinterpret_cast<const uint32_t *>(g->staging + px * 3);
+			}
+			launch_merge_statistics(root->stream, root->statVar, root->statN, sv, sn, px);
+			GHIP(g, hipGetLastError());
+		}
+		GHIP(g, hipStreamSynchronize(root->stream));
+	}
 	if (n == 1 && ordered_reduce != 2) return 0;
 	// 3: Film::putImageBlock -- the per-GPU films are summed into member 0's film
 	mtsgpu_ctx *root = g->members[0];
@@ -393,6 +416,14 @@ int mtsgpu_group_set_tuning(mtsgpu_group *g, const char *key, long value) {
 	for (size_t i = 0; i < g->members.size(); ++i)
 		if (int r = mtsgpu_set_tuning(g->members[i], key, value))
 			return gfail(g, r, "member %zu: %s", i, mtsgpu_last_error(g->members[i]));
+	return 0;
+}
+
+int mtsgpu_group_set_film_statistics(mtsgpu_group *g, int on) {
+	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
+	for (size_t i = 0; i < g->members.size(); ++i)
+		if (int r = mtsgpu_set_film_statistics(g->members[i], on))
+			return gfail(g, r, "set_film_statistics: %s", mtsgpu_last_error(g->members[i]));
 	return 0;
 }
 

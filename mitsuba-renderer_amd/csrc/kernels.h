@@ -361,6 +361,15 @@ void launch_prep(hipStream_t s, const uint32_t *cur, uint32_t *next_set, BinView
 void launch_accumulate(hipStream_t s, const DPaths &ps, const DConfig &cfg, uint32_t n_slots,
                        uint32_t spp_per_slot, float *film, unsigned long long *path_len);
 void launch_path_lengths(hipStream_t s, const DPaths &ps, uint32_t n_paths, unsigned long long *path_len);
+// Test-case mode (film statistics): the variance of the spp radiance samples of every pixel slot of a pass, Knuth's online
+// recurrence in sample-index order as SampleIntegrator::renderBlock runs it (integrator.cpp:171-202), and the sample count.
+// var [H][W][3], nsamp [H][W], indexed like the film; pixel_keys = the keys of the pass's slots.  wave: one wave per pixel
+// (true) or one lane per pixel (false); variance_wave_rule() is the choice launch_accumulate makes for the film sums
+bool variance_wave_rule(uint32_t n_slots, uint32_t spp_per_slot);
+void launch_variance(hipStream_t s, bool wave, const DPaths &ps, const DConfig &cfg, const uint32_t *pixel_keys, uint32_t n_slots,
+                     uint32_t spp_per_slot, float *var, uint32_t *nsamp);
+// statistics of a device group: the pixels src rendered (nsamp != 0) replace those of dst
+void launch_merge_statistics(hipStream_t s, float *dst_var, uint32_t *dst_nsamp, const float *src_var, const uint32_t *src_nsamp, size_t n_pixels);
 // a[i] = b[i] + s * c[i] over n float4
 // `blocks` workgroups of 256 stride over the arrays (0: 4096)
 void launch_triad(hipStream_t s, float4 *a, const float4 *b, const float4 *c, float scale, size_t n, unsigned blocks = 0);

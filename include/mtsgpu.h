@@ -469,6 +469,17 @@ int  mtsgpu_lum_eval(mtsgpu_ctx *ctx, uint32_t lum_type, const float *block, int
 /* MIPathTracer::Li for explicit camera samples: in [n][3] u32 = pixel x, y, sample index;
  * out [n][8] f32 = Li rgb, alpha, raster x, raster y, depth, unused */
 int  mtsgpu_li_samples(mtsgpu_ctx *ctx, const uint32_t *pix_samples, uint32_t n, float *out);
+/* What the film kernels consumed: records first .. first + n of the pass mtsgpu_render rendered last, in record order
+ * (record = slot * sampleCount + sample index; slots in the order of the pass's tiles, row-major inside a tile).
+ * out [n][8] f32 as for mtsgpu_li_samples = Li rgb (the parked direct-light term settled), alpha, raster x, raster y, depth;
+ * the eighth float holds the record's pixel key as a bit pattern: index of the raster pixel in the rendered grid, which with
+ * highQualityEdges is the full film grown by the filter border on every side (key = (y + border) * (film width + 2 * border)
+ * + x + border), so pixels of the border -- which mtsgpu_li_samples cannot address -- are there.  The film kernels only
+ * read the records, so the read-out is valid after mtsgpu_render; a frame rendered in one pass (max_paths large enough)
+ * has all its records in place.  MTSGPU_ESTATE when there is no valid last pass (nothing rendered; a setter,
+ * mtsgpu_li_samples or mtsgpu_trace_rays since), MTSGPU_EINVAL past its end.  A test hook: tests/ref64_film.py restates
+ * ImageBlock::putSample in binary64 over these records and the film must agree. */
+int  mtsgpu_pass_samples(mtsgpu_ctx *ctx, uint32_t first, uint32_t n, float *out);
 
 /* --- host-side flattening (what Scene::initialize does on the CPU) ---------
  * Builds everything a mtsgpu_scene needs from plain meshes: vertex normals

@@ -34,7 +34,7 @@ EXPORTS = [
     "mtsgpu_create_multi", "mtsgpu_group_destroy", "mtsgpu_group_size", "mtsgpu_group_ctx", "mtsgpu_group_last_error",
     "mtsgpu_group_upload_scene", "mtsgpu_group_set_camera", "mtsgpu_group_set_integrator", "mtsgpu_group_set_sampler",
     "mtsgpu_group_set_rfilter", "mtsgpu_group_render", "mtsgpu_group_last_reduce_kind", "mtsgpu_group_rccl_ranks", "mtsgpu_group_reduce_note", "mtsgpu_bsdf_eval", "mtsgpu_bsdf_eval_table", "mtsgpu_replay_roof", "mtsgpu_group_set_tuning",
-    "mtsgpu_sky_configure", "mtsgpu_lum_eval",
+    "mtsgpu_sky_configure", "mtsgpu_lum_eval", "mtsgpu_pass_samples",
     "mtsgpu_set_film_statistics", "mtsgpu_read_film_statistics", "mtsgpu_film_statistics_form", "mtsgpu_group_set_film_statistics",
 ]
 
@@ -151,6 +151,7 @@ def lib():
     L.mtsgpu_trace_rays.argtypes = [vp, f32p, C.c_uint32, C.c_int, u32p]
     L.mtsgpu_ld_tables.argtypes = [vp, C.c_uint32, f32p, f32p]
     L.mtsgpu_li_samples.argtypes = [vp, u32p, C.c_uint32, f32p]
+    L.mtsgpu_pass_samples.argtypes = [vp, C.c_uint32, C.c_uint32, f32p]
     L.mtsgpu_flatten.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.KdParams), C.POINTER(vp)]
     L.mtsgpu_flat_scene_get.argtypes = [vp]; L.mtsgpu_flat_scene_get.restype = C.POINTER(abi.Scene)
     L.mtsgpu_flat_scene_free.argtypes = [vp]; L.mtsgpu_flat_scene_free.restype = None
@@ -505,6 +506,12 @@ class MIPathTracer:
         self._chk(lib().mtsgpu_li_samples(self._ctx, abi.ptr(ps, abi.u32p), ps.shape[0], abi.ptr(out, abi.f32p)), "li_samples")
         return out
 
+    def pass_samples(self, first=0, n=None):
+        """records first .. first + n of the pass rendered last, as the film kernels read them (mtsgpu_pass_samples): [n][8]
+        float32 laid out like li_samples(), the pixel key as a bit pattern in column 7.  n = None: up to the end of the pass
+        (camera_samples of the last render when it took one pass)"""
+        return _pass_samples(self._ctx, first, self.stats()["camera_samples"] - int(first) if n is None else n)
+
     def close(self):
         if self._ctx and _lib is not None:
             _lib.mtsgpu_destroy(self._ctx)
@@ -610,6 +617,10 @@ class DeviceGroup:
             raise MtsGpuError("read_film_statistics: %s (code %d)" % (lib().mtsgpu_last_error(self.member(0)).decode(), rc))
         return var, n
 
+    def member_pass_samples(self, i, first=0, n=None):
+        """pass_samples() of member i, read through mtsgpu_group_ctx"""
+        return _pass_samples(self.member(i), first, self.member_stats(i)["camera_samples"] - int(first) if n is None else n)
+
     def member_stats(self, i):
         st = abi.Stats()
         lib().mtsgpu_get_stats(self.member(i), C.byref(st))
@@ -625,6 +636,14 @@ class DeviceGroup:
             self.close()
         except Exception:
             pass
+
+
+def _pass_samples(ctx, first, n):
+    out = np.zeros((int(n), 8), dtype=np.float32)
+    rc = lib().mtsgpu_pass_samples(ctx, int(first), int(n), abi.ptr(out, abi.f32p))
+    if rc != 0:
+        raise MtsGpuError("pass_samples: %s (code %d)" % (lib().mtsgpu_last_error(ctx).decode(), rc))
+    return out
 
 
 def sky_configure(block):

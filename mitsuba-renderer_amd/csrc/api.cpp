@@ -1753,6 +1753,39 @@ int mtsgpu_li_samples(mtsgpu_ctx *c, const uint32_t *pix_samples, uint32_t n, fl
 	return collectDeviceStats(c);
 }
 
+// The records the film kernels of the last pass consumed (include/mtsgpu.h): the film kernels only read them, so they
+// are still in place after mtsgpu_render.  Layout of mtsgpu_li_samples, plus the record's pixel key.
+int mtsgpu_pass_samples(mtsgpu_ctx *c, uint32_t first, uint32_t n, float *out) {
+	int rc = checkReady(c); if (rc) return rc;
+	const mtsgpu_ctx::LastPass &lp = c->lastPass;
+	if (!lp.valid) return fail(c, MTSGPU_ESTATE, "no pass to read: render first (setters, mtsgpu_li_samples and mtsgpu_trace_rays invalidate the last pass)");
+	if ((uint64_t) first + n > lp.nPaths || (uint64_t) first + n > c->pathCap)
+		return fail(c, MTSGPU_EINVAL, "records %u .. %llu lie past the end of the last pass (%u records)", first, (unsigned long long) first + n, lp.nPaths);
+	if (n == 0) return 0;
+	if (!out) return fail(c, MTSGPU_EINVAL, "null output");
+	std::vector<float> Li(4 * (size_t) n), thr(4 * (size_t) n), spos(4 * (size_t) n), parked(4 * (size_t) n), misc(4 * (size_t) n);
+	const size_t pitch = kPathSlots * sizeof(float4);
+	const float4 *rec = c->paths.base + (size_t) first * kPathSlots;
+	HIPCHK(c, hipMemcpy2DAsync(Li.data(), 16, rec + 4, pitch, 16, n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpy2DAsync(parked.data(), 16, rec + 2, pitch, 16, n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpy2DAsync(thr.data(), 16, rec + 3, pitch, 16, n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpy2DAsync(spos.data(), 16, rec + 7, pitch, 16, n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpy2DAsync(misc.data(), 16, rec + 6, pitch, 16, n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	for (size_t i = 0; i < n; ++i) {
+		uint32_t flags; int depth;
+		std::memcpy(&flags, &Li[4 * i + 3], 4); std::memcpy(&depth, &thr[4 * i + 3], 4);
+		float *o = out + 8 * i;
+		// a direct-light term still parked in the record of a path that has ended (DQueues::nee_parked), as the film kernels settle it
+		const float4 L = settled_Li(make_float4(Li[4 * i], Li[4 * i + 1], Li[4 * i + 2], 0.0f),
+		                            make_float4(parked[4 * i], parked[4 * i + 1], parked[4 * i + 2], parked[4 * i + 3]));
+		o[0] = L.x; o[1] = L.y; o[2] = L.z; o[3] = (flags & F_ALPHA) ? 1.0f : 0.0f;
+		o[4] = spos[4 * i]; o[5] = spos[4 * i + 1]; o[6] = (float) depth;
+		std::memcpy(&o[7], &misc[4 * i + 3], 4);           // the pixel key, as a bit pattern
+	}
+	return 0;
+}
+
 // --- host-side flattening ------------------------------------------------------
 struct mtsgpu_flat_scene { FlatScene fs; };
 

@@ -117,6 +117,9 @@ __global__ __launch_bounds__(kGenBlock) void k_generate(DScene sc, DPaths ps, DC
 // ===========================================================================
 // K7: ImageBlock::putSample with the tabulated box filter
 // (include/mitsuba/render/imageblock.h:80-138, src/librender/rfilter.cpp:40-69).
+// The pair below never reads a table: size 0.5, factor 15 / 0.5 and "weight 1 unless an index is 15" are hard-coded.
+// What ties that shortcut to TabulatedFilter is tests/ref64_film.py: it tabulates the box filter like any other and
+// runs the general putSample over the records these kernels read (mtsgpu_pass_samples); the film must agree.
 // One lane per pixel; its samples are added in sample-index order, so the film
 // is bit-reproducible and independent of how the image was sharded.
 // ===========================================================================

@@ -305,6 +305,31 @@ int  mtsgpu_set_options(mtsgpu_ctx *ctx, uint64_t max_paths, int count_traversal
  *   stats_wave (-1 rule, 0 lane, 1 wave)      form of the variance kernel of the test-case mode (below) */
 int  mtsgpu_set_tuning(mtsgpu_ctx *ctx, const char *key, long value);
 
+/* --- per-vertex colours and the `vertexcolors` texture (src/textures/vertexcolors.cpp: getValue(its) = its.color) -----
+ * A TriMesh may carry one Spectrum per vertex (trimesh.h:121-126); fillIntersectionRecord interpolates them with the hit's
+ * barycentrics in binary32, in the reference's operation order (skdtree.h:364,417-421):
+ *     b = ((1 - u) - v, u, v);   its.color = (c0 * b.x + c1 * b.y) + c2 * b.z   per channel.
+ * A `vertexcolors` texture in a texture-typed spectrum slot of a BSDF makes that slot take its.color instead of the three
+ * floats of the parameter block.  The slots of each type, in slot order (bit s of a mask = slot s):
+ *     lambertian  0 reflectance                       dielectric  0 specularReflectance  1 specularTransmittance
+ *     roughmetal  0 specularReflectance               microfacet  0 diffuseReflectance   1 specularReflectance
+ *     mirror      0 specularReflectance               phong       0 diffuseReflectance   1 specularReflectance
+ *     roughglass  0 specularReflectance  1 specularTransmittance
+ *     difftrans   0 transmittance                     ward        0 diffuseReflectance   1 specularReflectance
+ * Roughmetal's ior and k and roughglass's alpha are not slots (plain properties / a float texture); MTSGPU_BSDF_TWOSIDED
+ * does not change the meaning of a slot; a composite has no slot of its own and its children must not use one.  The three
+ * floats of a coloured slot in the block should hold 1, the texture's getAverage() / getMaximum() (vertexcolors.cpp:49-55),
+ * which is what Phong::configure and Ward::configure derive their sampling weights from.
+ *
+ * vtx_col [n_verts][3] follows the scene's global vertex pool (rows of shapes without colours are ignored),
+ * shape_has_colors [n_shapes] is non-zero for the meshes that carry colours, bsdf_color_slots [n_bsdfs] holds the masks
+ * (NULL = all zero).  Call after mtsgpu_upload_scene; a new upload clears it; all three NULL switch it off.  Scenes
+ * without a coloured slot launch the kernels they launch without this call.  MTSGPU_EINVAL, with the scene's colours
+ * switched off, when a mask names a slot beyond those of its type, a composite child has a coloured slot, a shape whose
+ * BSDF has a coloured slot is a sphere or a mesh without colours (the reference would read an its.color nobody wrote,
+ * shape.h:162-163), or a colour of a mesh that has them is not finite. */
+int  mtsgpu_set_vertex_colors(mtsgpu_ctx *ctx, const float *vtx_col, const uint32_t *shape_has_colors, const uint32_t *bsdf_color_slots);
+
 /* --- the hot path (replaces SampleIntegrator::render, integrator.cpp:87-120) */
 int  mtsgpu_render(mtsgpu_ctx *ctx, volatile const int *cancel);
 int  mtsgpu_sync(mtsgpu_ctx *ctx);
@@ -385,6 +410,8 @@ int  mtsgpu_group_set_tuning(mtsgpu_group *g, const char *key, long value);
  * like the ordered film sum; the u32 counts never pass through the f32 collective, and the film reduce is unchanged);
  * mtsgpu_read_film_statistics(mtsgpu_group_ctx(g, 0)) returns them. */
 int  mtsgpu_group_set_film_statistics(mtsgpu_group *g, int on);
+/* mtsgpu_set_vertex_colors on every member */
+int  mtsgpu_group_set_vertex_colors(mtsgpu_group *g, const float *vtx_col, const uint32_t *shape_has_colors, const uint32_t *bsdf_color_slots);
 
 /* HBM triad a[i] = b[i] + s * c[i] over three arrays of `bytes` each on `device` (float4 lanes, best of `iters`
  * launches): the practical bandwidth roof next to the 8 TB/s specification.  GB/s in *gbs. */
@@ -466,6 +493,16 @@ int  mtsgpu_sky_configure(const float *block, float *derived);
  * like mtsgpu_bsdf_eval: ops 0 and 1 call the device functions k_shade calls (sky_le, sky_sample), op 2 returns the constant
  * pdf_luminaire uses. */
 int  mtsgpu_lum_eval(mtsgpu_ctx *ctx, uint32_t lum_type, const float *block, int op, uint32_t n, const float *queries, float *out);
+/* its.color as the device computes it for the uploaded scene and its colours (mtsgpu_set_vertex_colors; MTSGPU_ESTATE without
+ * them): prim [n] primitive indices, uv [n][2] the hit's barycentrics, out [n][3].  Primitives of shapes without colours
+ * give 0.  A test hook: it calls the device function the shading kernels call. */
+int  mtsgpu_vertex_color_eval(mtsgpu_ctx *ctx, uint32_t n, const uint32_t *prim, const float *uv, float *out);
+/* mtsgpu_bsdf_eval with vertex colours: the slots of mask `slots` take color[3] instead of the block's floats.  Same ops,
+ * query and output layout; evaluated through the device function that builds the per-hit block for the shading kernels,
+ * so with slots == 0 it returns what mtsgpu_bsdf_eval returns, and otherwise what mtsgpu_bsdf_eval returns for the block
+ * with those slots overwritten. */
+int  mtsgpu_bsdf_eval_colored(mtsgpu_ctx *ctx, uint32_t bsdf_type, const float *params, uint32_t slots, const float color[3], int op,
+                              uint32_t n, const float *queries, float *out);
 /* MIPathTracer::Li for explicit camera samples: in [n][3] u32 = pixel x, y, sample index;
  * out [n][8] f32 = Li rgb, alpha, raster x, raster y, depth, unused */
 int  mtsgpu_li_samples(mtsgpu_ctx *ctx, const uint32_t *pix_samples, uint32_t n, float *out);
@@ -531,6 +568,13 @@ typedef struct mtsgpu_flat_scene mtsgpu_flat_scene; /* owns the arrays of a mtsg
 int  mtsgpu_flatten(const mtsgpu_scene_desc *desc, const mtsgpu_kd_params *kd, mtsgpu_flat_scene **out);
 const mtsgpu_scene *mtsgpu_flat_scene_get(const mtsgpu_flat_scene *fs);
 void mtsgpu_flat_scene_free(mtsgpu_flat_scene *fs);
+/* Per-vertex colours of mesh `mesh_index` of the description (trimesh.h:121-126): colors [that mesh's n_verts][3], copied into
+ * a pool the flat scene owns, in the flat scene's vertex order (the flattener keeps every mesh's vertices in the mesh's own
+ * order, so a colour stays with its vertex).  colors == NULL takes the mesh's colours away again. */
+int  mtsgpu_flat_scene_set_mesh_colors(mtsgpu_flat_scene *fs, uint32_t mesh_index, const float *colors);
+/* what mtsgpu_set_vertex_colors takes: the pool [n_verts][3] and the flags [n_shapes]; NULL while no mesh has colours */
+const float *mtsgpu_flat_scene_vertex_colors(const mtsgpu_flat_scene *fs);
+const uint32_t *mtsgpu_flat_scene_shape_has_colors(const mtsgpu_flat_scene *fs);
 /* kd-tree statistics logged by the reference builder (gkdtree.h:1178-1213) */
 int  mtsgpu_flat_scene_kdstats(const mtsgpu_flat_scene *fs, double *out6 /* inner, leaf, idx, expTrav, expLeaves, expPrims */);
 
@@ -541,6 +585,9 @@ int  mtsgpu_flat_scene_kdstats(const mtsgpu_flat_scene *fs, double *out6 /* inne
 typedef struct mtsgpu_loaded_mesh mtsgpu_loaded_mesh;
 int  mtsgpu_load_serialized(const char *path, int shape_index, mtsgpu_loaded_mesh **out, mtsgpu_mesh *mesh);
 void mtsgpu_loaded_mesh_free(mtsgpu_loaded_mesh *m);
+/* the per-vertex colours of the loaded shape, [n_verts][3] (single or double precision in the file, trimesh.cpp:113-118,
+ * 223-229), or NULL when the file has no EHasColors block; valid until mtsgpu_loaded_mesh_free */
+const float *mtsgpu_loaded_mesh_colors(const mtsgpu_loaded_mesh *m);
 
 /* TabulatedFilter (src/librender/rfilter.cpp:40-69) of the reconstruction filter plugins: kind 0 `box`,
  * 1 `gaussian` (p0 = stddev; src/rfilters/gaussian.cpp:30-42,62-65), 2 `mitchell` (p0 = B, p1 = C; mitchell.cpp),

@@ -118,8 +118,20 @@ struct FlatScene {
 	std::vector<uint32_t> triIdx, shapeTriOffset, shapeFlags, shapeType, kdNodes, kdIndices, triaccel, bsdfType, lumType, lumCdfOffset;
 	std::vector<int32_t> shapeBsdf, shapeLum, lumShape;
 	std::map<const BSDF *, int> bsdfIndex;
+	/* per-vertex colours (TriMesh::getVertexColors, trimesh.h:121-126) in the order of vtxPos, one flag per shape, and per BSDF
+	 * table entry the mask of its slots that hold a `vertexcolors` texture: what mtsgpu_group_set_vertex_colors takes */
+	std::vector<float> vtxCol;
+	std::vector<uint32_t> shapeHasColors, bsdfColorSlots;
+	bool anyColors, anyColorSlots;
 
-	FlatScene(const Scene *scene) {
+	/* after mtsgpu_group_upload_scene: hands the colours over when a mesh has some or a BSDF slot asks for them (then the
+	 * library refuses a coloured slot on a shape without colours, where the reference would read an its.color nobody wrote) */
+	int setVertexColors(mtsgpu_group *group) const {
+		if (!anyColors && !anyColorSlots) return MTSGPU_OK;
+		return mtsgpu_group_set_vertex_colors(group, anyColors ? ptr(vtxCol) : NULL, anyColors ? ptr(shapeHasColors) : NULL, ptr(bsdfColorSlots));
+	}
+
+	FlatScene(const Scene *scene) : anyColors(false), anyColorSlots(false) {
 		memset(&sc, 0, sizeof(sc));
 		sc.abi_version = MTSGPU_ABI_VERSION;
 		const ShapeKDTree *kd = scene->getKDTree();                                   /* scene.h:498 */
@@ -208,7 +220,13 @@ struct FlatScene {
 				const TriMesh *mesh = static_cast<const TriMesh *>(shape);
 				const uint32_t base = (uint32_t) (vtxPos.size() / 3);
 				const Point *pos = mesh->getVertexPositions(); const Normal *nrm = mesh->getVertexNormals();   /* trimesh.h:110,115 */
+				const Spectrum *col = mesh->hasVertexColors() ? mesh->getVertexColors() : NULL;               /* trimesh.h:121-126 */
+				shapeHasColors.push_back(col ? 1u : 0u);
+				if (col) anyColors = true;
 				for (size_t v = 0; v < mesh->getVertexCount(); ++v) {
+					float rgb[3] = { 0.0f, 0.0f, 0.0f };
+					if (col) rgbOf(col[v], rgb);
+					vtxCol.insert(vtxCol.end(), rgb, rgb + 3);
 					vtxPos.push_back((float) pos[v].x); vtxPos.push_back((float) pos[v].y); vtxPos.push_back((float) pos[v].z);
 					vtxNrm.push_back(nrm ? (float) nrm[v].x : 0.0f); vtxNrm.push_back(nrm ? (float) nrm[v].y : 0.0f); vtxNrm.push_back(nrm ? (float) nrm[v].z : 0.0f);
 				}
@@ -249,6 +267,7 @@ struct FlatScene {
 				shapeTriOffset.push_back(shapeTriOffset.back() + 1);
 				shapeFlags.push_back(0u);
 				shapeType.push_back(MTSGPU_SHAPE_SPHERE);
+				shapeHasColors.push_back(0u);
 				if (shape->isLuminaire()) {
 					const int l = lumIndex[shape->getLuminaire()];
 					lumShape[l] = (int32_t) s;
@@ -372,9 +391,10 @@ private:
 		/* one entry, or for a composite its children first and then the composite itself, whose block points at them */
 		ref<MemoryStream> st = serializedBSDF(bsdf);
 		std::string err;
-		const int index = mtsgpu_stream::parseBSDFTable<Float>(st->getData(), st->getSize(), bsdfType, bsdfParams, &err);
+		const int index = mtsgpu_stream::parseBSDFTable<Float>(st->getData(), st->getSize(), bsdfType, bsdfParams, &err, &bsdfColorSlots);
 		if (index < 0)
 			SLog(EError, "gpupath: %s", err.c_str());
+		for (size_t b = 0; b < bsdfColorSlots.size(); ++b) if (bsdfColorSlots[b]) anyColorSlots = true;
 		bsdfIndex[bsdf] = index;
 		return index;
 	}
@@ -428,6 +448,7 @@ struct GPURenderDriver {
 		{
 			FlatScene flat(scene);
 			check(mtsgpu_group_upload_scene(group, &flat.sc));
+			check(flat.setVertexColors(group));
 		}
 
 		/* --- camera: raster space of the FULL film, crop window as offset + size (perspective.cpp:43-71, film.cpp:33-41) --- */

@@ -95,13 +95,29 @@ public:
 	}
 	const std::string &className() const { return m_className; }
 	/* a texture child: [id][class name][Texture::serialize = parent reference][ConstantSpectrumTexture: the value]
-	 * (src/librender/texture.cpp:39-41, :89-93).  Anything but a constant needs computePartials + MIPMap: out of scope. */
-	void readConstantTexture(const char *what, float rgb[3]) {
+	 * (src/librender/texture.cpp:39-41, :89-93).  Anything but a constant needs computePartials + MIPMap: out of scope --
+	 * except `VertexColors` (src/textures/vertexcolors.cpp), see readSpectrumTexture. */
+	void readConstantTexture(const char *what, float rgb[3]) { readSpectrumTexture(what, rgb, -1); }
+	/* The texture of slot `slot` (0, 1: the texture-typed spectrum slots of include/mtsgpu.h) of the BSDF the reader stands on.
+	 * A `VertexColors` instance writes nothing of its own (vertexcolors.cpp:37-39: Texture::serialize, the parent reference);
+	 * its slot is reported in colorSlots() and the block receives (1, 1, 1), the texture's getAverage() / getMaximum()
+	 * (:49-55), from which Phong::configure and Ward::configure derived the weights that follow in the stream.  One
+	 * VertexColors instance in two slots arrives as a bare id the second time: refused, like every shared instance whose
+	 * fields are out of reach.  slot < 0: a slot that cannot take colours. */
+	void readSpectrumTexture(const char *what, float rgb[3], int slot) {
 		const uint32_t id = r.readUInt();
 		if (id != 0 && m_values.count(id)) { memcpy(rgb, m_values[id].v, sizeof(float) * 3); return; }      /* one texture shared by two slots */
 		if (id == 0) { r.fail(std::string(what) + " of " + m_className + " is missing"); return; }
+		if (m_colorIds.count(id)) { r.fail(std::string(what) + " of " + m_className + " is a VertexColors instance shared with another slot: shared instances are not supported"); return; }
 		m_seen.insert(id);
 		const std::string cls = r.readString();
+		if (cls == "VertexColors" && slot >= 0) {
+			skipReference();
+			rgb[0] = rgb[1] = rgb[2] = 1.0f;
+			m_colorSlots |= 1u << slot;
+			m_colorIds.insert(id);
+			return;
+		}
 		if (cls != "ConstantSpectrumTexture") {                                                 /* consttexture.h:28-60 */
 			r.fail(std::string(what) + " of " + m_className + " is a " + cls + "; only constant reflectances are supported");
 			return;
@@ -110,12 +126,16 @@ public:
 		r.readSpectrum(rgb);
 		memcpy(m_values[id].v, rgb, sizeof(float) * 3);
 	}
+	/* the slots of the block read since the last resetColorSlots() that hold a VertexColors texture (bit s = slot s) */
+	uint32_t colorSlots() const { return m_colorSlots; }
+	void resetColorSlots() { m_colorSlots = 0; }
 	/* a ConstantFloatTexture child (roughglass' alpha): [id][class name][Texture::serialize][the value] (texture.cpp:95-103) */
 	FloatT readConstantFloatTexture(const char *what) {
 		const uint32_t id = r.readUInt();
 		if (id == 0 || m_seen.count(id)) { r.fail(std::string(what) + " of " + m_className + " is missing or shared"); return 0; }
 		m_seen.insert(id);
 		const std::string cls = r.readString();
+		if (cls == "VertexColors") { r.fail(std::string(what) + " of " + m_className + " is a VertexColors texture: vertex colours are a spectrum, this slot takes a float texture; not supported"); return 0; }
 		if (cls != "ConstantFloatTexture") { r.fail(std::string(what) + " of " + m_className + " is a " + cls + "; only constant values are supported"); return 0; }
 		skipReference();
 		return r.readFloat();
@@ -144,68 +164,74 @@ private:
 		const uint32_t id = r.readUInt();
 		if (id != 0 && !m_seen.count(id)) r.fail("unexpected nested object in the serialized form of " + m_className);
 	}
-	std::set<uint32_t> m_seen;
+	std::set<uint32_t> m_seen, m_colorIds;
+	uint32_t m_colorSlots = 0;
 	std::map<uint32_t, RGB> m_values;
 	std::string m_className;
 };
 
-/* The fields of the class the reader stands on (after BSDF::serialize's own), for every class with ONE parameter block */
-template <typename FloatT> inline void parseBSDFFields(BSDFStream<FloatT> &rd, uint32_t flags, uint32_t *type, float *P) {
+/* The fields of the class the reader stands on (after BSDF::serialize's own), for every class with ONE parameter block.
+ * slots (optional): the mask of the block's texture slots that hold a VertexColors texture (bit s = slot s of the table in
+ * include/mtsgpu.h; Mirror keeps a plain Spectrum, mirror.cpp:51-55, and can have none). */
+template <typename FloatT> inline void parseBSDFFields(BSDFStream<FloatT> &rd, uint32_t flags, uint32_t *type, float *P, uint32_t *slots = NULL) {
 	const std::string cls = rd.className();
+	rd.resetColorSlots();
 	if (cls == "Lambertian") {                                               /* lambertian.cpp:137-141 */
 		*type = MTSGPU_BSDF_LAMBERTIAN | flags;
-		rd.readConstantTexture("reflectance", P);
+		rd.readSpectrumTexture("reflectance", P, 0);
 	} else if (cls == "Dielectric") {                                        /* dielectric.cpp:88-95 */
 		*type = MTSGPU_BSDF_DIELECTRIC | flags;
 		P[0] = (float) rd.r.readFloat(); P[1] = (float) rd.r.readFloat();
-		rd.readConstantTexture("specularReflectance", P + 2);
-		rd.readConstantTexture("specularTransmittance", P + 5);
+		rd.readSpectrumTexture("specularReflectance", P + 2, 0);
+		rd.readSpectrumTexture("specularTransmittance", P + 5, 1);
 	} else if (cls == "RoughMetal") {                                        /* roughmetal.cpp:169-176 */
 		*type = MTSGPU_BSDF_ROUGHMETAL | flags;
-		rd.readConstantTexture("specularReflectance", P + 7);
+		rd.readSpectrumTexture("specularReflectance", P + 7, 0);
 		P[0] = (float) rd.r.readFloat();
 		rd.r.readSpectrum(P + 1); rd.r.readSpectrum(P + 4);                  /* m_ior, m_k */
 	} else if (cls == "Microfacet") {                                        /* microfacet.cpp:283-293 */
 		*type = MTSGPU_BSDF_MICROFACET | flags;
-		rd.readConstantTexture("diffuseReflectance", P + 5);
-		rd.readConstantTexture("specularReflectance", P + 8);
+		rd.readSpectrumTexture("diffuseReflectance", P + 5, 0);
+		rd.readSpectrumTexture("specularReflectance", P + 8, 1);
 		for (int k = 0; k < 5; ++k) P[k] = (float) rd.r.readFloat();         /* alphaB, kd, ks, intIOR, extIOR */
 	} else if (cls == "Mirror") {                                            /* mirror.cpp:51-55 */
 		*type = MTSGPU_BSDF_MIRROR | flags;
 		rd.r.readSpectrum(P);
 	} else if (cls == "Phong") {                                             /* phong.cpp:246-256 (values after configure()) */
 		*type = MTSGPU_BSDF_PHONG | flags;
-		rd.readConstantTexture("diffuseReflectance", P + 5);
-		rd.readConstantTexture("specularReflectance", P + 8);
+		rd.readSpectrumTexture("diffuseReflectance", P + 5, 0);
+		rd.readSpectrumTexture("specularReflectance", P + 8, 1);
 		for (int k = 0; k < 5; ++k) P[k] = (float) rd.r.readFloat();         /* exponent, kd, ks, specular / diffuse sampling weight */
 	} else if (cls == "RoughGlass") {                                        /* roughglass.cpp:735-744 */
 		*type = MTSGPU_BSDF_ROUGHGLASS | flags;
 		P[0] = (float) rd.r.readInt();                                       /* EBeckmann 0, EPhong 1, EGGX 2 (:84-91) = the ABI's codes */
 		P[1] = (float) rd.readConstantFloatTexture("alpha");                 /* phong: already the exponent (:130-136) */
-		rd.readConstantTexture("specularReflectance", P + 4);
-		rd.readConstantTexture("specularTransmittance", P + 7);
+		rd.readSpectrumTexture("specularReflectance", P + 4, 0);
+		rd.readSpectrumTexture("specularTransmittance", P + 7, 1);
 		P[2] = (float) rd.r.readFloat(); P[3] = (float) rd.r.readFloat();    /* intIOR, extIOR */
 	} else if (cls == "DiffuseTransmitter") {                                /* difftrans.cpp:142-146 */
 		*type = MTSGPU_BSDF_DIFFTRANS | flags;
-		rd.readConstantTexture("transmittance", P);
+		rd.readSpectrumTexture("transmittance", P, 0);
 	} else if (cls == "Ward") {                                              /* ward.cpp:299-311 (values after configure()) */
 		*type = MTSGPU_BSDF_WARD | flags;
 		const uint32_t model = rd.r.readUInt();                              /* EWard 0, EWardDuer 1, EBalanced 2 (:45-52) = the ABI's codes */
 		if (model > 2 && rd.r.ok()) rd.r.fail("Ward: unknown model type");
 		P[0] = (float) model;
-		rd.readConstantTexture("diffuseReflectance", P + 7);
-		rd.readConstantTexture("specularReflectance", P + 10);
+		rd.readSpectrumTexture("diffuseReflectance", P + 7, 0);
+		rd.readSpectrumTexture("specularReflectance", P + 10, 1);
 		for (int k = 1; k <= 6; ++k) P[k] = (float) rd.r.readFloat();        /* alphaX, alphaY, kd, ks, specular / diffuse sampling weight */
 	} else {
 		rd.r.fail("BSDF class " + cls + " is not on this path (lambertian, dielectric, roughmetal, microfacet, mirror, phong, "
 		          "roughglass, difftrans, ward, composite and the twosided adapter are)");
 	}
+	if (slots) *slots = rd.colorSlots();
+	else if (rd.colorSlots() && rd.r.ok()) rd.r.fail(cls + " holds a VertexColors texture: the caller does not take colour slots");
 }
 
 /* One BSDF instance -> its type word (MTSGPU_BSDF_* | MTSGPU_BSDF_TWOSIDED) and parameter block P[MTSGPU_BSDF_NPARAMS]
  * (zeroed by the caller).  Returns false with `err` set for classes and textures that are not on this path, and for a
  * Composite, which is more than one block: parseBSDFTable reads those. */
-template <typename FloatT> inline bool parseBSDF(const uint8_t *data, size_t size, uint32_t *type, float *P, std::string *err) {
+template <typename FloatT> inline bool parseBSDF(const uint8_t *data, size_t size, uint32_t *type, float *P, std::string *err, uint32_t *slots = NULL) {
 	BSDFStream<FloatT> rd(data, size);
 	uint32_t flags = 0;
 	if (rd.className() == "TwoSidedBRDF") {                                  /* twosided.cpp:52-56: the nested BRDF follows */
@@ -213,7 +239,7 @@ template <typename FloatT> inline bool parseBSDF(const uint8_t *data, size_t siz
 		rd.enterNestedBSDF();
 	}
 	if (rd.className() == "Composite") rd.r.fail("a Composite BSDF fills several table entries: read it with parseBSDFTable");
-	else parseBSDFFields(rd, flags, type, P);
+	else parseBSDFFields(rd, flags, type, P, slots);
 	if (!rd.r.ok()) { if (err) *err = rd.r.error() + " (while reading a " + rd.className() + ")"; return false; }
 	return true;
 }
@@ -225,8 +251,10 @@ template <typename FloatT> inline bool parseBSDF(const uint8_t *data, size_t siz
  * [1..n] weights, [1+n..2n] the children's table indices as floats.  What the device cannot run is refused here with the
  * reason: more than MTSGPU_COMPOSITE_MAX children or none, a negative weight (composite.cpp:45-46), a nested composite, a
  * delta child (dielectric, mirror), a child instance that was written before (a bare id: its fields are not in reach). */
+/* colorSlots (optional): one mask per appended entry, next to `types` (what mtsgpu_set_vertex_colors takes as
+ * bsdf_color_slots).  A composite child with a coloured slot is refused with the child's number, as the library refuses it. */
 template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t size, std::vector<uint32_t> &types, std::vector<float> &params,
-                                                     std::string *err) {
+                                                     std::string *err, std::vector<uint32_t> *colorSlots = NULL) {
 	BSDFStream<FloatT> rd(data, size);
 	const size_t first = types.size();
 	uint32_t flags = 0;
@@ -234,7 +262,9 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 	int own = -1;
 	if (rd.className() != "Composite") {
 		types.push_back(0); params.insert(params.end(), MTSGPU_BSDF_NPARAMS, 0.0f);
-		parseBSDFFields(rd, flags, &types.back(), &params[params.size() - MTSGPU_BSDF_NPARAMS]);
+		uint32_t slots = 0;
+		parseBSDFFields(rd, flags, &types.back(), &params[params.size() - MTSGPU_BSDF_NPARAMS], colorSlots ? &slots : NULL);
+		if (colorSlots) colorSlots->push_back(slots);
 		own = (int) types.size() - 1;
 	} else {
 		const uint64_t n = rd.r.readSize();
@@ -255,17 +285,22 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 				rd.r.fail("Composite: child " + rd.className() + " is a delta BSDF (a composite would need fDelta / pdfDelta): not supported"); break;
 			}
 			types.push_back(0); params.insert(params.end(), MTSGPU_BSDF_NPARAMS, 0.0f);
-			parseBSDFFields(rd, childFlags, &types.back(), &params[params.size() - MTSGPU_BSDF_NPARAMS]);
+			uint32_t slots = 0;
+			parseBSDFFields(rd, childFlags, &types.back(), &params[params.size() - MTSGPU_BSDF_NPARAMS], &slots);
+			if (colorSlots) colorSlots->push_back(0u);
+			if (rd.r.ok() && slots) { rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " (" + rd.className() + ") takes vertex colours: a composite's children keep constant parameters, not supported"); break; }
 			block[1 + n + i] = (float) (types.size() - 1);
 		}
 		if (rd.r.ok()) {
 			types.push_back(MTSGPU_BSDF_COMPOSITE | flags);
+			if (colorSlots) colorSlots->push_back(0u);
 			params.insert(params.end(), block, block + MTSGPU_BSDF_NPARAMS);
 			own = (int) types.size() - 1;
 		}
 	}
 	if (!rd.r.ok()) {
 		types.resize(first); params.resize(first * MTSGPU_BSDF_NPARAMS);
+		if (colorSlots) colorSlots->resize(first);
 		if (err) *err = rd.r.error() + " (while reading a " + rd.className() + ")";
 		return -1;
 	}

@@ -36,6 +36,8 @@ EXPORTS = [
     "mtsgpu_group_set_rfilter", "mtsgpu_group_render", "mtsgpu_group_last_reduce_kind", "mtsgpu_group_rccl_ranks", "mtsgpu_group_reduce_note", "mtsgpu_bsdf_eval", "mtsgpu_bsdf_eval_table", "mtsgpu_replay_roof", "mtsgpu_group_set_tuning",
     "mtsgpu_sky_configure", "mtsgpu_lum_eval", "mtsgpu_pass_samples",
     "mtsgpu_set_film_statistics", "mtsgpu_read_film_statistics", "mtsgpu_film_statistics_form", "mtsgpu_group_set_film_statistics",
+    "mtsgpu_set_vertex_colors", "mtsgpu_group_set_vertex_colors", "mtsgpu_flat_scene_set_mesh_colors", "mtsgpu_flat_scene_vertex_colors",
+    "mtsgpu_flat_scene_shape_has_colors", "mtsgpu_loaded_mesh_colors", "mtsgpu_vertex_color_eval", "mtsgpu_bsdf_eval_colored",
 ]
 
 
@@ -53,8 +55,10 @@ def load_serialized(path, shape_index=0, bsdf=-1, lum=-1, name=None):
         pos = abi.np_from(m.positions, (m.n_verts, 3), np.float32)
         tri = abi.np_from(m.triangles, (m.n_tris, 3), np.uint32)
         nrm = abi.np_from(m.normals, (m.n_verts, 3), np.float32) if m.normals else None
+        cp = lib().mtsgpu_loaded_mesh_colors(h)             # the EHasColors block, or NULL
+        col = abi.np_from(cp, (m.n_verts, 3), np.float32) if cp else None
         return scenes.MeshDesc(pos, tri, bsdf=bsdf, lum=lum, face_normals=bool(m.face_normals), normals=nrm,
-                               name=name or "%s#%d" % (os.path.basename(path), shape_index))
+                               name=name or "%s#%d" % (os.path.basename(path), shape_index), colors=col)
     finally:
         lib().mtsgpu_loaded_mesh_free(h)
 
@@ -190,6 +194,14 @@ def lib():
     L.mtsgpu_read_film_statistics.argtypes = [vp, f32p, u32p]
     L.mtsgpu_film_statistics_form.argtypes = [vp]
     L.mtsgpu_group_set_film_statistics.argtypes = [vp, C.c_int]
+    L.mtsgpu_set_vertex_colors.argtypes = [vp, f32p, u32p, u32p]
+    L.mtsgpu_group_set_vertex_colors.argtypes = [vp, f32p, u32p, u32p]
+    L.mtsgpu_flat_scene_set_mesh_colors.argtypes = [vp, C.c_uint32, f32p]
+    L.mtsgpu_flat_scene_vertex_colors.argtypes = [vp]; L.mtsgpu_flat_scene_vertex_colors.restype = f32p
+    L.mtsgpu_flat_scene_shape_has_colors.argtypes = [vp]; L.mtsgpu_flat_scene_shape_has_colors.restype = u32p
+    L.mtsgpu_loaded_mesh_colors.argtypes = [vp]; L.mtsgpu_loaded_mesh_colors.restype = f32p
+    L.mtsgpu_vertex_color_eval.argtypes = [vp, C.c_uint32, u32p, f32p, f32p]
+    L.mtsgpu_bsdf_eval_colored.argtypes = [vp, C.c_uint32, f32p, C.c_uint32, f32p, C.c_int, C.c_uint32, f32p, f32p]
     _lib = L
     return L
 
@@ -215,10 +227,35 @@ class Scene:
         if rc != 0:
             raise MtsGpuError("mtsgpu_flatten: %s" % lib().mtsgpu_last_error(None).decode())
         self.ptr = lib().mtsgpu_flat_scene_get(self._h)
+        # per-vertex colours go into the flat scene's own pool; the slot masks of the BSDFs travel next to the blocks
+        for i, m in enumerate(description.meshes):
+            if getattr(m, "colors", None) is not None:
+                rc = lib().mtsgpu_flat_scene_set_mesh_colors(self._h, i, abi.ptr(m.colors, abi.f32p))
+                if rc != 0:
+                    raise MtsGpuError("mtsgpu_flat_scene_set_mesh_colors: %s" % lib().mtsgpu_last_error(None).decode())
+        slots = np.asarray(getattr(description, "bsdf_color_slots", []), dtype=np.uint32)
+        self.bsdf_color_slots = slots if slots.any() else None
 
     @property
     def sc(self):
         return self.ptr.contents
+
+    def vertex_color_args(self):
+        """what mtsgpu_set_vertex_colors takes for this scene: (vtx_col, shape_has_colors, bsdf_color_slots) pointers, or
+        None when the scene has neither coloured meshes nor coloured BSDF slots"""
+        col = lib().mtsgpu_flat_scene_vertex_colors(self._h)
+        has = lib().mtsgpu_flat_scene_shape_has_colors(self._h)
+        if not col and self.bsdf_color_slots is None:
+            return None
+        return (col if col else None, has if has else None, abi.ptr(self.bsdf_color_slots, abi.u32p))
+
+    def vertex_colors(self):
+        """(pool [n_verts][3] float32, flags [n_shapes] uint32) of the flat scene, or (None, None)"""
+        col = lib().mtsgpu_flat_scene_vertex_colors(self._h)
+        if not col:
+            return None, None
+        return (abi.np_from(col, (self.sc.n_verts, 3), np.float32),
+                abi.np_from(lib().mtsgpu_flat_scene_shape_has_colors(self._h), (self.sc.n_shapes,), np.uint32))
 
     def arrays(self):
         return abi.scene_arrays(self.sc)
@@ -322,6 +359,9 @@ class MIPathTracer:
         self.configure()
         sp = scene.ptr if isinstance(scene, Scene) else scene
         self._chk(lib().mtsgpu_upload_scene(self._ctx, sp), "upload_scene")
+        vc = scene.vertex_color_args() if isinstance(scene, Scene) else None
+        if vc is not None:
+            self._chk(lib().mtsgpu_set_vertex_colors(self._ctx, *vc), "set_vertex_colors")
         self.camera = camera
         self._chk(lib().mtsgpu_set_camera(self._ctx, C.byref(camera.c if hasattr(camera, "c") else camera)), "set_camera")
         kind = {"independent": abi.SAMPLER_INDEPENDENT_KEYED, "ldsampler": abi.SAMPLER_LD_KEYED, "halton": abi.SAMPLER_HALTON,
@@ -483,6 +523,36 @@ class MIPathTracer:
                                                abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)), "bsdf_eval_table")
         return out
 
+    def set_vertex_colors(self, vtx_col=None, shape_has_colors=None, bsdf_color_slots=None):
+        """mtsgpu_set_vertex_colors on the uploaded scene: the colour pool [n_verts][3], one flag per shape, one slot mask
+        per BSDF; all None switches the colours off"""
+        a = None if vtx_col is None else np.ascontiguousarray(vtx_col, dtype=np.float32)
+        b = None if shape_has_colors is None else np.ascontiguousarray(shape_has_colors, dtype=np.uint32)
+        c = None if bsdf_color_slots is None else np.ascontiguousarray(bsdf_color_slots, dtype=np.uint32)
+        self._chk(lib().mtsgpu_set_vertex_colors(self._ctx, abi.ptr(a, abi.f32p), abi.ptr(b, abi.u32p), abi.ptr(c, abi.u32p)), "set_vertex_colors")
+
+    def vertex_color_eval(self, prim, uv):
+        """its.color on the device for records (primitive, u, v) of the uploaded scene (mtsgpu_vertex_color_eval) -> [n][3]"""
+        p = np.ascontiguousarray(prim, dtype=np.uint32).reshape(-1)
+        q = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+        out = np.zeros((len(p), 3), dtype=np.float32)
+        self._chk(lib().mtsgpu_vertex_color_eval(self._ctx, len(p), abi.ptr(p, abi.u32p), abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)), "vertex_color_eval")
+        return out
+
+    def bsdf_eval_colored(self, bsdf_type, params, slots, color, op, wi, aux):
+        """bsdf_eval() with the texture slots of mask `slots` taking `color` (mtsgpu_bsdf_eval_colored) -> [n][8]"""
+        aux = np.atleast_2d(np.asarray(aux, dtype=np.float32))
+        n = aux.shape[0]
+        q = np.zeros((n, 6), dtype=np.float32)
+        q[:, :3] = np.asarray(wi, dtype=np.float32).reshape(-1, 3)
+        q[:, 3:3 + aux.shape[1]] = aux
+        P = np.zeros(abi.BSDF_NPARAMS, dtype=np.float32); P[:len(params)] = params
+        col = np.ascontiguousarray(color, dtype=np.float32).reshape(3)
+        out = np.zeros((n, 8), dtype=np.float32)
+        self._chk(lib().mtsgpu_bsdf_eval_colored(self._ctx, int(bsdf_type), abi.ptr(P, abi.f32p), int(slots), abi.ptr(col, abi.f32p), int(op), n,
+                                                 abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)), "bsdf_eval_colored")
+        return out
+
     def lum_eval(self, lum_type, block, op, a, b=None):
         """the luminaire plugins on the device for n query records (mtsgpu_lum_eval; the sky): op 0 Le(a = direction
         [n][3]); op 1 sample(a = p [n][3], b = the 2D sample [n][2]); op 2 pdf(a = p, b = lRec.d).  Returns [n][12]:
@@ -552,6 +622,9 @@ class DeviceGroup:
         sp = scene.ptr if isinstance(scene, Scene) else scene
         self._chk(lib().mtsgpu_group_set_integrator(self._g, self.maxDepth, self.rrDepth, int(self.strictNormals)), "set_integrator")
         self._chk(lib().mtsgpu_group_upload_scene(self._g, sp), "upload_scene")
+        vc = scene.vertex_color_args() if isinstance(scene, Scene) else None
+        if vc is not None:
+            self._chk(lib().mtsgpu_group_set_vertex_colors(self._g, *vc), "set_vertex_colors")
         self.camera = camera
         self._chk(lib().mtsgpu_group_set_camera(self._g, C.byref(camera.c)), "set_camera")
         kind = {"independent": abi.SAMPLER_INDEPENDENT_KEYED, "ldsampler": abi.SAMPLER_LD_KEYED, "halton": abi.SAMPLER_HALTON,

@@ -10,6 +10,8 @@ BSDF_LAMBERTIAN, BSDF_DIELECTRIC, BSDF_ROUGHMETAL, BSDF_MICROFACET, BSDF_MIRROR,
 BSDF_WARD, BSDF_COMPOSITE, BSDF_NTYPES = 8, 9, 10
 BSDF_TWOSIDED = 0x100
 COMPOSITE_MAX = 7
+# texture-typed spectrum slots per BSDF type (include/mtsgpu.h): the first float of each slot in the parameter block
+BSDF_COLOR_SLOTS = {0: (0,), 1: (2, 5), 2: (7,), 3: (5, 8), 4: (0,), 5: (5, 8), 6: (4, 7), 7: (0,), 8: (7, 10), 9: ()}
 BSDF_NPARAMS = 16
 LUM_AREA, LUM_CONSTANT, LUM_POINT, LUM_DIRECTIONAL, LUM_SPOT, LUM_ENVMAP, LUM_COLLIMATED, LUM_SKY = 0, 1, 2, 3, 4, 5, 6, 7
 LUM_NPARAMS = 32

@@ -36,9 +36,10 @@ template <typename T> int devAlloc(mtsgpu_ctx *ctx, T **p, size_t count, std::ve
 	return 0;
 }
 
-template <typename T> int upload(mtsgpu_ctx *ctx, const T **dst, const T *src, size_t count) {
+// owner: the list the allocation is filed under (NULL: the scene's)
+template <typename T> int upload(mtsgpu_ctx *ctx, const T **dst, const T *src, size_t count, std::vector<void *> *owner = nullptr) {
 	T *p = nullptr;
-	int rc = devAlloc(ctx, &p, count, ctx->sceneAllocs);
+	int rc = devAlloc(ctx, &p, count, owner ? *owner : ctx->sceneAllocs);
 	if (rc) return rc;
 	if (count) HIPCHK(ctx, hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
 	*dst = p;
@@ -341,7 +342,7 @@ int runDirectRounds(mtsgpu_ctx *c, const DConfig &cfg0, uint32_t nPaths, volatil
 		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
 		cfg.dr_mode = mode; cfg.dr_index = index;
 		for (int b = 0; b < (withTerminal ? kNumBins : kNumBsdfTypes); ++b)
-			launch_shade(s, b, c->dsc, c->paths, cfg, c->q, views[b]);
+			launch_shade(s, b, c->dsc, c->paths, cfg, c->q, views[b], nullptr, 0, nullptr, c->dcol);
 		if (sev) HIPCHK(c, hipEventRecord(sev[1], s));
 		HIPCHK(c, hipGetLastError());
 		return readCounters(c);
@@ -371,7 +372,7 @@ int runDirectRounds(mtsgpu_ctx *c, const DConfig &cfg0, uint32_t nPaths, volatil
 		hipEvent_t *sev = c->timeKernels ? nextEventPair(c, c->shadeEvents, c->shadeEvUsed) : nullptr;
 		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
 		cfg.dr_mode = 3; cfg.dr_index = j;
-		launch_shade(s, kNumBsdfTypes, c->dsc, c->paths, cfg, c->q, tail, nullptr, 0, c->queueB);
+		launch_shade(s, kNumBsdfTypes, c->dsc, c->paths, cfg, c->q, tail, nullptr, 0, c->queueB, c->dcol);
 		if (sev) HIPCHK(c, hipEventRecord(sev[1], s));
 		HIPCHK(c, hipGetLastError());
 	}
@@ -441,17 +442,17 @@ int runBouncesDevice(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatil
 			rc = timed(c->shadeEvents, c->shadeEvUsed, s1, 0); if (rc) return rc;
 			launch_prep(s1, set, prev, c->viewsDev, c->q.bin_seg_cap, c->devStats);
 			if (cfg.dr_mode == 0 && tuningOr(c, "shade_fused", 1) != 0) {
-				launch_shade_all(s1, c->dsc, c->paths, cfg, c->q, c->viewsDev, c->binMask & kShadeAllBins, upper);
+				launch_shade_all(s1, c->dsc, c->paths, cfg, c->q, c->viewsDev, c->binMask & kShadeAllBins, upper, c->dcol);
 				// the bins the fused kernel leaves out (the composite), one launch each, only when the scene has them
 				BinView none{};
 				for (int bin = 0; bin < kNumBins; ++bin)
 					if (c->binMask & ~kShadeAllBins & (1u << bin))
-						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper);
+						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper, nullptr, c->dcol);
 			} else {
 				BinView none{};
 				for (int bin = 0; bin < kNumBins; ++bin)
 					if (c->binMask & (1u << bin))
-						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper);
+						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper, nullptr, c->dcol);
 			}
 			rc = timed(c->shadeEvents, c->shadeEvUsed, s1, 1); if (rc) return rc;
 			HIPCHK(c, hipGetLastError());
@@ -529,7 +530,7 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 		hipEvent_t *sev = c->timeKernels ? nextEventPair(c, c->shadeEvents, c->shadeEvUsed) : nullptr;
 		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
 		for (int bin = 0; bin < kNumBins; ++bin)
-			launch_shade(s, bin, c->dsc, c->paths, cfg, c->q, views[bin]);
+			launch_shade(s, bin, c->dsc, c->paths, cfg, c->q, views[bin], nullptr, 0, nullptr, c->dcol);
 		if (sev) HIPCHK(c, hipEventRecord(sev[1], s));
 		HIPCHK(c, hipGetLastError());
 		rc = readCounters(c); if (rc) return rc;
@@ -689,7 +690,7 @@ void mtsgpu_destroy(mtsgpu_ctx *c) {
 	if (!c) return;
 	(void) hipSetDevice(c->device);
 	(void) hipDeviceSynchronize();
-	freeAll(c->sceneAllocs); freeAll(c->pathAllocs);
+	freeAll(c->sceneAllocs); freeAll(c->colorAllocs); freeAll(c->pathAllocs);
 	if (c->ownFilm && c->film) (void) hipFree(c->film);
 	if (c->pixelList) (void) hipFree(c->pixelList);
 	if (c->ldScr) (void) hipFree(c->ldScr);
@@ -838,6 +839,8 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 	if (sc->background_lum >= (int32_t) sc->n_lums) return fail(c, MTSGPU_EINVAL, "background luminaire out of range");
 
 	freeAll(c->sceneAllocs);
+	freeAll(c->colorAllocs);      // a new scene starts without vertex colours (mtsgpu_set_vertex_colors)
+	c->dcol = DColors{ nullptr, nullptr };
 	c->haveScene = false;
 	DScene d{};
 	int rc = 0;
@@ -985,11 +988,87 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 	d.n_lums = sc->n_lums; d.n_nodes = sc->n_nodes; d.n_tris = sc->n_tris; d.n_shapes = sc->n_shapes;
 	for (int a = 0; a < 3; ++a) { d.aabb_min[a] = sc->aabb_min[a]; d.aabb_max[a] = sc->aabb_max[a]; }
 	c->dsc = d; c->nTris = sc->n_tris;
+	{
+		mtsgpu_ctx::HostScene &h = c->host;
+		h.nVerts = sc->n_verts;
+		h.triIdx.assign(sc->tri_idx, sc->tri_idx + 3 * (size_t) sc->n_tris);
+		h.shapeTriOffset.assign(sc->shape_tri_offset, sc->shape_tri_offset + sc->n_shapes + 1);
+		h.shapeType.assign(sc->n_shapes, (uint32_t) MTSGPU_SHAPE_TRIMESH);
+		if (sc->shape_type) h.shapeType.assign(sc->shape_type, sc->shape_type + sc->n_shapes);
+		h.bsdfType.assign(sc->bsdf_type, sc->bsdf_type + sc->n_bsdfs);
+		h.bsdfParams.assign(sc->bsdf_params, sc->bsdf_params + (size_t) MTSGPU_BSDF_NPARAMS * sc->n_bsdfs);
+		h.shapeBsdf.assign(sc->shape_bsdf, sc->shape_bsdf + sc->n_shapes);
+	}
 	// material queues that can ever be non-empty: the BSDF types of shapes that have one, and the "terminal" bin
 	c->binMask = 1u << kNumBsdfTypes;
 	for (uint32_t sIdx = 0; sIdx < sc->n_shapes; ++sIdx)
 		if (sc->shape_bsdf[sIdx] >= 0) c->binMask |= 1u << (sc->bsdf_type[sc->shape_bsdf[sIdx]] & 0xFFu);
 	c->haveScene = true;
+	return 0;
+}
+
+// the slot tables of the host (host.h) and of the kernels (kernels.h) are one table
+constexpr bool colorSlotTablesAgree() {
+	for (int t = 0; t < MTSGPU_BSDF_NTYPES; ++t)
+		for (int k = 0; k < 2; ++k)
+			if (kBsdfColorSlotOffset[t][k] != bsdf_color_slot_offset(t, k)) return false;
+	return true;
+}
+static_assert(colorSlotTablesAgree(), "BSDF colour slot tables differ");
+
+int mtsgpu_set_vertex_colors(mtsgpu_ctx *c, const float *vtx_col, const uint32_t *shape_has_colors, const uint32_t *bsdf_color_slots) {
+	if (!c) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_set_vertex_colors before mtsgpu_upload_scene");
+	c->lastPass.valid = false;
+	HIPCHK(c, hipSetDevice(c->device));
+	// nothing may still read the arrays that go (the shading launches of a render that was not synchronised)
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
+	freeAll(c->colorAllocs);
+	c->dcol = DColors{ nullptr, nullptr };
+	if (!vtx_col && !shape_has_colors && !bsdf_color_slots) return 0;
+	if ((vtx_col == nullptr) != (shape_has_colors == nullptr))
+		return fail(c, MTSGPU_EINVAL, "vtx_col and shape_has_colors must both be given or both be NULL");
+	const mtsgpu_ctx::HostScene &h = c->host;
+	const uint32_t nShapes = (uint32_t) h.shapeBsdf.size(), nBsdfs = (uint32_t) h.bsdfType.size();
+	bool anySlot = false;
+	if (bsdf_color_slots) {
+		const std::string why = checkBsdfColorSlots(nBsdfs, h.bsdfType.data(), h.bsdfParams.data(), bsdf_color_slots);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+		for (uint32_t s = 0; s < nShapes; ++s) {
+			const int32_t b = h.shapeBsdf[s];
+			if (b < 0 || !bsdf_color_slots[b]) continue;
+			if (h.shapeType[s] != MTSGPU_SHAPE_TRIMESH)
+				return fail(c, MTSGPU_EINVAL, "shape %u: BSDF %d takes vertex colours, but a sphere has none (its.color would be read unwritten, shape.h:162-163)", s, b);
+			if (!shape_has_colors || !shape_has_colors[s])
+				return fail(c, MTSGPU_EINVAL, "shape %u: BSDF %d takes vertex colours, but the mesh has none (its.color would be read unwritten, shape.h:162-163)", s, b);
+		}
+		for (uint32_t b = 0; b < nBsdfs; ++b) anySlot |= bsdf_color_slots[b] != 0;
+	}
+	if (!vtx_col) return 0;       // masks that are all zero and no colours: nothing to keep
+	// the gather array: the colours of the three vertices of every primitive of a coloured mesh, zero elsewhere
+	const size_t CS = 4 * (size_t) kTriColStride;
+	std::vector<float> triCol(CS * ((size_t) c->nTris + 1), 0.0f);
+	bool anyColors = false;
+	for (uint32_t s = 0; s < nShapes; ++s) {
+		if (!shape_has_colors[s]) continue;
+		if (h.shapeType[s] != MTSGPU_SHAPE_TRIMESH) return fail(c, MTSGPU_EINVAL, "shape %u: only a triangle mesh can carry vertex colours", s);
+		anyColors = true;
+		for (uint32_t t = h.shapeTriOffset[s]; t < h.shapeTriOffset[s + 1]; ++t)
+			for (int k = 0; k < 3; ++k) {
+				const uint32_t v = h.triIdx[3 * (size_t) t + k];      // < n_verts: mtsgpu_upload_scene checked it
+				const float *col = vtx_col + 3 * (size_t) v;
+				if (!std::isfinite(col[0]) || !std::isfinite(col[1]) || !std::isfinite(col[2]))
+					return fail(c, MTSGPU_EINVAL, "shape %u: non-finite colour at vertex %u", s, v);
+				std::memcpy(&triCol[CS * (size_t) t + 4 * (size_t) k], col, 12);
+			}
+	}
+	if (!anyColors) return 0;
+	const float *dCol = nullptr; const uint32_t *dSlots = nullptr;
+	int rc = upload(c, &dCol, triCol.data(), triCol.size(), &c->colorAllocs);
+	if (!rc && anySlot) rc = upload(c, &dSlots, bsdf_color_slots, nBsdfs, &c->colorAllocs);
+	if (rc) { freeAll(c->colorAllocs); return rc; }
+	c->dcol = DColors{ reinterpret_cast<const float4 *>(dCol), dSlots };
 	return 0;
 }
 
@@ -1096,6 +1175,8 @@ int mtsgpu_load_serialized(const char *path, int shape_index, mtsgpu_loaded_mesh
 }
 
 void mtsgpu_loaded_mesh_free(mtsgpu_loaded_mesh *m) { delete m; }
+
+const float *mtsgpu_loaded_mesh_colors(const mtsgpu_loaded_mesh *m) { return (m && !m->m.colors.empty()) ? m->m.colors.data() : nullptr; }
 
 int mtsgpu_tabulate_filter(int kind, float half_size, float p0, float p1, float *size_xy, float *values) {
 	if (!size_xy || !values || kind < 0 || kind > 4) return fail(nullptr, MTSGPU_EINVAL, "bad filter arguments");
@@ -1655,6 +1736,60 @@ int mtsgpu_bsdf_eval_table(mtsgpu_ctx *c, uint32_t n_bsdfs, const uint32_t *type
 	return 0;
 }
 
+int mtsgpu_bsdf_eval_colored(mtsgpu_ctx *c, uint32_t bsdf_type, const float *params, uint32_t slots, const float color[3], int op,
+                             uint32_t n, const float *queries, float *out) {
+	if (!c || !params || !color || !queries || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	if ((bsdf_type & 0xFFu) >= (uint32_t) MTSGPU_BSDF_NTYPES || (bsdf_type & ~(0xFFu | (uint32_t) MTSGPU_BSDF_TWOSIDED)) || op < 0 || op > 2)
+		return fail(c, MTSGPU_EINVAL, "bad BSDF type or operation");
+	if ((bsdf_type & 0xFFu) == (uint32_t) MTSGPU_BSDF_COMPOSITE)
+		return fail(c, MTSGPU_EINVAL, "a composite has no texture slot of its own, and its children take no vertex colours");
+	if (slots >> bsdfColorSlotCount(bsdf_type))
+		return fail(c, MTSGPU_EINVAL, "vertex-colour slot mask %u names a slot beyond the %d texture slot(s) of BSDF type %u", slots, bsdfColorSlotCount(bsdf_type), bsdf_type & 0xFFu);
+	if (n == 0) return 0;
+	if (n > (1u << 24)) return fail(c, MTSGPU_EINVAL, "at most 2^24 query records per call");
+	HIPCHK(c, hipSetDevice(c->device));
+	float *dQ = nullptr, *dOut = nullptr;
+	HIPCHK(c, hipMalloc((void **) &dQ, (size_t) n * 6 * sizeof(float)));
+	hipError_t e = hipMalloc((void **) &dOut, (size_t) n * 8 * sizeof(float));
+	if (e == hipSuccess) e = hipMemcpyAsync(dQ, queries, (size_t) n * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) {
+		launch_bsdf_eval_colored(c->stream, bsdf_type, params, slots, color, op, n, dQ, dOut);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, (size_t) n * 8 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	(void) hipFree(dQ); if (dOut) (void) hipFree(dOut);
+	if (e != hipSuccess) return fail(c, MTSGPU_EHIP, "BSDF read-out failed: %s", hipGetErrorString(e));
+	return 0;
+}
+
+int mtsgpu_vertex_color_eval(mtsgpu_ctx *c, uint32_t n, const uint32_t *prim, const float *uv, float *out) {
+	if (!c || !prim || !uv || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (!c->haveScene || !c->dcol.tri_col) return fail(c, MTSGPU_ESTATE, "no vertex colours are set (mtsgpu_set_vertex_colors)");
+	if (n > (1u << 24)) return fail(c, MTSGPU_EINVAL, "at most 2^24 query records per call");
+	for (uint32_t i = 0; i < n; ++i)      // the kernel indexes tri_col with it
+		if (prim[i] >= c->nTris) return fail(c, MTSGPU_EINVAL, "record %u: primitive %u out of range", i, prim[i]);
+	if (n == 0) return 0;
+	HIPCHK(c, hipSetDevice(c->device));
+	uint32_t *dP = nullptr; float *dUV = nullptr, *dOut = nullptr;
+	hipError_t e = hipMalloc((void **) &dP, (size_t) n * sizeof(uint32_t));
+	if (e == hipSuccess) e = hipMalloc((void **) &dUV, (size_t) n * 2 * sizeof(float));
+	if (e == hipSuccess) e = hipMalloc((void **) &dOut, (size_t) n * 3 * sizeof(float));
+	if (e == hipSuccess) e = hipMemcpyAsync(dP, prim, (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(dUV, uv, (size_t) n * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) {
+		launch_vertex_color_eval(c->stream, c->dcol.tri_col, n, dP, dUV, dOut);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, (size_t) n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (dP) (void) hipFree(dP);
+	if (dUV) (void) hipFree(dUV);
+	if (dOut) (void) hipFree(dOut);
+	if (e != hipSuccess) return fail(c, MTSGPU_EHIP, "vertex-colour read-out failed: %s", hipGetErrorString(e));
+	return 0;
+}
+
 int mtsgpu_sky_configure(const float *block, float *derived) {
 	if (!block || !derived) return fail(nullptr, MTSGPU_EINVAL, "null argument");
 	skyConfigure(block, derived);
@@ -1804,6 +1939,21 @@ int mtsgpu_flatten(const mtsgpu_scene_desc *desc, const mtsgpu_kd_params *kd, mt
 
 const mtsgpu_scene *mtsgpu_flat_scene_get(const mtsgpu_flat_scene *fs) { return fs ? &fs->fs.sc : nullptr; }
 void mtsgpu_flat_scene_free(mtsgpu_flat_scene *fs) { delete fs; }
+
+int mtsgpu_flat_scene_set_mesh_colors(mtsgpu_flat_scene *fs, uint32_t mesh_index, const float *colors) {
+	if (!fs) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	const std::string why = setMeshColors(fs->fs, mesh_index, colors);
+	if (!why.empty()) return fail(nullptr, MTSGPU_EINVAL, "%s", why.c_str());
+	return 0;
+}
+
+static bool flatSceneHasColors(const mtsgpu_flat_scene *fs) {
+	if (!fs) return false;
+	for (uint32_t h : fs->fs.shapeHasColors) if (h) return true;
+	return false;
+}
+const float *mtsgpu_flat_scene_vertex_colors(const mtsgpu_flat_scene *fs) { return flatSceneHasColors(fs) ? fs->fs.vtxCol.data() : nullptr; }
+const uint32_t *mtsgpu_flat_scene_shape_has_colors(const mtsgpu_flat_scene *fs) { return flatSceneHasColors(fs) ? fs->fs.shapeHasColors.data() : nullptr; }
 
 int mtsgpu_flat_scene_kdstats(const mtsgpu_flat_scene *fs, double *out6) {
 	if (!fs || !out6) return fail(nullptr, MTSGPU_EINVAL, "null argument");

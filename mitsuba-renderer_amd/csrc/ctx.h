@@ -24,6 +24,17 @@ struct mtsgpu_ctx {
 	mg::DScene dsc{};
 	std::vector<void *> sceneAllocs;
 	uint32_t nTris = 0;
+	// What mtsgpu_set_vertex_colors needs of the uploaded scene once the caller's arrays may be gone: host copies, taken by
+	// mtsgpu_upload_scene.  colorAllocs: DColors::tri_col and bsdf_color_slots, owned apart from sceneAllocs because they
+	// come and go between two uploads.
+	struct HostScene {
+		uint32_t nVerts = 0;
+		std::vector<uint32_t> triIdx, shapeTriOffset, shapeType, bsdfType;
+		std::vector<int32_t> shapeBsdf;
+		std::vector<float> bsdfParams;
+	} host;
+	std::vector<void *> colorAllocs;
+	mg::DColors dcol{ nullptr, nullptr };   // what the vertex-colour kernels take (NULL, NULL without colours)
 
 	// configuration
 	bool haveCamera = false;

@@ -70,6 +70,22 @@ float buildCdf(const std::vector<float> &values, float *cdf, float *pdf) {
 
 void buildEnvMap(const mtsgpu_scene_desc &d, float *P, FlatScene &fs);     // defined below (needs the matrix inverse)
 
+std::string setMeshColors(FlatScene &f, uint32_t mesh, const float *colors) {
+	if (mesh >= f.sc.n_shapes) return "mesh index " + std::to_string(mesh) + " out of range";
+	if (f.shapeType[mesh] != MTSGPU_SHAPE_TRIMESH) return "mesh " + std::to_string(mesh) + ": only a triangle mesh can carry vertex colours";
+	const size_t first = f.shapeVtxOffset[mesh], count = f.shapeVtxOffset[mesh + 1] - first;
+	if (f.vtxCol.empty()) {
+		if (!colors) return std::string();
+		f.vtxCol.assign(3 * (size_t) f.sc.n_verts + 3, 0.0f);
+		f.shapeHasColors.assign((size_t) f.sc.n_shapes + 1, 0u);
+	}
+	// flattenScene lays the vertices of a mesh out in the mesh's own order, none duplicated: colour i belongs to pool row first + i
+	if (colors) std::memcpy(&f.vtxCol[3 * first], colors, sizeof(float) * 3 * count);
+	else std::fill(f.vtxCol.begin() + 3 * first, f.vtxCol.begin() + 3 * (first + count), 0.0f);
+	f.shapeHasColors[mesh] = colors ? 1u : 0u;
+	return std::string();
+}
+
 void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs) {
 	const uint32_t nShapes = d.n_meshes, nLums = d.n_lums;
 	size_t nVerts = 0, nTris = 0;
@@ -89,6 +105,8 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 	fs.vtxNrm.assign(3 * nVerts + 3, 0.0f);
 	fs.triIdx.assign(3 * nTris + 3, 0u);
 	fs.shapeTriOffset.assign(nShapes + 1, 0u);
+	fs.shapeVtxOffset.assign(nShapes + 1, 0u);
+	fs.vtxCol.clear(); fs.shapeHasColors.clear();
 	fs.shapeFlags.assign(nShapes + 1, 0u);
 	fs.shapeBsdf.assign(nShapes + 1, -1);
 	fs.shapeLum.assign(nShapes + 1, -1);
@@ -116,6 +134,7 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 		if (m.bsdf >= (int32_t) d.n_bsdfs || m.lum >= (int32_t) nLums)
 			throw std::runtime_error("flatten: mesh references a missing BSDF/luminaire");
 		fs.shapeTriOffset[s] = tbase;
+		fs.shapeVtxOffset[s] = vbase;
 		fs.shapeBsdf[s] = m.bsdf;
 		if (m.bsdf >= 0 && !shapeHasTangentFrame((uint32_t) m.shape_type) && bsdfIsAnisotropic(d.bsdf_type, d.bsdf_params, (uint32_t) m.bsdf))
 			throw std::runtime_error("flatten: " + anisotropicOnMeshMessage(s));
@@ -158,6 +177,7 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 		vbase += m.n_verts; tbase += m.n_tris;
 	}
 	fs.shapeTriOffset[nShapes] = tbase;
+	fs.shapeVtxOffset[nShapes] = vbase;
 
 	// kd-tree + TriAccel table (ShapeKDTree::build, skdtree.cpp:62-101)
 	buildKdTree(fs.vtxPos.data(), fs.triIdx.data(), tbase, genBox.data(), kp, fs.kd);

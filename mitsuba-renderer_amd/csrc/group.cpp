@@ -427,6 +427,18 @@ int mtsgpu_group_set_film_statistics(mtsgpu_group *g, int on) {
 	return 0;
 }
 
+int mtsgpu_group_set_vertex_colors(mtsgpu_group *g, const float *vtx_col, const uint32_t *shape_has_colors, const uint32_t *bsdf_color_slots) {
+	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
+	for (size_t i = 0; i < g->members.size(); ++i)
+		if (int r = mtsgpu_set_vertex_colors(g->members[i], vtx_col, shape_has_colors, bsdf_color_slots)) {
+			const std::string why = mtsgpu_last_error(g->members[i]);
+			// no member keeps colours another one could not take: the group renders one scene
+			for (size_t k = 0; k < i; ++k) (void) mtsgpu_set_vertex_colors(g->members[k], nullptr, nullptr, nullptr);
+			return gfail(g, r, "set_vertex_colors: %s", why.c_str());
+		}
+	return 0;
+}
+
 int mtsgpu_hbm_triad(int device, size_t bytes, int iters, double *gbs) {
 	if (!gbs || bytes < 4096 || iters <= 0) return gfail(nullptr, MTSGPU_EINVAL, "bad triad arguments");
 	*gbs = 0;

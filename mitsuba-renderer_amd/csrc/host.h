@@ -30,7 +30,40 @@ struct FlatScene {
 	std::vector<float> vtxPos, vtxNrm, shapeParams, bsdfParams, lumParams, lumInvArea, lumTriCdf, lumSelCdf, lumSelPdf;
 	std::vector<uint32_t> triIdx, shapeTriOffset, shapeFlags, shapeType, triaccel, bsdfType, lumType, lumCdfOffset;
 	std::vector<int32_t> shapeBsdf, shapeLum, lumShape;
+	// per-vertex colours (mtsgpu_flat_scene_set_mesh_colors): the pool [n_verts][3] in the order of vtxPos and one flag per
+	// shape, both empty until a mesh receives colours; shapeVtxOffset[s] = the first pool row of shape s
+	std::vector<float> vtxCol;
+	std::vector<uint32_t> shapeHasColors, shapeVtxOffset;
 };
+
+// Texture-typed spectrum slots per BSDF type, in slot order (include/mtsgpu.h): the first float of each slot's three in the
+// parameter block, -1 = no such slot.  The composite has none of its own.
+constexpr int kBsdfColorSlotOffset[MTSGPU_BSDF_NTYPES][2] = {
+	{ 0, -1 }, { 2, 5 }, { 7, -1 }, { 5, 8 }, { 0, -1 }, { 5, 8 }, { 4, 7 }, { 0, -1 }, { 7, 10 }, { -1, -1 } };
+inline int bsdfColorSlotCount(uint32_t type) {
+	const uint32_t t = type & 0xFFu;
+	if (t >= MTSGPU_BSDF_NTYPES) return 0;
+	return (kBsdfColorSlotOffset[t][0] >= 0) + (kBsdfColorSlotOffset[t][1] >= 0);
+}
+// What mtsgpu_set_vertex_colors requires of the slot masks against a checked BSDF table: no bit beyond the slots of the
+// type, none on a composite's child.  Returns the reason, or an empty string.
+inline std::string checkBsdfColorSlots(uint32_t n_bsdfs, const uint32_t *type, const float *params, const uint32_t *slots) {
+	auto msg = [](uint32_t b, const std::string &what) { return "BSDF " + std::to_string(b) + ": " + what; };
+	for (uint32_t b = 0; b < n_bsdfs; ++b) {
+		const int n = bsdfColorSlotCount(type[b]);
+		if (slots[b] >> n)
+			return msg(b, "vertex-colour slot mask " + std::to_string(slots[b]) + " names a slot beyond the " + std::to_string(n) + " texture slot(s) of its type");
+	}
+	for (uint32_t b = 0; b < n_bsdfs; ++b) {
+		if ((type[b] & 0xFFu) != MTSGPU_BSDF_COMPOSITE) continue;
+		const float *P = params + (size_t) MTSGPU_BSDF_NPARAMS * b;
+		const int n = (int) P[0];
+		for (int i = 0; i < n; ++i)
+			if (slots[(uint32_t) P[1 + n + i]])
+				return msg(b, "composite child " + std::to_string(i) + " takes vertex colours: a composite's children keep constant parameters, not supported");
+	}
+	return std::string();
+}
 
 // What the kernels require of a BSDF table (mtsgpu_upload_scene, mtsgpu_bsdf_eval_table and the flattener all ask here):
 // known types, and for a composite (block: [0] n, [1..n] weights, [1+n..2n] child indices as floats) 1 <= n <=
@@ -155,10 +188,15 @@ inline std::string checkSkyLuminaire(uint32_t l, const float *LP, int32_t backgr
 }
 
 void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs);
+// The per-vertex colours of shape `mesh` of a flattened scene (mtsgpu_flat_scene_set_mesh_colors): colors [that mesh's
+// n_verts][3] copied into fs.vtxCol at the mesh's rows, NULL takes them away again.  Returns the reason it refuses, or an
+// empty string.
+std::string setMeshColors(FlatScene &fs, uint32_t mesh, const float *colors);
 
 // One shape of a `.serialized` file (TriMesh::TriMesh(Stream *, int), src/librender/trimesh.cpp:156-236)
 struct LoadedMesh {
 	std::vector<float> positions, normals;     // normals empty when the file has none
+	std::vector<float> colors;                 // [n_verts][3], empty without the EHasColors block (trimesh.cpp:113-118,223-229)
 	std::vector<uint32_t> triangles;
 	bool faceNormals = false;
 };

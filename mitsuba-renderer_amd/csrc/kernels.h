@@ -116,6 +116,26 @@ struct DScene {
 	// background is not a sky: the shading launches pick their sky instantiations by it
 	const float *sky;
 };
+// Per-vertex colours (mtsgpu_set_vertex_colors), both NULL without them.  Kept apart from DScene and handed to the vertex-colour
+// kernels only, so that every other kernel keeps the argument layout it had.  tri_col: a gather array in primitive order like
+// tri_pos, three float4 per primitive = c0.rgb -, c1.rgb -, c2.rgb - (zero for the primitives of shapes without colours),
+// allocated only while colours are set.  bsdf_color_slots[n_bsdfs]: bit s = the s-th texture-typed spectrum slot of the
+// BSDF takes its.color instead of the three floats of its block (bsdf_color_slot_offset); non-NULL only while some mask
+// is non-zero, and the shading launches pick their vertex-colour kernels by it
+struct DColors {
+	const float4   *tri_col;
+	const uint32_t *bsdf_color_slots;
+};
+constexpr int kTriColStride = 3;      // float4 per primitive of DColors::tri_col
+// First float of texture slot s (0, 1) of BSDF type bt inside its parameter block, -1 = the type has no such slot
+// (include/mtsgpu.h): lambertian reflectance | dielectric specRefl, specTrans | roughmetal specRefl | microfacet diffuseRefl,
+// specRefl | mirror specRefl | phong diffuseRefl, specRefl | roughglass specRefl, specTrans | difftrans transmittance | ward
+// diffuseRefl, specRefl.  The composite has none: its children keep constant parameters.
+constexpr int bsdf_color_slot_offset(int bt, int s) {
+	return bt == 0 ? (s == 0 ? 0 : -1) : bt == 1 ? (s == 0 ? 2 : 5) : bt == 2 ? (s == 0 ? 7 : -1) : bt == 3 ? (s == 0 ? 5 : 8)
+	     : bt == 4 ? (s == 0 ? 0 : -1) : bt == 5 ? (s == 0 ? 5 : 8) : bt == 6 ? (s == 0 ? 4 : 7) : bt == 7 ? (s == 0 ? 0 : -1)
+	     : bt == 8 ? (s == 0 ? 7 : 10) : -1;
+}
 
 // What k_trace needs of the scene (a kernel argument: the fewer scalar registers it pins, the fewer get spilled)
 struct DTraceScene {
@@ -328,6 +348,11 @@ void launch_bsdf_eval(hipStream_t s, uint32_t type, const float *params, int op,
 // the same for entry `index` of a BSDF table in device memory, types[n_bsdfs] / params[n_bsdfs][16] (a composite reads its children there)
 void launch_bsdf_eval_table(hipStream_t s, const uint32_t *types, const float *params, uint32_t index, int op, uint32_t n,
                             const float *queries, float *out);
+// mtsgpu_bsdf_eval_colored: the same read-out through bsdf_block_with_color (slots of `slots` take color[3])
+void launch_bsdf_eval_colored(hipStream_t s, uint32_t type, const float *params, uint32_t slots, const float *color, int op, uint32_t n,
+                              const float *queries, float *out);
+// mtsgpu_vertex_color_eval: its.color for n (primitive, u, v) records of tri_col; uv [n][2], out [n][3]
+void launch_vertex_color_eval(hipStream_t s, const float4 *tri_col, uint32_t n, const uint32_t *prim, const float *uv, float *out);
 // the sky luminaire (mtsgpu_lum_eval): Le (op 0), sample (1), pdf (2) for n query records [n][6]; block = the parameter
 // block followed by its derived array, in device memory; out [n][12]
 void launch_sky_eval(hipStream_t s, const float *block, int op, uint32_t n, const float *queries, float *out);
@@ -348,11 +373,11 @@ struct BinView { uint32_t prefix[kBinShards + 1]; };
 // bin_ids: the bin's id segments (q.bin(bin) unless the caller shades another queue)
 void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                   const DQueues &q, const BinView &view, const BinView *views_dev = nullptr, uint32_t n_bound = 0,
-                  const uint32_t *bin_ids = nullptr);
+                  const uint32_t *bin_ids = nullptr, const DColors &col = DColors{ nullptr, nullptr });
 // device-driven bounces, path integrator / one-sample direct integrator: all bins of bin_mask in one launch; views_dev as
 // above, n_bound bounds the sum of the bin sizes
 void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,
-                      const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound);
+                      const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound, const DColors &col = DColors{ nullptr, nullptr });
 // device-driven bounces: per-bin views from the shard counters of the closest-hit launch that just ran (`cur`), and
 // the counter set of the next bounce zeroed
 void launch_prep(hipStream_t s, const uint32_t *cur, uint32_t *next_set, BinView *views_dev, uint32_t bin_seg_cap,

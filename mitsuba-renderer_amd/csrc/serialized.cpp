@@ -95,7 +95,8 @@ void loadSerializedMesh(const char *path, int index, LoadedMesh &out) {
 	out.normals.clear();
 	if (flags & kHasNormals) { out.normals.resize(3 * nv); z.readFloats(dbl, out.normals.data(), 3 * nv); }
 	if (flags & kHasTexcoords) { std::vector<float> skip(2 * nv); z.readFloats(dbl, skip.data(), 2 * nv); }     // no textures on this path
-	if (flags & kHasColors) { std::vector<float> skip(3 * nv); z.readFloats(dbl, skip.data(), 3 * nv); }
+	out.colors.clear();
+	if (flags & kHasColors) { out.colors.resize(3 * nv); z.readFloats(dbl, out.colors.data(), 3 * nv); }      // m_vertexColors (trimesh.cpp:223-229)
 	out.triangles.resize(3 * nt);
 	z.read(out.triangles.data(), 3 * nt * sizeof(uint32_t));
 	for (uint32_t v : out.triangles)

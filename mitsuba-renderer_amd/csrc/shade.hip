@@ -73,6 +73,27 @@ __device__ __forceinline__ void fill_its(const DScene &sc, V3 rayO, V3 rayD, flo
 	its.wi = V3(dot(md, its.shS), dot(md, its.shT), dot(md, its.shN));
 }
 
+// its.color of fillIntersectionRecord (skdtree.h:364,417-421): the three vertex colours of the primitive (DColors::tri_col)
+// weighted with b = ((1 - u) - v, u, v), in the reference's operation order: (c0 * b.x + c1 * b.y) + c2 * b.z per channel
+__device__ __forceinline__ V3 its_color(const float4 *tri_col, uint32_t prim, float u, float v) {
+	const float4 *TC = tri_col + kTriColStride * (size_t) prim;
+	const float4 c0 = TC[0], c1 = TC[1], c2 = TC[2];
+	const float bx = 1 - u - v, by = u, bz = v;
+	return V3(c0.x * bx + c1.x * by + c2.x * bz, c0.y * bx + c1.y * by + c2.y * bz, c0.z * bx + c1.z * by + c2.z * bz);
+}
+// The parameter block of one hit: Q = the BSDF's block P with the texture slots named by `slots` (bit s = slot s of type BT,
+// bsdf_color_slot_offset) replaced by `color` -- what a `vertexcolors` texture in that slot returns (vertexcolors.cpp:41-43).
+// Every index is a compile-time constant, so Q lives in registers.  The shading kernels and the read-out hook
+// (k_bsdf_eval_colored) both build their blocks here.
+template <int BT>
+__device__ __forceinline__ void bsdf_block_with_color(const float *P, uint32_t slots, V3 color, float (&Q)[kBsdfNParams]) {
+	#pragma unroll
+	for (int k = 0; k < kBsdfNParams; ++k) Q[k] = P[k];
+	constexpr int o0 = bsdf_color_slot_offset(BT, 0), o1 = bsdf_color_slot_offset(BT, 1);
+	if (o0 >= 0 && (slots & 1u)) { Q[o0 < 0 ? 0 : o0] = color.x; Q[o0 < 0 ? 0 : o0 + 1] = color.y; Q[o0 < 0 ? 0 : o0 + 2] = color.z; }
+	if (o1 >= 0 && (slots & 2u)) { Q[o1 < 0 ? 0 : o1] = color.x; Q[o1 < 0 ? 0 : o1 + 1] = color.y; Q[o1 < 0 ? 0 : o1 + 2] = color.z; }
+}
+
 struct LRec { V3 p, n, d, value; float pdf; int lum; };
 
 // DiscretePDF::sample / sampleReuse (include/mitsuba/core/pdf.h:102-133)
@@ -1132,6 +1153,43 @@ __global__ void k_bsdf_eval_table(const uint32_t *types, const float *params, ui
 	for (int k = 0; k < 8; ++k) out[8 * (size_t) i + k] = o[k];
 }
 
+// mtsgpu_bsdf_eval_colored: k_bsdf_eval on the block bsdf_block_with_color builds from (params, slots, color)
+template <int BT>
+__device__ __forceinline__ void bsdf_eval_colored_one(bool two, const float *P, uint32_t slots, V3 color, int op, const float *q, float *o) {
+	float Q[kBsdfNParams];
+	bsdf_block_with_color<BT>(P, slots, color, Q);
+	bsdf_eval_one<BT>(BsdfTable{ nullptr, nullptr }, two, Q, op, q, o);
+}
+__global__ void k_bsdf_eval_colored(uint32_t type, BsdfParams params, uint32_t slots, float cr, float cg, float cb, int op, uint32_t n,
+                                    const float *queries, float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const bool two = (type & 0x100u) != 0;
+	const float *P = params.v, *q = queries + 6 * (size_t) i;
+	const V3 color(cr, cg, cb);
+	float o[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+	switch (type & 0xFFu) {
+		case 0: bsdf_eval_colored_one<0>(two, P, slots, color, op, q, o); break;
+		case 1: bsdf_eval_colored_one<1>(two, P, slots, color, op, q, o); break;
+		case 2: bsdf_eval_colored_one<2>(two, P, slots, color, op, q, o); break;
+		case 3: bsdf_eval_colored_one<3>(two, P, slots, color, op, q, o); break;
+		case 4: bsdf_eval_colored_one<4>(two, P, slots, color, op, q, o); break;
+		case 5: bsdf_eval_colored_one<5>(two, P, slots, color, op, q, o); break;
+		case 6: bsdf_eval_colored_one<6>(two, P, slots, color, op, q, o); break;
+		case 7: bsdf_eval_colored_one<7>(two, P, slots, color, op, q, o); break;
+		default: bsdf_eval_colored_one<8>(two, P, slots, color, op, q, o); break;
+	}
+	#pragma unroll
+	for (int k = 0; k < 8; ++k) out[8 * (size_t) i + k] = o[k];
+}
+// mtsgpu_vertex_color_eval: its_color for n records; the host has checked prim < n_tris
+__global__ void k_vertex_color_eval(const float4 *tri_col, uint32_t n, const uint32_t *prim, const float *uv, float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const V3 c = its_color(tri_col, prim[i], uv[2 * (size_t) i], uv[2 * (size_t) i + 1]);
+	out[3 * (size_t) i] = c.x; out[3 * (size_t) i + 1] = c.y; out[3 * (size_t) i + 2] = c.z;
+}
+
 // The sky luminaire read out for n query records (mtsgpu_lum_eval): block = its parameters followed by the derived array
 // (kLumStride + MTSGPU_SKY_NDERIVED floats in device memory); queries [n][6], out [n][12]
 __global__ void k_sky_eval(const float *block, int op, uint32_t n, const float *queries, float *out) {
@@ -1188,10 +1246,12 @@ struct ShadeRow {
 };
 __device__ __forceinline__ uint32_t shade_row_index(uint32_t lane, uint32_t k) { return lane * kRowStride + (MG_SHADE_PACKED ? (k ^ (lane & 7u)) : k); }
 
-template <int BT, bool ROUNDS, bool SKY>
+// VCOL: the instantiation for scenes with a coloured BSDF slot (DColors::bsdf_color_slots != NULL): the block the BSDF reads
+// is built per hit by bsdf_block_with_color.  Every other scene runs the instantiation without that code.
+template <int BT, bool ROUNDS, bool SKY, bool VCOL>
 __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, const DConfig &cfg, const uint32_t id,
                                            const float4 ro, const float4 rd, const uint4 h, const float4 T4, const float4 L4,
-                                           const ShadeRow row, bool &continues, bool &wantShadow, V3 &neeV, V3 &shO, V3 &shD) {
+                                           const ShadeRow row, bool &continues, bool &wantShadow, V3 &neeV, V3 &shO, V3 &shD, const DColors &col) {
 	{
 		// rounds of MIDirectIntegrator (DConfig::dr_mode): later BSDF samples start again from the camera hit
 		const int mode = ROUNDS ? cfg.dr_mode : 0;
@@ -1292,6 +1352,14 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				break;                                      // bsdf == NULL (path.cpp:72-77)
 			const int bsdfIdx = sc.shape_bsdf[its.shape];
 			const float *BP = sc.bsdf_params + 16 * (size_t) bsdfIdx;
+			float colouredBlock[kBsdfNParams];
+			if (VCOL && BT < 9) {
+				// a `vertexcolors` texture in a slot of this BSDF: that slot holds its.color for this hit
+				const uint32_t slots = col.bsdf_color_slots[bsdfIdx];
+				const V3 color = slots ? its_color(col.tri_col, h.w, __uint_as_float(h.y), __uint_as_float(h.z)) : V3(0, 0, 0);
+				bsdf_block_with_color<BT>(BP, slots, color, colouredBlock);
+				BP = colouredBlock;
+			}
 			const bool twoSided = (sc.bsdf_type[bsdfIdx] & 0x100u) != 0;
 			const BsdfTable tab{ sc.bsdf_type, sc.bsdf_params };
 			if (shapeLum >= 0 && (flags & F_EMITTED) && !(skipToNee || skipToBsdf)) {
@@ -1393,9 +1461,9 @@ struct ShadeShared {
 };
 // One workgroup of k_shade: the paths block * kShadeBlock .. of the material queue whose segment sizes are `prefix`
 // (prefix[kBinShards] entries in kBinShards segments of bin_ids)
-template <int BT, bool ROUNDS, bool SKY>
+template <int BT, bool ROUNDS, bool SKY, bool VCOL>
 __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const uint32_t *prefix,
-                                            const uint32_t *bin_ids, const uint32_t block, ShadeShared &sh) {
+                                            const uint32_t *bin_ids, const uint32_t block, ShadeShared &sh, const DColors &col) {
 	uint32_t (&s_cnt)[2][kShadeBlock / 64] = sh.cnt;
 	uint32_t (&s_base)[2] = sh.base;
 	float4 (&s_rows)[kShadeBlock / 64][64 * kRowStride] = sh.rows;
@@ -1480,7 +1548,7 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	}
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	if (active)
-		shade_path<BT, ROUNDS, SKY>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD);
+		shade_path<BT, ROUNDS, SKY, VCOL>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col);
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	#pragma unroll
 	for (int r = 0; r < 8; ++r) {
@@ -1532,7 +1600,14 @@ __global__ MG_SHADE_BOUNDS void k_shade(DScene sc, DPaths ps, DConfig cfg, DQueu
                                                        const BinView *views_dev, const uint32_t *bin_ids) {
 	__shared__ ShadeShared sh;
 	// the bin's segment sizes: a kernel argument when the host read the counters back, otherwise what k_prep wrote
-	shade_block<BT, ROUNDS, SKY>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh);
+	shade_block<BT, ROUNDS, SKY, false>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, DColors{ nullptr, nullptr });
+}
+// the same for scenes with a coloured BSDF slot: the only kernels that take the colours
+template <int BT, bool ROUNDS, bool SKY>
+__global__ MG_SHADE_BOUNDS void k_shade_vcol(DScene sc, DPaths ps, DConfig cfg, DQueues q, BinView view_host,
+                                                            const BinView *views_dev, const uint32_t *bin_ids, DColors col) {
+	__shared__ ShadeShared sh;
+	shade_block<BT, ROUNDS, SKY, true>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col);
 }
 
 // All material queues of a bounce in ONE launch (device-driven bounces): the workgroups are dealt to the bins in bin order,
@@ -1540,10 +1615,11 @@ __global__ MG_SHADE_BOUNDS void k_shade(DScene sc, DPaths ps, DConfig cfg, DQueu
 // short launches, and a launch of k_shade -- 1024 threads and 148 KB of LDS per workgroup -- costs 10-20 us even when
 // nearly all of its worst-case grid exits at once: one launch per bounce instead of one per BSDF type present.
 // SKY: the launch for scenes whose background is a sky (launch_shade_all picks it): every other scene runs the instantiation
-// without that code, whose registers are what they were before the sky existed
-template <bool SKY>
-__global__ MG_SHADE_BOUNDS void k_shade_all(DScene sc, DPaths ps, DConfig cfg, DQueues q, const BinView *views_dev, uint32_t bin_mask) {
-	__shared__ ShadeShared sh;
+// without that code, whose registers are what they were before the sky existed.  VCOL: likewise for scenes with a coloured
+// BSDF slot; the bins that cannot have one (composite, terminal) run the same code either way
+template <bool SKY, bool VCOL>
+__device__ __forceinline__ void shade_all(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const BinView *views_dev, uint32_t bin_mask,
+                                          ShadeShared &sh, const DColors &col) {
 	uint32_t block = blockIdx.x;
 	int bin = -1;
 	for (int b = 0; b < kNumBins; ++b) {
@@ -1555,18 +1631,28 @@ __global__ MG_SHADE_BOUNDS void k_shade_all(DScene sc, DPaths ps, DConfig cfg, D
 	if (bin < 0) return;
 	const uint32_t *prefix = views_dev[bin].prefix, *ids = q.bin(bin);
 	switch (bin) {
-		case 0: shade_block<0, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 1: shade_block<1, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 2: shade_block<2, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 3: shade_block<3, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 4: shade_block<4, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 5: shade_block<5, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 6: shade_block<6, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 7: shade_block<7, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
-		case 8: shade_block<8, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		case 0: shade_block<0, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
+		case 1: shade_block<1, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
+		case 2: shade_block<2, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
+		case 3: shade_block<3, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
+		case 4: shade_block<4, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
+		case 5: shade_block<5, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
+		case 6: shade_block<6, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
+		case 7: shade_block<7, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
+		case 8: shade_block<8, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
 		case 9: return;      // the composite's loop over its children is launched on its own (kShadeAllBins)
-		default: shade_block<kNumBsdfTypes, false, SKY>(sc, ps, cfg, q, prefix, ids, block, sh); break;
+		default: shade_block<kNumBsdfTypes, false, SKY, false>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
 	}
+}
+template <bool SKY>
+__global__ MG_SHADE_BOUNDS void k_shade_all(DScene sc, DPaths ps, DConfig cfg, DQueues q, const BinView *views_dev, uint32_t bin_mask) {
+	__shared__ ShadeShared sh;
+	shade_all<SKY, false>(sc, ps, cfg, q, views_dev, bin_mask, sh, DColors{ nullptr, nullptr });
+}
+template <bool SKY>
+__global__ MG_SHADE_BOUNDS void k_shade_all_vcol(DScene sc, DPaths ps, DConfig cfg, DQueues q, const BinView *views_dev, uint32_t bin_mask, DColors col) {
+	__shared__ ShadeShared sh;
+	shade_all<SKY, true>(sc, ps, cfg, q, views_dev, bin_mask, sh, col);
 }
 
 void launch_bsdf_eval(hipStream_t s, uint32_t type, const float *params, int op, uint32_t n, const float *queries, float *out) {
@@ -1584,42 +1670,75 @@ void launch_sky_eval(hipStream_t s, const float *block, int op, uint32_t n, cons
 	if (n) hipLaunchKernelGGL(k_sky_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, block, op, n, queries, out);
 }
 
+// one material queue with the kernel its scene needs: a sky as background (DScene::sky) and / or a coloured BSDF slot
+// (DColors::bsdf_color_slots; bins 0..8 only -- a composite's children and the terminal bin take no colours)
+template <int BT>
+static void launch_shade_bin(hipStream_t s, const dim3 g, const dim3 b, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,
+                             const BinView &view, const BinView *views_dev, const uint32_t *bin_ids, const DColors &col) {
+	const bool rounds = cfg.dr_mode != 0, sky = sc.sky != nullptr;
+	if constexpr (BT < 9) {
+		if (col.bsdf_color_slots != nullptr) {
+			#define MG_SHADE(R, S) hipLaunchKernelGGL((k_shade_vcol<BT, R, S>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids, col)
+			if (rounds) { if (sky) MG_SHADE(true, true); else MG_SHADE(true, false); }
+			else if (sky) MG_SHADE(false, true);
+			else MG_SHADE(false, false);
+			#undef MG_SHADE
+			return;
+		}
+	}
+	#define MG_SHADE(R, S) hipLaunchKernelGGL((k_shade<BT, R, S>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids)
+	if (rounds) { if (sky) MG_SHADE(true, true); else MG_SHADE(true, false); }
+	else if (sky) MG_SHADE(false, true);
+	else MG_SHADE(false, false);
+	#undef MG_SHADE
+}
+
 void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, const DConfig &cfg,
-                  const DQueues &q, const BinView &view, const BinView *views_dev, uint32_t n_bound, const uint32_t *bin_ids) {
+                  const DQueues &q, const BinView &view, const BinView *views_dev, uint32_t n_bound, const uint32_t *bin_ids, const DColors &col) {
 	const uint32_t n = views_dev ? n_bound : view.prefix[kBinShards];
 	if (!n) return;
 	if (!bin_ids) bin_ids = q.bin(bin);
 	const dim3 g(blocks_for(n, kShadeBlock)), b(kShadeBlock);
-	// a scene whose background is a sky carries its derived block (DScene::sky) and runs the sky instantiations
-	const bool sky = sc.sky != nullptr;
-	#define MG_SHADE(BT) do { if (cfg.dr_mode != 0) { if (sky) hipLaunchKernelGGL((k_shade<BT, true, true>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids); \
-	                                                  else hipLaunchKernelGGL((k_shade<BT, true, false>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids); } \
-	                          else if (sky) hipLaunchKernelGGL((k_shade<BT, false, true>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids); \
-	                          else hipLaunchKernelGGL((k_shade<BT, false, false>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids); } while (0)
+	#define MG_SHADE_BIN(BT) launch_shade_bin<BT>(s, g, b, sc, ps, cfg, q, view, views_dev, bin_ids, col)
 	switch (bin) {
-		case 0: MG_SHADE(0); break;
-		case 1: MG_SHADE(1); break;
-		case 2: MG_SHADE(2); break;
-		case 3: MG_SHADE(3); break;
-		case 4: MG_SHADE(4); break;
-		case 5: MG_SHADE(5); break;
-		case 6: MG_SHADE(6); break;
-		case 7: MG_SHADE(7); break;
-		case 8: MG_SHADE(8); break;
-		case 9: MG_SHADE(9); break;
-		default: MG_SHADE(kNumBsdfTypes); break;
+		case 0: MG_SHADE_BIN(0); break;
+		case 1: MG_SHADE_BIN(1); break;
+		case 2: MG_SHADE_BIN(2); break;
+		case 3: MG_SHADE_BIN(3); break;
+		case 4: MG_SHADE_BIN(4); break;
+		case 5: MG_SHADE_BIN(5); break;
+		case 6: MG_SHADE_BIN(6); break;
+		case 7: MG_SHADE_BIN(7); break;
+		case 8: MG_SHADE_BIN(8); break;
+		case 9: MG_SHADE_BIN(9); break;
+		default: MG_SHADE_BIN(kNumBsdfTypes); break;
 	}
-	#undef MG_SHADE
+	#undef MG_SHADE_BIN
 }
 
 void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,
-                      const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound) {
+                      const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound, const DColors &col) {
 	bin_mask &= kShadeAllBins;
 	if (!n_bound || !bin_mask) return;
 	// every bin rounds its size up to whole workgroups
 	const unsigned blocks = blocks_for(n_bound, kShadeBlock) + (unsigned) __builtin_popcount(bin_mask);
-	if (sc.sky) hipLaunchKernelGGL(k_shade_all<true>, dim3(blocks), dim3(kShadeBlock), 0, s, sc, ps, cfg, q, views_dev, bin_mask);
-	else hipLaunchKernelGGL(k_shade_all<false>, dim3(blocks), dim3(kShadeBlock), 0, s, sc, ps, cfg, q, views_dev, bin_mask);
+	const dim3 g(blocks), b(kShadeBlock);
+	if (col.bsdf_color_slots) {
+		if (sc.sky) hipLaunchKernelGGL(k_shade_all_vcol<true>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask, col);
+		else hipLaunchKernelGGL(k_shade_all_vcol<false>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask, col);
+	} else if (sc.sky) hipLaunchKernelGGL(k_shade_all<true>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask);
+	else hipLaunchKernelGGL(k_shade_all<false>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask);
+}
+
+void launch_bsdf_eval_colored(hipStream_t s, uint32_t type, const float *params, uint32_t slots, const float *color, int op, uint32_t n,
+                              const float *queries, float *out) {
+	BsdfParams p;
+	for (int k = 0; k < kBsdfNParams; ++k) p.v[k] = params[k];
+	if (n) hipLaunchKernelGGL(k_bsdf_eval_colored, dim3(blocks_for(n, 256)), dim3(256), 0, s, type, p, slots, color[0], color[1], color[2], op, n, queries, out);
+}
+
+void launch_vertex_color_eval(hipStream_t s, const float4 *tri_col, uint32_t n, const uint32_t *prim, const float *uv, float *out) {
+	if (n) hipLaunchKernelGGL(k_vertex_color_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, tri_col, n, prim, uv, out);
 }
 
 } // namespace mg

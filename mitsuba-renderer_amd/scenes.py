@@ -12,11 +12,27 @@ from . import abi
 F = np.float32
 
 
+class _VertexColors:
+    """the `vertexcolors` texture (src/textures/vertexcolors.cpp): getValue(its) = its.color"""
+
+    def __repr__(self):
+        return "VERTEX_COLORS"
+
+
+# pass this where a BSDF constructor of SceneDescription takes a reflectance or transmittance: the slot then takes the
+# colour interpolated from the mesh's per-vertex colours, and the block holds the texture's getAverage() = getMaximum() = 1
+VERTEX_COLORS = _VertexColors()
+
+
 class MeshDesc:
-    def __init__(self, positions, triangles, bsdf=-1, lum=-1, face_normals=True, normals=None, name=""):
+    def __init__(self, positions, triangles, bsdf=-1, lum=-1, face_normals=True, normals=None, name="", colors=None):
         self.positions = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
         self.triangles = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
         self.normals = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        # per-vertex colours of a TriMesh (trimesh.h:121-126), [n_verts][3] linear RGB, or None
+        self.colors = None if colors is None else np.ascontiguousarray(colors, dtype=np.float32).reshape(-1, 3)
+        if self.colors is not None and self.colors.shape[0] != self.positions.shape[0]:
+            raise ValueError("one colour per vertex: %d colours, %d vertices" % (self.colors.shape[0], self.positions.shape[0]))
         self.bsdf, self.lum, self.face_normals, self.name = int(bsdf), int(lum), bool(face_normals), name
         self.shape_type, self.sphere = abi.SHAPE_TRIMESH, None
 
@@ -38,6 +54,7 @@ class SceneDescription:
         self.meshes = []
         self.bsdf_type = []
         self.bsdf_params = []
+        self.bsdf_color_slots = []  # per BSDF: bit s = its s-th texture slot takes its.color (include/mtsgpu.h)
         self.lum_type = []
         self.lum_params = []
         self.camera = dict(origin=(0.0, 1.0, 3.4), target=(0.0, 1.0, 0.0), up=(0.0, 1.0, 0.0), fov=39.3)
@@ -46,32 +63,46 @@ class SceneDescription:
         self.env_bitmap = None      # [H][W][3] float32 of the envmap luminaire
 
     # --- property blocks --------------------------------------------------
-    def add_bsdf(self, btype, params):
+    def add_bsdf(self, btype, params, color_slots=0):
         p = np.zeros(abi.BSDF_NPARAMS, dtype=np.float32)
         p[:len(params)] = np.asarray(params, dtype=np.float32)
         self.bsdf_type.append(int(btype))
         self.bsdf_params.append(p)
+        self.bsdf_color_slots.append(int(color_slots))
         return len(self.bsdf_type) - 1
 
+    @staticmethod
+    def _textured(*values):
+        """VERTEX_COLORS among the texture-typed arguments of a BSDF -> (the values with 1.0 in its place: the texture's
+        getAverage() / getMaximum(), vertexcolors.cpp:49-55; the slot mask, bit s for the s-th argument)"""
+        mask = sum(1 << s for s, v in enumerate(values) if v is VERTEX_COLORS)
+        return [1.0 if v is VERTEX_COLORS else v for v in values], mask
+
     def lambertian(self, r, g=None, b=None):
+        (r,), slots = self._textured(r)
         g = r if g is None else g
         b = r if b is None else b
-        return self.add_bsdf(abi.BSDF_LAMBERTIAN, [r, g, b])
+        return self.add_bsdf(abi.BSDF_LAMBERTIAN, [r, g, b], slots)
 
-    def dielectric(self, int_ior=1.5046, ext_ior=1.0):
-        return self.add_bsdf(abi.BSDF_DIELECTRIC, [int_ior, ext_ior, 1, 1, 1, 1, 1, 1])
+    def dielectric(self, int_ior=1.5046, ext_ior=1.0, refl=1.0, trans=1.0):
+        (refl, trans), slots = self._textured(refl, trans)
+        return self.add_bsdf(abi.BSDF_DIELECTRIC, [int_ior, ext_ior, refl, refl, refl, trans, trans, trans], slots)
 
-    def roughmetal(self, alpha=0.1, ior=0.37, k=2.82):
-        return self.add_bsdf(abi.BSDF_ROUGHMETAL, [alpha, ior, ior, ior, k, k, k, 1, 1, 1])
+    def roughmetal(self, alpha=0.1, ior=0.37, k=2.82, refl=1.0):
+        (refl,), slots = self._textured(refl)
+        return self.add_bsdf(abi.BSDF_ROUGHMETAL, [alpha, ior, ior, ior, k, k, k, refl, refl, refl], slots)
 
     def microfacet(self, alpha=0.1, kd=0.5, ks=0.5, int_ior=1.5, ext_ior=1.0, rd=1.0, rs=1.0):
-        return self.add_bsdf(abi.BSDF_MICROFACET, [alpha, kd, ks, int_ior, ext_ior, rd, rd, rd, rs, rs, rs])
+        (rd, rs), slots = self._textured(rd, rs)
+        return self.add_bsdf(abi.BSDF_MICROFACET, [alpha, kd, ks, int_ior, ext_ior, rd, rd, rd, rs, rs, rs], slots)
 
     def mirror(self, r=0.8):
-        return self.add_bsdf(abi.BSDF_MIRROR, [r, r, r])
+        (r,), slots = self._textured(r)
+        return self.add_bsdf(abi.BSDF_MIRROR, [r, r, r], slots)
 
     def phong(self, exponent=10.0, rd=0.5, rs=0.2, kd=1.0, ks=1.0):
         """parameter block as Phong::configure() leaves it (src/bsdfs/phong.cpp:74-96), float32 arithmetic"""
+        (rd, rs), slots = self._textured(rd, rs)
         kd, ks, rd, rs = F(kd), F(ks), F(rd), F(rs)
         if kd * rd + ks * rs > F(1.0):                       # verifyEnergyConservation
             norm = F(1) / (kd * rd + ks * rs)
@@ -80,24 +111,29 @@ class SceneDescription:
         avg_s = (rs + rs + rs) * F(1.0 / 3) * ks
         ssw = avg_s / (avg_d + avg_s)
         dsw = F(1.0) - ssw
-        return self.add_bsdf(abi.BSDF_PHONG, [exponent, kd, ks, ssw, dsw, rd, rd, rd, rs, rs, rs])
+        return self.add_bsdf(abi.BSDF_PHONG, [exponent, kd, ks, ssw, dsw, rd, rd, rd, rs, rs, rs], slots)
 
     def roughglass(self, alpha=0.1, int_ior=1.5046, ext_ior=1.0, distribution="beckmann", refl=1.0, trans=1.0):
         """src/bsdfs/roughglass.cpp: for `phong` the constructor maps alpha to the exponent 2/alpha^2 - 2 (:130-136)"""
         d = {"beckmann": 0, "phong": 1, "ggx": 2}[distribution]
+        if alpha is VERTEX_COLORS:
+            raise ValueError("roughglass: alpha is a float texture, vertex colours cannot drive it")
+        (refl, trans), slots = self._textured(refl, trans)
         a = F(alpha)
         if d == 1:
             a = F(2) / (a * a) - F(2)
-        return self.add_bsdf(abi.BSDF_ROUGHGLASS, [d, a, int_ior, ext_ior, refl, refl, refl, trans, trans, trans])
+        return self.add_bsdf(abi.BSDF_ROUGHGLASS, [d, a, int_ior, ext_ior, refl, refl, refl, trans, trans, trans], slots)
 
     def difftrans(self, t=0.5):
-        return self.add_bsdf(abi.BSDF_DIFFTRANS, [t, t, t])
+        (t,), slots = self._textured(t)
+        return self.add_bsdf(abi.BSDF_DIFFTRANS, [t, t, t], slots)
 
     def ward(self, alpha_x=0.1, alpha_y=0.1, rd=0.5, rs=0.2, kd=1.0, ks=1.0, model="balanced", specular_sampling_weight=-1.0,
              verify_energy_conservation=True):
         """parameter block as the constructor and Ward::configure() leave it (src/bsdfs/ward.cpp:54-88, :118-136), float32
         arithmetic; rd / rs: a grey level or an RGB triple"""
         m = {"ward": 0, "ward-duer": 1, "balanced": 2}[model]
+        (rd, rs), slots = self._textured(rd, rs)
         rd = np.broadcast_to(np.asarray(rd, dtype=np.float32), (3,)); rs = np.broadcast_to(np.asarray(rs, dtype=np.float32), (3,))
         kd, ks = F(kd), F(ks)
         if verify_energy_conservation and kd * rd.max() + ks * rs.max() > F(1.0):
@@ -109,7 +145,7 @@ class SceneDescription:
             avg_s = (rs[0] + rs[1] + rs[2]) * F(1.0 / 3) * ks
             ssw = avg_s / (avg_d + avg_s)
         dsw = F(1.0) - ssw
-        return self.add_bsdf(abi.BSDF_WARD, [m, alpha_x, alpha_y, kd, ks, ssw, dsw, rd[0], rd[1], rd[2], rs[0], rs[1], rs[2]])
+        return self.add_bsdf(abi.BSDF_WARD, [m, alpha_x, alpha_y, kd, ks, ssw, dsw, rd[0], rd[1], rd[2], rs[0], rs[1], rs[2]], slots)
 
     def composite(self, weights, children):
         """<bsdf type="composite"> (src/bsdfs/composite.cpp): weights and the indices of blocks added before.  Block:
@@ -650,5 +686,57 @@ def fuzz(seed, n_meshes=14):
     return sd
 
 
+def vcol_grid(cells=4, seed=7, material="lambertian", colors="random"):
+    """A planar grid of cells x cells x 2 triangles with shared vertices in the plane y = 0 (normal +y) whose (cells + 1)^2
+    vertices carry random colours, under one point light, seen straight down by an orthographic camera: every camera ray
+    hits the grid at the point below its raster position, so its.color has a closed form.  material: "lambertian"
+    (reflectance = vertex colours), "white" (constant reflectance 1), "black", "phong" (specularReflectance = vertex colours,
+    slot 1, over a black diffuse part: the radiance stays a multiple of the colour) or "phong_white" (the same with constant
+    specularReflectance 1); colors: "random", "zero" or None (a mesh without colours)"""
+    sd = SceneDescription("vcol_grid_%d_%s" % (cells, material))
+    rng = np.random.RandomState(seed)
+    n = cells + 1
+    g = np.linspace(-1.0, 1.0, n).astype(np.float32)
+    gx, gz = np.meshgrid(g, g, indexing="ij")
+    pos = np.stack([gx, np.zeros_like(gx), gz], axis=-1).reshape(-1, 3).astype(np.float32)
+    idx = np.arange(n * n).reshape(n, n)
+    a, b, c, d = idx[:-1, :-1].ravel(), idx[1:, :-1].ravel(), idx[1:, 1:].ravel(), idx[:-1, 1:].ravel()
+    tri = np.stack([np.stack([a, c, b], 1), np.stack([a, d, c], 1)], axis=1).reshape(-1, 3).astype(np.uint32)
+    col = rng.uniform(0.05, 0.95, (n * n, 3)).astype(np.float32)
+    col = {"random": col, "zero": np.zeros_like(col), None: None}[colors]
+    bsdf = {"lambertian": lambda: sd.lambertian(VERTEX_COLORS), "white": lambda: sd.lambertian(1.0), "black": lambda: sd.lambertian(0.0),
+            "phong": lambda: sd.phong(12.0, rd=0.0, rs=VERTEX_COLORS, kd=0.5, ks=0.5),
+            "phong_white": lambda: sd.phong(12.0, rd=0.0, rs=1.0, kd=0.5, ks=0.5)}[material]()
+    sd.add_mesh(pos, tri, bsdf=bsdf, face_normals=True, name="grid", colors=col)
+    sd.point_light((0.3, 1.5, -0.2), (5.0, 4.0, 3.0))
+    sd.camera = dict(origin=(0.0, 2.0, 0.0), target=(0.0, 0.0, 0.0), up=(0.0, 0.0, -1.0), ortho_scale=1.0)
+    sd.max_depth = 2
+    return sd
+
+
+def cornell_vcol(sky=False, sphere_subdiv=2):
+    """C1's box with two coloured meshes inside: an icosphere with smooth normals whose Lambertian reflectance is its vertex
+    colours (a function of the position), and a tilted grid whose twosided Phong takes them as specularReflectance; next to
+    them an uncoloured mesh and, with sky = True, the sky luminaire as background (the front of the box is open)"""
+    sd = cornell_c1()
+    sd.name = "cornell_vcol_sky" if sky else "cornell_vcol"
+    pos, tri = icosphere(sphere_subdiv, 0.35, (-0.35, 0.35, -0.2))
+    col = (F(0.5) + F(0.45) * np.sin(pos * F(9.0) + np.array([0.0, 2.0, 4.0], dtype=np.float32))).astype(np.float32)
+    sd.add_mesh(pos, tri, bsdf=sd.lambertian(VERTEX_COLORS), face_normals=False, name="coloured sphere", colors=col)
+    g = vcol_grid(3, seed=11).meshes[0]
+    c_, s_ = F(np.cos(0.6)), F(np.sin(0.6))
+    p = g.positions * F(0.3)
+    p = np.stack([p[:, 0], p[:, 2] * s_ + F(0.5), p[:, 2] * c_], axis=1) + np.array([0.45, 0.0, 0.25], dtype=np.float32)
+    sd.add_mesh(p.astype(np.float32), g.triangles, bsdf=sd.twosided(sd.phong(20.0, rd=0.3, rs=VERTEX_COLORS, kd=0.6, ks=0.4)),
+                face_normals=True, name="coloured sheet", colors=g.colors)
+    pos, tri = icosphere(1, 0.2, (0.1, 0.2, 0.6))
+    sd.add_mesh(pos, tri, bsdf=sd.roughmetal(0.2), face_normals=False, name="plain sphere")
+    if sky:
+        sd.sky(sun_direction=(0.3, 0.2, 0.8), turbidity=3.0, sky_scale=0.2)
+    sd.max_depth = 5
+    return sd
+
+
 def by_name(name, **kw):
-    return {"c1": cornell_c1, "c3": cornell_c3, "c5": cornell_c5, "next": next_rows, "spheres": spheres, "envlit": envlit}[name](**kw)
+    return {"c1": cornell_c1, "c3": cornell_c3, "c5": cornell_c5, "next": next_rows, "spheres": spheres, "envlit": envlit,
+            "vcol_grid": vcol_grid, "vcol": cornell_vcol}[name](**kw)

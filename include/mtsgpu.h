@@ -330,6 +330,42 @@ int  mtsgpu_set_tuning(mtsgpu_ctx *ctx, const char *key, long value);
  * shape.h:162-163), or a colour of a mesh that has them is not finite. */
 int  mtsgpu_set_vertex_colors(mtsgpu_ctx *ctx, const float *vtx_col, const uint32_t *shape_has_colors, const uint32_t *bsdf_color_slots);
 
+/* --- texture coordinates and the procedural uv textures `checkerboard` and `gridtexture` ------------------------------------
+ * Both answer usesRayDifferentials() == false and forward the filtered getValue to the plain one (checkerboard.cpp:48-64,
+ * gridtexture.cpp:51-73), so they need its.uv and nothing else.  All of it in binary32, in the reference's operation order:
+ *   its.uv, triangle mesh (skdtree.h:364,408-415):  b = ((1 - u) - v, u, v);  its.uv = (t0 * b.x + t1 * b.y) + t2 * b.z per
+ *     component; a mesh without texcoords gives (0, 0)
+ *   its.uv, sphere (sphere.cpp:136-145):  local = worldToObject(p - center);  theta = acos(clamp(local.z / radius));
+ *     phi = atan2(local.y, local.x), + 2 pi if negative;  its.uv = (phi * (0.5f * INV_PI), theta * INV_PI)
+ *   Texture2D::getValue(its) (texture.cpp:73-82):  uv' = (uv.x * uscale, uv.y * vscale) + (uoffset, voffset)
+ *   checkerboard:  x = 2 * modulo((int) (uv'.x * 2), 2) - 1, y likewise;  bright iff x * y == 1.  The cast truncates towards
+ *     zero (the cell around 0 is twice as wide); modulo is the non-negative remainder
+ *   gridtexture:   x = uv'.x - (int) uv'.x;  if (x > .5) x -= 1;  y likewise;  dark iff |x| < lineWidth || |y| < lineWidth
+ * A slot is one of the texture-typed spectrum slots listed above for the vertex colours.  The three floats of a textured slot
+ * in the block should hold the texture's getAverage(), which is what Phong::configure and Ward::configure derive their sampling
+ * weights from: dark * 0.5f for the checkerboard (sic, checkerboard.cpp:66-68), bright for the grid (gridtexture.cpp:79-81). */
+enum { MTSGPU_TEX_CHECKERBOARD = 0, MTSGPU_TEX_GRID = 1, MTSGPU_TEX_NKINDS = 2 };
+typedef struct mtsgpu_uv_texture {
+	uint32_t kind;                           /* MTSGPU_TEX_*                                              */
+	float uoffset, voffset, uscale, vscale;  /* Texture2D: defaults 0, 0, 1, 1                            */
+	float bright[3], dark[3];                /* brightColor (default .4), darkColor (default .2)          */
+	float line_width;                        /* gridtexture's lineWidth (default .01); ignored otherwise  */
+} mtsgpu_uv_texture;
+/* vtx_uv [n_verts][2] follows the scene's global vertex pool (rows of shapes without texcoords are ignored), shape_has_uv
+ * [n_shapes] is non-zero for the meshes that carry texcoords (both may be NULL: no mesh has any), textures [n_textures],
+ * bsdf_slot_texture [n_bsdfs][2] an index into textures per slot or -1.  Call after mtsgpu_upload_scene; a new upload clears
+ * it; everything NULL switches it off.  Scenes without a textured slot launch the kernels they launch without this call; a
+ * scene may colour one slot (mtsgpu_set_vertex_colors) and texture another, in either order of the two calls.
+ * MTSGPU_EINVAL, with the scene's textures switched off, when a slot lies beyond those of its type, a slot also has its
+ * colour bit set (mtsgpu_set_vertex_colors refuses the same from its side), a composite child has a textured slot, a kind is
+ * unknown, a parameter or a texcoord of a mesh that has them is not finite, or, for a texture some slot uses and a shape
+ * whose BSDF has that slot, 2 * uv' reaches 2^31 - 2^16 in magnitude at a vertex (on a sphere: at uv = 0 or 1) -- the
+ * reference's (int) cast is undefined from 2^31 on, and the margin covers the rounding of the interpolation.
+ * Spheres are accepted.  A mesh without texcoords whose BSDF has a textured slot is ACCEPTED and shaded with uv = (0, 0):
+ * that is the value the reference's Intersection carries there (skdtree.h:413-415), unlike its.color it is always written. */
+int  mtsgpu_set_uv_textures(mtsgpu_ctx *ctx, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
+                            const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture);
+
 /* --- the hot path (replaces SampleIntegrator::render, integrator.cpp:87-120) */
 int  mtsgpu_render(mtsgpu_ctx *ctx, volatile const int *cancel);
 int  mtsgpu_sync(mtsgpu_ctx *ctx);
@@ -412,6 +448,9 @@ int  mtsgpu_group_set_tuning(mtsgpu_group *g, const char *key, long value);
 int  mtsgpu_group_set_film_statistics(mtsgpu_group *g, int on);
 /* mtsgpu_set_vertex_colors on every member */
 int  mtsgpu_group_set_vertex_colors(mtsgpu_group *g, const float *vtx_col, const uint32_t *shape_has_colors, const uint32_t *bsdf_color_slots);
+/* mtsgpu_set_uv_textures on every member */
+int  mtsgpu_group_set_uv_textures(mtsgpu_group *g, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
+                                  const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture);
 
 /* HBM triad a[i] = b[i] + s * c[i] over three arrays of `bytes` each on `device` (float4 lanes, best of `iters`
  * launches): the practical bandwidth roof next to the 8 TB/s specification.  GB/s in *gbs. */
@@ -503,6 +542,18 @@ int  mtsgpu_vertex_color_eval(mtsgpu_ctx *ctx, uint32_t n, const uint32_t *prim,
  * with those slots overwritten. */
 int  mtsgpu_bsdf_eval_colored(mtsgpu_ctx *ctx, uint32_t bsdf_type, const float *params, uint32_t slots, const float color[3], int op,
                               uint32_t n, const float *queries, float *out);
+/* its.uv and the value of *tex there, as the device computes them for the uploaded scene and its texcoords
+ * (mtsgpu_set_uv_textures; without it every mesh gives uv = (0, 0)): prim [n] primitive indices, rec [n][3] = the hit's
+ * barycentrics (u, v, unused) on a triangle, the world-space hit point on a sphere; out [n][5] = uv.x, uv.y, r, g, b.  tex
+ * is checked like the textures of mtsgpu_set_uv_textures, but for the int range of the cast, which is the caller's to keep.
+ * A test hook: it calls the device functions the shading kernels call. */
+int  mtsgpu_uv_texture_eval(mtsgpu_ctx *ctx, const mtsgpu_uv_texture *tex, uint32_t n, const uint32_t *prim, const float *rec, float *out);
+/* mtsgpu_bsdf_eval_colored for scenes with uv textures: slot s takes nothing (slot_source[s] = 0), color[3] (1) or
+ * values[s][3] (2, the texture's value at the hit).  Same ops, query and output layout; evaluated through the device function
+ * that builds the per-hit block for the texture kernels, so it returns what mtsgpu_bsdf_eval returns for the block with
+ * those slots overwritten.  A source other than 0 for a slot the type does not have, and a composite, are MTSGPU_EINVAL. */
+int  mtsgpu_bsdf_eval_slots(mtsgpu_ctx *ctx, uint32_t bsdf_type, const float *params, const int32_t slot_source[2], const float color[3],
+                            const float *values, int op, uint32_t n, const float *queries, float *out);
 /* MIPathTracer::Li for explicit camera samples: in [n][3] u32 = pixel x, y, sample index;
  * out [n][8] f32 = Li rgb, alpha, raster x, raster y, depth, unused */
 int  mtsgpu_li_samples(mtsgpu_ctx *ctx, const uint32_t *pix_samples, uint32_t n, float *out);
@@ -575,6 +626,12 @@ int  mtsgpu_flat_scene_set_mesh_colors(mtsgpu_flat_scene *fs, uint32_t mesh_inde
 /* what mtsgpu_set_vertex_colors takes: the pool [n_verts][3] and the flags [n_shapes]; NULL while no mesh has colours */
 const float *mtsgpu_flat_scene_vertex_colors(const mtsgpu_flat_scene *fs);
 const uint32_t *mtsgpu_flat_scene_shape_has_colors(const mtsgpu_flat_scene *fs);
+/* The same for texture coordinates (trimesh.h m_texcoords): texcoords [that mesh's n_verts][2]; the pool [n_verts][2] and the
+ * flags [n_shapes] are what mtsgpu_set_uv_textures takes, NULL while no mesh has texcoords.  Costs 8 bytes per vertex here;
+ * on the device 32 bytes per primitive while textures are set. */
+int  mtsgpu_flat_scene_set_mesh_texcoords(mtsgpu_flat_scene *fs, uint32_t mesh_index, const float *texcoords);
+const float *mtsgpu_flat_scene_vertex_texcoords(const mtsgpu_flat_scene *fs);
+const uint32_t *mtsgpu_flat_scene_shape_has_texcoords(const mtsgpu_flat_scene *fs);
 /* kd-tree statistics logged by the reference builder (gkdtree.h:1178-1213) */
 int  mtsgpu_flat_scene_kdstats(const mtsgpu_flat_scene *fs, double *out6 /* inner, leaf, idx, expTrav, expLeaves, expPrims */);
 
@@ -588,6 +645,8 @@ void mtsgpu_loaded_mesh_free(mtsgpu_loaded_mesh *m);
 /* the per-vertex colours of the loaded shape, [n_verts][3] (single or double precision in the file, trimesh.cpp:113-118,
  * 223-229), or NULL when the file has no EHasColors block; valid until mtsgpu_loaded_mesh_free */
 const float *mtsgpu_loaded_mesh_colors(const mtsgpu_loaded_mesh *m);
+/* likewise the texture coordinates, [n_verts][2] (trimesh.cpp:105-111,214-221), NULL without an EHasTexcoords block */
+const float *mtsgpu_loaded_mesh_texcoords(const mtsgpu_loaded_mesh *m);
 
 /* TabulatedFilter (src/librender/rfilter.cpp:40-69) of the reconstruction filter plugins: kind 0 `box`,
  * 1 `gaussian` (p0 = stddev; src/rfilters/gaussian.cpp:30-42,62-65), 2 `mitchell` (p0 = B, p1 = C; mitchell.cpp),

@@ -123,6 +123,22 @@ struct FlatScene {
 	std::vector<float> vtxCol;
 	std::vector<uint32_t> shapeHasColors, bsdfColorSlots;
 	bool anyColors, anyColorSlots;
+	/* texture coordinates (TriMesh::getVertexTexcoords, trimesh.h) in the order of vtxPos, one flag per shape, the
+	 * Checkerboard / GridTexture instances of the BSDFs and per BSDF table entry the texture of its two slots (-1 = none):
+	 * what mtsgpu_group_set_uv_textures takes */
+	std::vector<float> vtxUv;
+	std::vector<uint32_t> shapeHasUv;
+	std::vector<mtsgpu_uv_texture> uvTextures;
+	std::vector<int32_t> bsdfSlotTexture;
+	bool anyUv;
+
+	/* after mtsgpu_group_upload_scene and setVertexColors: hands the textures over when a BSDF slot holds one (a mesh
+	 * without texcoords is then shaded with uv = (0, 0), as in the reference) */
+	int setUvTextures(mtsgpu_group *group) const {
+		if (uvTextures.empty()) return MTSGPU_OK;
+		return mtsgpu_group_set_uv_textures(group, anyUv ? ptr(vtxUv) : NULL, anyUv ? ptr(shapeHasUv) : NULL, (uint32_t) uvTextures.size(),
+			&uvTextures[0], ptr(bsdfSlotTexture));
+	}
 
 	/* after mtsgpu_group_upload_scene: hands the colours over when a mesh has some or a BSDF slot asks for them (then the
 	 * library refuses a coloured slot on a shape without colours, where the reference would read an its.color nobody wrote) */
@@ -131,7 +147,7 @@ struct FlatScene {
 		return mtsgpu_group_set_vertex_colors(group, anyColors ? ptr(vtxCol) : NULL, anyColors ? ptr(shapeHasColors) : NULL, ptr(bsdfColorSlots));
 	}
 
-	FlatScene(const Scene *scene) : anyColors(false), anyColorSlots(false) {
+	FlatScene(const Scene *scene) : anyColors(false), anyColorSlots(false), anyUv(false) {
 		memset(&sc, 0, sizeof(sc));
 		sc.abi_version = MTSGPU_ABI_VERSION;
 		const ShapeKDTree *kd = scene->getKDTree();                                   /* scene.h:498 */
@@ -223,10 +239,14 @@ struct FlatScene {
 				const Spectrum *col = mesh->hasVertexColors() ? mesh->getVertexColors() : NULL;               /* trimesh.h:121-126 */
 				shapeHasColors.push_back(col ? 1u : 0u);
 				if (col) anyColors = true;
+				const Point2 *uv = mesh->hasVertexTexcoords() ? mesh->getVertexTexcoords() : NULL;
+				shapeHasUv.push_back(uv ? 1u : 0u);
+				if (uv) anyUv = true;
 				for (size_t v = 0; v < mesh->getVertexCount(); ++v) {
 					float rgb[3] = { 0.0f, 0.0f, 0.0f };
 					if (col) rgbOf(col[v], rgb);
 					vtxCol.insert(vtxCol.end(), rgb, rgb + 3);
+					vtxUv.push_back(uv ? (float) uv[v].x : 0.0f); vtxUv.push_back(uv ? (float) uv[v].y : 0.0f);
 					vtxPos.push_back((float) pos[v].x); vtxPos.push_back((float) pos[v].y); vtxPos.push_back((float) pos[v].z);
 					vtxNrm.push_back(nrm ? (float) nrm[v].x : 0.0f); vtxNrm.push_back(nrm ? (float) nrm[v].y : 0.0f); vtxNrm.push_back(nrm ? (float) nrm[v].z : 0.0f);
 				}
@@ -268,6 +288,7 @@ struct FlatScene {
 				shapeFlags.push_back(0u);
 				shapeType.push_back(MTSGPU_SHAPE_SPHERE);
 				shapeHasColors.push_back(0u);
+				shapeHasUv.push_back(0u);
 				if (shape->isLuminaire()) {
 					const int l = lumIndex[shape->getLuminaire()];
 					lumShape[l] = (int32_t) s;
@@ -391,7 +412,7 @@ private:
 		/* one entry, or for a composite its children first and then the composite itself, whose block points at them */
 		ref<MemoryStream> st = serializedBSDF(bsdf);
 		std::string err;
-		const int index = mtsgpu_stream::parseBSDFTable<Float>(st->getData(), st->getSize(), bsdfType, bsdfParams, &err, &bsdfColorSlots);
+		const int index = mtsgpu_stream::parseBSDFTable<Float>(st->getData(), st->getSize(), bsdfType, bsdfParams, &err, &bsdfColorSlots, &uvTextures, &bsdfSlotTexture);
 		if (index < 0)
 			SLog(EError, "gpupath: %s", err.c_str());
 		for (size_t b = 0; b < bsdfColorSlots.size(); ++b) if (bsdfColorSlots[b]) anyColorSlots = true;
@@ -449,6 +470,7 @@ struct GPURenderDriver {
 			FlatScene flat(scene);
 			check(mtsgpu_group_upload_scene(group, &flat.sc));
 			check(flat.setVertexColors(group));
+			check(flat.setUvTextures(group));
 		}
 
 		/* --- camera: raster space of the FULL film, crop window as offset + size (perspective.cpp:43-71, film.cpp:33-41) --- */

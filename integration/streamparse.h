@@ -104,13 +104,35 @@ public:
 	 * (:49-55), from which Phong::configure and Ward::configure derived the weights that follow in the stream.  One
 	 * VertexColors instance in two slots arrives as a bare id the second time: refused, like every shared instance whose
 	 * fields are out of reach.  slot < 0: a slot that cannot take colours. */
+	/* A `Checkerboard` or `GridTexture` instance (src/textures/checkerboard.cpp:42-46, gridtexture.cpp:44-49) writes
+	 * Texture2D::serialize (texture.cpp:67-71: Texture::serialize, then uvOffset and uvScale, two Floats each), brightColor,
+	 * darkColor and, the grid, lineWidth.  A caller that called takeUvTextures() receives the descriptor in its list and the
+	 * list index in slotTextures(); the block receives the texture's getAverage(), darkColor * .5f (sic) or brightColor, which is
+	 * what Phong::configure and Ward::configure read.  Every other caller is refused as before.  A shared instance is refused. */
 	void readSpectrumTexture(const char *what, float rgb[3], int slot) {
 		const uint32_t id = r.readUInt();
 		if (id != 0 && m_values.count(id)) { memcpy(rgb, m_values[id].v, sizeof(float) * 3); return; }      /* one texture shared by two slots */
 		if (id == 0) { r.fail(std::string(what) + " of " + m_className + " is missing"); return; }
 		if (m_colorIds.count(id)) { r.fail(std::string(what) + " of " + m_className + " is a VertexColors instance shared with another slot: shared instances are not supported"); return; }
+		if (m_uvTexIds.count(id)) { r.fail(std::string(what) + " of " + m_className + " is a " + m_uvTexIds[id] + " instance shared with another slot: shared instances are not supported"); return; }
 		m_seen.insert(id);
 		const std::string cls = r.readString();
+		if ((cls == "Checkerboard" || cls == "GridTexture") && slot >= 0 && m_uvTextures) {
+			skipReference();
+			mtsgpu_uv_texture t;
+			memset(&t, 0, sizeof(t));
+			t.kind = cls == "GridTexture" ? MTSGPU_TEX_GRID : MTSGPU_TEX_CHECKERBOARD;
+			t.uoffset = (float) r.readFloat(); t.voffset = (float) r.readFloat();                /* Point2 m_uvOffset */
+			t.uscale = (float) r.readFloat(); t.vscale = (float) r.readFloat();                  /* Vector2 m_uvScale */
+			r.readSpectrum(t.bright); r.readSpectrum(t.dark);
+			if (t.kind == MTSGPU_TEX_GRID) t.line_width = (float) r.readFloat();
+			if (!r.ok()) return;
+			for (int k = 0; k < 3; ++k) rgb[k] = t.kind == MTSGPU_TEX_GRID ? t.bright[k] : t.dark[k] * .5f;      /* getAverage() */
+			m_slotTextures[slot] = (int32_t) m_uvTextures->size();
+			m_uvTextures->push_back(t);
+			m_uvTexIds[id] = cls;
+			return;
+		}
 		if (cls == "VertexColors" && slot >= 0) {
 			skipReference();
 			rgb[0] = rgb[1] = rgb[2] = 1.0f;
@@ -128,7 +150,13 @@ public:
 	}
 	/* the slots of the block read since the last resetColorSlots() that hold a VertexColors texture (bit s = slot s) */
 	uint32_t colorSlots() const { return m_colorSlots; }
-	void resetColorSlots() { m_colorSlots = 0; }
+	void resetColorSlots() { m_colorSlots = 0; m_slotTextures[0] = m_slotTextures[1] = -1; }
+	/* the list that receives the Checkerboard / GridTexture descriptors (what mtsgpu_set_uv_textures takes as `textures`);
+	 * without it these classes are refused like every non-constant texture */
+	void takeUvTextures(std::vector<mtsgpu_uv_texture> *list) { m_uvTextures = list; }
+	/* per slot of the block read since the last resetColorSlots(): the index of its texture in that list, or -1 */
+	const int32_t *slotTextures() const { return m_slotTextures; }
+	bool hasSlotTexture() const { return m_slotTextures[0] >= 0 || m_slotTextures[1] >= 0; }
 	/* a ConstantFloatTexture child (roughglass' alpha): [id][class name][Texture::serialize][the value] (texture.cpp:95-103) */
 	FloatT readConstantFloatTexture(const char *what) {
 		const uint32_t id = r.readUInt();
@@ -136,6 +164,7 @@ public:
 		m_seen.insert(id);
 		const std::string cls = r.readString();
 		if (cls == "VertexColors") { r.fail(std::string(what) + " of " + m_className + " is a VertexColors texture: vertex colours are a spectrum, this slot takes a float texture; not supported"); return 0; }
+		if (cls == "Checkerboard" || cls == "GridTexture") { r.fail(std::string(what) + " of " + m_className + " is a " + cls + " texture: uv textures are supported in spectrum slots only, this slot takes a float texture; not supported"); return 0; }
 		if (cls != "ConstantFloatTexture") { r.fail(std::string(what) + " of " + m_className + " is a " + cls + "; only constant values are supported"); return 0; }
 		skipReference();
 		return r.readFloat();
@@ -165,6 +194,9 @@ private:
 		if (id != 0 && !m_seen.count(id)) r.fail("unexpected nested object in the serialized form of " + m_className);
 	}
 	std::set<uint32_t> m_seen, m_colorIds;
+	std::map<uint32_t, std::string> m_uvTexIds;
+	std::vector<mtsgpu_uv_texture> *m_uvTextures = NULL;
+	int32_t m_slotTextures[2] = { -1, -1 };
 	uint32_t m_colorSlots = 0;
 	std::map<uint32_t, RGB> m_values;
 	std::string m_className;
@@ -253,10 +285,16 @@ template <typename FloatT> inline bool parseBSDF(const uint8_t *data, size_t siz
  * delta child (dielectric, mirror), a child instance that was written before (a bare id: its fields are not in reach). */
 /* colorSlots (optional): one mask per appended entry, next to `types` (what mtsgpu_set_vertex_colors takes as
  * bsdf_color_slots).  A composite child with a coloured slot is refused with the child's number, as the library refuses it. */
+/* uvTextures + slotTextures (optional, both or neither): the Checkerboard / GridTexture descriptors met are appended to
+ * uvTextures, and slotTextures receives two entries per appended table entry, the index of the slot's texture in uvTextures
+ * or -1 (what mtsgpu_set_uv_textures takes as `textures` and `bsdf_slot_texture`).  A composite child with a textured slot
+ * is refused with the child's number.  Without them a Checkerboard or GridTexture is refused like any other texture. */
 template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t size, std::vector<uint32_t> &types, std::vector<float> &params,
-                                                     std::string *err, std::vector<uint32_t> *colorSlots = NULL) {
+                                                     std::string *err, std::vector<uint32_t> *colorSlots = NULL,
+                                                     std::vector<mtsgpu_uv_texture> *uvTextures = NULL, std::vector<int32_t> *slotTextures = NULL) {
 	BSDFStream<FloatT> rd(data, size);
-	const size_t first = types.size();
+	const size_t first = types.size(), firstTex = uvTextures ? uvTextures->size() : 0;
+	if (uvTextures && slotTextures) rd.takeUvTextures(uvTextures);
 	uint32_t flags = 0;
 	if (rd.className() == "TwoSidedBRDF") { flags |= MTSGPU_BSDF_TWOSIDED; rd.enterNestedBSDF(); }
 	int own = -1;
@@ -265,6 +303,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 		uint32_t slots = 0;
 		parseBSDFFields(rd, flags, &types.back(), &params[params.size() - MTSGPU_BSDF_NPARAMS], colorSlots ? &slots : NULL);
 		if (colorSlots) colorSlots->push_back(slots);
+		if (slotTextures) slotTextures->insert(slotTextures->end(), rd.slotTextures(), rd.slotTextures() + 2);
 		own = (int) types.size() - 1;
 	} else {
 		const uint64_t n = rd.r.readSize();
@@ -288,12 +327,15 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 			uint32_t slots = 0;
 			parseBSDFFields(rd, childFlags, &types.back(), &params[params.size() - MTSGPU_BSDF_NPARAMS], &slots);
 			if (colorSlots) colorSlots->push_back(0u);
+			if (slotTextures) slotTextures->insert(slotTextures->end(), 2, (int32_t) -1);
+			if (rd.r.ok() && rd.hasSlotTexture()) { rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " (" + rd.className() + ") has a uv texture: a composite's children keep constant parameters, not supported"); break; }
 			if (rd.r.ok() && slots) { rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " (" + rd.className() + ") takes vertex colours: a composite's children keep constant parameters, not supported"); break; }
 			block[1 + n + i] = (float) (types.size() - 1);
 		}
 		if (rd.r.ok()) {
 			types.push_back(MTSGPU_BSDF_COMPOSITE | flags);
 			if (colorSlots) colorSlots->push_back(0u);
+			if (slotTextures) slotTextures->insert(slotTextures->end(), 2, (int32_t) -1);
 			params.insert(params.end(), block, block + MTSGPU_BSDF_NPARAMS);
 			own = (int) types.size() - 1;
 		}
@@ -301,6 +343,8 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 	if (!rd.r.ok()) {
 		types.resize(first); params.resize(first * MTSGPU_BSDF_NPARAMS);
 		if (colorSlots) colorSlots->resize(first);
+		if (slotTextures) slotTextures->resize(2 * first);
+		if (uvTextures) uvTextures->resize(firstTex);
 		if (err) *err = rd.r.error() + " (while reading a " + rd.className() + ")";
 		return -1;
 	}

@@ -38,6 +38,8 @@ EXPORTS = [
     "mtsgpu_set_film_statistics", "mtsgpu_read_film_statistics", "mtsgpu_film_statistics_form", "mtsgpu_group_set_film_statistics",
     "mtsgpu_set_vertex_colors", "mtsgpu_group_set_vertex_colors", "mtsgpu_flat_scene_set_mesh_colors", "mtsgpu_flat_scene_vertex_colors",
     "mtsgpu_flat_scene_shape_has_colors", "mtsgpu_loaded_mesh_colors", "mtsgpu_vertex_color_eval", "mtsgpu_bsdf_eval_colored",
+    "mtsgpu_set_uv_textures", "mtsgpu_group_set_uv_textures", "mtsgpu_flat_scene_set_mesh_texcoords", "mtsgpu_flat_scene_vertex_texcoords",
+    "mtsgpu_flat_scene_shape_has_texcoords", "mtsgpu_loaded_mesh_texcoords", "mtsgpu_uv_texture_eval", "mtsgpu_bsdf_eval_slots",
 ]
 
 
@@ -57,8 +59,10 @@ def load_serialized(path, shape_index=0, bsdf=-1, lum=-1, name=None):
         nrm = abi.np_from(m.normals, (m.n_verts, 3), np.float32) if m.normals else None
         cp = lib().mtsgpu_loaded_mesh_colors(h)             # the EHasColors block, or NULL
         col = abi.np_from(cp, (m.n_verts, 3), np.float32) if cp else None
+        tp = lib().mtsgpu_loaded_mesh_texcoords(h)          # the EHasTexcoords block, or NULL
+        uv = abi.np_from(tp, (m.n_verts, 2), np.float32) if tp else None
         return scenes.MeshDesc(pos, tri, bsdf=bsdf, lum=lum, face_normals=bool(m.face_normals), normals=nrm,
-                               name=name or "%s#%d" % (os.path.basename(path), shape_index), colors=col)
+                               name=name or "%s#%d" % (os.path.basename(path), shape_index), colors=col, texcoords=uv)
     finally:
         lib().mtsgpu_loaded_mesh_free(h)
 
@@ -202,12 +206,27 @@ def lib():
     L.mtsgpu_loaded_mesh_colors.argtypes = [vp]; L.mtsgpu_loaded_mesh_colors.restype = f32p
     L.mtsgpu_vertex_color_eval.argtypes = [vp, C.c_uint32, u32p, f32p, f32p]
     L.mtsgpu_bsdf_eval_colored.argtypes = [vp, C.c_uint32, f32p, C.c_uint32, f32p, C.c_int, C.c_uint32, f32p, f32p]
+    texp = C.POINTER(abi.UvTexture)
+    L.mtsgpu_set_uv_textures.argtypes = [vp, f32p, u32p, C.c_uint32, texp, abi.i32p]
+    L.mtsgpu_group_set_uv_textures.argtypes = [vp, f32p, u32p, C.c_uint32, texp, abi.i32p]
+    L.mtsgpu_flat_scene_set_mesh_texcoords.argtypes = [vp, C.c_uint32, f32p]
+    L.mtsgpu_flat_scene_vertex_texcoords.argtypes = [vp]; L.mtsgpu_flat_scene_vertex_texcoords.restype = f32p
+    L.mtsgpu_flat_scene_shape_has_texcoords.argtypes = [vp]; L.mtsgpu_flat_scene_shape_has_texcoords.restype = u32p
+    L.mtsgpu_loaded_mesh_texcoords.argtypes = [vp]; L.mtsgpu_loaded_mesh_texcoords.restype = f32p
+    L.mtsgpu_uv_texture_eval.argtypes = [vp, texp, C.c_uint32, u32p, f32p, f32p]
+    L.mtsgpu_bsdf_eval_slots.argtypes = [vp, C.c_uint32, f32p, abi.i32p, f32p, f32p, C.c_int, C.c_uint32, f32p, f32p]
     _lib = L
     return L
 
 
 def _f(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def uv_texture_array(textures):
+    """a ctypes array of mtsgpu_uv_texture from scenes.Checkerboard / GridTexture objects (or abi.UvTexture values)"""
+    items = [t if isinstance(t, abi.UvTexture) else t.descriptor() for t in textures]
+    return (abi.UvTexture * max(len(items), 1))(*items) if items else (abi.UvTexture * 1)()
 
 
 class Scene:
@@ -235,6 +254,15 @@ class Scene:
                     raise MtsGpuError("mtsgpu_flat_scene_set_mesh_colors: %s" % lib().mtsgpu_last_error(None).decode())
         slots = np.asarray(getattr(description, "bsdf_color_slots", []), dtype=np.uint32)
         self.bsdf_color_slots = slots if slots.any() else None
+        # likewise the texture coordinates, the uv textures and the table that names one per BSDF slot
+        for i, m in enumerate(description.meshes):
+            if getattr(m, "texcoords", None) is not None:
+                rc = lib().mtsgpu_flat_scene_set_mesh_texcoords(self._h, i, abi.ptr(m.texcoords, abi.f32p))
+                if rc != 0:
+                    raise MtsGpuError("mtsgpu_flat_scene_set_mesh_texcoords: %s" % lib().mtsgpu_last_error(None).decode())
+        self.textures = uv_texture_array(getattr(description, "textures", []))
+        table = np.asarray(getattr(description, "bsdf_slot_texture", []), dtype=np.int32).reshape(-1, 2)
+        self.bsdf_slot_texture = np.ascontiguousarray(table) if (table >= 0).any() else None
 
     @property
     def sc(self):
@@ -248,6 +276,23 @@ class Scene:
         if not col and self.bsdf_color_slots is None:
             return None
         return (col if col else None, has if has else None, abi.ptr(self.bsdf_color_slots, abi.u32p))
+
+    def uv_texture_args(self):
+        """what mtsgpu_set_uv_textures takes for this scene: (vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture),
+        or None when no BSDF slot of the scene has a uv texture"""
+        if self.bsdf_slot_texture is None:
+            return None
+        uv = lib().mtsgpu_flat_scene_vertex_texcoords(self._h)
+        has = lib().mtsgpu_flat_scene_shape_has_texcoords(self._h)
+        return (uv if uv else None, has if has else None, len(self.textures), self.textures, abi.ptr(self.bsdf_slot_texture, abi.i32p))
+
+    def vertex_texcoords(self):
+        """(pool [n_verts][2] float32, flags [n_shapes] uint32) of the flat scene, or (None, None)"""
+        uv = lib().mtsgpu_flat_scene_vertex_texcoords(self._h)
+        if not uv:
+            return None, None
+        return (abi.np_from(uv, (self.sc.n_verts, 2), np.float32),
+                abi.np_from(lib().mtsgpu_flat_scene_shape_has_texcoords(self._h), (self.sc.n_shapes,), np.uint32))
 
     def vertex_colors(self):
         """(pool [n_verts][3] float32, flags [n_shapes] uint32) of the flat scene, or (None, None)"""
@@ -362,6 +407,9 @@ class MIPathTracer:
         vc = scene.vertex_color_args() if isinstance(scene, Scene) else None
         if vc is not None:
             self._chk(lib().mtsgpu_set_vertex_colors(self._ctx, *vc), "set_vertex_colors")
+        ut = scene.uv_texture_args() if isinstance(scene, Scene) else None
+        if ut is not None:
+            self._chk(lib().mtsgpu_set_uv_textures(self._ctx, *ut), "set_uv_textures")
         self.camera = camera
         self._chk(lib().mtsgpu_set_camera(self._ctx, C.byref(camera.c if hasattr(camera, "c") else camera)), "set_camera")
         kind = {"independent": abi.SAMPLER_INDEPENDENT_KEYED, "ldsampler": abi.SAMPLER_LD_KEYED, "halton": abi.SAMPLER_HALTON,
@@ -531,6 +579,43 @@ class MIPathTracer:
         c = None if bsdf_color_slots is None else np.ascontiguousarray(bsdf_color_slots, dtype=np.uint32)
         self._chk(lib().mtsgpu_set_vertex_colors(self._ctx, abi.ptr(a, abi.f32p), abi.ptr(b, abi.u32p), abi.ptr(c, abi.u32p)), "set_vertex_colors")
 
+    def set_uv_textures(self, vtx_uv=None, shape_has_uv=None, textures=None, bsdf_slot_texture=None):
+        """mtsgpu_set_uv_textures on the uploaded scene: the texcoord pool [n_verts][2], one flag per shape, the textures
+        (scenes.Checkerboard / GridTexture objects or abi.UvTexture), the table [n_bsdfs][2]; all None switches them off"""
+        a = None if vtx_uv is None else np.ascontiguousarray(vtx_uv, dtype=np.float32)
+        b = None if shape_has_uv is None else np.ascontiguousarray(shape_has_uv, dtype=np.uint32)
+        t = None if textures is None else uv_texture_array(textures)
+        s = None if bsdf_slot_texture is None else np.ascontiguousarray(bsdf_slot_texture, dtype=np.int32)
+        self._chk(lib().mtsgpu_set_uv_textures(self._ctx, abi.ptr(a, abi.f32p), abi.ptr(b, abi.u32p), 0 if t is None else len(t), t,
+                                               abi.ptr(s, abi.i32p)), "set_uv_textures")
+
+    def uv_texture_eval(self, texture, prim, rec):
+        """its.uv and the texture's value on the device for records (primitive, (u, v, -) | world point) of the uploaded scene
+        (mtsgpu_uv_texture_eval) -> [n][5] = uv, rgb"""
+        p = np.ascontiguousarray(prim, dtype=np.uint32).reshape(-1)
+        q = np.ascontiguousarray(rec, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((len(p), 5), dtype=np.float32)
+        t = uv_texture_array([texture])
+        self._chk(lib().mtsgpu_uv_texture_eval(self._ctx, t, len(p), abi.ptr(p, abi.u32p), abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)), "uv_texture_eval")
+        return out
+
+    def bsdf_eval_slots(self, bsdf_type, params, source, color, values, op, wi, aux):
+        """bsdf_eval() with texture slot s taking nothing (source[s] = 0), `color` (1) or values[s] (2) (mtsgpu_bsdf_eval_slots)
+        -> [n][8]"""
+        aux = np.atleast_2d(np.asarray(aux, dtype=np.float32))
+        n = aux.shape[0]
+        q = np.zeros((n, 6), dtype=np.float32)
+        q[:, :3] = np.asarray(wi, dtype=np.float32).reshape(-1, 3)
+        q[:, 3:3 + aux.shape[1]] = aux
+        P = np.zeros(abi.BSDF_NPARAMS, dtype=np.float32); P[:len(params)] = params
+        src = np.ascontiguousarray(source, dtype=np.int32).reshape(2)
+        col = np.ascontiguousarray(color, dtype=np.float32).reshape(3)
+        val = np.ascontiguousarray(values, dtype=np.float32).reshape(6)
+        out = np.zeros((n, 8), dtype=np.float32)
+        self._chk(lib().mtsgpu_bsdf_eval_slots(self._ctx, int(bsdf_type), abi.ptr(P, abi.f32p), abi.ptr(src, abi.i32p), abi.ptr(col, abi.f32p),
+                                               abi.ptr(val, abi.f32p), int(op), n, abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)), "bsdf_eval_slots")
+        return out
+
     def vertex_color_eval(self, prim, uv):
         """its.color on the device for records (primitive, u, v) of the uploaded scene (mtsgpu_vertex_color_eval) -> [n][3]"""
         p = np.ascontiguousarray(prim, dtype=np.uint32).reshape(-1)
@@ -625,6 +710,9 @@ class DeviceGroup:
         vc = scene.vertex_color_args() if isinstance(scene, Scene) else None
         if vc is not None:
             self._chk(lib().mtsgpu_group_set_vertex_colors(self._g, *vc), "set_vertex_colors")
+        ut = scene.uv_texture_args() if isinstance(scene, Scene) else None
+        if ut is not None:
+            self._chk(lib().mtsgpu_group_set_uv_textures(self._g, *ut), "set_uv_textures")
         self.camera = camera
         self._chk(lib().mtsgpu_group_set_camera(self._g, C.byref(camera.c)), "set_camera")
         kind = {"independent": abi.SAMPLER_INDEPENDENT_KEYED, "ldsampler": abi.SAMPLER_LD_KEYED, "halton": abi.SAMPLER_HALTON,

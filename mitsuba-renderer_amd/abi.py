@@ -13,6 +13,7 @@ COMPOSITE_MAX = 7
 # texture-typed spectrum slots per BSDF type (include/mtsgpu.h): the first float of each slot in the parameter block
 BSDF_COLOR_SLOTS = {0: (0,), 1: (2, 5), 2: (7,), 3: (5, 8), 4: (0,), 5: (5, 8), 6: (4, 7), 7: (0,), 8: (7, 10), 9: ()}
 BSDF_NPARAMS = 16
+TEX_CHECKERBOARD, TEX_GRID = 0, 1
 LUM_AREA, LUM_CONSTANT, LUM_POINT, LUM_DIRECTIONAL, LUM_SPOT, LUM_ENVMAP, LUM_COLLIMATED, LUM_SKY = 0, 1, 2, 3, 4, 5, 6, 7
 LUM_NPARAMS = 32
 SKY_NDERIVED = 24
@@ -25,6 +26,12 @@ KNOTRIANGLE = 0xFFFFFFFF
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
 i32p = C.POINTER(C.c_int32)
+
+
+class UvTexture(C.Structure):
+    """mtsgpu_uv_texture"""
+    _fields_ = [("kind", C.c_uint32), ("uoffset", C.c_float), ("voffset", C.c_float), ("uscale", C.c_float), ("vscale", C.c_float),
+                ("bright", C.c_float * 3), ("dark", C.c_float * 3), ("line_width", C.c_float)]
 
 
 class Scene(C.Structure):

@@ -342,7 +342,7 @@ int runDirectRounds(mtsgpu_ctx *c, const DConfig &cfg0, uint32_t nPaths, volatil
 		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
 		cfg.dr_mode = mode; cfg.dr_index = index;
 		for (int b = 0; b < (withTerminal ? kNumBins : kNumBsdfTypes); ++b)
-			launch_shade(s, b, c->dsc, c->paths, cfg, c->q, views[b], nullptr, 0, nullptr, c->dcol);
+			launch_shade(s, b, c->dsc, c->paths, cfg, c->q, views[b], nullptr, 0, nullptr, c->dcol, c->dtex);
 		if (sev) HIPCHK(c, hipEventRecord(sev[1], s));
 		HIPCHK(c, hipGetLastError());
 		return readCounters(c);
@@ -372,7 +372,7 @@ int runDirectRounds(mtsgpu_ctx *c, const DConfig &cfg0, uint32_t nPaths, volatil
 		hipEvent_t *sev = c->timeKernels ? nextEventPair(c, c->shadeEvents, c->shadeEvUsed) : nullptr;
 		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
 		cfg.dr_mode = 3; cfg.dr_index = j;
-		launch_shade(s, kNumBsdfTypes, c->dsc, c->paths, cfg, c->q, tail, nullptr, 0, c->queueB, c->dcol);
+		launch_shade(s, kNumBsdfTypes, c->dsc, c->paths, cfg, c->q, tail, nullptr, 0, c->queueB, c->dcol, c->dtex);
 		if (sev) HIPCHK(c, hipEventRecord(sev[1], s));
 		HIPCHK(c, hipGetLastError());
 	}
@@ -442,17 +442,17 @@ int runBouncesDevice(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatil
 			rc = timed(c->shadeEvents, c->shadeEvUsed, s1, 0); if (rc) return rc;
 			launch_prep(s1, set, prev, c->viewsDev, c->q.bin_seg_cap, c->devStats);
 			if (cfg.dr_mode == 0 && tuningOr(c, "shade_fused", 1) != 0) {
-				launch_shade_all(s1, c->dsc, c->paths, cfg, c->q, c->viewsDev, c->binMask & kShadeAllBins, upper, c->dcol);
+				launch_shade_all(s1, c->dsc, c->paths, cfg, c->q, c->viewsDev, c->binMask & kShadeAllBins, upper, c->dcol, c->dtex);
 				// the bins the fused kernel leaves out (the composite), one launch each, only when the scene has them
 				BinView none{};
 				for (int bin = 0; bin < kNumBins; ++bin)
 					if (c->binMask & ~kShadeAllBins & (1u << bin))
-						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper, nullptr, c->dcol);
+						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper, nullptr, c->dcol, c->dtex);
 			} else {
 				BinView none{};
 				for (int bin = 0; bin < kNumBins; ++bin)
 					if (c->binMask & (1u << bin))
-						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper, nullptr, c->dcol);
+						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper, nullptr, c->dcol, c->dtex);
 			}
 			rc = timed(c->shadeEvents, c->shadeEvUsed, s1, 1); if (rc) return rc;
 			HIPCHK(c, hipGetLastError());
@@ -530,7 +530,7 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 		hipEvent_t *sev = c->timeKernels ? nextEventPair(c, c->shadeEvents, c->shadeEvUsed) : nullptr;
 		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
 		for (int bin = 0; bin < kNumBins; ++bin)
-			launch_shade(s, bin, c->dsc, c->paths, cfg, c->q, views[bin], nullptr, 0, nullptr, c->dcol);
+			launch_shade(s, bin, c->dsc, c->paths, cfg, c->q, views[bin], nullptr, 0, nullptr, c->dcol, c->dtex);
 		if (sev) HIPCHK(c, hipEventRecord(sev[1], s));
 		HIPCHK(c, hipGetLastError());
 		rc = readCounters(c); if (rc) return rc;
@@ -690,7 +690,7 @@ void mtsgpu_destroy(mtsgpu_ctx *c) {
 	if (!c) return;
 	(void) hipSetDevice(c->device);
 	(void) hipDeviceSynchronize();
-	freeAll(c->sceneAllocs); freeAll(c->colorAllocs); freeAll(c->pathAllocs);
+	freeAll(c->sceneAllocs); freeAll(c->colorAllocs); freeAll(c->texAllocs); freeAll(c->pathAllocs);
 	if (c->ownFilm && c->film) (void) hipFree(c->film);
 	if (c->pixelList) (void) hipFree(c->pixelList);
 	if (c->ldScr) (void) hipFree(c->ldScr);
@@ -841,6 +841,10 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 	freeAll(c->sceneAllocs);
 	freeAll(c->colorAllocs);      // a new scene starts without vertex colours (mtsgpu_set_vertex_colors)
 	c->dcol = DColors{ nullptr, nullptr };
+	c->hostColorSlots.clear();
+	freeAll(c->texAllocs);        // ... and without uv textures (mtsgpu_set_uv_textures)
+	c->dtex = DTextures{ nullptr, nullptr, nullptr };
+	c->hostSlotTex.clear();
 	c->haveScene = false;
 	DScene d{};
 	int rc = 0;
@@ -1026,6 +1030,7 @@ int mtsgpu_set_vertex_colors(mtsgpu_ctx *c, const float *vtx_col, const uint32_t
 	if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
 	freeAll(c->colorAllocs);
 	c->dcol = DColors{ nullptr, nullptr };
+	c->hostColorSlots.clear();
 	if (!vtx_col && !shape_has_colors && !bsdf_color_slots) return 0;
 	if ((vtx_col == nullptr) != (shape_has_colors == nullptr))
 		return fail(c, MTSGPU_EINVAL, "vtx_col and shape_has_colors must both be given or both be NULL");
@@ -1035,6 +1040,11 @@ int mtsgpu_set_vertex_colors(mtsgpu_ctx *c, const float *vtx_col, const uint32_t
 	if (bsdf_color_slots) {
 		const std::string why = checkBsdfColorSlots(nBsdfs, h.bsdfType.data(), h.bsdfParams.data(), bsdf_color_slots);
 		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+		if (!c->hostSlotTex.empty())      // a slot mtsgpu_set_uv_textures has given a texture
+			for (uint32_t b = 0; b < nBsdfs; ++b)
+				for (int s = 0; s < 2; ++s)
+					if (((bsdf_color_slots[b] >> s) & 1u) && c->hostSlotTex[2 * (size_t) b + s] >= 0)
+						return fail(c, MTSGPU_EINVAL, "BSDF %u: slot %d takes vertex colours and has a uv texture as well", b, s);
 		for (uint32_t s = 0; s < nShapes; ++s) {
 			const int32_t b = h.shapeBsdf[s];
 			if (b < 0 || !bsdf_color_slots[b]) continue;
@@ -1069,6 +1079,98 @@ int mtsgpu_set_vertex_colors(mtsgpu_ctx *c, const float *vtx_col, const uint32_t
 	if (!rc && anySlot) rc = upload(c, &dSlots, bsdf_color_slots, nBsdfs, &c->colorAllocs);
 	if (rc) { freeAll(c->colorAllocs); return rc; }
 	c->dcol = DColors{ reinterpret_cast<const float4 *>(dCol), dSlots };
+	if (anySlot) c->hostColorSlots.assign(bsdf_color_slots, bsdf_color_slots + nBsdfs);
+	return 0;
+}
+
+static_assert(sizeof(mtsgpu_uv_texture) == sizeof(DTexture) && offsetof(mtsgpu_uv_texture, line_width) == offsetof(DTexture, line_width)
+              && offsetof(mtsgpu_uv_texture, bright) == offsetof(DTexture, bright), "mtsgpu_uv_texture and DTexture are one layout");
+static_assert(MTSGPU_TEX_CHECKERBOARD == (int) kTexCheckerboard && MTSGPU_TEX_GRID == (int) kTexGrid, "texture kinds differ");
+
+// what mtsgpu_set_uv_textures and mtsgpu_uv_texture_eval require of one descriptor; the reason, or an empty string
+static std::string checkUvTexture(const mtsgpu_uv_texture &t) {
+	if (t.kind >= (uint32_t) MTSGPU_TEX_NKINDS) return "unknown kind " + std::to_string(t.kind);
+	const float *f = &t.uoffset;      // the eleven floats behind the kind
+	for (int i = 0; i < 11; ++i) if (!std::isfinite(f[i])) return "non-finite parameter";
+	return std::string();
+}
+// 2 * uv' of texture t at texcoord (u, v) stays inside the range of the reference's (int) cast, with the margin the header states
+static bool uvCastInRange(const mtsgpu_uv_texture &t, float u, float v) {
+	const double lim = 2147483648.0 - 65536.0;
+	const double x = 2.0 * ((double) u * t.uscale + t.uoffset), y = 2.0 * ((double) v * t.vscale + t.voffset);
+	return std::fabs(x) < lim && std::fabs(y) < lim;
+}
+
+int mtsgpu_set_uv_textures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
+                           const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture) {
+	if (!c) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_set_uv_textures before mtsgpu_upload_scene");
+	c->lastPass.valid = false;
+	HIPCHK(c, hipSetDevice(c->device));
+	// nothing may still read the arrays that go (the shading launches of a render that was not synchronised)
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
+	freeAll(c->texAllocs);
+	c->dtex = DTextures{ nullptr, nullptr, nullptr };
+	c->hostSlotTex.clear();
+	if (!vtx_uv && !shape_has_uv && !textures && !bsdf_slot_texture) return 0;
+	if ((vtx_uv == nullptr) != (shape_has_uv == nullptr))
+		return fail(c, MTSGPU_EINVAL, "vtx_uv and shape_has_uv must both be given or both be NULL");
+	if (n_textures && !textures) return fail(c, MTSGPU_EINVAL, "n_textures without textures");
+	if (n_textures > (1u << 20)) return fail(c, MTSGPU_EINVAL, "at most 2^20 textures");
+	const mtsgpu_ctx::HostScene &h = c->host;
+	const uint32_t nShapes = (uint32_t) h.shapeBsdf.size(), nBsdfs = (uint32_t) h.bsdfType.size();
+	for (uint32_t k = 0; k < n_textures; ++k) {
+		const std::string why = checkUvTexture(textures[k]);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "texture %u: %s", k, why.c_str());
+	}
+	bool anySlot = false;
+	if (bsdf_slot_texture) {
+		const std::string why = checkBsdfSlotTextures(nBsdfs, h.bsdfType.data(), h.bsdfParams.data(), bsdf_slot_texture, n_textures,
+		                                              c->hostColorSlots.empty() ? nullptr : c->hostColorSlots.data());
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+		for (size_t i = 0; i < 2 * (size_t) nBsdfs; ++i) anySlot |= bsdf_slot_texture[i] >= 0;
+	}
+	// the gather array: the texcoords of the three vertices of every primitive of a mesh that has them, zero elsewhere
+	const size_t US = 4 * (size_t) kTriUvStride;
+	std::vector<float> triUv(US * ((size_t) c->nTris + 1), 0.0f);
+	for (uint32_t s = 0; s < nShapes; ++s) {
+		const bool hasUv = shape_has_uv && shape_has_uv[s];
+		const bool mesh = h.shapeType[s] == MTSGPU_SHAPE_TRIMESH;
+		if (hasUv && !mesh) return fail(c, MTSGPU_EINVAL, "shape %u: only a triangle mesh can carry texture coordinates", s);
+		if (hasUv)
+			for (uint32_t t = h.shapeTriOffset[s]; t < h.shapeTriOffset[s + 1]; ++t)
+				for (int k = 0; k < 3; ++k) {
+					const uint32_t v = h.triIdx[3 * (size_t) t + k];      // < n_verts: mtsgpu_upload_scene checked it
+					const float *uv = vtx_uv + 2 * (size_t) v;
+					if (!std::isfinite(uv[0]) || !std::isfinite(uv[1]))
+						return fail(c, MTSGPU_EINVAL, "shape %u: non-finite texcoord at vertex %u", s, v);
+					std::memcpy(&triUv[US * (size_t) t + 2 * (size_t) k], uv, 8);
+				}
+		// the casts of the textures this shape is shaded with
+		const int32_t b = h.shapeBsdf[s];
+		if (b < 0 || !bsdf_slot_texture) continue;
+		for (int slot = 0; slot < 2; ++slot) {
+			const int32_t k = bsdf_slot_texture[2 * (size_t) b + slot];
+			if (k < 0) continue;
+			bool ok = true;
+			if (!mesh) ok = uvCastInRange(textures[k], 0.0f, 0.0f) && uvCastInRange(textures[k], 1.0f, 1.0f);
+			else if (!hasUv) ok = uvCastInRange(textures[k], 0.0f, 0.0f);
+			else
+				for (uint32_t t = h.shapeTriOffset[s]; ok && t < h.shapeTriOffset[s + 1]; ++t)
+					for (int v = 0; v < 3; ++v) ok = ok && uvCastInRange(textures[k], triUv[US * (size_t) t + 2 * v], triUv[US * (size_t) t + 2 * v + 1]);
+			if (!ok)
+				return fail(c, MTSGPU_EINVAL, "shape %u: texture %d maps a texcoord outside the range of the (int) cast (|2 uv'| >= 2^31 - 2^16)", s, k);
+		}
+	}
+	if (!anySlot && !vtx_uv) return 0;       // nothing to keep
+	const float *dUv = nullptr; const DTexture *dTex = nullptr; const int32_t *dSlots = nullptr;
+	int rc = upload(c, &dUv, triUv.data(), triUv.size(), &c->texAllocs);
+	if (!rc && anySlot) rc = upload(c, &dTex, reinterpret_cast<const DTexture *>(textures), n_textures, &c->texAllocs);
+	if (!rc && anySlot) rc = upload(c, &dSlots, bsdf_slot_texture, 2 * (size_t) nBsdfs, &c->texAllocs);
+	if (rc) { freeAll(c->texAllocs); return rc; }
+	c->dtex = DTextures{ reinterpret_cast<const float4 *>(dUv), dTex, dSlots };
+	if (anySlot) c->hostSlotTex.assign(bsdf_slot_texture, bsdf_slot_texture + 2 * (size_t) nBsdfs);
 	return 0;
 }
 
@@ -1176,6 +1278,7 @@ int mtsgpu_load_serialized(const char *path, int shape_index, mtsgpu_loaded_mesh
 
 void mtsgpu_loaded_mesh_free(mtsgpu_loaded_mesh *m) { delete m; }
 
+const float *mtsgpu_loaded_mesh_texcoords(const mtsgpu_loaded_mesh *m) { return (m && !m->m.texcoords.empty()) ? m->m.texcoords.data() : nullptr; }
 const float *mtsgpu_loaded_mesh_colors(const mtsgpu_loaded_mesh *m) { return (m && !m->m.colors.empty()) ? m->m.colors.data() : nullptr; }
 
 int mtsgpu_tabulate_filter(int kind, float half_size, float p0, float p1, float *size_xy, float *values) {
@@ -1790,6 +1893,78 @@ int mtsgpu_vertex_color_eval(mtsgpu_ctx *c, uint32_t n, const uint32_t *prim, co
 	return 0;
 }
 
+int mtsgpu_bsdf_eval_slots(mtsgpu_ctx *c, uint32_t bsdf_type, const float *params, const int32_t slot_source[2], const float color[3],
+                           const float *values, int op, uint32_t n, const float *queries, float *out) {
+	if (!c || !params || !slot_source || !color || !values || !queries || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	if ((bsdf_type & 0xFFu) >= (uint32_t) MTSGPU_BSDF_NTYPES || (bsdf_type & ~(0xFFu | (uint32_t) MTSGPU_BSDF_TWOSIDED)) || op < 0 || op > 2)
+		return fail(c, MTSGPU_EINVAL, "bad BSDF type or operation");
+	if ((bsdf_type & 0xFFu) == (uint32_t) MTSGPU_BSDF_COMPOSITE)
+		return fail(c, MTSGPU_EINVAL, "a composite has no texture slot of its own, and its children take no textures");
+	int src[2];
+	for (int s = 0; s < 2; ++s) {
+		src[s] = slot_source[s];
+		if (src[s] < kSlotBlock || src[s] > kSlotTexture) return fail(c, MTSGPU_EINVAL, "slot %d: unknown source %d", s, src[s]);
+		if (src[s] != kSlotBlock && s >= bsdfColorSlotCount(bsdf_type))
+			return fail(c, MTSGPU_EINVAL, "slot %d lies beyond the %d texture slot(s) of BSDF type %u", s, bsdfColorSlotCount(bsdf_type), bsdf_type & 0xFFu);
+	}
+	if (n == 0) return 0;
+	if (n > (1u << 24)) return fail(c, MTSGPU_EINVAL, "at most 2^24 query records per call");
+	HIPCHK(c, hipSetDevice(c->device));
+	float *dQ = nullptr, *dOut = nullptr;
+	HIPCHK(c, hipMalloc((void **) &dQ, (size_t) n * 6 * sizeof(float)));
+	hipError_t e = hipMalloc((void **) &dOut, (size_t) n * 8 * sizeof(float));
+	if (e == hipSuccess) e = hipMemcpyAsync(dQ, queries, (size_t) n * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) {
+		launch_bsdf_eval_slots(c->stream, bsdf_type, params, src, color, values, op, n, dQ, dOut);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, (size_t) n * 8 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	(void) hipFree(dQ); if (dOut) (void) hipFree(dOut);
+	if (e != hipSuccess) return fail(c, MTSGPU_EHIP, "BSDF read-out failed: %s", hipGetErrorString(e));
+	return 0;
+}
+
+int mtsgpu_uv_texture_eval(mtsgpu_ctx *c, const mtsgpu_uv_texture *tex, uint32_t n, const uint32_t *prim, const float *rec, float *out) {
+	if (!c || !tex || !prim || !rec || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_uv_texture_eval before mtsgpu_upload_scene");
+	const std::string why = checkUvTexture(*tex);
+	if (!why.empty()) return fail(c, MTSGPU_EINVAL, "texture: %s", why.c_str());
+	if (n > (1u << 24)) return fail(c, MTSGPU_EINVAL, "at most 2^24 query records per call");
+	for (uint32_t i = 0; i < n; ++i)      // the kernel indexes tri_pos and tri_uv with it
+		if (prim[i] >= c->nTris) return fail(c, MTSGPU_EINVAL, "record %u: primitive %u out of range", i, prim[i]);
+	if (n == 0) return 0;
+	HIPCHK(c, hipSetDevice(c->device));
+	uint32_t *dP = nullptr; float *dRec = nullptr, *dOut = nullptr, *dZero = nullptr;
+	hipError_t e = hipMalloc((void **) &dP, (size_t) n * sizeof(uint32_t));
+	if (e == hipSuccess) e = hipMalloc((void **) &dRec, (size_t) n * 3 * sizeof(float));
+	if (e == hipSuccess) e = hipMalloc((void **) &dOut, (size_t) n * 5 * sizeof(float));
+	const float4 *triUv = c->dtex.tri_uv;
+	if (e == hipSuccess && !triUv) {
+		// no texcoords set: every mesh reads zero rows
+		const size_t bytes = sizeof(float4) * kTriUvStride * ((size_t) c->nTris + 1);
+		e = hipMalloc((void **) &dZero, bytes);
+		if (e == hipSuccess) e = hipMemsetAsync(dZero, 0, bytes, c->stream);
+		triUv = reinterpret_cast<const float4 *>(dZero);
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(dP, prim, (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(dRec, rec, (size_t) n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) {
+		DTexture t;
+		std::memcpy(&t, tex, sizeof t);
+		launch_uv_texture_eval(c->stream, c->dsc, triUv, t, n, dP, dRec, dOut);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, (size_t) n * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (dP) (void) hipFree(dP);
+	if (dRec) (void) hipFree(dRec);
+	if (dOut) (void) hipFree(dOut);
+	if (dZero) (void) hipFree(dZero);
+	if (e != hipSuccess) return fail(c, MTSGPU_EHIP, "uv-texture read-out failed: %s", hipGetErrorString(e));
+	return 0;
+}
+
 int mtsgpu_sky_configure(const float *block, float *derived) {
 	if (!block || !derived) return fail(nullptr, MTSGPU_EINVAL, "null argument");
 	skyConfigure(block, derived);
@@ -1954,6 +2129,20 @@ static bool flatSceneHasColors(const mtsgpu_flat_scene *fs) {
 }
 const float *mtsgpu_flat_scene_vertex_colors(const mtsgpu_flat_scene *fs) { return flatSceneHasColors(fs) ? fs->fs.vtxCol.data() : nullptr; }
 const uint32_t *mtsgpu_flat_scene_shape_has_colors(const mtsgpu_flat_scene *fs) { return flatSceneHasColors(fs) ? fs->fs.shapeHasColors.data() : nullptr; }
+
+int mtsgpu_flat_scene_set_mesh_texcoords(mtsgpu_flat_scene *fs, uint32_t mesh_index, const float *texcoords) {
+	if (!fs) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	const std::string why = setMeshTexcoords(fs->fs, mesh_index, texcoords);
+	if (!why.empty()) return fail(nullptr, MTSGPU_EINVAL, "%s", why.c_str());
+	return 0;
+}
+static bool flatSceneHasTexcoords(const mtsgpu_flat_scene *fs) {
+	if (!fs) return false;
+	for (uint32_t h : fs->fs.shapeHasUv) if (h) return true;
+	return false;
+}
+const float *mtsgpu_flat_scene_vertex_texcoords(const mtsgpu_flat_scene *fs) { return flatSceneHasTexcoords(fs) ? fs->fs.vtxUv.data() : nullptr; }
+const uint32_t *mtsgpu_flat_scene_shape_has_texcoords(const mtsgpu_flat_scene *fs) { return flatSceneHasTexcoords(fs) ? fs->fs.shapeHasUv.data() : nullptr; }
 
 int mtsgpu_flat_scene_kdstats(const mtsgpu_flat_scene *fs, double *out6) {
 	if (!fs || !out6) return fail(nullptr, MTSGPU_EINVAL, "null argument");

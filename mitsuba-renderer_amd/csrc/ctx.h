@@ -35,6 +35,12 @@ struct mtsgpu_ctx {
 	} host;
 	std::vector<void *> colorAllocs;
 	mg::DColors dcol{ nullptr, nullptr };   // what the vertex-colour kernels take (NULL, NULL without colours)
+	// mtsgpu_set_uv_textures: DTextures' arrays, owned like the colours', and host copies of the two slot tables in force
+	// (empty = none), so that each of the two calls can refuse a slot the other one has taken
+	std::vector<void *> texAllocs;
+	mg::DTextures dtex{ nullptr, nullptr, nullptr };
+	std::vector<uint32_t> hostColorSlots;
+	std::vector<int32_t> hostSlotTex;
 
 	// configuration
 	bool haveCamera = false;

@@ -86,6 +86,22 @@ std::string setMeshColors(FlatScene &f, uint32_t mesh, const float *colors) {
 	return std::string();
 }
 
+std::string setMeshTexcoords(FlatScene &f, uint32_t mesh, const float *texcoords) {
+	if (mesh >= f.sc.n_shapes) return "mesh index " + std::to_string(mesh) + " out of range";
+	if (f.shapeType[mesh] != MTSGPU_SHAPE_TRIMESH) return "mesh " + std::to_string(mesh) + ": only a triangle mesh can carry texture coordinates";
+	const size_t first = f.shapeVtxOffset[mesh], count = f.shapeVtxOffset[mesh + 1] - first;
+	if (f.vtxUv.empty()) {
+		if (!texcoords) return std::string();
+		f.vtxUv.assign(2 * (size_t) f.sc.n_verts + 2, 0.0f);
+		f.shapeHasUv.assign((size_t) f.sc.n_shapes + 1, 0u);
+	}
+	// as for the colours: texcoord i of the mesh belongs to pool row first + i
+	if (texcoords) std::memcpy(&f.vtxUv[2 * first], texcoords, sizeof(float) * 2 * count);
+	else std::fill(f.vtxUv.begin() + 2 * first, f.vtxUv.begin() + 2 * (first + count), 0.0f);
+	f.shapeHasUv[mesh] = texcoords ? 1u : 0u;
+	return std::string();
+}
+
 void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs) {
 	const uint32_t nShapes = d.n_meshes, nLums = d.n_lums;
 	size_t nVerts = 0, nTris = 0;
@@ -107,6 +123,7 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 	fs.shapeTriOffset.assign(nShapes + 1, 0u);
 	fs.shapeVtxOffset.assign(nShapes + 1, 0u);
 	fs.vtxCol.clear(); fs.shapeHasColors.clear();
+	fs.vtxUv.clear(); fs.shapeHasUv.clear();
 	fs.shapeFlags.assign(nShapes + 1, 0u);
 	fs.shapeBsdf.assign(nShapes + 1, -1);
 	fs.shapeLum.assign(nShapes + 1, -1);

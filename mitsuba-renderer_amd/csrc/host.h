@@ -34,6 +34,9 @@ struct FlatScene {
 	// shape, both empty until a mesh receives colours; shapeVtxOffset[s] = the first pool row of shape s
 	std::vector<float> vtxCol;
 	std::vector<uint32_t> shapeHasColors, shapeVtxOffset;
+	// texture coordinates (mtsgpu_flat_scene_set_mesh_texcoords): the pool [n_verts][2] and the flags, kept like the colours
+	std::vector<float> vtxUv;
+	std::vector<uint32_t> shapeHasUv;
 };
 
 // Texture-typed spectrum slots per BSDF type, in slot order (include/mtsgpu.h): the first float of each slot's three in the
@@ -61,6 +64,38 @@ inline std::string checkBsdfColorSlots(uint32_t n_bsdfs, const uint32_t *type, c
 		for (int i = 0; i < n; ++i)
 			if (slots[(uint32_t) P[1 + n + i]])
 				return msg(b, "composite child " + std::to_string(i) + " takes vertex colours: a composite's children keep constant parameters, not supported");
+	}
+	return std::string();
+}
+
+// What mtsgpu_set_uv_textures requires of the slot table [n_bsdfs][2] (a texture index, or -1) against a checked BSDF table
+// and the colour masks in force (NULL = none): indices inside the texture list, no slot beyond those of the type, none that
+// is coloured as well, none on a composite's child.  Returns the reason, or an empty string.
+inline std::string checkBsdfSlotTextures(uint32_t n_bsdfs, const uint32_t *type, const float *params, const int32_t *slotTex, uint32_t n_textures,
+                                         const uint32_t *colorSlots) {
+	auto msg = [](uint32_t b, const std::string &what) { return "BSDF " + std::to_string(b) + ": " + what; };
+	for (uint32_t b = 0; b < n_bsdfs; ++b) {
+		const int n = bsdfColorSlotCount(type[b]);
+		for (int s = 0; s < 2; ++s) {
+			const int32_t k = slotTex[2 * (size_t) b + s];
+			if (k < -1 || k >= (int64_t) n_textures)
+				return msg(b, "slot " + std::to_string(s) + " names texture " + std::to_string(k) + " of " + std::to_string(n_textures));
+			if (k < 0) continue;
+			if (s >= n)
+				return msg(b, "uv texture in slot " + std::to_string(s) + ", beyond the " + std::to_string(n) + " texture slot(s) of its type");
+			if (colorSlots && ((colorSlots[b] >> s) & 1u))
+				return msg(b, "slot " + std::to_string(s) + " has a uv texture and takes vertex colours as well");
+		}
+	}
+	for (uint32_t b = 0; b < n_bsdfs; ++b) {
+		if ((type[b] & 0xFFu) != MTSGPU_BSDF_COMPOSITE) continue;
+		const float *P = params + (size_t) MTSGPU_BSDF_NPARAMS * b;
+		const int n = (int) P[0];
+		for (int i = 0; i < n; ++i) {
+			const uint32_t ch = (uint32_t) P[1 + n + i];
+			if (slotTex[2 * (size_t) ch] >= 0 || slotTex[2 * (size_t) ch + 1] >= 0)
+				return msg(b, "composite child " + std::to_string(i) + " has a uv texture: a composite's children keep constant parameters, not supported");
+		}
 	}
 	return std::string();
 }
@@ -192,11 +227,14 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 // n_verts][3] copied into fs.vtxCol at the mesh's rows, NULL takes them away again.  Returns the reason it refuses, or an
 // empty string.
 std::string setMeshColors(FlatScene &fs, uint32_t mesh, const float *colors);
+// the same for texture coordinates: texcoords [that mesh's n_verts][2] into fs.vtxUv
+std::string setMeshTexcoords(FlatScene &fs, uint32_t mesh, const float *texcoords);
 
 // One shape of a `.serialized` file (TriMesh::TriMesh(Stream *, int), src/librender/trimesh.cpp:156-236)
 struct LoadedMesh {
 	std::vector<float> positions, normals;     // normals empty when the file has none
 	std::vector<float> colors;                 // [n_verts][3], empty without the EHasColors block (trimesh.cpp:113-118,223-229)
+	std::vector<float> texcoords;              // [n_verts][2], empty without the EHasTexcoords block (trimesh.cpp:105-111,214-221)
 	std::vector<uint32_t> triangles;
 	bool faceNormals = false;
 };

@@ -136,6 +136,26 @@ constexpr int bsdf_color_slot_offset(int bt, int s) {
 	     : bt == 4 ? (s == 0 ? 0 : -1) : bt == 5 ? (s == 0 ? 5 : 8) : bt == 6 ? (s == 0 ? 4 : 7) : bt == 7 ? (s == 0 ? 0 : -1)
 	     : bt == 8 ? (s == 0 ? 7 : 10) : -1;
 }
+// The procedural uv textures (mtsgpu_set_uv_textures), all NULL without them.  Like DColors an argument of kernels of its own
+// (k_shade_tex, k_shade_all_tex) only.  tri_uv: a gather array in primitive order, kTriUvStride float4 per primitive =
+// t0.uv t1.uv | t2.uv - - (32 bytes, two aligned 16-byte loads; zero for spheres and for meshes without texcoords).
+// textures[n_textures]: one descriptor each.  bsdf_slot_texture[n_bsdfs][2]: the texture of slot s of the BSDF, -1 = none;
+// non-NULL only while some slot has one, and the shading launches pick their texture kernels by it
+struct DTexture {
+	uint32_t kind;                          // MTSGPU_TEX_CHECKERBOARD, MTSGPU_TEX_GRID
+	float uoffset, voffset, uscale, vscale; // Texture2D (texture.cpp:43-52)
+	float bright[3], dark[3];
+	float line_width;                       // gridtexture only
+};
+struct DTextures {
+	const float4   *tri_uv;
+	const DTexture *textures;
+	const int32_t  *bsdf_slot_texture;
+};
+constexpr uint32_t kTexCheckerboard = 0, kTexGrid = 1;      // DTexture::kind = MTSGPU_TEX_*
+constexpr int kTriUvStride = 2;       // float4 per primitive of DTextures::tri_uv
+// what a texture slot of a BSDF takes at a hit (bsdf_block_with_slots)
+enum : int { kSlotBlock = 0, kSlotColor = 1, kSlotTexture = 2 };
 
 // What k_trace needs of the scene (a kernel argument: the fewer scalar registers it pins, the fewer get spilled)
 struct DTraceScene {
@@ -353,6 +373,14 @@ void launch_bsdf_eval_colored(hipStream_t s, uint32_t type, const float *params,
                               const float *queries, float *out);
 // mtsgpu_vertex_color_eval: its.color for n (primitive, u, v) records of tri_col; uv [n][2], out [n][3]
 void launch_vertex_color_eval(hipStream_t s, const float4 *tri_col, uint32_t n, const uint32_t *prim, const float *uv, float *out);
+// mtsgpu_bsdf_eval_slots: the same read-out through bsdf_block_with_slots; slot s takes nothing (source[s] = kSlotBlock),
+// color[3] (kSlotColor) or values[s][3] (kSlotTexture)
+void launch_bsdf_eval_slots(hipStream_t s, uint32_t type, const float *params, const int *source, const float *color, const float *values,
+                            int op, uint32_t n, const float *queries, float *out);
+// mtsgpu_uv_texture_eval: its.uv (its_uv) and tex_eval of `tex` there for n records of the uploaded scene; rec [n][3] =
+// (u, v, -) on a triangle, the world-space hit point on a sphere; out [n][5] = uv, rgb
+void launch_uv_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, uint32_t n, const uint32_t *prim,
+                            const float *rec, float *out);
 // the sky luminaire (mtsgpu_lum_eval): Le (op 0), sample (1), pdf (2) for n query records [n][6]; block = the parameter
 // block followed by its derived array, in device memory; out [n][12]
 void launch_sky_eval(hipStream_t s, const float *block, int op, uint32_t n, const float *queries, float *out);
@@ -373,11 +401,13 @@ struct BinView { uint32_t prefix[kBinShards + 1]; };
 // bin_ids: the bin's id segments (q.bin(bin) unless the caller shades another queue)
 void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                   const DQueues &q, const BinView &view, const BinView *views_dev = nullptr, uint32_t n_bound = 0,
-                  const uint32_t *bin_ids = nullptr, const DColors &col = DColors{ nullptr, nullptr });
+                  const uint32_t *bin_ids = nullptr, const DColors &col = DColors{ nullptr, nullptr },
+                  const DTextures &tex = DTextures{ nullptr, nullptr, nullptr });
 // device-driven bounces, path integrator / one-sample direct integrator: all bins of bin_mask in one launch; views_dev as
 // above, n_bound bounds the sum of the bin sizes
 void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,
-                      const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound, const DColors &col = DColors{ nullptr, nullptr });
+                      const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound, const DColors &col = DColors{ nullptr, nullptr },
+                      const DTextures &tex = DTextures{ nullptr, nullptr, nullptr });
 // device-driven bounces: per-bin views from the shard counters of the closest-hit launch that just ran (`cur`), and
 // the counter set of the next bounce zeroed
 void launch_prep(hipStream_t s, const uint32_t *cur, uint32_t *next_set, BinView *views_dev, uint32_t bin_seg_cap,

@@ -94,7 +94,8 @@ void loadSerializedMesh(const char *path, int index, LoadedMesh &out) {
 	z.readFloats(dbl, out.positions.data(), 3 * nv);
 	out.normals.clear();
 	if (flags & kHasNormals) { out.normals.resize(3 * nv); z.readFloats(dbl, out.normals.data(), 3 * nv); }
-	if (flags & kHasTexcoords) { std::vector<float> skip(2 * nv); z.readFloats(dbl, skip.data(), 2 * nv); }     // no textures on this path
+	out.texcoords.clear();
+	if (flags & kHasTexcoords) { out.texcoords.resize(2 * nv); z.readFloats(dbl, out.texcoords.data(), 2 * nv); }      // m_texcoords (trimesh.cpp:105-111,214-221)
 	out.colors.clear();
 	if (flags & kHasColors) { out.colors.resize(3 * nv); z.readFloats(dbl, out.colors.data(), 3 * nv); }      // m_vertexColors (trimesh.cpp:223-229)
 	out.triangles.resize(3 * nt);

@@ -94,6 +94,68 @@ __device__ __forceinline__ void bsdf_block_with_color(const float *P, uint32_t s
 	if (o1 >= 0 && (slots & 2u)) { Q[o1 < 0 ? 0 : o1] = color.x; Q[o1 < 0 ? 0 : o1 + 1] = color.y; Q[o1 < 0 ? 0 : o1 + 2] = color.z; }
 }
 
+// its.uv of a hit.  Triangle mesh (skdtree.h:364,408-415): the three texcoords of the primitive (DTextures::tri_uv) weighted
+// with b = ((1 - u) - v, u, v) as (t0 * b.x + t1 * b.y) + t2 * b.z per component; a mesh without texcoords has zero rows and
+// gets (0, 0), the reference's value.  Sphere (sphere.cpp:136-145): spherical coordinates of the hit point p in object space,
+// `local` formed as fill_its forms it.
+__device__ __forceinline__ void its_uv(const DScene &sc, const float4 *tri_uv, uint32_t prim, uint32_t shape, float u, float v, V3 p,
+                                       float &uvx, float &uvy) {
+	if (sc.shape_type[shape] == 1u) {
+		const float *SP = sc.shape_params + 24 * (size_t) shape;
+		const float *W2O = SP + 14;
+		const V3 center(SP[0], SP[1], SP[2]);
+		const float radius = SP[3];
+		const V3 pc = p - center;
+		const V3 local(W2O[0] * pc.x + W2O[1] * pc.y + W2O[2] * pc.z, W2O[3] * pc.x + W2O[4] * pc.y + W2O[5] * pc.z,
+		               W2O[6] * pc.x + W2O[7] * pc.y + W2O[8] * pc.z);
+		const float theta = dacos(smin(smax(local.z / radius, -1.0f), 1.0f));
+		float phi = datan2(local.y, local.x);
+		if (phi < 0) phi += 2 * kPi;
+		uvx = phi * (0.5f * kInvPi);
+		uvy = theta * kInvPi;
+	} else {
+		const float4 *TU = tri_uv + kTriUvStride * (size_t) prim;
+		const float4 a = TU[0], c = TU[1];
+		const float bx = 1 - u - v, by = u, bz = v;
+		uvx = a.x * bx + a.z * by + c.x * bz;
+		uvy = a.y * bx + a.w * by + c.y * bz;
+	}
+}
+// Texture2D::getValue(its) (texture.cpp:73-82) of a checkerboard (checkerboard.cpp:48-56) or a grid texture
+// (gridtexture.cpp:51-64) at its.uv = (uvx, uvy).  The casts truncate towards zero as the reference's (int) does; the host
+// has checked that they stay inside the int range for every texcoord of the scene (mtsgpu_set_uv_textures).
+__device__ __forceinline__ V3 tex_eval(const DTexture &t, float uvx, float uvy) {
+	const float x = uvx * t.uscale + t.uoffset, y = uvy * t.vscale + t.voffset;
+	bool bright;
+	if (t.kind == kTexCheckerboard) {
+		// 2 * modulo(i, 2) - 1 with the non-negative remainder: +1 for an odd i, -1 for an even one
+		const int cx = 2 * (((int) (x * 2)) & 1) - 1, cy = 2 * (((int) (y * 2)) & 1) - 1;
+		bright = cx * cy == 1;
+	} else {
+		float fx = x - (float) (int) x, fy = y - (float) (int) y;
+		if (fx > .5f) fx -= 1;
+		if (fy > .5f) fy -= 1;
+		bright = !(fabsf(fx) < t.line_width || fabsf(fy) < t.line_width);
+	}
+	return bright ? V3(t.bright[0], t.bright[1], t.bright[2]) : V3(t.dark[0], t.dark[1], t.dark[2]);
+}
+// bsdf_block_with_color for scenes with uv textures: slot S of type BT takes nothing (src = kSlotBlock) or w, which is its.color
+// (kSlotColor) or the value of the slot's texture at its.uv (kSlotTexture).  Every index is a compile-time constant.  The shading
+// kernels copy the block (bsdf_block_with_slots with both sources kSlotBlock) and then write one slot after the other, so that one
+// value is alive at a time; the read-out hook (k_bsdf_eval_slots) hands both over at once.  Both write through bsdf_block_set_slot.
+template <int BT, int S>
+__device__ __forceinline__ void bsdf_block_set_slot(float (&Q)[kBsdfNParams], int src, V3 w) {
+	constexpr int o = bsdf_color_slot_offset(BT, S);
+	if (o >= 0 && src != kSlotBlock) { Q[o < 0 ? 0 : o] = w.x; Q[o < 0 ? 0 : o + 1] = w.y; Q[o < 0 ? 0 : o + 2] = w.z; }
+}
+template <int BT>
+__device__ __forceinline__ void bsdf_block_with_slots(const float *P, int src0, int src1, V3 color, V3 val0, V3 val1, float (&Q)[kBsdfNParams]) {
+	#pragma unroll
+	for (int k = 0; k < kBsdfNParams; ++k) Q[k] = P[k];
+	bsdf_block_set_slot<BT, 0>(Q, src0, src0 == kSlotColor ? color : val0);
+	bsdf_block_set_slot<BT, 1>(Q, src1, src1 == kSlotColor ? color : val1);
+}
+
 struct LRec { V3 p, n, d, value; float pdf; int lum; };
 
 // DiscretePDF::sample / sampleReuse (include/mitsuba/core/pdf.h:102-133)
@@ -1190,6 +1252,48 @@ __global__ void k_vertex_color_eval(const float4 *tri_col, uint32_t n, const uin
 	out[3 * (size_t) i] = c.x; out[3 * (size_t) i + 1] = c.y; out[3 * (size_t) i + 2] = c.z;
 }
 
+// mtsgpu_bsdf_eval_slots: k_bsdf_eval on the block bsdf_block_with_slots builds
+struct SlotValues { int src[2]; float color[3]; float val[2][3]; };
+template <int BT>
+__device__ __forceinline__ void bsdf_eval_slots_one(bool two, const float *P, const SlotValues &sv, int op, const float *q, float *o) {
+	float Q[kBsdfNParams];
+	bsdf_block_with_slots<BT>(P, sv.src[0], sv.src[1], V3(sv.color[0], sv.color[1], sv.color[2]), V3(sv.val[0][0], sv.val[0][1], sv.val[0][2]),
+	                          V3(sv.val[1][0], sv.val[1][1], sv.val[1][2]), Q);
+	bsdf_eval_one<BT>(BsdfTable{ nullptr, nullptr }, two, Q, op, q, o);
+}
+__global__ void k_bsdf_eval_slots(uint32_t type, BsdfParams params, SlotValues sv, int op, uint32_t n, const float *queries, float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const bool two = (type & 0x100u) != 0;
+	const float *P = params.v, *q = queries + 6 * (size_t) i;
+	float o[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+	switch (type & 0xFFu) {
+		case 0: bsdf_eval_slots_one<0>(two, P, sv, op, q, o); break;
+		case 1: bsdf_eval_slots_one<1>(two, P, sv, op, q, o); break;
+		case 2: bsdf_eval_slots_one<2>(two, P, sv, op, q, o); break;
+		case 3: bsdf_eval_slots_one<3>(two, P, sv, op, q, o); break;
+		case 4: bsdf_eval_slots_one<4>(two, P, sv, op, q, o); break;
+		case 5: bsdf_eval_slots_one<5>(two, P, sv, op, q, o); break;
+		case 6: bsdf_eval_slots_one<6>(two, P, sv, op, q, o); break;
+		case 7: bsdf_eval_slots_one<7>(two, P, sv, op, q, o); break;
+		default: bsdf_eval_slots_one<8>(two, P, sv, op, q, o); break;
+	}
+	#pragma unroll
+	for (int k = 0; k < 8; ++k) out[8 * (size_t) i + k] = o[k];
+}
+// mtsgpu_uv_texture_eval: its_uv and tex_eval for n records; the host has checked prim < n_tris
+__global__ void k_uv_texture_eval(DScene sc, const float4 *tri_uv, DTexture tex, uint32_t n, const uint32_t *prim, const float *rec, float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t shape = __float_as_uint(sc.tri_pos[kTriStride * (size_t) prim[i] + 2].z);
+	const float *r = rec + 3 * (size_t) i;
+	float uvx, uvy;
+	its_uv(sc, tri_uv, prim[i], shape, r[0], r[1], V3(r[0], r[1], r[2]), uvx, uvy);
+	const V3 c = tex_eval(tex, uvx, uvy);
+	float *o = out + 5 * (size_t) i;
+	o[0] = uvx; o[1] = uvy; o[2] = c.x; o[3] = c.y; o[4] = c.z;
+}
+
 // The sky luminaire read out for n query records (mtsgpu_lum_eval): block = its parameters followed by the derived array
 // (kLumStride + MTSGPU_SKY_NDERIVED floats in device memory); queries [n][6], out [n][12]
 __global__ void k_sky_eval(const float *block, int op, uint32_t n, const float *queries, float *out) {
@@ -1246,12 +1350,15 @@ struct ShadeRow {
 };
 __device__ __forceinline__ uint32_t shade_row_index(uint32_t lane, uint32_t k) { return lane * kRowStride + (MG_SHADE_PACKED ? (k ^ (lane & 7u)) : k); }
 
-// VCOL: the instantiation for scenes with a coloured BSDF slot (DColors::bsdf_color_slots != NULL): the block the BSDF reads
-// is built per hit by bsdf_block_with_color.  Every other scene runs the instantiation without that code.
-template <int BT, bool ROUNDS, bool SKY, bool VCOL>
+// VCOL: kSlotColor = the instantiation for scenes with a coloured BSDF slot (DColors::bsdf_color_slots != NULL): the block the
+// BSDF reads is built per hit by bsdf_block_with_color.  kSlotTexture = the one for scenes with a uv-textured slot
+// (DTextures::bsdf_slot_texture != NULL), which serves coloured slots as well: bsdf_block_with_slots.  Every other scene
+// (kSlotBlock) runs the instantiation without that code.
+template <int BT, bool ROUNDS, bool SKY, int VCOL>
 __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, const DConfig &cfg, const uint32_t id,
                                            const float4 ro, const float4 rd, const uint4 h, const float4 T4, const float4 L4,
-                                           const ShadeRow row, bool &continues, bool &wantShadow, V3 &neeV, V3 &shO, V3 &shD, const DColors &col) {
+                                           const ShadeRow row, bool &continues, bool &wantShadow, V3 &neeV, V3 &shO, V3 &shD, const DColors &col,
+                                           const DTextures &tex) {
 	{
 		// rounds of MIDirectIntegrator (DConfig::dr_mode): later BSDF samples start again from the camera hit
 		const int mode = ROUNDS ? cfg.dr_mode : 0;
@@ -1353,7 +1460,31 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			const int bsdfIdx = sc.shape_bsdf[its.shape];
 			const float *BP = sc.bsdf_params + 16 * (size_t) bsdfIdx;
 			float colouredBlock[kBsdfNParams];
-			if (VCOL && BT < 9) {
+			if (VCOL == kSlotTexture && BT < 9) {
+				// a checkerboard or grid texture in a slot of this BSDF: that slot holds the texture's value at its.uv; a
+				// `vertexcolors` texture in the other one its.color
+				const int k0 = tex.bsdf_slot_texture[2 * (size_t) bsdfIdx], k1 = tex.bsdf_slot_texture[2 * (size_t) bsdfIdx + 1];
+				const uint32_t slots = col.bsdf_color_slots ? col.bsdf_color_slots[bsdfIdx] : 0u;
+				float uvx = 0, uvy = 0;
+				if (k0 >= 0 || k1 >= 0)
+					its_uv(sc, tex.tri_uv, h.w, its.shape, __uint_as_float(h.y), __uint_as_float(h.z), its.p, uvx, uvy);
+				// one slot after the other, so that only one value is alive next to the block
+				const V3 zero(0, 0, 0);
+				bsdf_block_with_slots<BT>(BP, kSlotBlock, kSlotBlock, zero, zero, zero, colouredBlock);
+				{
+					const int src = k0 >= 0 ? kSlotTexture : (slots & 1u) ? kSlotColor : kSlotBlock;
+					const V3 w = src == kSlotTexture ? tex_eval(tex.textures[k0], uvx, uvy)
+					           : src == kSlotColor ? its_color(col.tri_col, h.w, __uint_as_float(h.y), __uint_as_float(h.z)) : zero;
+					bsdf_block_set_slot<BT, 0>(colouredBlock, src, w);
+				}
+				{
+					const int src = k1 >= 0 ? kSlotTexture : (slots & 2u) ? kSlotColor : kSlotBlock;
+					const V3 w = src == kSlotTexture ? tex_eval(tex.textures[k1], uvx, uvy)
+					           : src == kSlotColor ? its_color(col.tri_col, h.w, __uint_as_float(h.y), __uint_as_float(h.z)) : zero;
+					bsdf_block_set_slot<BT, 1>(colouredBlock, src, w);
+				}
+				BP = colouredBlock;
+			} else if (VCOL == kSlotColor && BT < 9) {
 				// a `vertexcolors` texture in a slot of this BSDF: that slot holds its.color for this hit
 				const uint32_t slots = col.bsdf_color_slots[bsdfIdx];
 				const V3 color = slots ? its_color(col.tri_col, h.w, __uint_as_float(h.y), __uint_as_float(h.z)) : V3(0, 0, 0);
@@ -1461,9 +1592,10 @@ struct ShadeShared {
 };
 // One workgroup of k_shade: the paths block * kShadeBlock .. of the material queue whose segment sizes are `prefix`
 // (prefix[kBinShards] entries in kBinShards segments of bin_ids)
-template <int BT, bool ROUNDS, bool SKY, bool VCOL>
+template <int BT, bool ROUNDS, bool SKY, int VCOL>
 __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const uint32_t *prefix,
-                                            const uint32_t *bin_ids, const uint32_t block, ShadeShared &sh, const DColors &col) {
+                                            const uint32_t *bin_ids, const uint32_t block, ShadeShared &sh, const DColors &col,
+                                            const DTextures &tex = DTextures{ nullptr, nullptr, nullptr }) {
 	uint32_t (&s_cnt)[2][kShadeBlock / 64] = sh.cnt;
 	uint32_t (&s_base)[2] = sh.base;
 	float4 (&s_rows)[kShadeBlock / 64][64 * kRowStride] = sh.rows;
@@ -1548,7 +1680,7 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	}
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	if (active)
-		shade_path<BT, ROUNDS, SKY, VCOL>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col);
+		shade_path<BT, ROUNDS, SKY, VCOL>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col, tex);
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	#pragma unroll
 	for (int r = 0; r < 8; ++r) {
@@ -1600,14 +1732,21 @@ __global__ MG_SHADE_BOUNDS void k_shade(DScene sc, DPaths ps, DConfig cfg, DQueu
                                                        const BinView *views_dev, const uint32_t *bin_ids) {
 	__shared__ ShadeShared sh;
 	// the bin's segment sizes: a kernel argument when the host read the counters back, otherwise what k_prep wrote
-	shade_block<BT, ROUNDS, SKY, false>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, DColors{ nullptr, nullptr });
+	shade_block<BT, ROUNDS, SKY, kSlotBlock>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, DColors{ nullptr, nullptr });
 }
 // the same for scenes with a coloured BSDF slot: the only kernels that take the colours
 template <int BT, bool ROUNDS, bool SKY>
 __global__ MG_SHADE_BOUNDS void k_shade_vcol(DScene sc, DPaths ps, DConfig cfg, DQueues q, BinView view_host,
                                                             const BinView *views_dev, const uint32_t *bin_ids, DColors col) {
 	__shared__ ShadeShared sh;
-	shade_block<BT, ROUNDS, SKY, true>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col);
+	shade_block<BT, ROUNDS, SKY, kSlotColor>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col);
+}
+// and for scenes with a uv-textured BSDF slot: the only kernels that take the textures
+template <int BT, bool ROUNDS, bool SKY>
+__global__ MG_SHADE_BOUNDS void k_shade_tex(DScene sc, DPaths ps, DConfig cfg, DQueues q, BinView view_host,
+                                                           const BinView *views_dev, const uint32_t *bin_ids, DColors col, DTextures tex) {
+	__shared__ ShadeShared sh;
+	shade_block<BT, ROUNDS, SKY, kSlotTexture>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col, tex);
 }
 
 // All material queues of a bounce in ONE launch (device-driven bounces): the workgroups are dealt to the bins in bin order,
@@ -1617,9 +1756,9 @@ __global__ MG_SHADE_BOUNDS void k_shade_vcol(DScene sc, DPaths ps, DConfig cfg, 
 // SKY: the launch for scenes whose background is a sky (launch_shade_all picks it): every other scene runs the instantiation
 // without that code, whose registers are what they were before the sky existed.  VCOL: likewise for scenes with a coloured
 // BSDF slot; the bins that cannot have one (composite, terminal) run the same code either way
-template <bool SKY, bool VCOL>
+template <bool SKY, int VCOL>
 __device__ __forceinline__ void shade_all(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const BinView *views_dev, uint32_t bin_mask,
-                                          ShadeShared &sh, const DColors &col) {
+                                          ShadeShared &sh, const DColors &col, const DTextures &tex = DTextures{ nullptr, nullptr, nullptr }) {
 	uint32_t block = blockIdx.x;
 	int bin = -1;
 	for (int b = 0; b < kNumBins; ++b) {
@@ -1631,28 +1770,34 @@ __device__ __forceinline__ void shade_all(const DScene &sc, const DPaths &ps, co
 	if (bin < 0) return;
 	const uint32_t *prefix = views_dev[bin].prefix, *ids = q.bin(bin);
 	switch (bin) {
-		case 0: shade_block<0, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
-		case 1: shade_block<1, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
-		case 2: shade_block<2, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
-		case 3: shade_block<3, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
-		case 4: shade_block<4, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
-		case 5: shade_block<5, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
-		case 6: shade_block<6, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
-		case 7: shade_block<7, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
-		case 8: shade_block<8, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
+		case 0: shade_block<0, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
+		case 1: shade_block<1, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
+		case 2: shade_block<2, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
+		case 3: shade_block<3, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
+		case 4: shade_block<4, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
+		case 5: shade_block<5, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
+		case 6: shade_block<6, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
+		case 7: shade_block<7, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
+		case 8: shade_block<8, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
 		case 9: return;      // the composite's loop over its children is launched on its own (kShadeAllBins)
-		default: shade_block<kNumBsdfTypes, false, SKY, false>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
+		default: shade_block<kNumBsdfTypes, false, SKY, kSlotBlock>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
 	}
 }
 template <bool SKY>
 __global__ MG_SHADE_BOUNDS void k_shade_all(DScene sc, DPaths ps, DConfig cfg, DQueues q, const BinView *views_dev, uint32_t bin_mask) {
 	__shared__ ShadeShared sh;
-	shade_all<SKY, false>(sc, ps, cfg, q, views_dev, bin_mask, sh, DColors{ nullptr, nullptr });
+	shade_all<SKY, kSlotBlock>(sc, ps, cfg, q, views_dev, bin_mask, sh, DColors{ nullptr, nullptr });
 }
 template <bool SKY>
 __global__ MG_SHADE_BOUNDS void k_shade_all_vcol(DScene sc, DPaths ps, DConfig cfg, DQueues q, const BinView *views_dev, uint32_t bin_mask, DColors col) {
 	__shared__ ShadeShared sh;
-	shade_all<SKY, true>(sc, ps, cfg, q, views_dev, bin_mask, sh, col);
+	shade_all<SKY, kSlotColor>(sc, ps, cfg, q, views_dev, bin_mask, sh, col);
+}
+template <bool SKY>
+__global__ MG_SHADE_BOUNDS void k_shade_all_tex(DScene sc, DPaths ps, DConfig cfg, DQueues q, const BinView *views_dev, uint32_t bin_mask, DColors col,
+                                                DTextures tex) {
+	__shared__ ShadeShared sh;
+	shade_all<SKY, kSlotTexture>(sc, ps, cfg, q, views_dev, bin_mask, sh, col, tex);
 }
 
 void launch_bsdf_eval(hipStream_t s, uint32_t type, const float *params, int op, uint32_t n, const float *queries, float *out) {
@@ -1674,9 +1819,17 @@ void launch_sky_eval(hipStream_t s, const float *block, int op, uint32_t n, cons
 // (DColors::bsdf_color_slots; bins 0..8 only -- a composite's children and the terminal bin take no colours)
 template <int BT>
 static void launch_shade_bin(hipStream_t s, const dim3 g, const dim3 b, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,
-                             const BinView &view, const BinView *views_dev, const uint32_t *bin_ids, const DColors &col) {
+                             const BinView &view, const BinView *views_dev, const uint32_t *bin_ids, const DColors &col, const DTextures &tex) {
 	const bool rounds = cfg.dr_mode != 0, sky = sc.sky != nullptr;
 	if constexpr (BT < 9) {
+		if (tex.bsdf_slot_texture != nullptr) {
+			#define MG_SHADE(R, S) hipLaunchKernelGGL((k_shade_tex<BT, R, S>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids, col, tex)
+			if (rounds) { if (sky) MG_SHADE(true, true); else MG_SHADE(true, false); }
+			else if (sky) MG_SHADE(false, true);
+			else MG_SHADE(false, false);
+			#undef MG_SHADE
+			return;
+		}
 		if (col.bsdf_color_slots != nullptr) {
 			#define MG_SHADE(R, S) hipLaunchKernelGGL((k_shade_vcol<BT, R, S>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids, col)
 			if (rounds) { if (sky) MG_SHADE(true, true); else MG_SHADE(true, false); }
@@ -1694,12 +1847,13 @@ static void launch_shade_bin(hipStream_t s, const dim3 g, const dim3 b, const DS
 }
 
 void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, const DConfig &cfg,
-                  const DQueues &q, const BinView &view, const BinView *views_dev, uint32_t n_bound, const uint32_t *bin_ids, const DColors &col) {
+                  const DQueues &q, const BinView &view, const BinView *views_dev, uint32_t n_bound, const uint32_t *bin_ids, const DColors &col,
+                  const DTextures &tex) {
 	const uint32_t n = views_dev ? n_bound : view.prefix[kBinShards];
 	if (!n) return;
 	if (!bin_ids) bin_ids = q.bin(bin);
 	const dim3 g(blocks_for(n, kShadeBlock)), b(kShadeBlock);
-	#define MG_SHADE_BIN(BT) launch_shade_bin<BT>(s, g, b, sc, ps, cfg, q, view, views_dev, bin_ids, col)
+	#define MG_SHADE_BIN(BT) launch_shade_bin<BT>(s, g, b, sc, ps, cfg, q, view, views_dev, bin_ids, col, tex)
 	switch (bin) {
 		case 0: MG_SHADE_BIN(0); break;
 		case 1: MG_SHADE_BIN(1); break;
@@ -1717,13 +1871,16 @@ void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, co
 }
 
 void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,
-                      const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound, const DColors &col) {
+                      const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound, const DColors &col, const DTextures &tex) {
 	bin_mask &= kShadeAllBins;
 	if (!n_bound || !bin_mask) return;
 	// every bin rounds its size up to whole workgroups
 	const unsigned blocks = blocks_for(n_bound, kShadeBlock) + (unsigned) __builtin_popcount(bin_mask);
 	const dim3 g(blocks), b(kShadeBlock);
-	if (col.bsdf_color_slots) {
+	if (tex.bsdf_slot_texture) {
+		if (sc.sky) hipLaunchKernelGGL(k_shade_all_tex<true>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask, col, tex);
+		else hipLaunchKernelGGL(k_shade_all_tex<false>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask, col, tex);
+	} else if (col.bsdf_color_slots) {
 		if (sc.sky) hipLaunchKernelGGL(k_shade_all_vcol<true>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask, col);
 		else hipLaunchKernelGGL(k_shade_all_vcol<false>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask, col);
 	} else if (sc.sky) hipLaunchKernelGGL(k_shade_all<true>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask);
@@ -1735,6 +1892,22 @@ void launch_bsdf_eval_colored(hipStream_t s, uint32_t type, const float *params,
 	BsdfParams p;
 	for (int k = 0; k < kBsdfNParams; ++k) p.v[k] = params[k];
 	if (n) hipLaunchKernelGGL(k_bsdf_eval_colored, dim3(blocks_for(n, 256)), dim3(256), 0, s, type, p, slots, color[0], color[1], color[2], op, n, queries, out);
+}
+
+void launch_bsdf_eval_slots(hipStream_t s, uint32_t type, const float *params, const int *source, const float *color, const float *values,
+                            int op, uint32_t n, const float *queries, float *out) {
+	BsdfParams p;
+	for (int k = 0; k < kBsdfNParams; ++k) p.v[k] = params[k];
+	SlotValues sv;
+	for (int k = 0; k < 2; ++k) sv.src[k] = source[k];
+	for (int k = 0; k < 3; ++k) sv.color[k] = color[k];
+	for (int k = 0; k < 6; ++k) sv.val[k / 3][k % 3] = values[k];
+	if (n) hipLaunchKernelGGL(k_bsdf_eval_slots, dim3(blocks_for(n, 256)), dim3(256), 0, s, type, p, sv, op, n, queries, out);
+}
+
+void launch_uv_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, uint32_t n, const uint32_t *prim,
+                            const float *rec, float *out) {
+	if (n) hipLaunchKernelGGL(k_uv_texture_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, tri_uv, tex, n, prim, rec, out);
 }
 
 void launch_vertex_color_eval(hipStream_t s, const float4 *tri_col, uint32_t n, const uint32_t *prim, const float *uv, float *out) {

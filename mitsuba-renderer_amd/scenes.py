@@ -24,8 +24,63 @@ class _VertexColors:
 VERTEX_COLORS = _VertexColors()
 
 
+class _UvTexture:
+    """Texture2D (src/librender/texture.cpp:43-52): uv' = uv * (uscale, vscale) + (uoffset, voffset); brightColor and
+    darkColor as a grey level or an RGB triple"""
+    kind = -1
+
+    def __init__(self, bright=0.4, dark=0.2, uoffset=0.0, voffset=0.0, uscale=1.0, vscale=1.0, line_width=0.01):
+        self.bright = np.broadcast_to(np.asarray(bright, dtype=np.float32), (3,)).copy()
+        self.dark = np.broadcast_to(np.asarray(dark, dtype=np.float32), (3,)).copy()
+        self.uoffset, self.voffset, self.uscale, self.vscale = F(uoffset), F(voffset), F(uscale), F(vscale)
+        self.line_width = F(line_width)
+
+    def maximum(self):
+        return self.bright.copy()
+
+    def descriptor(self):
+        """the twelve words of mtsgpu_uv_texture"""
+        return abi.UvTexture(self.kind, self.uoffset, self.voffset, self.uscale, self.vscale, (C.c_float * 3)(*self.bright),
+                             (C.c_float * 3)(*self.dark), self.line_width)
+
+
+class Checkerboard(_UvTexture):
+    """the `checkerboard` texture (src/textures/checkerboard.cpp); pass it where a BSDF constructor of SceneDescription takes a
+    reflectance or transmittance.  The block then holds getAverage() = darkColor * .5f (sic, :66-68)"""
+    kind = abi.TEX_CHECKERBOARD
+
+    def __init__(self, bright=0.4, dark=0.2, uoffset=0.0, voffset=0.0, uscale=1.0, vscale=1.0):
+        _UvTexture.__init__(self, bright, dark, uoffset, voffset, uscale, vscale)
+
+    def average(self):
+        return self.dark * F(0.5)
+
+
+class GridTexture(_UvTexture):
+    """the `gridtexture` texture (src/textures/gridtexture.cpp): dark lines of half-width lineWidth on the integer uv'
+    lines.  The block holds getAverage() = brightColor (:79-81)"""
+    kind = abi.TEX_GRID
+
+    def average(self):
+        return self.bright.copy()
+
+
+def _slot_average(v):
+    """what a texture-typed argument of a BSDF leaves in the block: Texture::getAverage() (a constant: itself)"""
+    return v.average() if isinstance(v, _UvTexture) else F(1.0) if v is VERTEX_COLORS else v
+
+
+def _slot_maximum(v):
+    """Texture::getMaximum(), which verifyEnergyConservation reads (phong.cpp:81-90, ward.cpp)"""
+    return v.maximum() if isinstance(v, _UvTexture) else F(1.0) if v is VERTEX_COLORS else v
+
+
+def _rgb(v):
+    return [F(x) for x in np.broadcast_to(np.asarray(v, dtype=np.float32), (3,))]
+
+
 class MeshDesc:
-    def __init__(self, positions, triangles, bsdf=-1, lum=-1, face_normals=True, normals=None, name="", colors=None):
+    def __init__(self, positions, triangles, bsdf=-1, lum=-1, face_normals=True, normals=None, name="", colors=None, texcoords=None):
         self.positions = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
         self.triangles = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
         self.normals = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
@@ -33,6 +88,10 @@ class MeshDesc:
         self.colors = None if colors is None else np.ascontiguousarray(colors, dtype=np.float32).reshape(-1, 3)
         if self.colors is not None and self.colors.shape[0] != self.positions.shape[0]:
             raise ValueError("one colour per vertex: %d colours, %d vertices" % (self.colors.shape[0], self.positions.shape[0]))
+        # texture coordinates of a TriMesh (m_texcoords), [n_verts][2], or None
+        self.texcoords = None if texcoords is None else np.ascontiguousarray(texcoords, dtype=np.float32).reshape(-1, 2)
+        if self.texcoords is not None and self.texcoords.shape[0] != self.positions.shape[0]:
+            raise ValueError("one texcoord per vertex: %d texcoords, %d vertices" % (self.texcoords.shape[0], self.positions.shape[0]))
         self.bsdf, self.lum, self.face_normals, self.name = int(bsdf), int(lum), bool(face_normals), name
         self.shape_type, self.sphere = abi.SHAPE_TRIMESH, None
 
@@ -55,6 +114,9 @@ class SceneDescription:
         self.bsdf_type = []
         self.bsdf_params = []
         self.bsdf_color_slots = []  # per BSDF: bit s = its s-th texture slot takes its.color (include/mtsgpu.h)
+        self.textures = []          # the Checkerboard / GridTexture objects in use (what mtsgpu_set_uv_textures takes)
+        self.bsdf_slot_texture = [] # per BSDF: [index into textures or -1] for its two texture slots
+        self._slot_textures = ()
         self.lum_type = []
         self.lum_params = []
         self.camera = dict(origin=(0.0, 1.0, 3.4), target=(0.0, 1.0, 0.0), up=(0.0, 1.0, 0.0), fov=39.3)
@@ -69,75 +131,88 @@ class SceneDescription:
         self.bsdf_type.append(int(btype))
         self.bsdf_params.append(p)
         self.bsdf_color_slots.append(int(color_slots))
+        row = [-1, -1]
+        for s, t in enumerate(self._slot_textures):        # left by _textured() for the constructor that called it
+            if t is not None:
+                if not any(t is u for u in self.textures):
+                    self.textures.append(t)
+                row[s] = [i for i, u in enumerate(self.textures) if u is t][0]
+        self._slot_textures = ()
+        self.bsdf_slot_texture.append(row)
         return len(self.bsdf_type) - 1
 
-    @staticmethod
-    def _textured(*values):
+    def _textured(self, *values):
         """VERTEX_COLORS among the texture-typed arguments of a BSDF -> (the values with 1.0 in its place: the texture's
-        getAverage() / getMaximum(), vertexcolors.cpp:49-55; the slot mask, bit s for the s-th argument)"""
+        getAverage() / getMaximum(), vertexcolors.cpp:49-55; the slot mask, bit s for the s-th argument).  A Checkerboard or
+        GridTexture is replaced by its getAverage(), an RGB triple, and noted for add_bsdf, which fills bsdf_slot_texture"""
         mask = sum(1 << s for s, v in enumerate(values) if v is VERTEX_COLORS)
-        return [1.0 if v is VERTEX_COLORS else v for v in values], mask
+        self._slot_textures = tuple(v if isinstance(v, _UvTexture) else None for v in values)
+        return [1.0 if v is VERTEX_COLORS else _slot_average(v) for v in values], mask
 
     def lambertian(self, r, g=None, b=None):
         (r,), slots = self._textured(r)
+        if np.ndim(r):
+            r, g, b = r
         g = r if g is None else g
         b = r if b is None else b
         return self.add_bsdf(abi.BSDF_LAMBERTIAN, [r, g, b], slots)
 
     def dielectric(self, int_ior=1.5046, ext_ior=1.0, refl=1.0, trans=1.0):
         (refl, trans), slots = self._textured(refl, trans)
-        return self.add_bsdf(abi.BSDF_DIELECTRIC, [int_ior, ext_ior, refl, refl, refl, trans, trans, trans], slots)
+        return self.add_bsdf(abi.BSDF_DIELECTRIC, [int_ior, ext_ior] + _rgb(refl) + _rgb(trans), slots)
 
     def roughmetal(self, alpha=0.1, ior=0.37, k=2.82, refl=1.0):
         (refl,), slots = self._textured(refl)
-        return self.add_bsdf(abi.BSDF_ROUGHMETAL, [alpha, ior, ior, ior, k, k, k, refl, refl, refl], slots)
+        return self.add_bsdf(abi.BSDF_ROUGHMETAL, [alpha, ior, ior, ior, k, k, k] + _rgb(refl), slots)
 
     def microfacet(self, alpha=0.1, kd=0.5, ks=0.5, int_ior=1.5, ext_ior=1.0, rd=1.0, rs=1.0):
         (rd, rs), slots = self._textured(rd, rs)
-        return self.add_bsdf(abi.BSDF_MICROFACET, [alpha, kd, ks, int_ior, ext_ior, rd, rd, rd, rs, rs, rs], slots)
+        return self.add_bsdf(abi.BSDF_MICROFACET, [alpha, kd, ks, int_ior, ext_ior] + _rgb(rd) + _rgb(rs), slots)
 
     def mirror(self, r=0.8):
         (r,), slots = self._textured(r)
-        return self.add_bsdf(abi.BSDF_MIRROR, [r, r, r], slots)
+        return self.add_bsdf(abi.BSDF_MIRROR, _rgb(r), slots)
 
     def phong(self, exponent=10.0, rd=0.5, rs=0.2, kd=1.0, ks=1.0):
         """parameter block as Phong::configure() leaves it (src/bsdfs/phong.cpp:74-96), float32 arithmetic"""
+        max_d, max_s = max(_rgb(_slot_maximum(rd))), max(_rgb(_slot_maximum(rs)))      # getMaximum().max()
         (rd, rs), slots = self._textured(rd, rs)
-        kd, ks, rd, rs = F(kd), F(ks), F(rd), F(rs)
-        if kd * rd + ks * rs > F(1.0):                       # verifyEnergyConservation
-            norm = F(1) / (kd * rd + ks * rs)
+        kd, ks, rd, rs = F(kd), F(ks), _rgb(rd), _rgb(rs)
+        if kd * max_d + ks * max_s > F(1.0):                 # verifyEnergyConservation
+            norm = F(1) / (kd * max_d + ks * max_s)
             kd, ks = kd * norm, ks * norm
-        avg_d = (rd + rd + rd) * F(1.0 / 3) * kd             # Spectrum::average() * m_kd
-        avg_s = (rs + rs + rs) * F(1.0 / 3) * ks
+        avg_d = (rd[0] + rd[1] + rd[2]) * F(1.0 / 3) * kd    # getAverage().average() * m_kd
+        avg_s = (rs[0] + rs[1] + rs[2]) * F(1.0 / 3) * ks
         ssw = avg_s / (avg_d + avg_s)
         dsw = F(1.0) - ssw
-        return self.add_bsdf(abi.BSDF_PHONG, [exponent, kd, ks, ssw, dsw, rd, rd, rd, rs, rs, rs], slots)
+        return self.add_bsdf(abi.BSDF_PHONG, [exponent, kd, ks, ssw, dsw] + rd + rs, slots)
 
     def roughglass(self, alpha=0.1, int_ior=1.5046, ext_ior=1.0, distribution="beckmann", refl=1.0, trans=1.0):
         """src/bsdfs/roughglass.cpp: for `phong` the constructor maps alpha to the exponent 2/alpha^2 - 2 (:130-136)"""
         d = {"beckmann": 0, "phong": 1, "ggx": 2}[distribution]
-        if alpha is VERTEX_COLORS:
-            raise ValueError("roughglass: alpha is a float texture, vertex colours cannot drive it")
+        if alpha is VERTEX_COLORS or isinstance(alpha, _UvTexture):
+            raise ValueError("roughglass: alpha is a float texture, neither vertex colours nor a uv texture can drive it")
         (refl, trans), slots = self._textured(refl, trans)
         a = F(alpha)
         if d == 1:
             a = F(2) / (a * a) - F(2)
-        return self.add_bsdf(abi.BSDF_ROUGHGLASS, [d, a, int_ior, ext_ior, refl, refl, refl, trans, trans, trans], slots)
+        return self.add_bsdf(abi.BSDF_ROUGHGLASS, [d, a, int_ior, ext_ior] + _rgb(refl) + _rgb(trans), slots)
 
     def difftrans(self, t=0.5):
         (t,), slots = self._textured(t)
-        return self.add_bsdf(abi.BSDF_DIFFTRANS, [t, t, t], slots)
+        return self.add_bsdf(abi.BSDF_DIFFTRANS, _rgb(t), slots)
 
     def ward(self, alpha_x=0.1, alpha_y=0.1, rd=0.5, rs=0.2, kd=1.0, ks=1.0, model="balanced", specular_sampling_weight=-1.0,
              verify_energy_conservation=True):
         """parameter block as the constructor and Ward::configure() leave it (src/bsdfs/ward.cpp:54-88, :118-136), float32
         arithmetic; rd / rs: a grey level or an RGB triple"""
         m = {"ward": 0, "ward-duer": 1, "balanced": 2}[model]
+        max_d, max_s = max(_rgb(_slot_maximum(rd))), max(_rgb(_slot_maximum(rs)))      # getMaximum().max()
         (rd, rs), slots = self._textured(rd, rs)
         rd = np.broadcast_to(np.asarray(rd, dtype=np.float32), (3,)); rs = np.broadcast_to(np.asarray(rs, dtype=np.float32), (3,))
         kd, ks = F(kd), F(ks)
-        if verify_energy_conservation and kd * rd.max() + ks * rs.max() > F(1.0):
-            norm = F(1) / (kd * rd.max() + ks * rs.max())
+        if verify_energy_conservation and kd * max_d + ks * max_s > F(1.0):
+            norm = F(1) / (kd * max_d + ks * max_s)
             kd, ks = kd * norm, ks * norm
         ssw = F(specular_sampling_weight)
         if ssw == F(-1):
@@ -737,6 +812,68 @@ def cornell_vcol(sky=False, sphere_subdiv=2):
     return sd
 
 
+def tex_grid_mesh(cells=4, seed=3):
+    """vcol_grid's planar grid (the same triangles in the same order) with per-triangle, unshared vertices -> (positions,
+    triangles, texcoords).  The texcoords are a sheared affine map of (x, z) that reaches below zero, plus an offset of its
+    own per triangle, so that uv jumps across every edge: a texcoord fetched from the neighbour's vertex shows"""
+    g = vcol_grid(cells).meshes[0]
+    pos = g.positions[g.triangles.ravel()].astype(np.float32)
+    tri = np.arange(pos.shape[0], dtype=np.uint32).reshape(-1, 3)
+    rng = np.random.RandomState(seed)
+    M = np.array([[0.9, -0.35], [0.3, 0.8]], dtype=np.float32)
+    uv = (pos[:, [0, 2]] @ M.T + np.array([-0.15, 0.1], dtype=np.float32)).astype(np.float32)
+    uv = (uv.reshape(-1, 3, 2) + rng.uniform(-0.02, 0.02, (tri.shape[0], 1, 2)).astype(np.float32)).reshape(-1, 2)
+    return pos, tri, uv.astype(np.float32)
+
+
+def tex_scene(reflectance, shape="grid", cells=4, env=0.25, sky=False):
+    """A Lambertian floor (shape = "grid": tex_grid_mesh in the plane y = 0) or one sphere (shape = "sphere") under a point
+    light and a constant environment (or, sky = True, the sky), seen straight down by an orthographic camera, maxDepth 2.
+    Neither shape can be hit twice by one path, so every radiance sample is linear in the reflectance at the camera hit.
+    reflectance: a Checkerboard / GridTexture, a grey level or an RGB triple"""
+    sd = SceneDescription("tex_%s" % shape)
+    bsdf = sd.lambertian(reflectance)
+    if shape == "grid":
+        pos, tri, uv = tex_grid_mesh(cells)
+        sd.add_mesh(pos, tri, bsdf=bsdf, face_normals=True, name="floor", texcoords=uv)
+    else:
+        sd.add_sphere((0.05, -0.1, -0.02), 0.8, bsdf=bsdf)
+    sd.point_light((0.3, 1.5, -0.2), (5.0, 4.0, 3.0))
+    if sky:
+        sd.sky(sun_direction=(0.3, 0.2, 0.8), turbidity=3.0, sky_scale=0.2, to_world=[1, 0, 0, 0, 0, 1, 0, -1, 0])
+    else:
+        sd.add_lum(abi.LUM_CONSTANT, [env, env, env])
+    sd.camera = dict(origin=(0.0, 2.0, 0.0), target=(0.0, 0.0, 0.0), up=(0.0, 0.0, -1.0), ortho_scale=1.0)
+    sd.max_depth = 2
+    return sd
+
+
+def cornell_tex(sky=False):
+    """C1's box with a checkerboard on a sphere shape, a sheet whose twosided Phong takes a grid texture as
+    diffuseReflectance (slot 0) and the mesh's vertex colours as specularReflectance (slot 1), a mesh without texcoords
+    under a checkerboard (uv = (0, 0) all over) and an untextured rough metal; with sky = True the sky as background"""
+    sd = cornell_c1()
+    sd.name = "cornell_tex_sky" if sky else "cornell_tex"
+    check = Checkerboard(bright=(0.8, 0.7, 0.2), dark=(0.1, 0.15, 0.4), uscale=6.0, vscale=-3.0, uoffset=0.25)
+    sd.add_sphere((-0.35, 0.35, -0.2), 0.35, bsdf=sd.lambertian(check))
+    pos, tri, uv = tex_grid_mesh(3, seed=11)
+    c_, s_ = F(np.cos(0.6)), F(np.sin(0.6))
+    p = pos * F(0.3)
+    p = np.stack([p[:, 0], p[:, 2] * s_ + F(0.5), p[:, 2] * c_], axis=1) + np.array([0.45, 0.0, 0.25], dtype=np.float32)
+    col = (F(0.5) + F(0.45) * np.sin(pos * F(5.0) + np.array([0.0, 2.0, 4.0], dtype=np.float32))).astype(np.float32)
+    grid = GridTexture(bright=(0.7, 0.7, 0.6), dark=0.05, uscale=3.7, vscale=-3.7, uoffset=0.3, voffset=-0.3, line_width=0.08)
+    sd.add_mesh(p.astype(np.float32), tri, bsdf=sd.twosided(sd.phong(20.0, rd=grid, rs=VERTEX_COLORS, kd=0.6, ks=0.4)),
+                face_normals=True, name="textured sheet", colors=col, texcoords=uv)
+    pos, tri = icosphere(1, 0.2, (0.1, 0.2, 0.6))
+    sd.add_mesh(pos, tri, bsdf=sd.microfacet(0.2, rd=check, rs=0.5), face_normals=False, name="no texcoords")
+    pos, tri = icosphere(1, 0.15, (0.5, 0.15, -0.4))
+    sd.add_mesh(pos, tri, bsdf=sd.roughmetal(0.2), face_normals=False, name="plain sphere")
+    if sky:
+        sd.sky(sun_direction=(0.3, 0.2, 0.8), turbidity=3.0, sky_scale=0.2)
+    sd.max_depth = 5
+    return sd
+
+
 def by_name(name, **kw):
     return {"c1": cornell_c1, "c3": cornell_c3, "c5": cornell_c5, "next": next_rows, "spheres": spheres, "envlit": envlit,
-            "vcol_grid": vcol_grid, "vcol": cornell_vcol}[name](**kw)
+            "vcol_grid": vcol_grid, "vcol": cornell_vcol, "tex": cornell_tex}[name](**kw)

@@ -263,6 +263,19 @@ int  mtsgpu_set_stream(mtsgpu_ctx *ctx, void *hip_stream);
 
 /* --- scene / integrator state (replaces Scene::initialize + plugin configure) */
 int  mtsgpu_upload_scene(mtsgpu_ctx *ctx, const mtsgpu_scene *scene);
+/* mtsgpu_upload_scene plus the vertex tangents of the meshes whose BSDF is anisotropic (TriMesh::computeTangentSpaceBasis,
+ * trimesh.cpp:547-669; mtsgpu_flatten_tangents computes them): vtx_dpdu [n_verts][3] follows the scene's global vertex pool
+ * (rows of shapes without tangents are ignored), shape_has_tangents [n_shapes] is non-zero for the meshes that carry them;
+ * both may be NULL.  A hit on such a mesh gets the shading frame of skdtree.h:392-399 instead of Frame(n):
+ *   dpdu = (t0.dpdu * b.x + t1.dpdu * b.y) + t2.dpdu * b.z;  n = normalize(interpolated normal);
+ *   s = normalize(dpdu - n * dot(n, dpdu));  t = cross(n, s)
+ * in binary32.  Every other shape keeps its frame, and a scene without a tangent mesh launches the kernels it launches after
+ * mtsgpu_upload_scene.  A mesh with an anisotropic BSDF is accepted with tangents; without them it is accepted when it has no
+ * vertex normals (the reference warns and renders it with the frame it has, trimesh.cpp:562-565) and refused otherwise, with
+ * the reference's message.  MTSGPU_EINVAL also for tangents on a shape that is no mesh or has no vertex normals, and for a
+ * non-finite tangent.  Costs 48 bytes per primitive on the device.  mtsgpu_set_vertex_colors and
+ * mtsgpu_set_uv_textures work after either upload. */
+int  mtsgpu_upload_scene_tangents(mtsgpu_ctx *ctx, const mtsgpu_scene *scene, const float *vtx_dpdu, const uint32_t *shape_has_tangents);
 int  mtsgpu_set_camera(mtsgpu_ctx *ctx, const mtsgpu_camera *cam);
 /* MonteCarloIntegrator properties (src/librender/integrator.cpp:272-292) */
 int  mtsgpu_set_integrator(mtsgpu_ctx *ctx, int max_depth, int rr_depth, int strict_normals);
@@ -417,6 +430,8 @@ mtsgpu_ctx *mtsgpu_group_ctx(mtsgpu_group *g, int i);
 const char *mtsgpu_group_last_error(const mtsgpu_group *g);
 /* the same call on every member (scene upload runs on all devices concurrently) */
 int  mtsgpu_group_upload_scene(mtsgpu_group *g, const mtsgpu_scene *scene);
+/* mtsgpu_upload_scene_tangents on every member */
+int  mtsgpu_group_upload_scene_tangents(mtsgpu_group *g, const mtsgpu_scene *scene, const float *vtx_dpdu, const uint32_t *shape_has_tangents);
 int  mtsgpu_group_set_camera(mtsgpu_group *g, const mtsgpu_camera *cam);
 int  mtsgpu_group_set_integrator(mtsgpu_group *g, int max_depth, int rr_depth, int strict_normals);
 int  mtsgpu_group_set_sampler(mtsgpu_group *g, int kind, uint32_t spp, int ld_depth, uint64_t seed);
@@ -554,6 +569,10 @@ int  mtsgpu_uv_texture_eval(mtsgpu_ctx *ctx, const mtsgpu_uv_texture *tex, uint3
  * those slots overwritten.  A source other than 0 for a slot the type does not have, and a composite, are MTSGPU_EINVAL. */
 int  mtsgpu_bsdf_eval_slots(mtsgpu_ctx *ctx, uint32_t bsdf_type, const float *params, const int32_t slot_source[2], const float color[3],
                             const float *values, int op, uint32_t n, const float *queries, float *out);
+/* The shading frame as the device computes it for the uploaded scene and its tangents (mtsgpu_upload_scene_tangents; without
+ * them every mesh gets Frame(n)): prim [n] primitive indices, rec [n][3] as for mtsgpu_uv_texture_eval; out [n][9] = s, t, n.
+ * A test hook: it calls the device function the tangent shading kernels call. */
+int  mtsgpu_shading_frame_eval(mtsgpu_ctx *ctx, uint32_t n, const uint32_t *prim, const float *rec, float *out);
 /* MIPathTracer::Li for explicit camera samples: in [n][3] u32 = pixel x, y, sample index;
  * out [n][8] f32 = Li rgb, alpha, raster x, raster y, depth, unused */
 int  mtsgpu_li_samples(mtsgpu_ctx *ctx, const uint32_t *pix_samples, uint32_t n, float *out);
@@ -632,6 +651,18 @@ const uint32_t *mtsgpu_flat_scene_shape_has_colors(const mtsgpu_flat_scene *fs);
 int  mtsgpu_flat_scene_set_mesh_texcoords(mtsgpu_flat_scene *fs, uint32_t mesh_index, const float *texcoords);
 const float *mtsgpu_flat_scene_vertex_texcoords(const mtsgpu_flat_scene *fs);
 const uint32_t *mtsgpu_flat_scene_shape_has_texcoords(const mtsgpu_flat_scene *fs);
+/* mtsgpu_flatten with the texture coordinates known at flatten time: mesh_texcoords [n_meshes], entry s = the texcoords [that
+ * mesh's n_verts][2] or NULL (always NULL for a sphere).  A mesh whose BSDF is anisotropic (a Ward with alphaU != alphaV, alone,
+ * inside a composite or a twosided) is accepted when it has texcoords, and receives vertex tangents as
+ * TriMesh::computeTangentSpaceBasis computes them (trimesh.cpp:547-669, binary32, triangle order; a zero vertex normal of such
+ * a mesh becomes (1, 0, 0) in vtx_nrm as well); without texcoords it is refused with the reference's message; with texcoords
+ * but without vertex normals (face_normals) it is accepted and gets no tangents.  No other mesh is touched.  The texcoords are
+ * recorded as mtsgpu_flat_scene_set_mesh_texcoords records them. */
+int  mtsgpu_flatten_tangents(const mtsgpu_scene_desc *desc, const mtsgpu_kd_params *kd, const float *const *mesh_texcoords, mtsgpu_flat_scene **out);
+/* the tangents [n_verts][6] = dpdu, dpdv (rows of shapes without tangents are zero) and the flags [n_shapes]; NULL while no
+ * mesh has tangents.  mtsgpu_upload_scene_tangents takes the dpdu halves. */
+const float *mtsgpu_flat_scene_vertex_tangents(const mtsgpu_flat_scene *fs);
+const uint32_t *mtsgpu_flat_scene_shape_has_tangents(const mtsgpu_flat_scene *fs);
 /* kd-tree statistics logged by the reference builder (gkdtree.h:1178-1213) */
 int  mtsgpu_flat_scene_kdstats(const mtsgpu_flat_scene *fs, double *out6 /* inner, leaf, idx, expTrav, expLeaves, expPrims */);
 

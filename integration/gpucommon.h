@@ -15,7 +15,7 @@
  * What of a Mitsuba scene reaches the GPU (everything else stops with an error message that names the class):
  *   shapes      every TriMesh (obj, ply, serialized, ...: TriMesh accessors), `sphere`
  *   BSDFs       lambertian, dielectric, roughmetal, microfacet, mirror, phong, roughglass, difftrans, ward (anisotropic on
- *               spheres only), twosided(any of them), composite(up to 7 of the non-delta ones, each with or without twosided);
+ *               spheres and on meshes with texture coordinates, whose vertex tangents travel along), twosided(any of them), composite(up to 7 of the non-delta ones, each with or without twosided);
  *               constant reflectances only (textures need uv partials and a MIPMap lookup per hit: out of scope)
  *   luminaires  area (on meshes and spheres), constant, point, spot (no projection texture), directional, collimated, envmap
  *   cameras     perspective (pinhole and thin lens), orthographic
@@ -131,8 +131,21 @@ struct FlatScene {
 	std::vector<mtsgpu_uv_texture> uvTextures;
 	std::vector<int32_t> bsdfSlotTexture;
 	bool anyUv;
+	/* vertex tangents (TriMesh::getVertexTangents, trimesh.h:136-140: TriMesh::configure computes them for a mesh whose BSDF is
+	 * anisotropic, trimesh.cpp:288-290): dpdu in the order of vtxPos, one flag per shape -- what
+	 * mtsgpu_group_upload_scene_tangents takes */
+	std::vector<float> vtxDpdu;
+	std::vector<uint32_t> shapeHasTangents;
+	bool anyTangents;
 
-	/* after mtsgpu_group_upload_scene and setVertexColors: hands the textures over when a BSDF slot holds one (a mesh
+	/* the scene, with the tangents when a mesh has some; an anisotropic BSDF on a mesh that has vertex normals but no
+	 * tangents (no texture coordinates: Mitsuba has stopped with an error long before) is refused by the library */
+	int upload(mtsgpu_group *group) const {
+		if (!anyTangents) return mtsgpu_group_upload_scene(group, &sc);
+		return mtsgpu_group_upload_scene_tangents(group, &sc, ptr(vtxDpdu), ptr(shapeHasTangents));
+	}
+
+	/* after upload() and setVertexColors: hands the textures over when a BSDF slot holds one (a mesh
 	 * without texcoords is then shaded with uv = (0, 0), as in the reference) */
 	int setUvTextures(mtsgpu_group *group) const {
 		if (uvTextures.empty()) return MTSGPU_OK;
@@ -140,14 +153,14 @@ struct FlatScene {
 			&uvTextures[0], ptr(bsdfSlotTexture));
 	}
 
-	/* after mtsgpu_group_upload_scene: hands the colours over when a mesh has some or a BSDF slot asks for them (then the
+	/* after upload(): hands the colours over when a mesh has some or a BSDF slot asks for them (then the
 	 * library refuses a coloured slot on a shape without colours, where the reference would read an its.color nobody wrote) */
 	int setVertexColors(mtsgpu_group *group) const {
 		if (!anyColors && !anyColorSlots) return MTSGPU_OK;
 		return mtsgpu_group_set_vertex_colors(group, anyColors ? ptr(vtxCol) : NULL, anyColors ? ptr(shapeHasColors) : NULL, ptr(bsdfColorSlots));
 	}
 
-	FlatScene(const Scene *scene) : anyColors(false), anyColorSlots(false), anyUv(false) {
+	FlatScene(const Scene *scene) : anyColors(false), anyColorSlots(false), anyUv(false), anyTangents(false) {
 		memset(&sc, 0, sizeof(sc));
 		sc.abi_version = MTSGPU_ABI_VERSION;
 		const ShapeKDTree *kd = scene->getKDTree();                                   /* scene.h:498 */
@@ -242,7 +255,12 @@ struct FlatScene {
 				const Point2 *uv = mesh->hasVertexTexcoords() ? mesh->getVertexTexcoords() : NULL;
 				shapeHasUv.push_back(uv ? 1u : 0u);
 				if (uv) anyUv = true;
+				const TangentSpace *tan = mesh->hasVertexTangents() ? mesh->getVertexTangents() : NULL;       /* trimesh.h:136-140 */
+				shapeHasTangents.push_back(tan ? 1u : 0u);
+				if (tan) anyTangents = true;
 				for (size_t v = 0; v < mesh->getVertexCount(); ++v) {
+					vtxDpdu.push_back(tan ? (float) tan[v].dpdu.x : 0.0f); vtxDpdu.push_back(tan ? (float) tan[v].dpdu.y : 0.0f);
+					vtxDpdu.push_back(tan ? (float) tan[v].dpdu.z : 0.0f);
 					float rgb[3] = { 0.0f, 0.0f, 0.0f };
 					if (col) rgbOf(col[v], rgb);
 					vtxCol.insert(vtxCol.end(), rgb, rgb + 3);
@@ -289,6 +307,7 @@ struct FlatScene {
 				shapeType.push_back(MTSGPU_SHAPE_SPHERE);
 				shapeHasColors.push_back(0u);
 				shapeHasUv.push_back(0u);
+				shapeHasTangents.push_back(0u);
 				if (shape->isLuminaire()) {
 					const int l = lumIndex[shape->getLuminaire()];
 					lumShape[l] = (int32_t) s;
@@ -468,7 +487,7 @@ struct GPURenderDriver {
 		/* --- scene (re-uploaded per render call: the GUI edits scenes between renders) --- */
 		{
 			FlatScene flat(scene);
-			check(mtsgpu_group_upload_scene(group, &flat.sc));
+			check(flat.upload(group));
 			check(flat.setVertexColors(group));
 			check(flat.setUvTextures(group));
 		}

@@ -40,6 +40,8 @@ EXPORTS = [
     "mtsgpu_flat_scene_shape_has_colors", "mtsgpu_loaded_mesh_colors", "mtsgpu_vertex_color_eval", "mtsgpu_bsdf_eval_colored",
     "mtsgpu_set_uv_textures", "mtsgpu_group_set_uv_textures", "mtsgpu_flat_scene_set_mesh_texcoords", "mtsgpu_flat_scene_vertex_texcoords",
     "mtsgpu_flat_scene_shape_has_texcoords", "mtsgpu_loaded_mesh_texcoords", "mtsgpu_uv_texture_eval", "mtsgpu_bsdf_eval_slots",
+    "mtsgpu_flatten_tangents", "mtsgpu_flat_scene_vertex_tangents", "mtsgpu_flat_scene_shape_has_tangents", "mtsgpu_upload_scene_tangents",
+    "mtsgpu_group_upload_scene_tangents", "mtsgpu_shading_frame_eval",
 ]
 
 
@@ -215,6 +217,12 @@ def lib():
     L.mtsgpu_loaded_mesh_texcoords.argtypes = [vp]; L.mtsgpu_loaded_mesh_texcoords.restype = f32p
     L.mtsgpu_uv_texture_eval.argtypes = [vp, texp, C.c_uint32, u32p, f32p, f32p]
     L.mtsgpu_bsdf_eval_slots.argtypes = [vp, C.c_uint32, f32p, abi.i32p, f32p, f32p, C.c_int, C.c_uint32, f32p, f32p]
+    L.mtsgpu_flatten_tangents.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.KdParams), C.POINTER(f32p), C.POINTER(vp)]
+    L.mtsgpu_flat_scene_vertex_tangents.argtypes = [vp]; L.mtsgpu_flat_scene_vertex_tangents.restype = f32p
+    L.mtsgpu_flat_scene_shape_has_tangents.argtypes = [vp]; L.mtsgpu_flat_scene_shape_has_tangents.restype = u32p
+    L.mtsgpu_upload_scene_tangents.argtypes = [vp, C.POINTER(abi.Scene), f32p, u32p]
+    L.mtsgpu_group_upload_scene_tangents.argtypes = [vp, C.POINTER(abi.Scene), f32p, u32p]
+    L.mtsgpu_shading_frame_eval.argtypes = [vp, C.c_uint32, u32p, f32p, f32p]
     _lib = L
     return L
 
@@ -242,7 +250,18 @@ class Scene:
         self._h = C.c_void_p()
         kp = kd_params if kd_params is not None else abi.KdParams()
         kp.gpu_binning = (kp.gpu_binning & ~3) | (1 if gpu_binning else 0) | (2 if gpu_exact else 0)
-        rc = lib().mtsgpu_flatten(C.byref(self._desc), C.byref(kp), C.byref(self._h))
+        # the _tangents calls only when a mesh with texcoords has an anisotropic BSDF (TriMesh::configure asks for tangents
+        # then, trimesh.cpp:288-290); every other scene goes through the calls it always went through
+        self.wants_tangents = any(m.shape_type == abi.SHAPE_TRIMESH and getattr(m, "texcoords", None) is not None and m.bsdf >= 0
+                                  and description.bsdf_is_anisotropic(m.bsdf) for m in description.meshes)
+        if self.wants_tangents:
+            tcs = (abi.f32p * max(len(description.meshes), 1))()
+            for i, m in enumerate(description.meshes):
+                if m.shape_type == abi.SHAPE_TRIMESH and getattr(m, "texcoords", None) is not None:
+                    tcs[i] = abi.ptr(m.texcoords, abi.f32p)
+            rc = lib().mtsgpu_flatten_tangents(C.byref(self._desc), C.byref(kp), tcs, C.byref(self._h))
+        else:
+            rc = lib().mtsgpu_flatten(C.byref(self._desc), C.byref(kp), C.byref(self._h))
         if rc != 0:
             raise MtsGpuError("mtsgpu_flatten: %s" % lib().mtsgpu_last_error(None).decode())
         self.ptr = lib().mtsgpu_flat_scene_get(self._h)
@@ -285,6 +304,25 @@ class Scene:
         uv = lib().mtsgpu_flat_scene_vertex_texcoords(self._h)
         has = lib().mtsgpu_flat_scene_shape_has_texcoords(self._h)
         return (uv if uv else None, has if has else None, len(self.textures), self.textures, abi.ptr(self.bsdf_slot_texture, abi.i32p))
+
+    def vertex_tangents(self):
+        """(pool [n_verts][6] float32 = dpdu, dpdv; flags [n_shapes] uint32) of the flat scene, or (None, None) when no mesh has
+        tangents (mtsgpu_flat_scene_vertex_tangents)"""
+        tan = lib().mtsgpu_flat_scene_vertex_tangents(self._h)
+        if not tan:
+            return None, None
+        return (abi.np_from(tan, (self.sc.n_verts, 6), np.float32),
+                abi.np_from(lib().mtsgpu_flat_scene_shape_has_tangents(self._h), (self.sc.n_shapes,), np.uint32))
+
+    def tangent_args(self):
+        """what mtsgpu_upload_scene_tangents takes behind the scene: (vtx_dpdu [n_verts][3], shape_has_tangents) arrays, or None
+        when the scene was flattened without the tangents call"""
+        if not self.wants_tangents:
+            return None
+        tan, has = self.vertex_tangents()
+        if tan is None:
+            return (None, None)
+        return (np.ascontiguousarray(tan[:, :3]), np.ascontiguousarray(has))
 
     def vertex_texcoords(self):
         """(pool [n_verts][2] float32, flags [n_shapes] uint32) of the flat scene, or (None, None)"""
@@ -403,7 +441,11 @@ class MIPathTracer:
         """Scene::preprocess -> Integrator::preprocess: upload the flattened scene, camera and sampler."""
         self.configure()
         sp = scene.ptr if isinstance(scene, Scene) else scene
-        self._chk(lib().mtsgpu_upload_scene(self._ctx, sp), "upload_scene")
+        ta = scene.tangent_args() if isinstance(scene, Scene) else None
+        if ta is not None:
+            self._chk(lib().mtsgpu_upload_scene_tangents(self._ctx, sp, abi.ptr(ta[0], abi.f32p), abi.ptr(ta[1], abi.u32p)), "upload_scene_tangents")
+        else:
+            self._chk(lib().mtsgpu_upload_scene(self._ctx, sp), "upload_scene")
         vc = scene.vertex_color_args() if isinstance(scene, Scene) else None
         if vc is not None:
             self._chk(lib().mtsgpu_set_vertex_colors(self._ctx, *vc), "set_vertex_colors")
@@ -616,6 +658,23 @@ class MIPathTracer:
                                                abi.ptr(val, abi.f32p), int(op), n, abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)), "bsdf_eval_slots")
         return out
 
+    def upload_scene_tangents(self, scene, vtx_dpdu=None, shape_has_tangents=None):
+        """mtsgpu_upload_scene_tangents with explicit arrays: vtx_dpdu [n_verts][3], shape_has_tangents [n_shapes] (both None =
+        none); clears vertex colours and uv textures like every upload"""
+        sp = scene.ptr if isinstance(scene, Scene) else scene
+        a = None if vtx_dpdu is None else np.ascontiguousarray(vtx_dpdu, dtype=np.float32)
+        b = None if shape_has_tangents is None else np.ascontiguousarray(shape_has_tangents, dtype=np.uint32)
+        self._chk(lib().mtsgpu_upload_scene_tangents(self._ctx, sp, abi.ptr(a, abi.f32p), abi.ptr(b, abi.u32p)), "upload_scene_tangents")
+
+    def shading_frame_eval(self, prim, rec):
+        """the shading frame on the device for records (primitive, (u, v, -) | world point) of the uploaded scene
+        (mtsgpu_shading_frame_eval) -> [n][9] = s, t, n"""
+        p = np.ascontiguousarray(prim, dtype=np.uint32).reshape(-1)
+        q = np.ascontiguousarray(rec, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((len(p), 9), dtype=np.float32)
+        self._chk(lib().mtsgpu_shading_frame_eval(self._ctx, len(p), abi.ptr(p, abi.u32p), abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)), "shading_frame_eval")
+        return out
+
     def vertex_color_eval(self, prim, uv):
         """its.color on the device for records (primitive, u, v) of the uploaded scene (mtsgpu_vertex_color_eval) -> [n][3]"""
         p = np.ascontiguousarray(prim, dtype=np.uint32).reshape(-1)
@@ -706,7 +765,11 @@ class DeviceGroup:
     def preprocess(self, scene, camera, sampler="independent", sampleCount=4, depth=3, seed=0x5EED):
         sp = scene.ptr if isinstance(scene, Scene) else scene
         self._chk(lib().mtsgpu_group_set_integrator(self._g, self.maxDepth, self.rrDepth, int(self.strictNormals)), "set_integrator")
-        self._chk(lib().mtsgpu_group_upload_scene(self._g, sp), "upload_scene")
+        ta = scene.tangent_args() if isinstance(scene, Scene) else None
+        if ta is not None:
+            self._chk(lib().mtsgpu_group_upload_scene_tangents(self._g, sp, abi.ptr(ta[0], abi.f32p), abi.ptr(ta[1], abi.u32p)), "upload_scene_tangents")
+        else:
+            self._chk(lib().mtsgpu_group_upload_scene(self._g, sp), "upload_scene")
         vc = scene.vertex_color_args() if isinstance(scene, Scene) else None
         if vc is not None:
             self._chk(lib().mtsgpu_group_set_vertex_colors(self._g, *vc), "set_vertex_colors")

@@ -342,7 +342,7 @@ int runDirectRounds(mtsgpu_ctx *c, const DConfig &cfg0, uint32_t nPaths, volatil
 		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
 		cfg.dr_mode = mode; cfg.dr_index = index;
 		for (int b = 0; b < (withTerminal ? kNumBins : kNumBsdfTypes); ++b)
-			launch_shade(s, b, c->dsc, c->paths, cfg, c->q, views[b], nullptr, 0, nullptr, c->dcol, c->dtex);
+			launch_shade(s, b, c->dsc, c->paths, cfg, c->q, views[b], nullptr, 0, nullptr, c->dcol, c->dtex, c->dtan);
 		if (sev) HIPCHK(c, hipEventRecord(sev[1], s));
 		HIPCHK(c, hipGetLastError());
 		return readCounters(c);
@@ -372,7 +372,7 @@ int runDirectRounds(mtsgpu_ctx *c, const DConfig &cfg0, uint32_t nPaths, volatil
 		hipEvent_t *sev = c->timeKernels ? nextEventPair(c, c->shadeEvents, c->shadeEvUsed) : nullptr;
 		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
 		cfg.dr_mode = 3; cfg.dr_index = j;
-		launch_shade(s, kNumBsdfTypes, c->dsc, c->paths, cfg, c->q, tail, nullptr, 0, c->queueB, c->dcol, c->dtex);
+		launch_shade(s, kNumBsdfTypes, c->dsc, c->paths, cfg, c->q, tail, nullptr, 0, c->queueB, c->dcol, c->dtex, c->dtan);
 		if (sev) HIPCHK(c, hipEventRecord(sev[1], s));
 		HIPCHK(c, hipGetLastError());
 	}
@@ -442,17 +442,17 @@ int runBouncesDevice(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatil
 			rc = timed(c->shadeEvents, c->shadeEvUsed, s1, 0); if (rc) return rc;
 			launch_prep(s1, set, prev, c->viewsDev, c->q.bin_seg_cap, c->devStats);
 			if (cfg.dr_mode == 0 && tuningOr(c, "shade_fused", 1) != 0) {
-				launch_shade_all(s1, c->dsc, c->paths, cfg, c->q, c->viewsDev, c->binMask & kShadeAllBins, upper, c->dcol, c->dtex);
+				launch_shade_all(s1, c->dsc, c->paths, cfg, c->q, c->viewsDev, c->binMask & kShadeAllBins, upper, c->dcol, c->dtex, c->dtan);
 				// the bins the fused kernel leaves out (the composite), one launch each, only when the scene has them
 				BinView none{};
 				for (int bin = 0; bin < kNumBins; ++bin)
 					if (c->binMask & ~kShadeAllBins & (1u << bin))
-						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper, nullptr, c->dcol, c->dtex);
+						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper, nullptr, c->dcol, c->dtex, c->dtan);
 			} else {
 				BinView none{};
 				for (int bin = 0; bin < kNumBins; ++bin)
 					if (c->binMask & (1u << bin))
-						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper, nullptr, c->dcol, c->dtex);
+						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper, nullptr, c->dcol, c->dtex, c->dtan);
 			}
 			rc = timed(c->shadeEvents, c->shadeEvUsed, s1, 1); if (rc) return rc;
 			HIPCHK(c, hipGetLastError());
@@ -530,7 +530,7 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 		hipEvent_t *sev = c->timeKernels ? nextEventPair(c, c->shadeEvents, c->shadeEvUsed) : nullptr;
 		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
 		for (int bin = 0; bin < kNumBins; ++bin)
-			launch_shade(s, bin, c->dsc, c->paths, cfg, c->q, views[bin], nullptr, 0, nullptr, c->dcol, c->dtex);
+			launch_shade(s, bin, c->dsc, c->paths, cfg, c->q, views[bin], nullptr, 0, nullptr, c->dcol, c->dtex, c->dtan);
 		if (sev) HIPCHK(c, hipEventRecord(sev[1], s));
 		HIPCHK(c, hipGetLastError());
 		rc = readCounters(c); if (rc) return rc;
@@ -726,7 +726,8 @@ int mtsgpu_set_stream(mtsgpu_ctx *c, void *hip_stream) {
 	return 0;
 }
 
-int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
+// mtsgpu_upload_scene (vtx_dpdu = shape_has_tangents = NULL, withTangents = false) and mtsgpu_upload_scene_tangents
+static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_dpdu, const uint32_t *shape_has_tangents, bool withTangents) {
 	if (!c || !sc) return fail(c, MTSGPU_EINVAL, "null argument");
 	c->lastPass.valid = false;
 	if (sc->abi_version != MTSGPU_ABI_VERSION) return fail(c, MTSGPU_EINVAL, "scene ABI version %u != %d", sc->abi_version, MTSGPU_ABI_VERSION);
@@ -804,10 +805,41 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 	{
 		const std::string why = checkBsdfTable(sc->n_bsdfs, sc->bsdf_type, sc->bsdf_params);
 		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
-		// an anisotropic BSDF needs a tangent frame: spheres have one (dpdu / dpdv), triangle meshes carry no texture coordinates
-		for (uint32_t s = 0; s < sc->n_shapes; ++s)
-			if (sc->shape_bsdf[s] >= 0 && !shapeHasTangentFrame(shapeType(s)) && bsdfIsAnisotropic(sc->bsdf_type, sc->bsdf_params, (uint32_t) sc->shape_bsdf[s]))
+		// an anisotropic BSDF needs a tangent frame: spheres have one (dpdu / dpdv), a triangle mesh when the caller hands its
+		// vertex tangents over.  Without them the reference renders a mesh that has no vertex normals with the frame it has
+		// (trimesh.cpp:562-565); mtsgpu_upload_scene keeps refusing every such mesh
+		for (uint32_t s = 0; s < sc->n_shapes; ++s) {
+			const bool has = shape_has_tangents && shape_has_tangents[s];
+			if (has && shapeType(s) != MTSGPU_SHAPE_TRIMESH) return fail(c, MTSGPU_EINVAL, "shape %u: only a triangle mesh can carry tangents", s);
+			if (has && !(sc->shape_flags[s] & MTSGPU_SHAPE_HAS_NORMALS)) return fail(c, MTSGPU_EINVAL, "shape %u: tangents need vertex normals (trimesh.cpp:562-565)", s);
+			if (has || !(sc->shape_bsdf[s] >= 0 && !shapeHasTangentFrame(shapeType(s)) && bsdfIsAnisotropic(sc->bsdf_type, sc->bsdf_params, (uint32_t) sc->shape_bsdf[s])))
+				continue;
+			if (!withTangents || (sc->shape_flags[s] & MTSGPU_SHAPE_HAS_NORMALS))
 				return fail(c, MTSGPU_EINVAL, "%s", anisotropicOnMeshMessage(s).c_str());
+		}
+	}
+	// the gather array of the tangents: dpdu of the three vertices of every primitive of a mesh that has them, zero elsewhere
+	std::vector<float> triDpdu;
+	std::vector<uint32_t> hasTan;
+	{
+		bool any = false;
+		for (uint32_t s = 0; s < sc->n_shapes; ++s) any |= shape_has_tangents && shape_has_tangents[s];
+		if (any) {
+			const size_t DS = 4 * (size_t) kTriDpduStride;
+			triDpdu.assign(DS * ((size_t) sc->n_tris + 1), 0.0f);
+			hasTan.assign((size_t) sc->n_shapes + 1, 0u);
+			for (uint32_t s = 0; s < sc->n_shapes; ++s) {
+				if (!shape_has_tangents[s]) continue;
+				hasTan[s] = 1u;
+				for (uint32_t t = sc->shape_tri_offset[s]; t < sc->shape_tri_offset[s + 1]; ++t)
+					for (int k = 0; k < 3; ++k) {
+						const float *d = vtx_dpdu + 3 * (size_t) sc->tri_idx[3 * (size_t) t + k];      // the index was checked above
+						if (!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2]))
+							return fail(c, MTSGPU_EINVAL, "shape %u: non-finite tangent at vertex %u", s, sc->tri_idx[3 * (size_t) t + k]);
+						std::memcpy(&triDpdu[DS * (size_t) t + 4 * (size_t) k], d, 12);
+					}
+			}
+		}
 	}
 	float skyDerived[MTSGPU_SKY_NDERIVED] = { 0 };      // SkyLuminaire::configure() of the background sky, filled by its check
 	for (uint32_t l = 0; l < sc->n_lums; ++l) {
@@ -845,6 +877,7 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 	freeAll(c->texAllocs);        // ... and without uv textures (mtsgpu_set_uv_textures)
 	c->dtex = DTextures{ nullptr, nullptr, nullptr };
 	c->hostSlotTex.clear();
+	c->dtan = DTangents{ nullptr, nullptr };      // ... and its tangents go with the scene's arrays
 	c->haveScene = false;
 	DScene d{};
 	int rc = 0;
@@ -985,7 +1018,13 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 		// what SkyLuminaire::configure() derives (sky.cpp:139-179), once per scene
 		rc |= upload(c, (const float **) &d.sky, (const float *) skyDerived, (size_t) MTSGPU_SKY_NDERIVED);
 	}
+	const float *dDpdu = nullptr; const uint32_t *dHasTan = nullptr;
+	if (!triDpdu.empty()) {
+		rc |= upload(c, &dDpdu, triDpdu.data(), triDpdu.size());
+		rc |= upload(c, &dHasTan, hasTan.data(), hasTan.size());
+	}
 	if (rc) { freeAll(c->sceneAllocs); return rc; }
+	c->dtan = DTangents{ reinterpret_cast<const float4 *>(dDpdu), dHasTan };
 	d.lum_sel_sum = sc->lum_sel_sum; d.background_lum = sc->background_lum;
 	d.has_shapes = 0;
 	for (uint32_t s = 0; s < sc->n_shapes; ++s) if (shapeType(s) != MTSGPU_SHAPE_TRIMESH) d.has_shapes = 1;
@@ -1009,6 +1048,14 @@ int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) {
 		if (sc->shape_bsdf[sIdx] >= 0) c->binMask |= 1u << (sc->bsdf_type[sc->shape_bsdf[sIdx]] & 0xFFu);
 	c->haveScene = true;
 	return 0;
+}
+
+int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) { return uploadScene(c, sc, nullptr, nullptr, false); }
+
+int mtsgpu_upload_scene_tangents(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_dpdu, const uint32_t *shape_has_tangents) {
+	if ((vtx_dpdu == nullptr) != (shape_has_tangents == nullptr))
+		return fail(c, MTSGPU_EINVAL, "vtx_dpdu and shape_has_tangents must both be given or both be NULL");
+	return uploadScene(c, sc, vtx_dpdu, shape_has_tangents, true);
 }
 
 // the slot tables of the host (host.h) and of the kernels (kernels.h) are one table
@@ -1965,6 +2012,42 @@ int mtsgpu_uv_texture_eval(mtsgpu_ctx *c, const mtsgpu_uv_texture *tex, uint32_t
 	return 0;
 }
 
+int mtsgpu_shading_frame_eval(mtsgpu_ctx *c, uint32_t n, const uint32_t *prim, const float *rec, float *out) {
+	if (!c || !prim || !rec || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_shading_frame_eval before mtsgpu_upload_scene");
+	if (n > (1u << 24)) return fail(c, MTSGPU_EINVAL, "at most 2^24 query records per call");
+	for (uint32_t i = 0; i < n; ++i)      // the kernel indexes tri_pos and tri_dpdu with it
+		if (prim[i] >= c->nTris) return fail(c, MTSGPU_EINVAL, "record %u: primitive %u out of range", i, prim[i]);
+	if (n == 0) return 0;
+	HIPCHK(c, hipSetDevice(c->device));
+	uint32_t *dP = nullptr, *dZero = nullptr; float *dRec = nullptr, *dOut = nullptr;
+	hipError_t e = hipMalloc((void **) &dP, (size_t) n * sizeof(uint32_t));
+	if (e == hipSuccess) e = hipMalloc((void **) &dRec, (size_t) n * 3 * sizeof(float));
+	if (e == hipSuccess) e = hipMalloc((void **) &dOut, (size_t) n * 9 * sizeof(float));
+	DTangents tan = c->dtan;
+	if (e == hipSuccess && !tan.shape_has_tan) {
+		// no tangents uploaded: every shape reads a zero flag, and tri_dpdu is never touched
+		const size_t bytes = sizeof(uint32_t) * ((size_t) c->host.shapeBsdf.size() + 1);
+		e = hipMalloc((void **) &dZero, bytes);
+		if (e == hipSuccess) e = hipMemsetAsync(dZero, 0, bytes, c->stream);
+		tan.shape_has_tan = dZero;
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(dP, prim, (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(dRec, rec, (size_t) n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) {
+		launch_shading_frame_eval(c->stream, c->dsc, tan, n, dP, dRec, dOut);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, (size_t) n * 9 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (dP) (void) hipFree(dP);
+	if (dRec) (void) hipFree(dRec);
+	if (dOut) (void) hipFree(dOut);
+	if (dZero) (void) hipFree(dZero);
+	if (e != hipSuccess) return fail(c, MTSGPU_EHIP, "shading-frame read-out failed: %s", hipGetErrorString(e));
+	return 0;
+}
+
 int mtsgpu_sky_configure(const float *block, float *derived) {
 	if (!block || !derived) return fail(nullptr, MTSGPU_EINVAL, "null argument");
 	skyConfigure(block, derived);
@@ -2111,6 +2194,31 @@ int mtsgpu_flatten(const mtsgpu_scene_desc *desc, const mtsgpu_kd_params *kd, mt
 	}
 	return 0;
 }
+
+int mtsgpu_flatten_tangents(const mtsgpu_scene_desc *desc, const mtsgpu_kd_params *kd, const float *const *mesh_texcoords, mtsgpu_flat_scene **out) {
+	if (!desc || !out || !mesh_texcoords) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	*out = nullptr;
+	try {
+		std::unique_ptr<mtsgpu_flat_scene> p(new mtsgpu_flat_scene());
+		flattenScene(*desc, kd, p->fs, mesh_texcoords);
+		for (uint32_t s = 0; s < desc->n_meshes; ++s)
+			if (mesh_texcoords[s] && desc->meshes[s].shape_type == MTSGPU_SHAPE_TRIMESH) {
+				const std::string why = setMeshTexcoords(p->fs, s, mesh_texcoords[s]);
+				if (!why.empty()) throw std::runtime_error(why);
+			}
+		*out = p.release();
+	} catch (const std::exception &e) {
+		return fail(nullptr, MTSGPU_EINVAL, "%s", e.what());
+	}
+	return 0;
+}
+static bool flatSceneHasTangents(const mtsgpu_flat_scene *fs) {
+	if (!fs) return false;
+	for (uint32_t h : fs->fs.shapeHasTan) if (h) return true;
+	return false;
+}
+const float *mtsgpu_flat_scene_vertex_tangents(const mtsgpu_flat_scene *fs) { return flatSceneHasTangents(fs) ? fs->fs.vtxTan.data() : nullptr; }
+const uint32_t *mtsgpu_flat_scene_shape_has_tangents(const mtsgpu_flat_scene *fs) { return flatSceneHasTangents(fs) ? fs->fs.shapeHasTan.data() : nullptr; }
 
 const mtsgpu_scene *mtsgpu_flat_scene_get(const mtsgpu_flat_scene *fs) { return fs ? &fs->fs.sc : nullptr; }
 void mtsgpu_flat_scene_free(mtsgpu_flat_scene *fs) { delete fs; }

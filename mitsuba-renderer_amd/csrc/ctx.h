@@ -39,6 +39,8 @@ struct mtsgpu_ctx {
 	// (empty = none), so that each of the two calls can refuse a slot the other one has taken
 	std::vector<void *> texAllocs;
 	mg::DTextures dtex{ nullptr, nullptr, nullptr };
+	// mtsgpu_upload_scene_tangents: DTangents' arrays, owned with the scene (sceneAllocs); NULL, NULL without a tangent mesh
+	mg::DTangents dtan{ nullptr, nullptr };
 	std::vector<uint32_t> hostColorSlots;
 	std::vector<int32_t> hostSlotTex;
 

@@ -51,6 +51,68 @@ void computeVertexNormals(const float *pos, uint32_t nVerts, const uint32_t *tri
 	}
 }
 
+// TriMesh::computeTangentSpaceBasis past its two early returns (src/librender/trimesh.cpp:567-661), in binary32 and in its
+// operation order: a zero vertex normal becomes (1, 0, 0); per triangle, in triangle order, dpdu / dpdv from the position and
+// texcoord differences with invDet = 1 for a zero determinant, the two recoveries for a zero-length dpdu / dpdv, and the sums
+// at the three vertices; per vertex coordinateSystem(normal) when either sum has squared length 0, otherwise the division
+// by the number of triangles that share the vertex.  tan [nVerts][6] = dpdu, dpdv
+void computeTangentSpaceBasis(const float *pos, float *nrm, const float *uv, uint32_t nVerts, const uint32_t *tris, uint32_t nTris, float *tan) {
+	std::vector<uint32_t> sharers(nVerts, 0u);
+	std::memset(tan, 0, sizeof(float) * 6 * (size_t) nVerts);
+	for (uint32_t v = 0; v < nVerts; ++v)
+		if (isZero(ld3(nrm + 3 * (size_t) v))) st3(nrm + 3 * (size_t) v, V3(1.0f, 0.0f, 0.0f));
+	for (uint32_t t = 0; t < nTris; ++t) {
+		const uint32_t *idx = tris + 3 * (size_t) t;
+		const V3 v0 = ld3(pos + 3 * (size_t) idx[0]), v1 = ld3(pos + 3 * (size_t) idx[1]), v2 = ld3(pos + 3 * (size_t) idx[2]);
+		const float *uv0 = uv + 2 * (size_t) idx[0], *uv1 = uv + 2 * (size_t) idx[1], *uv2 = uv + 2 * (size_t) idx[2];
+		const V3 dP1 = v1 - v0, dP2 = v2 - v0;
+		const float dUV1x = uv1[0] - uv0[0], dUV1y = uv1[1] - uv0[1], dUV2x = uv2[0] - uv0[0], dUV2y = uv2[1] - uv0[1];
+		float invDet = 1.0f;
+		const float determinant = dUV1x * dUV2y - dUV1y * dUV2x;
+		if (determinant != 0)
+			invDet = 1.0f / determinant;
+		V3 dpdu = (dP1 * dUV2y - dP2 * dUV1y) * invDet;
+		V3 dpdv = (dP1 * -dUV2x + dP2 * dUV1x) * invDet;
+		if (length(dpdu) == 0.0f) {
+			V3 n = cross(v1 - v0, v2 - v0);
+			const float len = length(n);
+			if (len != 0) {
+				n = divs(n, len);
+				dpdu = cross(n, dpdv);
+				if (length(dpdu) == 0.0f)
+					coordinateSystem(n, dpdu, dpdv);
+			}
+		}
+		if (length(dpdv) == 0.0f) {
+			V3 n = cross(v1 - v0, v2 - v0);
+			const float len = length(n);
+			if (len != 0) {
+				n = divs(n, len);
+				dpdv = cross(dpdu, n);
+				if (length(dpdv) == 0.0f)
+					coordinateSystem(n, dpdu, dpdv);
+			}
+		}
+		for (int k = 0; k < 3; ++k) {
+			float *d = tan + 6 * (size_t) idx[k];
+			d[0] += dpdu.x; d[1] += dpdu.y; d[2] += dpdu.z;
+			d[3] += dpdv.x; d[4] += dpdv.y; d[5] += dpdv.z;
+			sharers[idx[k]]++;
+		}
+	}
+	for (uint32_t v = 0; v < nVerts; ++v) {
+		float *d = tan + 6 * (size_t) v;
+		V3 dpdu = ld3(d), dpdv = ld3(d + 3);
+		if (dot(dpdu, dpdu) == 0.0f || dot(dpdv, dpdv) == 0.0f) {
+			coordinateSystem(ld3(nrm + 3 * (size_t) v), dpdu, dpdv);
+		} else if (sharers[v] > 0) {
+			dpdu = divs(dpdu, (float) sharers[v]);
+			dpdv = divs(dpdv, (float) sharers[v]);
+		}
+		st3(d, dpdu); st3(d + 3, dpdv);
+	}
+}
+
 // DiscretePDF::build (include/mitsuba/core/pdf.h:82-95)
 float buildCdf(const std::vector<float> &values, float *cdf, float *pdf) {
 	const size_t n = values.size();
@@ -102,7 +164,7 @@ std::string setMeshTexcoords(FlatScene &f, uint32_t mesh, const float *texcoords
 	return std::string();
 }
 
-void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs) {
+void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs, const float *const *meshTexcoords) {
 	const uint32_t nShapes = d.n_meshes, nLums = d.n_lums;
 	size_t nVerts = 0, nTris = 0;
 	// m_shapeMap (skdtree.cpp:43-60): a TriMesh contributes its triangles, any other shape ONE primitive
@@ -124,6 +186,7 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 	fs.shapeVtxOffset.assign(nShapes + 1, 0u);
 	fs.vtxCol.clear(); fs.shapeHasColors.clear();
 	fs.vtxUv.clear(); fs.shapeHasUv.clear();
+	fs.vtxTan.clear(); fs.shapeHasTan.clear();
 	fs.shapeFlags.assign(nShapes + 1, 0u);
 	fs.shapeBsdf.assign(nShapes + 1, -1);
 	fs.shapeLum.assign(nShapes + 1, -1);
@@ -153,7 +216,11 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 		fs.shapeTriOffset[s] = tbase;
 		fs.shapeVtxOffset[s] = vbase;
 		fs.shapeBsdf[s] = m.bsdf;
-		if (m.bsdf >= 0 && !shapeHasTangentFrame((uint32_t) m.shape_type) && bsdfIsAnisotropic(d.bsdf_type, d.bsdf_params, (uint32_t) m.bsdf))
+		// TriMesh::configure (trimesh.cpp:288-290) asks for tangents when the BSDF is anisotropic; they need texcoords, which
+		// only mtsgpu_flatten_tangents knows at this point
+		const bool anisoMesh = m.bsdf >= 0 && !shapeHasTangentFrame((uint32_t) m.shape_type) && bsdfIsAnisotropic(d.bsdf_type, d.bsdf_params, (uint32_t) m.bsdf);
+		const float *texcoords = (meshTexcoords && m.shape_type == MTSGPU_SHAPE_TRIMESH) ? meshTexcoords[s] : nullptr;
+		if (anisoMesh && !texcoords)
 			throw std::runtime_error("flatten: " + anisotropicOnMeshMessage(s));
 		fs.shapeLum[s] = m.lum;
 		if (m.lum >= 0) {
@@ -190,6 +257,17 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 			if (m.triangles[k] >= m.n_verts)
 				throw std::runtime_error("flatten: triangle index out of range");
 			fs.triIdx[3 * (size_t) tbase + k] = m.triangles[k] + vbase;
+		}
+		if (anisoMesh && !m.face_normals) {
+			// without vertex normals the reference warns and leaves the mesh the frame it has (trimesh.cpp:562-565)
+			for (size_t k = 0; k < 2 * (size_t) m.n_verts; ++k)
+				if (!std::isfinite(texcoords[k])) throw std::runtime_error("flatten: non-finite texture coordinate");
+			if (fs.vtxTan.empty()) {
+				fs.vtxTan.assign(6 * nVerts + 6, 0.0f);
+				fs.shapeHasTan.assign((size_t) nShapes + 1, 0u);
+			}
+			computeTangentSpaceBasis(m.positions, &fs.vtxNrm[3 * (size_t) vbase], texcoords, m.n_verts, m.triangles, m.n_tris, &fs.vtxTan[6 * (size_t) vbase]);
+			fs.shapeHasTan[s] = 1u;
 		}
 		vbase += m.n_verts; tbase += m.n_tris;
 	}

@@ -37,6 +37,10 @@ struct FlatScene {
 	// texture coordinates (mtsgpu_flat_scene_set_mesh_texcoords): the pool [n_verts][2] and the flags, kept like the colours
 	std::vector<float> vtxUv;
 	std::vector<uint32_t> shapeHasUv;
+	// tangents (mtsgpu_flatten_tangents): the pool [n_verts][6] = dpdu, dpdv and one flag per shape, both empty unless a mesh
+	// with texcoords has an anisotropic BSDF (TriMesh::computeTangentSpaceBasis)
+	std::vector<float> vtxTan;
+	std::vector<uint32_t> shapeHasTan;
 };
 
 // Texture-typed spectrum slots per BSDF type, in slot order (include/mtsgpu.h): the first float of each slot's three in the
@@ -144,14 +148,15 @@ inline bool bsdfIsAnisotropic(const uint32_t *type, const float *params, uint32_
 	}
 	return false;
 }
-// Shapes that give the shading frame a tangent an anisotropic BSDF can use: spheres (dpdu / dpdv).  Triangle meshes carry no
-// texture coordinates here, and any shape type added later has none until it says so here.
+// Shapes that give the shading frame a tangent an anisotropic BSDF can use on their own: spheres (dpdu / dpdv).  A triangle
+// mesh has one when tangents were computed from its texture coordinates (mtsgpu_flatten_tangents,
+// mtsgpu_upload_scene_tangents); any shape type added later has none until it says so here.
 inline bool shapeHasTangentFrame(uint32_t shape_type) { return shape_type == MTSGPU_SHAPE_SPHERE; }
 // the reference's refusal of an anisotropic BSDF on a mesh without texture coordinates (trimesh.cpp:288-290, :547-556)
 inline std::string anisotropicOnMeshMessage(uint32_t shape) {
 	return "shape " + std::to_string(shape) + ": computeTangentSpace(): texture coordinates are required to generate tangent vectors. "
 	       "If you want to render with an anisotropic material, please make sure that all associated shapes have valid texture "
-	       "coordinates (triangle meshes have none here: an anisotropic Ward BSDF needs a sphere)";
+	       "coordinates (a triangle mesh has none here unless mtsgpu_flatten_tangents / mtsgpu_upload_scene_tangents supplied them)";
 }
 
 // SkyLuminaire::configure() (src/luminaires/sky.cpp:139-179) and the parts of getDistribution() that depend on the
@@ -222,7 +227,9 @@ inline std::string checkSkyLuminaire(uint32_t l, const float *LP, int32_t backgr
 	return std::string();
 }
 
-void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs);
+// meshTexcoords [n_meshes] (mtsgpu_flatten_tangents): the texcoords [that mesh's n_verts][2] of each mesh or NULL; with them a
+// mesh whose BSDF is anisotropic is accepted and receives tangents (fs.vtxTan, fs.shapeHasTan).  NULL: no mesh has any.
+void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs, const float *const *meshTexcoords = nullptr);
 // The per-vertex colours of shape `mesh` of a flattened scene (mtsgpu_flat_scene_set_mesh_colors): colors [that mesh's
 // n_verts][3] copied into fs.vtxCol at the mesh's rows, NULL takes them away again.  Returns the reason it refuses, or an
 // empty string.

@@ -154,6 +154,16 @@ struct DTextures {
 };
 constexpr uint32_t kTexCheckerboard = 0, kTexGrid = 1;      // DTexture::kind = MTSGPU_TEX_*
 constexpr int kTriUvStride = 2;       // float4 per primitive of DTextures::tri_uv
+// The vertex tangents of the meshes whose BSDF is anisotropic (mtsgpu_upload_scene_tangents), both NULL without such a mesh.
+// Like DColors and DTextures an argument of kernels of its own (k_shade_tan, k_shade_all_tan) only.  tri_dpdu: a gather array
+// in primitive order, kTriDpduStride float4 per primitive = d0.xyz - | d1.xyz - | d2.xyz - (48 bytes, three aligned 16-byte
+// loads; zero for every primitive of a shape without tangents).  shape_has_tan[n_shapes]: non-zero for the meshes whose hits
+// take the frame of skdtree.h:392-399 (fill_its_tan); the shading launches pick the tangent kernels by tri_dpdu != NULL
+struct DTangents {
+	const float4   *tri_dpdu;
+	const uint32_t *shape_has_tan;
+};
+constexpr int kTriDpduStride = 3;     // float4 per primitive of DTangents::tri_dpdu
 // what a texture slot of a BSDF takes at a hit (bsdf_block_with_slots)
 enum : int { kSlotBlock = 0, kSlotColor = 1, kSlotTexture = 2 };
 
@@ -381,6 +391,9 @@ void launch_bsdf_eval_slots(hipStream_t s, uint32_t type, const float *params, c
 // (u, v, -) on a triangle, the world-space hit point on a sphere; out [n][5] = uv, rgb
 void launch_uv_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, uint32_t n, const uint32_t *prim,
                             const float *rec, float *out);
+// mtsgpu_shading_frame_eval: the shading frame of fill_its_tan for n records of the uploaded scene; rec as for
+// launch_uv_texture_eval; tan.shape_has_tan must be readable (all zero without tangents); out [n][9] = s, t, n
+void launch_shading_frame_eval(hipStream_t s, const DScene &sc, const DTangents &tan, uint32_t n, const uint32_t *prim, const float *rec, float *out);
 // the sky luminaire (mtsgpu_lum_eval): Le (op 0), sample (1), pdf (2) for n query records [n][6]; block = the parameter
 // block followed by its derived array, in device memory; out [n][12]
 void launch_sky_eval(hipStream_t s, const float *block, int op, uint32_t n, const float *queries, float *out);
@@ -402,12 +415,12 @@ struct BinView { uint32_t prefix[kBinShards + 1]; };
 void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                   const DQueues &q, const BinView &view, const BinView *views_dev = nullptr, uint32_t n_bound = 0,
                   const uint32_t *bin_ids = nullptr, const DColors &col = DColors{ nullptr, nullptr },
-                  const DTextures &tex = DTextures{ nullptr, nullptr, nullptr });
+                  const DTextures &tex = DTextures{ nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr });
 // device-driven bounces, path integrator / one-sample direct integrator: all bins of bin_mask in one launch; views_dev as
 // above, n_bound bounds the sum of the bin sizes
 void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,
                       const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound, const DColors &col = DColors{ nullptr, nullptr },
-                      const DTextures &tex = DTextures{ nullptr, nullptr, nullptr });
+                      const DTextures &tex = DTextures{ nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr });
 // device-driven bounces: per-bin views from the shard counters of the closest-hit launch that just ran (`cur`), and
 // the counter set of the next bounce zeroed
 void launch_prep(hipStream_t s, const uint32_t *cur, uint32_t *next_set, BinView *views_dev, uint32_t bin_seg_cap,

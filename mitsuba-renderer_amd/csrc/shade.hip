@@ -73,6 +73,26 @@ __device__ __forceinline__ void fill_its(const DScene &sc, V3 rayO, V3 rayD, flo
 	its.wi = V3(dot(md, its.shS), dot(md, its.shT), dot(md, its.shN));
 }
 
+// The intersection record of scenes with a tangent mesh (DTangents): fill_its, and on a mesh that has tangents the shading
+// frame of skdtree.h:392-399 in its operation order -- dpdu = (t0.dpdu * b.x + t1.dpdu * b.y) + t2.dpdu * b.z from the three
+// vertex tangents of the primitive (DTangents::tri_dpdu), n the normalised interpolated normal fill_its has left in its.shN,
+// s = normalize(dpdu - n * dot(n, dpdu)), t = cross(n, s) -- and its.wi in that frame.  Every other shape (spheres, meshes
+// without tangents) keeps what fill_its wrote.  The shading kernels and the read-out hook (k_shading_frame_eval) both call this.
+__device__ __forceinline__ void fill_its_tan(const DScene &sc, const DTangents &tan, V3 rayO, V3 rayD, float t, uint32_t prim, float u, float v,
+                                             const float4 t0, const float4 t1, const float4 t2, Its &its) {
+	fill_its(sc, rayO, rayD, t, prim, u, v, t0, t1, t2, its);
+	if (!tan.shape_has_tan[its.shape]) return;
+	const float4 *TD = tan.tri_dpdu + kTriDpduStride * (size_t) prim;
+	const float4 d0 = TD[0], d1 = TD[1], d2 = TD[2];
+	const float bx = 1 - u - v, by = u, bz = v;
+	const V3 dpdu(d0.x * bx + d1.x * by + d2.x * bz, d0.y * bx + d1.y * by + d2.y * bz, d0.z * bx + d1.z * by + d2.z * bz);
+	const V3 n = its.shN;
+	its.shS = normalize(dpdu - n * dot(n, dpdu));
+	its.shT = cross(n, its.shS);
+	const V3 md = -rayD;
+	its.wi = V3(dot(md, its.shS), dot(md, its.shT), dot(md, its.shN));
+}
+
 // its.color of fillIntersectionRecord (skdtree.h:364,417-421): the three vertex colours of the primitive (DColors::tri_col)
 // weighted with b = ((1 - u) - v, u, v), in the reference's operation order: (c0 * b.x + c1 * b.y) + c2 * b.z per channel
 __device__ __forceinline__ V3 its_color(const float4 *tri_col, uint32_t prim, float u, float v) {
@@ -1294,6 +1314,21 @@ __global__ void k_uv_texture_eval(DScene sc, const float4 *tri_uv, DTexture tex,
 	o[0] = uvx; o[1] = uvy; o[2] = c.x; o[3] = c.y; o[4] = c.z;
 }
 
+// mtsgpu_shading_frame_eval: the shading frame fill_its_tan leaves for n records; the host has checked prim < n_tris.  rec =
+// (u, v, -) on a triangle, the world-space hit point on a sphere (then the ray starts there with t = 0)
+__global__ void k_shading_frame_eval(DScene sc, DTangents tan, uint32_t n, const uint32_t *prim, const float *rec, float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float4 *TP = sc.tri_pos + kTriStride * (size_t) prim[i];
+	const float *r = rec + 3 * (size_t) i;
+	Its its;
+	fill_its_tan(sc, tan, V3(r[0], r[1], r[2]), V3(0.0f, 0.0f, 1.0f), 0.0f, prim[i], r[0], r[1], TP[0], TP[1], TP[2], its);
+	float *o = out + 9 * (size_t) i;
+	o[0] = its.shS.x; o[1] = its.shS.y; o[2] = its.shS.z;
+	o[3] = its.shT.x; o[4] = its.shT.y; o[5] = its.shT.z;
+	o[6] = its.shN.x; o[7] = its.shN.y; o[8] = its.shN.z;
+}
+
 // The sky luminaire read out for n query records (mtsgpu_lum_eval): block = its parameters followed by the derived array
 // (kLumStride + MTSGPU_SKY_NDERIVED floats in device memory); queries [n][6], out [n][12]
 __global__ void k_sky_eval(const float *block, int op, uint32_t n, const float *queries, float *out) {
@@ -1353,12 +1388,13 @@ __device__ __forceinline__ uint32_t shade_row_index(uint32_t lane, uint32_t k) {
 // VCOL: kSlotColor = the instantiation for scenes with a coloured BSDF slot (DColors::bsdf_color_slots != NULL): the block the
 // BSDF reads is built per hit by bsdf_block_with_color.  kSlotTexture = the one for scenes with a uv-textured slot
 // (DTextures::bsdf_slot_texture != NULL), which serves coloured slots as well: bsdf_block_with_slots.  Every other scene
-// (kSlotBlock) runs the instantiation without that code.
-template <int BT, bool ROUNDS, bool SKY, int VCOL>
+// (kSlotBlock) runs the instantiation without that code.  TAN: the instantiation for scenes with a tangent mesh
+// (DTangents::tri_dpdu != NULL), on top of kSlotTexture: the record comes from fill_its_tan, and the texture table may be NULL.
+template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false>
 __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, const DConfig &cfg, const uint32_t id,
                                            const float4 ro, const float4 rd, const uint4 h, const float4 T4, const float4 L4,
                                            const ShadeRow row, bool &continues, bool &wantShadow, V3 &neeV, V3 &shO, V3 &shD, const DColors &col,
-                                           const DTextures &tex) {
+                                           const DTextures &tex, const DTangents &tan = DTangents{ nullptr, nullptr }) {
 	{
 		// rounds of MIDirectIntegrator (DConfig::dr_mode): later BSDF samples start again from the camera hit
 		const int mode = ROUNDS ? cfg.dr_mode : 0;
@@ -1380,8 +1416,10 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 		}
 		const bool direct = cfg.integrator == 1;
 		Its its;
-		if (valid)
-			fill_its(sc, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
+		if (valid) {
+			if (TAN) fill_its_tan(sc, tan, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
+			else fill_its(sc, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
+		}
 		const int shapeLum = valid ? sc.shape_lum[its.shape] : -1;
 
 		do {
@@ -1463,7 +1501,9 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			if (VCOL == kSlotTexture && BT < 9) {
 				// a checkerboard or grid texture in a slot of this BSDF: that slot holds the texture's value at its.uv; a
 				// `vertexcolors` texture in the other one its.color
-				const int k0 = tex.bsdf_slot_texture[2 * (size_t) bsdfIdx], k1 = tex.bsdf_slot_texture[2 * (size_t) bsdfIdx + 1];
+				// (a scene that is here for its tangents alone has no texture table)
+				const bool noTex = TAN && tex.bsdf_slot_texture == nullptr;
+				const int k0 = noTex ? -1 : tex.bsdf_slot_texture[2 * (size_t) bsdfIdx], k1 = noTex ? -1 : tex.bsdf_slot_texture[2 * (size_t) bsdfIdx + 1];
 				const uint32_t slots = col.bsdf_color_slots ? col.bsdf_color_slots[bsdfIdx] : 0u;
 				float uvx = 0, uvy = 0;
 				if (k0 >= 0 || k1 >= 0)
@@ -1592,10 +1632,10 @@ struct ShadeShared {
 };
 // One workgroup of k_shade: the paths block * kShadeBlock .. of the material queue whose segment sizes are `prefix`
 // (prefix[kBinShards] entries in kBinShards segments of bin_ids)
-template <int BT, bool ROUNDS, bool SKY, int VCOL>
+template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false>
 __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const uint32_t *prefix,
                                             const uint32_t *bin_ids, const uint32_t block, ShadeShared &sh, const DColors &col,
-                                            const DTextures &tex = DTextures{ nullptr, nullptr, nullptr }) {
+                                            const DTextures &tex = DTextures{ nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr }) {
 	uint32_t (&s_cnt)[2][kShadeBlock / 64] = sh.cnt;
 	uint32_t (&s_base)[2] = sh.base;
 	float4 (&s_rows)[kShadeBlock / 64][64 * kRowStride] = sh.rows;
@@ -1680,7 +1720,7 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	}
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	if (active)
-		shade_path<BT, ROUNDS, SKY, VCOL>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col, tex);
+		shade_path<BT, ROUNDS, SKY, VCOL, TAN>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col, tex, tan);
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	#pragma unroll
 	for (int r = 0; r < 8; ++r) {
@@ -1748,6 +1788,14 @@ __global__ MG_SHADE_BOUNDS void k_shade_tex(DScene sc, DPaths ps, DConfig cfg, D
 	__shared__ ShadeShared sh;
 	shade_block<BT, ROUNDS, SKY, kSlotTexture>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col, tex);
 }
+// and for scenes with a tangent mesh (DTangents), built on the texture kernels: the only ones that take the tangents.  Bins
+// 0..9: a composite (bin 9) reads no colours or textures, but its anisotropic Ward child needs the frame
+template <int BT, bool ROUNDS, bool SKY>
+__global__ MG_SHADE_BOUNDS void k_shade_tan(DScene sc, DPaths ps, DConfig cfg, DQueues q, BinView view_host,
+                                                           const BinView *views_dev, const uint32_t *bin_ids, DColors col, DTextures tex, DTangents tan) {
+	__shared__ ShadeShared sh;
+	shade_block<BT, ROUNDS, SKY, kSlotTexture, true>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col, tex, tan);
+}
 
 // All material queues of a bounce in ONE launch (device-driven bounces): the workgroups are dealt to the bins in bin order,
 // ceil(size / kShadeBlock) each, the sizes read from what k_prep left in device memory.  A frame of few paths is a chain of
@@ -1756,9 +1804,10 @@ __global__ MG_SHADE_BOUNDS void k_shade_tex(DScene sc, DPaths ps, DConfig cfg, D
 // SKY: the launch for scenes whose background is a sky (launch_shade_all picks it): every other scene runs the instantiation
 // without that code, whose registers are what they were before the sky existed.  VCOL: likewise for scenes with a coloured
 // BSDF slot; the bins that cannot have one (composite, terminal) run the same code either way
-template <bool SKY, int VCOL>
+template <bool SKY, int VCOL, bool TAN = false>
 __device__ __forceinline__ void shade_all(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const BinView *views_dev, uint32_t bin_mask,
-                                          ShadeShared &sh, const DColors &col, const DTextures &tex = DTextures{ nullptr, nullptr, nullptr }) {
+                                          ShadeShared &sh, const DColors &col, const DTextures &tex = DTextures{ nullptr, nullptr, nullptr },
+                                          const DTangents &tan = DTangents{ nullptr, nullptr }) {
 	uint32_t block = blockIdx.x;
 	int bin = -1;
 	for (int b = 0; b < kNumBins; ++b) {
@@ -1770,15 +1819,15 @@ __device__ __forceinline__ void shade_all(const DScene &sc, const DPaths &ps, co
 	if (bin < 0) return;
 	const uint32_t *prefix = views_dev[bin].prefix, *ids = q.bin(bin);
 	switch (bin) {
-		case 0: shade_block<0, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
-		case 1: shade_block<1, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
-		case 2: shade_block<2, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
-		case 3: shade_block<3, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
-		case 4: shade_block<4, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
-		case 5: shade_block<5, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
-		case 6: shade_block<6, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
-		case 7: shade_block<7, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
-		case 8: shade_block<8, false, SKY, VCOL>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex); break;
+		case 0: shade_block<0, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
+		case 1: shade_block<1, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
+		case 2: shade_block<2, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
+		case 3: shade_block<3, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
+		case 4: shade_block<4, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
+		case 5: shade_block<5, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
+		case 6: shade_block<6, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
+		case 7: shade_block<7, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
+		case 8: shade_block<8, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
 		case 9: return;      // the composite's loop over its children is launched on its own (kShadeAllBins)
 		default: shade_block<kNumBsdfTypes, false, SKY, kSlotBlock>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
 	}
@@ -1798,6 +1847,12 @@ __global__ MG_SHADE_BOUNDS void k_shade_all_tex(DScene sc, DPaths ps, DConfig cf
                                                 DTextures tex) {
 	__shared__ ShadeShared sh;
 	shade_all<SKY, kSlotTexture>(sc, ps, cfg, q, views_dev, bin_mask, sh, col, tex);
+}
+template <bool SKY>
+__global__ MG_SHADE_BOUNDS void k_shade_all_tan(DScene sc, DPaths ps, DConfig cfg, DQueues q, const BinView *views_dev, uint32_t bin_mask, DColors col,
+                                                DTextures tex, DTangents tan) {
+	__shared__ ShadeShared sh;
+	shade_all<SKY, kSlotTexture, true>(sc, ps, cfg, q, views_dev, bin_mask, sh, col, tex, tan);
 }
 
 void launch_bsdf_eval(hipStream_t s, uint32_t type, const float *params, int op, uint32_t n, const float *queries, float *out) {
@@ -1819,8 +1874,19 @@ void launch_sky_eval(hipStream_t s, const float *block, int op, uint32_t n, cons
 // (DColors::bsdf_color_slots; bins 0..8 only -- a composite's children and the terminal bin take no colours)
 template <int BT>
 static void launch_shade_bin(hipStream_t s, const dim3 g, const dim3 b, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,
-                             const BinView &view, const BinView *views_dev, const uint32_t *bin_ids, const DColors &col, const DTextures &tex) {
+                             const BinView &view, const BinView *views_dev, const uint32_t *bin_ids, const DColors &col, const DTextures &tex, const DTangents &tan) {
 	const bool rounds = cfg.dr_mode != 0, sky = sc.sky != nullptr;
+	if constexpr (BT <= 9) {
+		// a scene with a tangent mesh: bins 0..9 (the composite too, for the frame of its children)
+		if (tan.tri_dpdu != nullptr) {
+			#define MG_SHADE(R, S) hipLaunchKernelGGL((k_shade_tan<BT, R, S>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids, col, tex, tan)
+			if (rounds) { if (sky) MG_SHADE(true, true); else MG_SHADE(true, false); }
+			else if (sky) MG_SHADE(false, true);
+			else MG_SHADE(false, false);
+			#undef MG_SHADE
+			return;
+		}
+	}
 	if constexpr (BT < 9) {
 		if (tex.bsdf_slot_texture != nullptr) {
 			#define MG_SHADE(R, S) hipLaunchKernelGGL((k_shade_tex<BT, R, S>), g, b, 0, s, sc, ps, cfg, q, view, views_dev, bin_ids, col, tex)
@@ -1848,12 +1914,12 @@ static void launch_shade_bin(hipStream_t s, const dim3 g, const dim3 b, const DS
 
 void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                   const DQueues &q, const BinView &view, const BinView *views_dev, uint32_t n_bound, const uint32_t *bin_ids, const DColors &col,
-                  const DTextures &tex) {
+                  const DTextures &tex, const DTangents &tan) {
 	const uint32_t n = views_dev ? n_bound : view.prefix[kBinShards];
 	if (!n) return;
 	if (!bin_ids) bin_ids = q.bin(bin);
 	const dim3 g(blocks_for(n, kShadeBlock)), b(kShadeBlock);
-	#define MG_SHADE_BIN(BT) launch_shade_bin<BT>(s, g, b, sc, ps, cfg, q, view, views_dev, bin_ids, col, tex)
+	#define MG_SHADE_BIN(BT) launch_shade_bin<BT>(s, g, b, sc, ps, cfg, q, view, views_dev, bin_ids, col, tex, tan)
 	switch (bin) {
 		case 0: MG_SHADE_BIN(0); break;
 		case 1: MG_SHADE_BIN(1); break;
@@ -1871,13 +1937,17 @@ void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, co
 }
 
 void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,
-                      const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound, const DColors &col, const DTextures &tex) {
+                      const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound, const DColors &col, const DTextures &tex,
+                      const DTangents &tan) {
 	bin_mask &= kShadeAllBins;
 	if (!n_bound || !bin_mask) return;
 	// every bin rounds its size up to whole workgroups
 	const unsigned blocks = blocks_for(n_bound, kShadeBlock) + (unsigned) __builtin_popcount(bin_mask);
 	const dim3 g(blocks), b(kShadeBlock);
-	if (tex.bsdf_slot_texture) {
+	if (tan.tri_dpdu) {
+		if (sc.sky) hipLaunchKernelGGL(k_shade_all_tan<true>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask, col, tex, tan);
+		else hipLaunchKernelGGL(k_shade_all_tan<false>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask, col, tex, tan);
+	} else if (tex.bsdf_slot_texture) {
 		if (sc.sky) hipLaunchKernelGGL(k_shade_all_tex<true>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask, col, tex);
 		else hipLaunchKernelGGL(k_shade_all_tex<false>, g, b, 0, s, sc, ps, cfg, q, views_dev, bin_mask, col, tex);
 	} else if (col.bsdf_color_slots) {
@@ -1908,6 +1978,10 @@ void launch_bsdf_eval_slots(hipStream_t s, uint32_t type, const float *params, c
 void launch_uv_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, uint32_t n, const uint32_t *prim,
                             const float *rec, float *out) {
 	if (n) hipLaunchKernelGGL(k_uv_texture_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, tri_uv, tex, n, prim, rec, out);
+}
+
+void launch_shading_frame_eval(hipStream_t s, const DScene &sc, const DTangents &tan, uint32_t n, const uint32_t *prim, const float *rec, float *out) {
+	if (n) hipLaunchKernelGGL(k_shading_frame_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, tan, n, prim, rec, out);
 }
 
 void launch_vertex_color_eval(hipStream_t s, const float4 *tri_col, uint32_t n, const uint32_t *prim, const float *uv, float *out) {

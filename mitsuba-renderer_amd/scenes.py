@@ -232,6 +232,17 @@ class SceneDescription:
             raise ValueError("a composite holds at most %d children" % abi.COMPOSITE_MAX)
         return self.add_bsdf(abi.BSDF_COMPOSITE, [len(weights)] + weights + children)
 
+    def bsdf_is_anisotropic(self, b):
+        """BSDF::EAnisotropic of block b: a Ward with alphaU != alphaV (ward.cpp:84-85), alone or as a composite's child; the
+        twosided adapter passes its child's type on"""
+        t, P = self.bsdf_type[b] & 0xFF, self.bsdf_params[b]
+        if t == abi.BSDF_WARD:
+            return bool(P[1] != P[2])
+        if t == abi.BSDF_COMPOSITE:
+            n = int(P[0])
+            return any(self.bsdf_is_anisotropic(int(P[1 + n + i])) for i in range(n))
+        return False
+
     def twosided(self, bsdf):
         """wrap an existing BSDF block in the `twosided` adapter (src/bsdfs/twosided.cpp)"""
         self.bsdf_type[bsdf] |= abi.BSDF_TWOSIDED

@@ -69,16 +69,17 @@ def load_serialized(path, shape_index=0, bsdf=-1, lum=-1, name=None):
         lib().mtsgpu_loaded_mesh_free(h)
 
 
-_SOURCES = ["api.cpp", "group.cpp", "sampler.hip", "film.hip", "trace.hip", "shade.hip", "measure.hip",   # SRCS, then HDRS of csrc/Makefile
-            "kdbuild.cpp", "flatten.cpp", "serialized.cpp",
-            "host.h", "ctx.h", "kernels.h", "kdevice.h", "sampler.h", "devmath.h", os.path.join("..", "..", "include", "mtsgpu.h")]
+def sources():
+    """csrc/sources.txt: the hashed inputs of the library in hash order, relative to csrc/ -- the one list that csrc/Makefile,
+    tools/build_variant.sh and tools/kernel_resources.sh read as well"""
+    return open(os.path.join(_HERE, "csrc", "sources.txt")).read().split()
 
 
 def source_hash():
     """the hash csrc/Makefile stamps into the library (csrc/stamp.cpp), recomputed from the sources on disk"""
     import hashlib
     h = hashlib.sha256()
-    for f in _SOURCES:
+    for f in sources():
         h.update(open(os.path.join(_HERE, "csrc", f), "rb").read())
     return h.hexdigest()[:16]
 
@@ -103,18 +104,26 @@ def _probe_hash(lib_path):
     return r.stdout.decode().strip(), None
 
 
+def _make_jobs():
+    """the -j of build(): MAX_JOBS when it is set (16 at the most), otherwise 4"""
+    try:
+        return "-j%d" % max(1, min(16, int(os.environ["MAX_JOBS"])))
+    except (KeyError, ValueError):
+        return "-j4"
+
+
 def build(force=False):
     """Compile libmtsgpu.so for gfx950 (hipcc cross-compiles without a GPU).  make is incremental; a binary whose stamped
     source hash differs from the sources on disk (e.g. a copied-in .so newer than the files) is rebuilt from scratch.  A
     library that cannot be LOADED is reported as such (with the loader's message), not mistaken for a stale one."""
     csrc = os.path.join(_HERE, "csrc")
     lib_path = os.path.join(_HERE, "libmtsgpu.so")          # what csrc/Makefile builds; MTSGPU_LIB variants are built by tools/build_variant.sh
-    subprocess.check_call(["make", "-C", csrc, "-j4"] + (["-B"] if force else []), stdout=subprocess.DEVNULL)
+    subprocess.check_call(["make", "-C", csrc, _make_jobs()] + (["-B"] if force else []), stdout=subprocess.DEVNULL)
     got, why = _probe_hash(lib_path)
     if why is not None:
         raise MtsGpuError("libmtsgpu.so was built but cannot be loaded: %s" % "; ".join(why))
     if got != source_hash():
-        subprocess.check_call(["make", "-C", csrc, "-j4", "-B"], stdout=subprocess.DEVNULL)
+        subprocess.check_call(["make", "-C", csrc, _make_jobs(), "-B"], stdout=subprocess.DEVNULL)
         got, why = _probe_hash(lib_path)
         if why is not None:
             raise MtsGpuError("libmtsgpu.so cannot be loaded after a full rebuild: %s" % "; ".join(why))

@@ -259,6 +259,26 @@ def test_library_is_built_from_the_sources_on_disk(mts):
     assert mts.lib().mtsgpu_source_hash().decode() == mts.source_hash()
 
 
+def test_every_source_of_the_library_is_on_the_one_list(mts):
+    """csrc/sources.txt names what csrc/Makefile compiles and stamps, what source_hash() hashes and what tools/build_variant.sh
+    and tools/kernel_resources.sh build: a file in csrc/ that is missing from it would leave the stale-binary check blind"""
+    csrc = os.path.join(os.path.dirname(os.path.abspath(mts.__file__)), "csrc")
+    listed = mts.sources()
+    assert len(set(listed)) == len(listed)
+    for f in listed:
+        assert os.path.isfile(os.path.join(csrc, f)), f
+    on_disk = {f for f in os.listdir(csrc) if f.endswith((".hip", ".cpp", ".h"))} - {"stamp.cpp"}
+    assert on_disk <= set(listed), sorted(on_disk - set(listed))
+
+
+def test_build_takes_its_job_count_from_max_jobs(mts, monkeypatch):
+    monkeypatch.delenv("MAX_JOBS", raising=False)
+    assert mts._make_jobs() == "-j4"
+    for value, flag in (("16", "-j16"), ("7", "-j7"), ("64", "-j16"), ("0", "-j1"), ("many", "-j4")):
+        monkeypatch.setenv("MAX_JOBS", value)
+        assert mts._make_jobs() == flag
+
+
 REFERENCE_INCLUDE = "/root/reference/include"
 
 

@@ -492,7 +492,8 @@ int  mtsgpu_gather_roof(int device, size_t footprint_bytes, double *lane_request
  *      with the closest-hit kernel in the plain 64-ray batches of a first bounce;
  *   2  every stride-th slot of the shadow queue as the frame left it (slot i holds the ray of the deepest bounce that
  *      queued more than i shadow rays; host-driven passes only), moved to the front of the queue, with the any-hit
- *      kernel (which adds the rays' pending terms to the dead path records).
+ *      kernel as the bounces launch it (direct-light terms parked in the path records: it clears the parked term of
+ *      every occluded ray of the sample, in the dead path records).
  * out[12]: rays, recorded requests, rays whose list was truncated (256 requests), product ms, replay ms (best of reps),
  * then the issued-request counters of the sample: pairs global / LDS, nodes global / LDS, record heads, tails, spills.
  * Overwrites the hits of the sampled path records; call after the film has been read. */

@@ -99,10 +99,11 @@ bool samplerHasTables(const mtsgpu_ctx *c) {
 	return c->samplerKind == MTSGPU_SAMPLER_LD_KEYED || c->samplerKind == MTSGPU_SAMPLER_STRATIFIED_KEYED;
 }
 
-// Device bytes ensurePaths() allocates per path of a pass: the 128-byte record, the shadow ray (3 x 16), the eleven material
+// Device bytes ensurePaths() allocates per path of a pass: the 128-byte record, the shadow ray (2 x 16), the eleven material
 // bins sized for the all-in-one-bin case with a quarter of headroom (id 4 + hit 16 bytes per entry), the two next queues
-// (id 4 + ray 32 bytes each) and the shadow queue's ids -- about 530 bytes, 38 GB for the default pass of 72 M paths.
-constexpr size_t kBytesPerPath = kPathSlots * 16 + 3 * 16 + (size_t) (kNumBins * (4 + 16) * 5 / 4) + 2 * (4 + 32) + 4 + 4;
+// (id 4 + ray 32 bytes each) and the shadow queue's ids -- about 515 bytes, 37 GB for the default pass of 72 M paths.
+// (A frame that does not park its direct-light terms adds 16 bytes per path for them: ensureNeeQueue.)
+constexpr size_t kBytesPerPath = kPathSlots * 16 + 2 * 16 + (size_t) (kNumBins * (4 + 16) * 5 / 4) + 2 * (4 + 32) + 4 + 4;
 // Paths per pass when the caller set none (mtsgpu_set_options max_paths == 0): 72 M, or what 60 % of the free device memory
 // holds if that is less (the sampler tables, the film and the scene of a later upload need room too)
 uint64_t defaultMaxPaths(mtsgpu_ctx *c) {
@@ -127,7 +128,7 @@ int ensurePaths(mtsgpu_ctx *c, size_t cap) {
 	auto &o = c->pathAllocs;
 	int rc = 0;
 	rc |= devAlloc(c, &c->paths.base, cap * kPathSlots, o);
-	rc |= devAlloc(c, &c->paths.shq_o, cap, o); rc |= devAlloc(c, &c->paths.shq_d, cap, o); rc |= devAlloc(c, &c->paths.shq_nee, cap, o);
+	rc |= devAlloc(c, &c->paths.shq_o, cap, o); rc |= devAlloc(c, &c->paths.shq_d, cap, o);
 	// With static dealing every shard (workgroups with blockIdx % kBinShards == s) sees at most 1/kBinShards of the
 	// 256-ray batches plus one per workgroup, and all of them may land in one bin.  The dynamically claimed tail of a
 	// large launch (a quarter of the queue) goes to whichever waves are free, so a shard can take more than its share:
@@ -169,6 +170,15 @@ template <typename T> int ensureBuf(mtsgpu_ctx *c, T **p, size_t *cap, size_t ne
 	HIPCHK(c, hipMalloc(&raw, need * sizeof(T)));
 	*p = static_cast<T *>(raw); *cap = need;
 	return 0;
+}
+
+// The direct-light terms of the shadow queue (DPaths::shq_nee), for a frame that runs with DQueues::nee_parked == 0: the
+// rounds of MIDirectIntegrator and the "nee_parked" knob at 0.  Every other frame parks the terms in the path records and
+// does without the 16 bytes per path.
+int ensureNeeQueue(mtsgpu_ctx *c) {
+	int rc = ensureBuf(c, &c->shqNee, &c->shqNeeCap, c->pathCap);
+	c->paths.shq_nee = c->shqNee;
+	return rc;
 }
 
 // what launch_ld_tables needs besides the tables: one stream word per slot and, above 512 samples per pixel, the scratch
@@ -328,6 +338,7 @@ int runDirectRounds(mtsgpu_ctx *c, const DConfig &cfg0, uint32_t nPaths, volatil
 		c->stats.trace_launches++;
 		return 0;
 	};
+	{ int rc = ensureNeeQueue(c); if (rc) return rc; }      // the rounds add their terms to Li one after the other: nothing is parked
 	HIPCHK(c, hipMemsetAsync(c->q.counters, 0, counterBytes, s));
 	c->q.next = c->queueB;
 	BinView views[kNumBins];
@@ -406,9 +417,9 @@ int runBouncesDevice(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatil
 	bool shadowPending = false;
 	int b = 0;
 	// Every way out of this function -- cancel, a failed HIP call, the normal end -- leaves the context as the host-driven
-	// loop expects it and the second stream joined: a shadow launch still running on it adds to Li with a plain
-	// read-modify-write (k_trace MODE 1), and the next frame's clear / generate kernels on c->stream are not ordered
-	// against it otherwise (a GUI cancels and re-renders at once).
+	// loop expects it and the second stream joined: a shadow launch still running on it writes into the path records
+	// (k_trace MODE 1: cancels, or a plain read-modify-write of Li), and the next frame's clear / generate kernels on
+	// c->stream are not ordered against it otherwise (a GUI cancels and re-renders at once).
 	struct Restore {
 		mtsgpu_ctx *c; hipStream_t s2; const bool &pending;
 		~Restore() {
@@ -418,6 +429,7 @@ int runBouncesDevice(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatil
 	} restore{ c, s2, shadowPending };
 	RayQueuesOff rqOff{ c };
 	c->q.nee_parked = tuningOr(c, "nee_parked", 1) != 0 ? 1u : 0u;
+	if (!c->q.nee_parked) { int rc = ensureNeeQueue(c); if (rc) return rc; }
 	// cls >= 0: a traversal launch of that class (ctx.h: traceEvClass)
 	auto timed = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>> &pool, size_t &used, hipStream_t s, int which, int cls = -1) -> int {
 		if (!c->timeKernels) return 0;
@@ -514,6 +526,7 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 	const size_t setBytes = (size_t) kNumCounters * kCounterStride * sizeof(uint32_t);
 	RayQueuesOff rqOff{ c };
 	c->q.nee_parked = tuningOr(c, "nee_parked", 1) != 0 ? 1u : 0u;
+	if (!c->q.nee_parked) { int rc = ensureNeeQueue(c); if (rc) return rc; }
 	for (int b = 0; nQ > 0; ++b) {
 		if (cancel && *cancel)
 			return fail(c, MTSGPU_ECANCEL, "render cancelled");
@@ -535,7 +548,8 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 		HIPCHK(c, hipGetLastError());
 		rc = readCounters(c); if (rc) return rc;
 		const uint32_t nNext = c->hostCounters[kNextWord], nShadow = c->hostCounters[kShadowWord];
-		// shadow rays of this bounce (they add the direct-light term before the next bounce adds its own); the shading above has completed
+		// shadow rays of this bounce (they cancel the parked direct-light terms of the occluded ones -- or, unparked, add the others' --
+		// before the next bounce reads the records); the shading above has completed
 		if (nShadow) {
 			DQueues q2 = c->q; q2.spill = c->spillShadow;
 			c->lastPass.shadowMax = std::max(c->lastPass.shadowMax, nShadow);
@@ -701,6 +715,7 @@ void mtsgpu_destroy(mtsgpu_ctx *c) {
 	if (c->arrPerm) (void) hipFree(c->arrPerm);
 	if (c->arrPts) (void) hipFree(c->arrPts);
 	if (c->primSave) (void) hipFree(c->primSave);
+	if (c->shqNee) (void) hipFree(c->shqNee);
 	if (c->primes) (void) hipFree(c->primes);
 	if (c->pathLen) (void) hipFree(c->pathLen);
 	if (c->explicitSamples) (void) hipFree(c->explicitSamples);
@@ -1682,13 +1697,14 @@ int mtsgpu_replay_roof(mtsgpu_ctx *c, int kind, uint32_t n, uint32_t stride, int
 		c->lastPass.valid = false;             // the path records no longer hold that pass
 	}
 	if (kind == 2) {
-		// any-hit rays are addressed by their queue position: the sampled slots move to the front of the shadow queue
-		RR_CHK(hipMalloc((void **) &tmp, (size_t) n * 3 * sizeof(float4)));
+		// any-hit rays are addressed by their queue position: the sampled slots move to the front of the shadow queue, origin
+		// (with the path id in its w) and direction.  The launches below run as the bounces launch this class of rays, with
+		// the direct-light terms parked in the records (DQueues::nee_parked): they write a cancel for every occluded ray of
+		// the sample, into records of a frame that is already accumulated, and read no term
+		RR_CHK(hipMalloc((void **) &tmp, (size_t) n * 2 * sizeof(float4)));
 		launch_gather_strided(s, tmp, c->paths.shq_o, n, stride); launch_gather_strided(s, tmp + n, c->paths.shq_d, n, stride);
-		launch_gather_strided(s, tmp + 2 * (size_t) n, c->paths.shq_nee, n, stride);
 		RR_CHK(hipMemcpyAsync(c->paths.shq_o, tmp, (size_t) n * sizeof(float4), hipMemcpyDeviceToDevice, s));
 		RR_CHK(hipMemcpyAsync(c->paths.shq_d, tmp + n, (size_t) n * sizeof(float4), hipMemcpyDeviceToDevice, s));
-		RR_CHK(hipMemcpyAsync(c->paths.shq_nee, tmp + 2 * (size_t) n, (size_t) n * sizeof(float4), hipMemcpyDeviceToDevice, s));
 		c->lastPass.shadowMax = 0;             // the queue is no longer the frame's
 	} else {
 		// every stride-th path record, its ray copied into queue order the way the bounces hand rays to this kernel
@@ -1698,6 +1714,7 @@ int mtsgpu_replay_roof(mtsgpu_ctx *c, int kind, uint32_t n, uint32_t stride, int
 		rayQueues(c, c->queueA, nullptr);
 	}
 	RayQueuesOff rqOff{ c };
+	c->q.nee_parked = mode == 1 ? 1u : 0u;
 	const uint32_t *queue = mode == 1 ? c->q.shadow : c->queueA;
 	// 1. the counting kernel records what every ray asks for
 	RR_CHK(hipMemsetAsync(recLen, 0, (size_t) n * 4, s));

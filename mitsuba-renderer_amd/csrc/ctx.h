@@ -87,6 +87,7 @@ struct mtsgpu_ctx {
 	unsigned long long *ldState = nullptr; size_t ldStateCap = 0;
 	uint32_t *arrScr = nullptr; uint16_t *arrPerm = nullptr; float2 *arrPts = nullptr; size_t arrScrCap = 0, arrPermCap = 0, arrPtsCap = 0;
 	float4 *primSave = nullptr; size_t primSaveCap = 0;
+	float4 *shqNee = nullptr; size_t shqNeeCap = 0;      // DPaths::shq_nee, once a frame has run with DQueues::nee_parked == 0
 	uint16_t *primes = nullptr;        // primeTable (util.cpp:64-122) on the device
 	uint32_t *explicitSamples = nullptr; size_t explicitCap = 0;
 	uint32_t *hostCounters = nullptr;       // pinned

@@ -201,8 +201,10 @@ struct DPaths {
 	__host__ __device__ float4 &spos(size_t id) const { return slot(id, 7); }    // raster position x, y
 	// shadow rays live in queue order, not in the record: written coalesced by k_shade at the slot the stream
 	// compaction assigns, read coalesced by k_trace<shadow>
-	float4 *shq_o, *shq_d;        // origin p1, direction p2 - p1
-	float4 *shq_nee;              // pending direct-light contribution rgb, w = path id (uint bits)
+	float4 *shq_o, *shq_d;        // origin p1, w = path id (uint bits); direction p2 - p1
+	// pending direct-light contribution rgb, w = path id (uint bits): only frames that run with DQueues::nee_parked == 0
+	// write and read it, and only they allocate it (api.cpp: ensureNeeQueue); NULL otherwise
+	float4 *shq_nee;
 	// MIDirectIntegrator with several BSDF samples: the camera ray and its hit, [id][3] (ray_o, ray_d, hit), kept
 	// while the record carries the ray of the current BSDF sample
 	float4 *prim;
@@ -299,11 +301,14 @@ struct DQueues {
 	uint32_t tune_dyn_min_rounds;      // launches of at least this many rounds claim their last rounds dynamically (0 = 8)
 	uint32_t tune_blocks_per_cu;       // experiment: fewer resident workgroups of kTraceBlock threads per CU than trace_blocks_per_cu(mode)
 	                                   // (3 closest-hit / 4 shadow at 512 threads); 0 or a value >= that = all.  Range 0..kTraceBlocksPerCuMax
-	// The direct-light term of a shadow ray that came through (path.cpp:124: Li += ...): 0 = the any-hit kernel adds it to the
-	// path's radiance itself (a random line read and a partial-line write per ray, with the wave waiting for the read);
-	// 1 = it PARKS the term in slot 2 of the path record, tagged kNeeTag (one 16-byte store, nobody waits), and whoever reads
-	// the record next adds it first -- the path's next shading, or the film kernels if the path has ended.  Same addition,
-	// same place in the path's order of sums.  Slot 2 is free for it: the hits of binned paths travel with the bins.
+	// The direct-light term of a shadow ray that came through (path.cpp:124: Li += ...): 0 = the term travels with the ray
+	// (DPaths::shq_nee) and the any-hit kernel adds it to the path's radiance itself (a queue read, a random line read and a
+	// partial-line write per unoccluded ray, with the wave waiting for the reads); 1 = the shading PARKS the term in slot 2 of
+	// the path record, tagged kNeeTag, in the write-back of the whole line it does anyway, the any-hit kernel CANCELS it
+	// (clears the slot: one 16-byte store, nothing loaded, nobody waits) for the occluded rays only, and whoever reads the
+	// record next adds a term that is still there first -- the path's next shading, or the film kernels if the path has
+	// ended.  Same addition, same place in the path's order of sums.  Slot 2 is free for it: the hits of binned paths
+	// travel with the bins.
 	uint32_t nee_parked;
 };
 constexpr uint32_t kNeeTag = 0x4E454521u;      // not a primitive index (< 2^29) and not kNoPrim

@@ -211,8 +211,8 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 						const float bsdfPdf = (lt <= 1u || lt == 5u || (SKY && lt == 7u)) ? Bsdf2<BT>::pdf(tab, twoSided, BP, its.wi, woL) : 0.0f;
 						const float weight = direct ? mi_weight(lRec.pdf * cfg.frac_lum, bsdfPdf * cfg.frac_bsdf) * cfg.weight_lum
 						                            : mi_weight(lRec.pdf, bsdfPdf);          // direct.cpp:143-145
-						// added to Li by k_trace<shadow> iff the segment is unoccluded
-						// (kept in registers until the shadow-queue slot of this path is known, see the end of the kernel)
+						// added to Li iff the segment is unoccluded: parked in the record by shade_block and cancelled by
+						// k_trace<shadow>, or sent along with the shadow ray (DQueues::nee_parked)
 						neeV = V3(thr.x * lRec.value.x * bsdfVal.x * weight,
 						          thr.y * lRec.value.y * bsdfVal.y * weight,
 						          thr.z * lRec.value.z * bsdfVal.z * weight);
@@ -329,12 +329,13 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	float4 ro = make_float4(0, 0, 0, 0), rd = ro, T4 = ro, L4 = ro;
 	uint4 h = make_uint4(0u, 0u, 0u, kNoPrim);
 	if (active) {
-		// a direct-light term the any-hit kernel parked in slot 2 (DQueues::nee_parked) is added before anything else of this
-		// Li iteration, where the sequential loop adds it (path.cpp:124)
+		// a direct-light term the previous shading parked in slot 2 and the any-hit kernel did not cancel (DQueues::nee_parked)
+		// is added before anything else of this Li iteration, where the sequential loop adds it (path.cpp:124)
 		const float4 slot2 = row[2];
 		L4 = settled_Li(row[4], slot2);
 		h = haveBinHit ? binHit : reinterpret_cast<const uint4 &>(slot2);
-		// what the write-back below leaves in slot 2: nothing while terms are parked there, otherwise the hit
+		// what the write-back below leaves in slot 2: nothing while terms are parked there (unless this shading parks one,
+		// see below), otherwise the hit
 		if (q.nee_parked) row[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 		else reinterpret_cast<uint4 &>(row[2]) = h;
 		ro = row[0]; rd = row[1]; T4 = row[3];
@@ -367,13 +368,17 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	if (active)
 		shade_path<BT, ROUNDS, SKY, VCOL, TAN>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col, tex, tan);
+	// the pending direct-light term is parked in the record with the write-back below (the line is written whole anyway):
+	// the any-hit kernel clears the slot if the shadow ray is occluded, the record's next reader adds what is still there
+	if (q.nee_parked && wantShadow) row[2] = make_float4(neeV.x, neeV.y, neeV.z, __uint_as_float(kNeeTag));
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	#pragma unroll
 	for (int r = 0; r < 8; ++r) {
 		const uint32_t src = grp + 8u * r;
 		const uint32_t sid = (uint32_t) __shfl((int) id, (int) src);
 		// whole lines again: slot 7 does not change here; slot 2 does when direct-light terms are parked in it (the term this
-		// shading added has to go: every later reader would add it again), otherwise it holds the hit, unchanged
+		// shading added has to go: every later reader would add it again; the term it parks arrives), otherwise it holds the
+		// hit, unchanged
 		if ((actMask >> src) & 1ull) st_stream<4>(&ps.base[(size_t) sid * kPathSlots + sub], rows[shade_row_index(src, sub)]);
 	}
 
@@ -405,11 +410,12 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 		}
 	}
 	if (wantShadow) {
-		// the shadow ray lives in queue order (coalesced for both kernels); the path id rides in nee.w
+		// the shadow ray lives in queue order (coalesced for both kernels); the path id rides in the origin's w.  The term
+		// goes with it only when it is not parked in the record (DQueues::nee_parked)
 		const uint32_t pos = offS + (uint32_t) __popcll(mS & below);
-		st_stream<4>(&ps.shq_o[pos], make_float4(shO.x, shO.y, shO.z, 0.0f));
+		st_stream<4>(&ps.shq_o[pos], make_float4(shO.x, shO.y, shO.z, __uint_as_float(id)));
 		st_stream<4>(&ps.shq_d[pos], make_float4(shD.x, shD.y, shD.z, 0.0f));
-		st_stream<4>(&ps.shq_nee[pos], make_float4(neeV.x, neeV.y, neeV.z, __uint_as_float(id)));
+		if (!q.nee_parked) st_stream<4>(&ps.shq_nee[pos], make_float4(neeV.x, neeV.y, neeV.z, __uint_as_float(id)));
 	}
 }
 

@@ -43,7 +43,9 @@ uint32_t trace_top_nodes() { return kTopNodes; }
 __device__ __forceinline__ const uint4 *leaf_head(const DTraceScene &sc, uint32_t e) { return &sc.leaf_ta[kLeafStride * (size_t) e]; }
 __device__ __forceinline__ const uint4 *leaf_tail(const DTraceScene &sc, uint32_t e, uint32_t half) { return &sc.leaf_ta[kLeafStride * (size_t) e + 1 + half]; }
 
-template <int MODE, bool COUNT, bool BIN>
+// PARKED (any-hit only): the launches of frames that park their direct-light terms in the path records (DQueues::nee_parked):
+// the kernel without the code that carries a term along and adds it to Li, which frames that do not park run
+template <int MODE, bool COUNT, bool BIN, bool PARKED>
 __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &ps, const DQueues &q, const TracePlan &plan,
                                            const uint32_t *queue, uint32_t n, const uint32_t first, const uint32_t stride,
                                            uint32_t (*s_stack)[kTraceBlock], uint32_t (*s_mbox)[kTraceBlock], const uint4 *s_top) {
@@ -172,18 +174,18 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 					}
 				}
 			} else if (MODE == 1) {
-				// Scene::sampleLuminaire's visibility test passed: add the pending contribution (path.cpp:124)
-				if (done && !found) {
+				if (PARKED) {
+					// the shading parked the pending contribution in the path's record (DQueues::nee_parked), where the record's
+					// next reader adds it: an occluded ray takes it out again.  id = the path; nothing is loaded, and an
+					// unoccluded ray -- Scene::sampleLuminaire's visibility test passed (path.cpp:124) -- has nothing to do
+					if (done && found) ps.slot(id, 2) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+				} else if (done && !found) {
+					// the visibility test passed: add the pending contribution
 					const float4 c = ps.shq_nee[id];            // id = position in the shadow queue; c.w = path id
 					const uint32_t pid = __float_as_uint(c.w);
-					if (q.nee_parked) {
-						// parked in the record (DQueues::nee_parked): its next reader adds it
-						ps.slot(pid, 2) = make_float4(c.x, c.y, c.z, __uint_as_float(kNeeTag));
-					} else {
-						float4 L = ps.Li(pid);
-						L.x += c.x; L.y += c.y; L.z += c.z;
-						ps.Li(pid) = L;
-					}
+					float4 L = ps.Li(pid);
+					L.x += c.x; L.y += c.y; L.z += c.z;
+					ps.Li(pid) = L;
 				}
 			} else {
 				if (done)
@@ -201,7 +203,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 			sup_base += taken; sup_left -= taken;
 			MG_WSLOT(w_batch);
 			if (take) {
-				id = (MODE == 1) ? my : ld_stream<1>(&queue[my]);       // shadow rays are addressed by their queue position
+				id = (MODE == 1) ? my : ld_stream<1>(&queue[my]);       // shadow rays are addressed by their queue position, see below
 				// (rays that arrive in queue order are streamed, like shadow rays: not part of the recorded request list)
 				if (COUNT && q.rec) { rec_slot = my; rec_n = 0; if (MODE != 1 && !(MODE == 0 && ps.rq_o)) { rec_add(kReqRay, id * kPathSlots); rec_add(kReqRay, id * kPathSlots + 1); } }
 				float4 a, b;
@@ -209,6 +211,9 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 				if (MODE == 1) {
 					a = ld_stream<1>(&ps.shq_o[my]); b = ld_stream<1>(&ps.shq_d[my]);
 					rmint = kShadowEpsilon; rmaxt = 1 - kShadowEpsilon;      // Scene::isOccluded, scene.h:241-246
+					// with the term parked in the record, all the retirement needs is the path, which came with the origin;
+					// otherwise the queue position, behind which the term waits
+					if (PARKED) id = __float_as_uint(a.w);
 				} else {
 					if (MODE == 0 && ps.rq_o) { a = ld_stream<1>(&ps.rq_o[my]); b = ld_stream<1>(&ps.rq_d[my]); }    // in queue order: no trip behind the id
 					else { a = ld_stream<1>(&ps.ray_o(id)); b = ld_stream<1>(&ps.ray_d(id)); }
@@ -456,7 +461,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 	}
 }
 
-template <int MODE, bool COUNT, bool BIN>
+template <int MODE, bool COUNT, bool BIN, bool PARKED = false>
 __global__ __launch_bounds__(kTraceBlock, trace_waves_per_simd(MODE)) void k_trace(DTraceScene sc, DPaths ps, DQueues q,
                                                           const uint32_t *queue, uint32_t n_host, const uint32_t *n_dev) {
 	__shared__ uint32_t s_stack[kStackLDS][kTraceBlock];
@@ -478,7 +483,7 @@ __global__ __launch_bounds__(kTraceBlock, trace_waves_per_simd(MODE)) void k_tra
 		for (uint32_t t = threadIdx.x; t < kTopPairs; t += kTraceBlock) s_top[t] = reinterpret_cast<const uint4 *>(sc.nodes)[t];
 		__syncthreads();
 	}
-	trace_body<MODE, COUNT, BIN>(sc, ps, q, plan, queue, n, first, stride, s_stack, s_mbox, s_top);
+	trace_body<MODE, COUNT, BIN, PARKED>(sc, ps, q, plan, queue, n, first, stride, s_stack, s_mbox, s_top);
 }
 
 // Device-driven bounces: the per-bin views k_shade needs, from the shard counters the closest-hit launch left in `cur`
@@ -505,7 +510,7 @@ __global__ __launch_bounds__(256) void k_prep(const uint32_t *cur, uint32_t *nex
 	}
 }
 
-template <int MODE, bool COUNT, bool BIN>
+template <int MODE, bool COUNT, bool BIN, bool PARKED = false>
 static void launch_trace_t(hipStream_t s, const DScene &sc, const DPaths &ps, const DQueues &q, const uint32_t *queue, uint32_t n,
                            const uint32_t *n_dev) {
 	// persistent grid: enough workgroups to fill every CU, never more than there are rays (trace_plan); when only the
@@ -519,7 +524,7 @@ static void launch_trace_t(hipStream_t s, const DScene &sc, const DPaths &ps, co
 		blocks = std::min<unsigned>(blocks_for(n, minBatch * (kTraceBlock / 64)), q.n_cus * perCu);
 	}
 	if (!blocks) return;
-	hipLaunchKernelGGL((k_trace<MODE, COUNT, BIN>), dim3(blocks), dim3(kTraceBlock), 0, s, trace_scene(sc), ps, q, queue, n, n_dev);
+	hipLaunchKernelGGL((k_trace<MODE, COUNT, BIN, PARKED>), dim3(blocks), dim3(kTraceBlock), 0, s, trace_scene(sc), ps, q, queue, n, n_dev);
 }
 
 void launch_trace(hipStream_t s, int mode, bool count, bool bin, const DScene &sc, const DPaths &ps,
@@ -533,7 +538,8 @@ void launch_trace(hipStream_t s, int mode, bool count, bool bin, const DScene &s
 		if (bin) { if (count) launch_trace_t<0, true, true>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<0, false, true>(s, sc, ps, qq, queue, n, n_dev); }
 		else     { if (count) launch_trace_t<0, true, false>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<0, false, false>(s, sc, ps, qq, queue, n, n_dev); }
 	} else if (mode == 1) {
-		if (count) launch_trace_t<1, true, false>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<1, false, false>(s, sc, ps, qq, queue, n, n_dev);
+		if (qq.nee_parked) { if (count) launch_trace_t<1, true, false, true>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<1, false, false, true>(s, sc, ps, qq, queue, n, n_dev); }
+		else               { if (count) launch_trace_t<1, true, false>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<1, false, false>(s, sc, ps, qq, queue, n, n_dev); }
 	} else {
 		if (count) launch_trace_t<2, true, false>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<2, false, false>(s, sc, ps, qq, queue, n, n_dev);
 	}

@@ -50,7 +50,7 @@ out = {
     "workload": {"grid": 320, "res": 1024, "spp": 64},
     "kernel_source_hash": bench.kernel_source_hash(),
     "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc TCC_EA0_RDREQ* (separate passes), tools/profile_round.sh %s -> python3 tools/pmc_workload.py 64 (production kernels)" % tag,
-    "kernel": "k_trace<0,false,true> + k_trace<1,false,false> (%d launches per frame)" % launches,
+    "kernel": "k_trace<0,false,true,false> + k_trace<1,false,false,true> (%d launches per frame)" % launches,
     "fetch_size_kb": fetch, "write_size_kb": write, "read_correction": 2.0,
     "read_correction_source": "measured, profiles/r06a_fetch_size_calibration.txt: FETCH_SIZE tallies 64 B per fabric read request and every request is one "
                               "128-byte line (TCC_EA0_RDREQ = TCC_EA0_RDREQ_128B = TCC_MISS = 1 per line touched) for 8-byte gathers, 16-byte gathers and "

@@ -548,6 +548,24 @@ int  mtsgpu_sky_configure(const float *block, float *derived);
  * like mtsgpu_bsdf_eval: ops 0 and 1 call the device functions k_shade calls (sky_le, sky_sample), op 2 returns the constant
  * pdf_luminaire uses. */
 int  mtsgpu_lum_eval(mtsgpu_ctx *ctx, uint32_t lum_type, const float *block, int op, uint32_t n, const float *queries, float *out);
+/* The luminaires of the uploaded scene (mtsgpu_upload_scene; MTSGPU_ESTATE without one) as the shading kernels run them,
+ * for n query records.  queries [n][16], out [n][16], one stride for the three operations:
+ *   op 0  Scene::sampleLuminaire without its occlusion test (scene.cpp:396-415)
+ *           queries = p.xyz, s.x, s.y
+ *           out = found (0 / 1), luminaire index (-1 when not found), lRec.sRec.p.xyz, lRec.sRec.n.xyz, lRec.d.xyz,
+ *                 lRec.pdf (multiplied by the selection probability), lRec.value.rgb (divided by that pdf)
+ *           as the device function leaves them; p, n, d and value of a sample that was not found are not meaningful
+ *   op 1  Scene::pdfLuminaire (scene.cpp:381-394)
+ *           queries = p.xyz, lRec.sRec.p.xyz, lRec.sRec.n.xyz, lRec.d.xyz, luminaire index      out = pdf
+ *           MTSGPU_EINVAL for an index >= n_lums and for a delta luminaire (point, directional, spot, collimated), for
+ *           which no integrator asks
+ *   op 2  Scene::LeBackground: Le(normalize(direction)) of the constant, envmap or sky background
+ *           queries = direction.xyz (any length but 0)      out = Le.rgb
+ *           MTSGPU_EINVAL when the scene has no background luminaire
+ * Indices and `found` are floats holding small integers.  A test hook like mtsgpu_bsdf_eval: the three operations call
+ * sample_luminaire, pdf_luminaire and background_le, the device functions k_shade calls, in the instantiation (sky or
+ * not) the scene's frames use. */
+int  mtsgpu_scene_lum_eval(mtsgpu_ctx *ctx, int op, uint32_t n, const float *queries, float *out);
 /* its.color as the device computes it for the uploaded scene and its colours (mtsgpu_set_vertex_colors; MTSGPU_ESTATE without
  * them): prim [n] primitive indices, uv [n][2] the hit's barycentrics, out [n][3].  Primitives of shapes without colours
  * give 0.  A test hook: it calls the device function the shading kernels call. */

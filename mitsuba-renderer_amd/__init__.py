@@ -34,7 +34,7 @@ EXPORTS = [
     "mtsgpu_create_multi", "mtsgpu_group_destroy", "mtsgpu_group_size", "mtsgpu_group_ctx", "mtsgpu_group_last_error",
     "mtsgpu_group_upload_scene", "mtsgpu_group_set_camera", "mtsgpu_group_set_integrator", "mtsgpu_group_set_sampler",
     "mtsgpu_group_set_rfilter", "mtsgpu_group_render", "mtsgpu_group_last_reduce_kind", "mtsgpu_group_rccl_ranks", "mtsgpu_group_reduce_note", "mtsgpu_bsdf_eval", "mtsgpu_bsdf_eval_table", "mtsgpu_replay_roof", "mtsgpu_group_set_tuning",
-    "mtsgpu_sky_configure", "mtsgpu_lum_eval", "mtsgpu_pass_samples",
+    "mtsgpu_sky_configure", "mtsgpu_lum_eval", "mtsgpu_scene_lum_eval", "mtsgpu_pass_samples",
     "mtsgpu_set_film_statistics", "mtsgpu_read_film_statistics", "mtsgpu_film_statistics_form", "mtsgpu_group_set_film_statistics",
     "mtsgpu_set_vertex_colors", "mtsgpu_group_set_vertex_colors", "mtsgpu_flat_scene_set_mesh_colors", "mtsgpu_flat_scene_vertex_colors",
     "mtsgpu_flat_scene_shape_has_colors", "mtsgpu_loaded_mesh_colors", "mtsgpu_vertex_color_eval", "mtsgpu_bsdf_eval_colored",
@@ -188,6 +188,7 @@ def lib():
     L.mtsgpu_bsdf_eval_table.argtypes = [vp, C.c_uint32, u32p, f32p, C.c_uint32, C.c_int, C.c_uint32, f32p, f32p]
     L.mtsgpu_sky_configure.argtypes = [f32p, f32p]
     L.mtsgpu_lum_eval.argtypes = [vp, C.c_uint32, f32p, C.c_int, C.c_uint32, f32p, f32p]
+    L.mtsgpu_scene_lum_eval.argtypes = [vp, C.c_int, C.c_uint32, f32p, f32p]
     L.mtsgpu_hbm_triad.argtypes = [C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
     L.mtsgpu_replay_roof.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_double)]
     L.mtsgpu_create_multi.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
@@ -721,6 +722,15 @@ class MIPathTracer:
         out = np.zeros((n, 12), dtype=np.float32)
         self._chk(lib().mtsgpu_lum_eval(self._ctx, int(lum_type), abi.ptr(P, abi.f32p), int(op), n, abi.ptr(q, abi.f32p),
                                         abi.ptr(out, abi.f32p)), "lum_eval")
+        return out
+
+    def scene_lum_eval(self, op, queries):
+        """the luminaires of the uploaded scene on the device (mtsgpu_scene_lum_eval) for query records [n][16]: op 0
+        sampleLuminaire(p, s) without the occlusion test, op 1 pdfLuminaire(p, lRec.p, lRec.n, lRec.d, index), op 2 the
+        background's Le(direction).  Returns [n][16]: found, index, p, n, d, pdf, value | pdf | Le.rgb"""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 16)
+        out = np.zeros((q.shape[0], 16), dtype=np.float32)
+        self._chk(lib().mtsgpu_scene_lum_eval(self._ctx, int(op), q.shape[0], abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)), "scene_lum_eval")
         return out
 
     def li_samples(self, pix_samples):

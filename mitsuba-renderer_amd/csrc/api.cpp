@@ -1056,6 +1056,7 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 		h.bsdfType.assign(sc->bsdf_type, sc->bsdf_type + sc->n_bsdfs);
 		h.bsdfParams.assign(sc->bsdf_params, sc->bsdf_params + (size_t) MTSGPU_BSDF_NPARAMS * sc->n_bsdfs);
 		h.shapeBsdf.assign(sc->shape_bsdf, sc->shape_bsdf + sc->n_shapes);
+		h.lumType.assign(sc->lum_type, sc->lum_type + sc->n_lums);
 	}
 	// material queues that can ever be non-empty: the BSDF types of shapes that have one, and the "terminal" bin
 	c->binMask = 1u << kNumBsdfTypes;
@@ -2101,6 +2102,40 @@ int mtsgpu_lum_eval(mtsgpu_ctx *c, uint32_t lum_type, const float *block, int op
 	if (dOut) (void) hipFree(dOut);
 	if (dB) (void) hipFree(dB);
 	if (e != hipSuccess) return fail(c, MTSGPU_EHIP, "luminaire read-out failed: %s", hipGetErrorString(e));
+	return 0;
+}
+
+int mtsgpu_scene_lum_eval(mtsgpu_ctx *c, int op, uint32_t n, const float *queries, float *out) {
+	if (!c || !queries || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_scene_lum_eval before mtsgpu_upload_scene");
+	if (op < 0 || op > 2) return fail(c, MTSGPU_EINVAL, "bad luminaire operation");
+	if (n > (1u << 24)) return fail(c, MTSGPU_EINVAL, "at most 2^24 query records per call");
+	const std::vector<uint32_t> &lumType = c->host.lumType;
+	if (op == 1)      // the kernel indexes the luminaire tables with it
+		for (uint32_t i = 0; i < n; ++i) {
+			const float lf = queries[16 * (size_t) i + 12];
+			if (!(lf >= 0.0f && lf < (float) lumType.size()) || lf != (float) (uint32_t) lf)
+				return fail(c, MTSGPU_EINVAL, "record %u: luminaire index %g out of range", i, (double) lf);
+			const uint32_t t = lumType[(uint32_t) lf];
+			if (t != (uint32_t) MTSGPU_LUM_AREA && t != (uint32_t) MTSGPU_LUM_CONSTANT && t != (uint32_t) MTSGPU_LUM_ENVMAP && t != (uint32_t) MTSGPU_LUM_SKY)
+				return fail(c, MTSGPU_EINVAL, "record %u: luminaire %u is a delta luminaire (type %u), Scene::pdfLuminaire is never asked for one", i, (uint32_t) lf, t);
+		}
+	if (op == 2 && c->dsc.background_lum < 0) return fail(c, MTSGPU_EINVAL, "the scene has no background luminaire");
+	if (n == 0) return 0;
+	HIPCHK(c, hipSetDevice(c->device));
+	float *dQ = nullptr, *dOut = nullptr;
+	hipError_t e = hipMalloc((void **) &dQ, (size_t) n * 16 * sizeof(float));
+	if (e == hipSuccess) e = hipMalloc((void **) &dOut, (size_t) n * 16 * sizeof(float));
+	if (e == hipSuccess) e = hipMemcpyAsync(dQ, queries, (size_t) n * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess) {
+		launch_scene_lum_eval(c->stream, c->dsc, op, n, dQ, dOut);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, (size_t) n * 16 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (dQ) (void) hipFree(dQ);
+	if (dOut) (void) hipFree(dOut);
+	if (e != hipSuccess) return fail(c, MTSGPU_EHIP, "scene luminaire read-out failed: %s", hipGetErrorString(e));
 	return 0;
 }
 

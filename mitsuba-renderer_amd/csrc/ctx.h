@@ -29,7 +29,7 @@ struct mtsgpu_ctx {
 	// come and go between two uploads.
 	struct HostScene {
 		uint32_t nVerts = 0;
-		std::vector<uint32_t> triIdx, shapeTriOffset, shapeType, bsdfType;
+		std::vector<uint32_t> triIdx, shapeTriOffset, shapeType, bsdfType, lumType;
 		std::vector<int32_t> shapeBsdf;
 		std::vector<float> bsdfParams;
 	} host;

@@ -402,6 +402,9 @@ void launch_shading_frame_eval(hipStream_t s, const DScene &sc, const DTangents 
 // the sky luminaire (mtsgpu_lum_eval): Le (op 0), sample (1), pdf (2) for n query records [n][6]; block = the parameter
 // block followed by its derived array, in device memory; out [n][12]
 void launch_sky_eval(hipStream_t s, const float *block, int op, uint32_t n, const float *queries, float *out);
+// the luminaires of the uploaded scene (mtsgpu_scene_lum_eval): sample_luminaire (op 0), pdf_luminaire (1), background_le (2)
+// for n query records [n][16]; out [n][16]
+void launch_scene_lum_eval(hipStream_t s, const DScene &sc, int op, uint32_t n, const float *queries, float *out);
 void launch_generate(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                      const uint32_t *pixel_list, uint32_t n_slots, const uint32_t *explicit_samples,
                      uint32_t n_paths, uint32_t *queue);

@@ -185,6 +185,40 @@ __global__ void k_sky_eval(const float *block, int op, uint32_t n, const float *
 	for (int k = 0; k < 12; ++k) out[12 * (size_t) i + k] = o[k];
 }
 
+// The luminaires of the uploaded scene read out for n query records (mtsgpu_scene_lum_eval): queries [n][16], out [n][16].
+// SKY is chosen the way the shading launches choose it (shade_launch.h): by DScene::sky.  The host has checked op, and for
+// op 1 the luminaire index and type of every record, for op 2 that the scene has a background luminaire.
+template <bool SKY>
+__device__ __forceinline__ void scene_lum_eval_one(const DScene &sc, int op, const float *q, float *o) {
+	const V3 p(q[0], q[1], q[2]);
+	if (op == 0) {
+		LRec r;
+		r.p = r.n = r.d = r.value = V3(0.0f, 0.0f, 0.0f); r.pdf = 0.0f; r.lum = -1;
+		const bool found = sample_luminaire<SKY>(sc, p, q[3], q[4], r);
+		o[0] = found ? 1.0f : 0.0f; o[1] = (float) r.lum;
+		o[2] = r.p.x; o[3] = r.p.y; o[4] = r.p.z;
+		o[5] = r.n.x; o[6] = r.n.y; o[7] = r.n.z;
+		o[8] = r.d.x; o[9] = r.d.y; o[10] = r.d.z;
+		o[11] = r.pdf;
+		o[12] = r.value.x; o[13] = r.value.y; o[14] = r.value.z;
+	} else if (op == 1) {
+		o[0] = pdf_luminaire(sc, p, (int) q[12], V3(q[3], q[4], q[5]), V3(q[6], q[7], q[8]), V3(q[9], q[10], q[11]));
+	} else {
+		const V3 le = background_le<SKY>(sc, p);
+		o[0] = le.x; o[1] = le.y; o[2] = le.z;
+	}
+}
+__global__ void k_scene_lum_eval(DScene sc, int op, uint32_t n, const float *queries, float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float *q = queries + 16 * (size_t) i;
+	float o[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	if (sc.sky) scene_lum_eval_one<true>(sc, op, q, o);
+	else scene_lum_eval_one<false>(sc, op, q, o);
+	#pragma unroll
+	for (int k = 0; k < 16; ++k) out[16 * (size_t) i + k] = o[k];
+}
+
 void launch_bsdf_eval(hipStream_t s, uint32_t type, const float *params, int op, uint32_t n, const float *queries, float *out) {
 	BsdfParams p;
 	for (int k = 0; k < kBsdfNParams; ++k) p.v[k] = params[k];
@@ -198,6 +232,10 @@ void launch_bsdf_eval_table(hipStream_t s, const uint32_t *types, const float *p
 
 void launch_sky_eval(hipStream_t s, const float *block, int op, uint32_t n, const float *queries, float *out) {
 	if (n) hipLaunchKernelGGL(k_sky_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, block, op, n, queries, out);
+}
+
+void launch_scene_lum_eval(hipStream_t s, const DScene &sc, int op, uint32_t n, const float *queries, float *out) {
+	if (n) hipLaunchKernelGGL(k_scene_lum_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, op, n, queries, out);
 }
 
 void launch_bsdf_eval_colored(hipStream_t s, uint32_t type, const float *params, uint32_t slots, const float *color, int op, uint32_t n,

@@ -156,6 +156,9 @@ void orc_chord_rays(const float center[3], float radius, uint32_t n, float *rays
  * Scene::pdfLuminaire */
 void orc_luminaire_sample(const mtsgpu_scene *sc, int l, const float p[3], const float sample[2], float out[13]);
 float orc_luminaire_pdf(const mtsgpu_scene *sc, int l, const float p[3], const float lp[3], const float ln[3], const float ld[3]);
+/* mtsgpu_scene_lum_eval (include/mtsgpu.h) on the oracle: same ops, same [n][16] records; Scene::sampleLuminaire is taken
+ * without its occlusion test.  -1 for what that call refuses, and for a scene with a sky. */
+int orc_scene_lum_eval(const mtsgpu_scene *sc, int op, uint32_t n, const float *queries, float *out);
 
 void orc_render_tiles(const mtsgpu_scene *sc, const mtsgpu_camera *cam, const orc_render_params *p,
                       const orc_tabfilter *filter, int block_size, int part, int n_parts, int hq_edges,

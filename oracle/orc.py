@@ -113,6 +113,7 @@ def lib():
     L.orc_chord_rays.argtypes = [f32p, C.c_float, C.c_uint32, f32p]
     L.orc_luminaire_sample.argtypes = [C.POINTER(abi.Scene), C.c_int, f32p, f32p, f32p]
     L.orc_luminaire_pdf.argtypes = [C.POINTER(abi.Scene), C.c_int, f32p, f32p, f32p, f32p]; L.orc_luminaire_pdf.restype = C.c_float
+    L.orc_scene_lum_eval.argtypes = [C.POINTER(abi.Scene), C.c_int, C.c_uint32, f32p, f32p]; L.orc_scene_lum_eval.restype = C.c_int
     L.orc_bsdf_f.argtypes = [C.c_uint32, f32p, f32p, f32p, f32p]
     L.orc_bsdf_pdf.argtypes = [C.c_uint32, f32p, f32p, f32p]; L.orc_bsdf_pdf.restype = C.c_float
     L.orc_bsdf_eval.argtypes = [C.c_uint32, f32p, C.c_int, C.c_uint32, f32p, f32p]; L.orc_bsdf_eval.restype = None
@@ -197,6 +198,16 @@ def bsdf_eval(bsdf_type, params, op, wi, aux):
     P = np.zeros(abi.BSDF_NPARAMS, dtype=np.float32); P[:len(params)] = params
     out = np.zeros((n, 8), dtype=np.float32)
     lib().orc_bsdf_eval(int(bsdf_type), abi.ptr(P, abi.f32p), int(op), n, abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p))
+    return out
+
+
+def scene_lum_eval(scene_ptr, op, queries):
+    """the oracle's luminaires for n query records [n][16], laid out like mtsgpu_scene_lum_eval: returns [n][16]"""
+    q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 16)
+    out = np.zeros((q.shape[0], 16), dtype=np.float32)
+    rc = lib().orc_scene_lum_eval(scene_ptr, int(op), q.shape[0], abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p))
+    if rc != 0:
+        raise ValueError("orc_scene_lum_eval refused the call (%d)" % rc)
     return out
 
 

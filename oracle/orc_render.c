@@ -769,6 +769,54 @@ float orc_luminaire_pdf(const mtsgpu_scene *sc, int l, const float p[3], const f
 	return scene_pdf_luminaire(sc, p, &r);
 }
 
+/* The luminaires of a flattened scene read out for n records, laid out like mtsgpu_scene_lum_eval (include/mtsgpu.h):
+ * queries [n][16], out [n][16].  op 0: Scene::sampleLuminaire without the occlusion test; op 1: Scene::pdfLuminaire;
+ * op 2: the background's Le(normalize(direction)).  Returns 0, or -1 (MTSGPU_EINVAL) for what mtsgpu_scene_lum_eval
+ * refuses and for a sky, which the oracle does not have. */
+int orc_scene_lum_eval(const mtsgpu_scene *sc, int op, uint32_t n, const float *queries, float *out) {
+	if (!sc || !queries || !out || op < 0 || op > 2 || sc->n_lums == 0) return -1;
+	for (uint32_t l = 0; l < sc->n_lums; ++l) if (sc->lum_type[l] == MTSGPU_LUM_SKY) return -1;
+	if (op == 2 && sc->background_lum < 0) return -1;
+	for (uint32_t i = 0; i < n; ++i) {
+		const float *q = queries + 16 * (size_t) i;
+		float *o = out + 16 * (size_t) i;
+		for (int k = 0; k < 16; ++k) o[k] = 0.0f;
+		if (op == 0) {
+			lrec_t r; memset(&r, 0, sizeof(r));
+			r.lum = -1;
+			float sample[2] = { q[3], q[4] };
+			const int index = dpdf_sample_reuse(sc->lum_sel_cdf, sc->n_lums, &sample[0]);
+			const float lumPdf = sc->lum_sel_pdf[index];
+			luminaire_sample(sc, index, q, &r, sample);
+			int found = 0;
+			if (r.pdf != 0) {
+				r.pdf *= lumPdf;
+				const float recip = 1.0f / r.pdf;
+				r.value[0] *= recip; r.value[1] *= recip; r.value[2] *= recip;
+				r.lum = index;
+				found = 1;
+			}
+			o[0] = (float) found; o[1] = (float) r.lum;
+			for (int k = 0; k < 3; ++k) { o[2 + k] = r.p[k]; o[5 + k] = r.n[k]; o[8 + k] = r.d[k]; o[12 + k] = r.value[k]; }
+			o[11] = r.pdf;
+		} else if (op == 1) {
+			const float lf = q[12];
+			if (!(lf >= 0.0f && lf < (float) sc->n_lums) || lf != (float) (int) lf) return -1;
+			const uint32_t t = sc->lum_type[(int) lf];
+			if (t != MTSGPU_LUM_AREA && t != MTSGPU_LUM_CONSTANT && t != MTSGPU_LUM_ENVMAP) return -1;
+			lrec_t r; memset(&r, 0, sizeof(r));
+			for (int k = 0; k < 3; ++k) { r.p[k] = q[3 + k]; r.n[k] = q[6 + k]; r.d[k] = q[9 + k]; }
+			r.lum = (int) lf;
+			o[0] = scene_pdf_luminaire(sc, q, &r);
+		} else {
+			const float *P = sc->lum_params + MTSGPU_LUM_NPARAMS * (size_t) sc->background_lum;
+			o[0] = P[0]; o[1] = P[1]; o[2] = P[2];
+			if (sc->lum_type[sc->background_lum] == MTSGPU_LUM_ENVMAP) env_le_ray(sc, P, q, o);
+		}
+	}
+	return 0;
+}
+
 /* AreaLuminaire::Le (area.cpp:62-66) */
 static void area_le(const mtsgpu_scene *sc, int l, const float n[3], const float d[3], float out[3]) {
 	const float *P = sc->lum_params + MTSGPU_LUM_NPARAMS * (size_t) l;

@@ -315,7 +315,9 @@ int  mtsgpu_set_options(mtsgpu_ctx *ctx, uint64_t max_paths, int count_traversal
  *                                             turns it on for passes of at most 8 Mi paths
  *   chunk (1..1024, default 8)                bounces enqueued between two looks at the queue size (sync_free)
  *   test_retry (0/1)                          treat every first closest-hit launch as overflowed (exercises the retry)
- *   stats_wave (-1 rule, 0 lane, 1 wave)      form of the variance kernel of the test-case mode (below) */
+ *   stats_wave (-1 rule, 0 lane, 1 wave)      form of the variance kernel of the test-case mode (below)
+ *   miss_shaded (0/1, default 0)              1: a ray that leaves a scene without a background luminaire goes through the
+ *                                             terminal queue and the shading kernel; 0: its path ends in the traversal kernel */
 int  mtsgpu_set_tuning(mtsgpu_ctx *ctx, const char *key, long value);
 
 /* --- per-vertex colours and the `vertexcolors` texture (src/textures/vertexcolors.cpp: getValue(its) = its.color) -----
@@ -606,6 +608,12 @@ int  mtsgpu_li_samples(mtsgpu_ctx *ctx, const uint32_t *pix_samples, uint32_t n,
  * mtsgpu_li_samples or mtsgpu_trace_rays since), MTSGPU_EINVAL past its end.  A test hook: tests/ref64_film.py restates
  * ImageBlock::putSample in binary64 over these records and the film must agree. */
 int  mtsgpu_pass_samples(mtsgpu_ctx *ctx, uint32_t first, uint32_t n, float *out);
+/* How many entries the closest-hit launches of the last mtsgpu_render / mtsgpu_li_samples appended to every material queue,
+ * summed over the bounces: out [MTSGPU_BSDF_NTYPES + 1] u64, entry t = hits on shapes whose BSDF has type t, the last one the
+ * terminal queue (hits on shapes without a BSDF and -- in frames that shade their misses: scenes with a background luminaire,
+ * the rounds of the direct integrator, the "miss_shaded" knob at 1 -- rays that hit nothing).  Every other frame ends a path
+ * whose ray leaves the scene inside the traversal kernel, and that ray is in no queue.  A test hook. */
+int  mtsgpu_bin_entries(mtsgpu_ctx *ctx, uint64_t *out);
 
 /* --- host-side flattening (what Scene::initialize does on the CPU) ---------
  * Builds everything a mtsgpu_scene needs from plain meshes: vertex normals

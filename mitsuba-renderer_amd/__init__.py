@@ -41,7 +41,7 @@ EXPORTS = [
     "mtsgpu_set_uv_textures", "mtsgpu_group_set_uv_textures", "mtsgpu_flat_scene_set_mesh_texcoords", "mtsgpu_flat_scene_vertex_texcoords",
     "mtsgpu_flat_scene_shape_has_texcoords", "mtsgpu_loaded_mesh_texcoords", "mtsgpu_uv_texture_eval", "mtsgpu_bsdf_eval_slots",
     "mtsgpu_flatten_tangents", "mtsgpu_flat_scene_vertex_tangents", "mtsgpu_flat_scene_shape_has_tangents", "mtsgpu_upload_scene_tangents",
-    "mtsgpu_group_upload_scene_tangents", "mtsgpu_shading_frame_eval",
+    "mtsgpu_group_upload_scene_tangents", "mtsgpu_shading_frame_eval", "mtsgpu_bin_entries",
 ]
 
 
@@ -171,6 +171,7 @@ def lib():
     L.mtsgpu_ld_tables.argtypes = [vp, C.c_uint32, f32p, f32p]
     L.mtsgpu_li_samples.argtypes = [vp, u32p, C.c_uint32, f32p]
     L.mtsgpu_pass_samples.argtypes = [vp, C.c_uint32, C.c_uint32, f32p]
+    L.mtsgpu_bin_entries.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.mtsgpu_flatten.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.KdParams), C.POINTER(vp)]
     L.mtsgpu_flat_scene_get.argtypes = [vp]; L.mtsgpu_flat_scene_get.restype = C.POINTER(abi.Scene)
     L.mtsgpu_flat_scene_free.argtypes = [vp]; L.mtsgpu_flat_scene_free.restype = None
@@ -535,6 +536,13 @@ class MIPathTracer:
         st = abi.Stats()
         self._chk(lib().mtsgpu_get_stats(self._ctx, C.byref(st)), "get_stats")
         return st.as_dict()
+
+    def bin_entries(self):
+        """entries the closest-hit launches of the last frame appended to every material queue (mtsgpu_bin_entries): one count per
+        BSDF type, then the terminal queue"""
+        out = (C.c_uint64 * (abi.BSDF_NTYPES + 1))()
+        self._chk(lib().mtsgpu_bin_entries(self._ctx, out), "bin_entries")
+        return [int(v) for v in out]
 
     # --- test-case mode (`mitsuba -t`, testmode.py) -----------------------------
     def set_film_statistics(self, on=True):

@@ -216,6 +216,14 @@ DConfig makeConfig(const mtsgpu_ctx *c, bool slotPerPath) {
 	}
 	cfg.arr_scr = c->arrScr; cfg.arr_perm = c->arrPerm; cfg.arr_pts = c->arrPts;
 	cfg.filt_size_x = c->filtSizeX; cfg.filt_size_y = c->filtSizeY; cfg.filt_border = c->filtBorder; cfg.filt_values = c->filtValues;
+	// Without a background luminaire a ray that leaves the scene ends its path and adds nothing: the records are kept so that
+	// such a ray needs no shading (kernels.h: DConfig::miss_settled).  The rounds of MIDirectIntegrator keep the shaded route,
+	// and so does the "miss_shaded" knob at 1 (A/B runs, tests)
+	{
+		const auto it = c->tuning.find("miss_shaded");
+		const bool rounds = c->integrator == 1 && (c->nLumSamples > 1 || c->nBsdfSamples > 1);
+		cfg.miss_settled = (c->dsc.background_lum < 0 && !rounds && !(it != c->tuning.end() && it->second == 1)) ? 1 : 0;
+	}
 	return cfg;
 }
 
@@ -266,7 +274,7 @@ void rayQueues(mtsgpu_ctx *c, const uint32_t *cur, const uint32_t *nxt) {
 }
 // ... and outside the bounce loops nobody reads or writes them (test hooks and the replay measurement trace rays they put
 // into the records)
-struct RayQueuesOff { mtsgpu_ctx *c; ~RayQueuesOff() { rayQueues(c, nullptr, nullptr); c->q.nee_parked = 0; } };
+struct RayQueuesOff { mtsgpu_ctx *c; ~RayQueuesOff() { rayQueues(c, nullptr, nullptr); c->q.nee_parked = 0; c->q.miss_settled = 0; } };
 
 // an event pair for a traversal launch of class cls (ctx.h: traceEvClass)
 hipEvent_t *nextTraceEvents(mtsgpu_ctx *c, int cls) {
@@ -314,7 +322,10 @@ int traceAndBin(mtsgpu_ctx *c, const uint32_t *queue, uint32_t n, bool coherent,
 			views[b].prefix[kBinShards] = acc;
 		}
 		if (attempt == 0 && c->tuning.count("test_retry") && c->tuning["test_retry"]) overflow = true;   // exercises the retry (tests)
-		if (!overflow) return 0;
+		if (!overflow) {
+			for (int b = 0; b < kNumBins; ++b) c->binEntries[b] += views[b].prefix[kBinShards];
+			return 0;
+		}
 		c->stats.bin_overflow_retries++;
 	}
 	return fail(c, MTSGPU_EHIP, "internal: bin segment overflow with static dealing");
@@ -430,6 +441,7 @@ int runBouncesDevice(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatil
 	RayQueuesOff rqOff{ c };
 	c->q.nee_parked = tuningOr(c, "nee_parked", 1) != 0 ? 1u : 0u;
 	if (!c->q.nee_parked) { int rc = ensureNeeQueue(c); if (rc) return rc; }
+	c->q.miss_settled = cfg.miss_settled ? 1u : 0u;      // k_trace<closest> and k_shade agree on who settles a miss
 	// cls >= 0: a traversal launch of that class (ctx.h: traceEvClass)
 	auto timed = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>> &pool, size_t &used, hipStream_t s, int which, int cls = -1) -> int {
 		if (!c->timeKernels) return 0;
@@ -502,6 +514,7 @@ int collectDeviceStats(mtsgpu_ctx *c) {
 	unsigned long long h[kNumDevStats];
 	HIPCHK(c, hipMemcpy(h, c->devStats, sizeof(h), hipMemcpyDeviceToHost));
 	c->stats.rays_closest += h[kStatClosest]; c->stats.rays_shadow += h[kStatShadow]; c->stats.trace_launches += h[kStatLaunches];
+	for (int b = 0; b < kNumBins; ++b) c->binEntries[b] += h[kStatBin0 + b];
 	if (h[kStatOverflow]) return fail(c, MTSGPU_EHIP, "internal: bin segment overflow in a device-driven frame");
 	return 0;
 }
@@ -527,6 +540,7 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 	RayQueuesOff rqOff{ c };
 	c->q.nee_parked = tuningOr(c, "nee_parked", 1) != 0 ? 1u : 0u;
 	if (!c->q.nee_parked) { int rc = ensureNeeQueue(c); if (rc) return rc; }
+	c->q.miss_settled = cfg.miss_settled ? 1u : 0u;      // k_trace<closest> and k_shade agree on who settles a miss
 	for (int b = 0; nQ > 0; ++b) {
 		if (cancel && *cancel)
 			return fail(c, MTSGPU_ECANCEL, "render cancelled");
@@ -1361,7 +1375,7 @@ int mtsgpu_set_tuning(mtsgpu_ctx *c, const char *key, long value) {
 	if (!c || !key) return fail(c, MTSGPU_EINVAL, "null argument");
 	struct Knob { const char *key; long lo, hi; };
 	static const Knob knobs[] = { { "refill_min", 1, 64 }, { "desc_min", 1, 64 }, { "leaf_min", 1, 64 }, { "batch", 0, 64 },
-	                              { "dyn_div", 0, 1 << 20 }, { "test_retry", 0, 1 }, { "sync_free", -1, 1 }, { "chunk", 1, 1024 }, { "blocks_per_cu", 0, (long) kTraceBlocksPerCuMax }, { "plain_below", 0, 1 << 30 }, { "dyn_min_rounds", 0, 1 << 20 }, { "shade_fused", 0, 1 }, { "ray_queues", 0, 1 }, { "nee_parked", 0, 1 }, { "stats_wave", -1, 1 } };
+	                              { "dyn_div", 0, 1 << 20 }, { "test_retry", 0, 1 }, { "sync_free", -1, 1 }, { "chunk", 1, 1024 }, { "blocks_per_cu", 0, (long) kTraceBlocksPerCuMax }, { "plain_below", 0, 1 << 30 }, { "dyn_min_rounds", 0, 1 << 20 }, { "shade_fused", 0, 1 }, { "ray_queues", 0, 1 }, { "nee_parked", 0, 1 }, { "stats_wave", -1, 1 }, { "miss_shaded", 0, 1 } };
 	for (const Knob &k : knobs)
 		if (std::strcmp(k.key, key) == 0) {
 			if (value < k.lo || value > k.hi) return fail(c, MTSGPU_EINVAL, "tuning knob %s: %ld outside [%ld, %ld]", key, value, k.lo, k.hi);
@@ -1493,6 +1507,7 @@ int mtsgpu_render(mtsgpu_ctx *c, volatile const int *cancel) {
 		c->renderKey = key; c->renderListValid = false;
 	}
 	std::memset(&c->stats, 0, sizeof(c->stats));
+	std::memset(c->binEntries, 0, sizeof(c->binEntries));
 	c->traceEvUsed = c->shadeEvUsed = 0;
 	if (pixels.empty()) return 0;
 	if (!reuse) {
@@ -1716,6 +1731,7 @@ int mtsgpu_replay_roof(mtsgpu_ctx *c, int kind, uint32_t n, uint32_t stride, int
 	}
 	RayQueuesOff rqOff{ c };
 	c->q.nee_parked = mode == 1 ? 1u : 0u;
+	c->q.miss_settled = 0;
 	const uint32_t *queue = mode == 1 ? c->q.shadow : c->queueA;
 	// 1. the counting kernel records what every ray asks for
 	RR_CHK(hipMemsetAsync(recLen, 0, (size_t) n * 4, s));
@@ -2143,6 +2159,7 @@ int mtsgpu_li_samples(mtsgpu_ctx *c, const uint32_t *pix_samples, uint32_t n, fl
 	int rc = checkReady(c); if (rc) return rc;
 	if (!pix_samples || !out) return fail(c, MTSGPU_EINVAL, "null argument");
 	std::memset(&c->stats, 0, sizeof(c->stats));
+	std::memset(c->binEntries, 0, sizeof(c->binEntries));
 	c->traceEvUsed = c->shadeEvUsed = 0;
 	if (n == 0) return 0;
 	const uint32_t spp = effectiveSpp(c);
@@ -2228,6 +2245,12 @@ int mtsgpu_pass_samples(mtsgpu_ctx *c, uint32_t first, uint32_t n, float *out) {
 		o[4] = spos[4 * i]; o[5] = spos[4 * i + 1]; o[6] = (float) depth;
 		std::memcpy(&o[7], &misc[4 * i + 3], 4);           // the pixel key, as a bit pattern
 	}
+	return 0;
+}
+
+int mtsgpu_bin_entries(mtsgpu_ctx *c, uint64_t *out) {
+	if (!c || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	for (int b = 0; b < kNumBins; ++b) out[b] = c->binEntries[b];
 	return 0;
 }
 

@@ -102,6 +102,9 @@ struct mtsgpu_ctx {
 
 	// stats
 	mtsgpu_stats stats{};
+	// entries the closest-hit launches of the last frame appended to every material queue (mtsgpu_bin_entries): counted by the
+	// host where it reads the shard counters back, by k_prep otherwise
+	uint64_t binEntries[mg::kNumBins] = {};
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> traceEvents, shadeEvents;
 	size_t traceEvUsed = 0, shadeEvUsed = 0;
 	std::vector<unsigned char> traceEvClass;      // per traversal launch: 0 closest-hit, 1 closest-hit of a pass's first bounce, 2 any-hit

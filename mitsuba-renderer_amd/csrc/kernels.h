@@ -78,7 +78,8 @@ enum { kCntPairGlobal = 8, kCntPairLds = 9, kCntNodeGlobal = 10, kCntNodeLds = 1
 // request kinds of a recorded ray (DQueues::rec): index in units of the access size into the node array (16-byte sibling
 // pairs, 8-byte nodes), the leaf records (16 bytes) or the path records (16-byte slots; loads of the ray, store of the hit)
 enum : uint32_t { kReqPair = 1, kReqNode = 2, kReqLeaf = 3, kReqRay = 4, kReqHit = 5, kReqNone = 0xFFFFFFFFu };
-enum { kStatClosest = 0, kStatShadow = 1, kStatOverflow = 2, kStatLaunches = 3, kNumDevStats = 4 };
+// kStatBin0 + b: entries the closest-hit launches appended to material queue b (mtsgpu_bin_entries)
+enum { kStatClosest = 0, kStatShadow = 1, kStatOverflow = 2, kStatLaunches = 3, kStatBin0 = 4, kNumDevStats = kStatBin0 + kNumBins };
 
 // Scene in HBM (all pointers are device pointers); see DESIGN.md section 3
 struct DScene {
@@ -260,6 +261,11 @@ struct DConfig {
 	const uint32_t *ld_scr;       // [slot][3*ld_depth]
 	const uint16_t *ld_perm;      // [slot][2*ld_depth][spp]
 	const uint16_t *primes;       // primeTable (util.cpp:64-122) for the halton / hammersley samplers
+	// 1: a path record at rest describes its path as if the ray now in flight missed -- a continuing path is written back with
+	// depth + 1, and a shading with a valid hit that is not the camera ray's starts from depth - 1 -- so a miss needs no shading
+	// and k_trace<closest> drops it (DQueues::miss_settled, the same value).  Set per frame (api.cpp: makeConfig): scenes without
+	// a background luminaire, path frames and one-sample direct frames, unless the "miss_shaded" knob is 1
+	int32_t miss_settled;
 };
 
 struct DQueues {
@@ -284,6 +290,10 @@ struct DQueues {
 	// see kReq* -- to rec[r * rec_cap ..] and their number to rec_len[r]
 	uint32_t *rec, *rec_len;
 	uint32_t rec_cap;
+	// DConfig::miss_settled of the frame: the closest-hit kernel with the material sort gives a ray that hit nothing no bin at
+	// all (no store, no slot, not counted); hits on shapes without a BSDF still go to the terminal bin.  (Here, in the four
+	// bytes that were padding: the counting kernels keep a copy of this struct in scratch, which grows with it)
+	uint32_t miss_settled;
 	unsigned long long *dev_stats;     // kStat* (may be NULL)
 	uint32_t *spill;              // traversal stack overflow: [level][thread]; one buffer per traversal mode (the two run concurrently)
 	uint32_t spill_stride;

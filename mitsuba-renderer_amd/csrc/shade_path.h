@@ -61,6 +61,10 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			smp.d1 = (flags >> F_D1_SHIFT) & 0xFFu; smp.d2 = (flags >> F_D2_SHIFT) & 0xFFu;
 		}
 		const bool direct = cfg.integrator == 1;
+		// DConfig::miss_settled: while its ray was in flight the record held depth + 1, what a miss would have left.  The ray of
+		// this shading hit something, so in the tail below `depth` is one ahead until the place of its depth++ (the camera ray's
+		// record holds depth 1 either way)
+		const bool settled = !ROUNDS && cfg.miss_settled && !direct;
 		Its its;
 		if (valid) {
 			if (TAN) fill_its_tan(sc, tan, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
@@ -102,7 +106,7 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 						lvalue = background_le<SKY>(sc, rayD);
 						hitLuminaire = true;
 					} else {
-						if (!direct) depth++;
+						if (!direct && !settled) depth++;       // settled: the record counted this ray already
 						break;
 					}
 				}
@@ -118,14 +122,16 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				if (!valid || direct)
 					break;                                  // MIDirectIntegrator stops after its BSDF sample (direct.cpp:193)
 				flags &= ~F_EMITTED;                       // rRec.type = ERadianceNoEmission
-				if (depth >= cfg.rr_depth && !(sampledType & T_TRANSMISSION)) {
+				if (depth >= cfg.rr_depth + (settled ? 1 : 0) && !(sampledType & T_TRANSMISSION)) {
 					const float approxAlbedo = smin(0.9f, smax(smax(bsdfVal.x, bsdfVal.y), bsdfVal.z));
-					if (sampler_next1d(cfg, smp) > approxAlbedo)
+					if (sampler_next1d(cfg, smp) > approxAlbedo) {
+						if (settled) depth--;                   // the path ends before the depth++ the record had counted
 						break;
+					}
 					thr = thr * (1.0f / approxAlbedo);
 				}
 				thr = thr * bsdfVal;
-				depth++;
+				if (!settled) depth++;
 				if (!(depth <= cfg.max_depth || cfg.max_depth < 0))
 					break;
 			}
@@ -255,7 +261,7 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 		if (!continues) { row[0] = ro; row[1] = rd; }      // a path that ends keeps its last ray (the slots held triangle data)
 
 		flags = (flags & ~((0xFFu << F_D1_SHIFT) | (0xFFu << F_D2_SHIFT))) | (smp.d1 << F_D1_SHIFT) | (smp.d2 << F_D2_SHIFT);
-		row[3] = make_float4(thr.x, thr.y, thr.z, __int_as_float(depth));
+		row[3] = make_float4(thr.x, thr.y, thr.z, __int_as_float(depth + ((settled && continues) ? 1 : 0)));
 		row[4] = make_float4(Li.x, Li.y, Li.z, __uint_as_float(flags));
 		reinterpret_cast<uint4 &>(row[6]) = make_uint4((uint32_t) (smp.stream & 0xFFFFFFFFull), (uint32_t) (smp.stream >> 32), misc_zw.x, misc_zw.y);
 	}

@@ -146,6 +146,8 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 						bin = kNumBins - 1;
 						if (found) {
 							bin = (int) sc.shape_bin[best_shape];      // BSDF type of the hit shape, or the terminal bin (one lookup)
+						} else if (q.miss_settled) {
+							bin = -1;      // the record already describes the path that ends here (DConfig::miss_settled): nothing to shade
 						}
 					}
 				}
@@ -507,6 +509,7 @@ __global__ __launch_bounds__(256) void k_prep(const uint32_t *cur, uint32_t *nex
 			acc += c < bin_seg_cap ? c : bin_seg_cap;      // entries beyond the capacity were dropped (and flagged)
 		}
 		views[t].prefix[kBinShards] = acc;
+		if (dev_stats && acc) atomicAdd(&dev_stats[kStatBin0 + t], (unsigned long long) acc);
 	}
 }
 

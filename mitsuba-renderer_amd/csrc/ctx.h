@@ -1,7 +1,9 @@
-// ctx.h -- the context behind the C ABI (include/mtsgpu.h), shared by api.cpp and group.cpp.
+// ctx.h -- the context behind the C ABI (include/mtsgpu.h) and the helpers its translation units share: api.cpp (context,
+// setters, film), scene_upload.cpp, render.cpp (the wavefront engine), readout.cpp (test and measurement hooks), group.cpp.
 #pragma once
 #include "host.h"
 #include "kernels.h"
+#include <algorithm>
 #include <map>
 #include <string>
 #include <utility>
@@ -122,3 +124,65 @@ int fail(mtsgpu_ctx *ctx, int code, const char *fmt, ...);
 
 #define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
 	return mg::fail(ctx, MTSGPU_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+
+// What the translation units behind the C ABI share besides the context.  Only what a second file uses is declared here;
+// everything else is local to its file.
+#pragma GCC visibility push(hidden)      // internal to the library: the exported names are the C ABI's
+namespace mg {
+template <typename T> int devAlloc(mtsgpu_ctx *ctx, T **p, size_t count, std::vector<void *> &owner) {
+	void *raw = nullptr;
+	HIPCHK(ctx, hipMalloc(&raw, std::max<size_t>(count, 1) * sizeof(T)));
+	owner.push_back(raw);
+	*p = static_cast<T *>(raw);
+	return 0;
+}
+
+// owner: the list the allocation is filed under (NULL: the scene's)
+template <typename T> int upload(mtsgpu_ctx *ctx, const T **dst, const T *src, size_t count, std::vector<void *> *owner = nullptr) {
+	T *p = nullptr;
+	int rc = devAlloc(ctx, &p, count, owner ? *owner : ctx->sceneAllocs);
+	if (rc) return rc;
+	if (count) HIPCHK(ctx, hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+	*dst = p;
+	return 0;
+}
+
+inline void freeAll(std::vector<void *> &v) { for (void *p : v) (void) hipFree(p); v.clear(); }
+
+template <typename T> int ensureBuf(mtsgpu_ctx *c, T **p, size_t *cap, size_t need) {
+	if (need <= *cap) return 0;
+	if (*p) (void) hipFree(*p);
+	*p = nullptr; *cap = 0;
+	void *raw = nullptr;
+	HIPCHK(c, hipMalloc(&raw, need * sizeof(T)));
+	*p = static_cast<T *>(raw); *cap = need;
+	return 0;
+}
+
+// a pair of timing events, released on every way out of the function that holds it
+struct EventPair {
+	hipEvent_t a = nullptr, b = nullptr;
+	~EventPair() { if (a) (void) hipEventDestroy(a); if (b) (void) hipEventDestroy(b); }
+};
+
+// api.cpp
+uint32_t effectiveSpp(const mtsgpu_ctx *c);
+int checkReady(mtsgpu_ctx *c);
+int ensureFilm(mtsgpu_ctx *c);
+int ensureFilmStats(mtsgpu_ctx *c);
+
+// scene_upload.cpp
+std::string checkUvTexture(const mtsgpu_uv_texture &t);
+
+// render.cpp
+void applyTuning(mtsgpu_ctx *c);
+bool samplerHasTables(const mtsgpu_ctx *c);
+int ensureTableWork(mtsgpu_ctx *c, size_t nSlots, uint32_t spp);
+DConfig makeConfig(const mtsgpu_ctx *c, bool slotPerPath);
+void rayQueues(mtsgpu_ctx *c, const uint32_t *cur, const uint32_t *nxt);
+// ... and outside the bounce loops nobody reads or writes them (test hooks and the replay measurement trace rays they put
+// into the records)
+struct RayQueuesOff { mtsgpu_ctx *c; ~RayQueuesOff() { rayQueues(c, nullptr, nullptr); c->q.nee_parked = 0; c->q.miss_settled = 0; } };
+
+} // namespace mg
+#pragma GCC visibility pop

@@ -204,7 +204,7 @@ struct DPaths {
 	// compaction assigns, read coalesced by k_trace<shadow>
 	float4 *shq_o, *shq_d;        // origin p1, w = path id (uint bits); direction p2 - p1
 	// pending direct-light contribution rgb, w = path id (uint bits): only frames that run with DQueues::nee_parked == 0
-	// write and read it, and only they allocate it (api.cpp: ensureNeeQueue); NULL otherwise
+	// write and read it, and only they allocate it (render.cpp: ensureNeeQueue); NULL otherwise
 	float4 *shq_nee;
 	// MIDirectIntegrator with several BSDF samples: the camera ray and its hit, [id][3] (ray_o, ray_d, hit), kept
 	// while the record carries the ray of the current BSDF sample
@@ -263,7 +263,7 @@ struct DConfig {
 	const uint16_t *primes;       // primeTable (util.cpp:64-122) for the halton / hammersley samplers
 	// 1: a path record at rest describes its path as if the ray now in flight missed -- a continuing path is written back with
 	// depth + 1, and a shading with a valid hit that is not the camera ray's starts from depth - 1 -- so a miss needs no shading
-	// and k_trace<closest> drops it (DQueues::miss_settled, the same value).  Set per frame (api.cpp: makeConfig): scenes without
+	// and k_trace<closest> drops it (DQueues::miss_settled, the same value).  Set per frame (render.cpp: makeConfig): scenes without
 	// a background luminaire, path frames and one-sample direct frames, unless the "miss_shaded" knob is 1
 	int32_t miss_settled;
 };

@@ -1,0 +1,511 @@
+// scene_upload.cpp -- HBM residency of the flattened scene (include/mtsgpu.h): what mtsgpu_upload_scene validates, re-lays
+// out and uploads, and the per-vertex attributes that come and go between two uploads (vertex colours, uv textures).
+#include "ctx.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace mg;
+
+// what mtsgpu_set_uv_textures and mtsgpu_uv_texture_eval require of one descriptor; the reason, or an empty string
+std::string mg::checkUvTexture(const mtsgpu_uv_texture &t) {
+	if (t.kind >= (uint32_t) MTSGPU_TEX_NKINDS) return "unknown kind " + std::to_string(t.kind);
+	const float *f = &t.uoffset;      // the eleven floats behind the kind
+	for (int i = 0; i < 11; ++i) if (!std::isfinite(f[i])) return "non-finite parameter";
+	return std::string();
+}
+
+namespace {
+
+// The rows of one mesh in a per-primitive gather array: for each of its primitives [t0, t1) the attribute of the three
+// vertices (`comps` floats per vertex: 4 floats apart for tangents and colours, 2 for texcoords), in rows of 4 * stride
+// floats.  A non-finite component is refused: false, and *bad names the vertex.
+bool gatherMeshRows(const uint32_t *triIdx, uint32_t t0, uint32_t t1, const float *vtx, int comps, size_t stride, float *rows, uint32_t *bad) {
+	const size_t slot = comps == 3 ? 4 : (size_t) comps;
+	for (uint32_t t = t0; t < t1; ++t)
+		for (int k = 0; k < 3; ++k) {
+			const uint32_t v = triIdx[3 * (size_t) t + k];      // < n_verts: mtsgpu_upload_scene checked it
+			const float *a = vtx + (size_t) comps * v;
+			for (int i = 0; i < comps; ++i) if (!std::isfinite(a[i])) { *bad = v; return false; }
+			std::memcpy(&rows[4 * stride * (size_t) t + slot * (size_t) k], a, sizeof(float) * (size_t) comps);
+		}
+	return true;
+}
+
+} // namespace
+
+extern "C" {
+
+// mtsgpu_upload_scene (vtx_dpdu = shape_has_tangents = NULL, withTangents = false) and mtsgpu_upload_scene_tangents
+static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_dpdu, const uint32_t *shape_has_tangents, bool withTangents) {
+	if (!c || !sc) return fail(c, MTSGPU_EINVAL, "null argument");
+	c->lastPass.valid = false;
+	if (sc->abi_version != MTSGPU_ABI_VERSION) return fail(c, MTSGPU_EINVAL, "scene ABI version %u != %d", sc->abi_version, MTSGPU_ABI_VERSION);
+	if (sc->n_nodes == 0 || !sc->kd_nodes) return fail(c, MTSGPU_EINVAL, "scene has no kd-tree");
+	if (sc->n_lums == 0) return fail(c, MTSGPU_EINVAL, "scene has no luminaire (Scene::initialize would add a constant one, scene.cpp:310-318)");
+	HIPCHK(c, hipSetDevice(c->device));
+	// --- validate everything the kernels index with (an out-of-range index would fault the GPU) ---
+	for (uint32_t i = 0; i < sc->n_nodes; ++i) {
+		const uint32_t a = sc->kd_nodes[2 * (size_t) i], b = sc->kd_nodes[2 * (size_t) i + 1];
+		if (a & 0x80000000u) {
+			if ((a & 0x7FFFFFFFu) > b || b > sc->n_indices) return fail(c, MTSGPU_EINVAL, "kd leaf %u: index range out of bounds", i);
+		} else {
+			if (a & 0x40000000u) return fail(c, MTSGPU_EINVAL, "kd node %u: indirection nodes are not supported (gkdtree.h:1116-1126 removes them)", i);
+			const uint64_t left = (uint64_t) i + ((a & 0x3FFFFFFCu) >> 2);
+			if ((a & 3u) == 3u || left <= i || left + 1 >= sc->n_nodes) return fail(c, MTSGPU_EINVAL, "kd node %u: bad axis/child offset", i);
+		}
+	}
+	{
+		// every node is reached exactly once from the root (the device order below is built by walking the tree: an
+		// unreached node would land on the root's slot, a shared one twice) and no branch is deeper than the traversal
+		// stack of k_trace (LDS levels + spill levels; the reference's own limit is MTS_KD_MAXDEPTH = 48, gkdtree.h:35)
+		const uint32_t depthLimit = (uint32_t) trace_stack_levels() - 2;
+		std::vector<uint8_t> seen(sc->n_nodes, 0);
+		std::vector<std::pair<uint32_t, uint32_t>> stack;       // node, depth
+		stack.emplace_back(0u, 1u);
+		uint32_t visited = 0;
+		while (!stack.empty()) {
+			const auto [i, depth] = stack.back(); stack.pop_back();
+			if (seen[i]) return fail(c, MTSGPU_EINVAL, "kd node %u is the child of two nodes", i);
+			seen[i] = 1; ++visited;
+			const uint32_t a = sc->kd_nodes[2 * (size_t) i];
+			if (a & 0x80000000u) continue;
+			if (depth >= depthLimit) return fail(c, MTSGPU_EINVAL, "kd-tree deeper than %u levels", depthLimit);
+			const uint32_t left = i + ((a & 0x3FFFFFFCu) >> 2);
+			stack.emplace_back(left + 1, depth + 1); stack.emplace_back(left, depth + 1);
+		}
+		if (visited != sc->n_nodes) return fail(c, MTSGPU_EINVAL, "kd-tree: %u of %u nodes are unreachable from the root", sc->n_nodes - visited, sc->n_nodes);
+	}
+	for (uint32_t i = 0; i < sc->n_indices; ++i)
+		if (sc->kd_indices[i] >= sc->n_tris) return fail(c, MTSGPU_EINVAL, "kd index %u out of range", i);
+	if ((sc->shape_type == nullptr) != (sc->shape_params == nullptr)) return fail(c, MTSGPU_EINVAL, "shape_type and shape_params must both be given or both be NULL");
+	auto shapeType = [&](uint32_t s) { return sc->shape_type ? sc->shape_type[s] : (uint32_t) MTSGPU_SHAPE_TRIMESH; };
+	for (uint32_t s = 0; s < sc->n_shapes; ++s) {
+		if (shapeType(s) > MTSGPU_SHAPE_SPHERE) return fail(c, MTSGPU_EINVAL, "shape %u: unknown shape type", s);
+		if (sc->shape_tri_offset[s] > sc->shape_tri_offset[s + 1] || sc->shape_tri_offset[s + 1] > sc->n_tris) return fail(c, MTSGPU_EINVAL, "shape_tri_offset not monotone");
+		const bool mesh = shapeType(s) == MTSGPU_SHAPE_TRIMESH;
+		if (!mesh) {
+			// any other shape is ONE kd-tree primitive (skdtree.cpp:54-57)
+			if (sc->shape_tri_offset[s + 1] - sc->shape_tri_offset[s] != 1) return fail(c, MTSGPU_EINVAL, "shape %u: a non-mesh shape must own exactly one primitive", s);
+			const float *SP = sc->shape_params + (size_t) MTSGPU_SHAPE_NPARAMS * s;
+			for (int i = 0; i < MTSGPU_SHAPE_NPARAMS; ++i) if (!std::isfinite(SP[i])) return fail(c, MTSGPU_EINVAL, "shape %u: non-finite parameter", s);
+			if (SP[3] == 0.0f) return fail(c, MTSGPU_EINVAL, "shape %u: zero radius", s);
+		}
+		for (uint32_t t = sc->shape_tri_offset[s]; t < sc->shape_tri_offset[s + 1]; ++t) {
+			const uint32_t k = sc->triaccel[12 * (size_t) t];
+			if (mesh) {
+				if (k == MTSGPU_KNOTRIANGLE) return fail(c, MTSGPU_EINVAL, "TriAccel %u: a mesh triangle is marked as a shape", t);
+				for (int j = 0; j < 3; ++j)
+					if (sc->tri_idx[3 * (size_t) t + j] >= sc->n_verts) return fail(c, MTSGPU_EINVAL, "triangle vertex index out of range");
+			} else if (k != MTSGPU_KNOTRIANGLE) {
+				return fail(c, MTSGPU_EINVAL, "TriAccel %u: the primitive of a non-mesh shape must have k = KNoTriangleFlag", t);
+			}
+			if (sc->triaccel[12 * (size_t) t + 10] != s) return fail(c, MTSGPU_EINVAL, "TriAccel %u: shape index does not match shape_tri_offset", t);
+		}
+	}
+	for (uint32_t s = 0; s < sc->n_shapes; ++s) {
+		if (sc->shape_bsdf[s] >= (int32_t) sc->n_bsdfs || sc->shape_lum[s] >= (int32_t) sc->n_lums) return fail(c, MTSGPU_EINVAL, "shape %u: bad BSDF/luminaire index", s);
+		if (sc->shape_tri_offset[s] > sc->shape_tri_offset[s + 1]) return fail(c, MTSGPU_EINVAL, "shape_tri_offset not monotone");
+		if (sc->shape_lum[s] >= 0 && (sc->lum_type[sc->shape_lum[s]] != MTSGPU_LUM_AREA || sc->lum_shape[sc->shape_lum[s]] != (int32_t) s))
+			return fail(c, MTSGPU_EINVAL, "shape %u: luminaire link is inconsistent", s);
+	}
+	if (sc->shape_tri_offset[sc->n_shapes] != sc->n_tris) return fail(c, MTSGPU_EINVAL, "shape_tri_offset does not cover all triangles");
+	for (uint32_t t = 0; t < sc->n_tris; ++t)
+		if (sc->triaccel[12 * (size_t) t + 10] >= sc->n_shapes) return fail(c, MTSGPU_EINVAL, "TriAccel %u: shape index out of range", t);
+	{
+		const std::string why = checkBsdfTable(sc->n_bsdfs, sc->bsdf_type, sc->bsdf_params);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+		// an anisotropic BSDF needs a tangent frame: spheres have one (dpdu / dpdv), a triangle mesh when the caller hands its
+		// vertex tangents over.  Without them the reference renders a mesh that has no vertex normals with the frame it has
+		// (trimesh.cpp:562-565); mtsgpu_upload_scene keeps refusing every such mesh
+		for (uint32_t s = 0; s < sc->n_shapes; ++s) {
+			const bool has = shape_has_tangents && shape_has_tangents[s];
+			if (has && shapeType(s) != MTSGPU_SHAPE_TRIMESH) return fail(c, MTSGPU_EINVAL, "shape %u: only a triangle mesh can carry tangents", s);
+			if (has && !(sc->shape_flags[s] & MTSGPU_SHAPE_HAS_NORMALS)) return fail(c, MTSGPU_EINVAL, "shape %u: tangents need vertex normals (trimesh.cpp:562-565)", s);
+			if (has || !(sc->shape_bsdf[s] >= 0 && !shapeHasTangentFrame(shapeType(s)) && bsdfIsAnisotropic(sc->bsdf_type, sc->bsdf_params, (uint32_t) sc->shape_bsdf[s])))
+				continue;
+			if (!withTangents || (sc->shape_flags[s] & MTSGPU_SHAPE_HAS_NORMALS))
+				return fail(c, MTSGPU_EINVAL, "%s", anisotropicOnMeshMessage(s).c_str());
+		}
+	}
+	// the gather array of the tangents: dpdu of the three vertices of every primitive of a mesh that has them, zero elsewhere
+	std::vector<float> triDpdu;
+	std::vector<uint32_t> hasTan;
+	{
+		bool any = false;
+		for (uint32_t s = 0; s < sc->n_shapes; ++s) any |= shape_has_tangents && shape_has_tangents[s];
+		if (any) {
+			triDpdu.assign(4 * (size_t) kTriDpduStride * ((size_t) sc->n_tris + 1), 0.0f);
+			hasTan.assign((size_t) sc->n_shapes + 1, 0u);
+			for (uint32_t s = 0; s < sc->n_shapes; ++s) {
+				if (!shape_has_tangents[s]) continue;
+				hasTan[s] = 1u;
+				uint32_t v;      // the indices were checked above
+				if (!gatherMeshRows(sc->tri_idx, sc->shape_tri_offset[s], sc->shape_tri_offset[s + 1], vtx_dpdu, 3, kTriDpduStride, triDpdu.data(), &v))
+					return fail(c, MTSGPU_EINVAL, "shape %u: non-finite tangent at vertex %u", s, v);
+			}
+		}
+	}
+	float skyDerived[MTSGPU_SKY_NDERIVED] = { 0 };      // SkyLuminaire::configure() of the background sky, filled by its check
+	for (uint32_t l = 0; l < sc->n_lums; ++l) {
+		if (sc->lum_type[l] == MTSGPU_LUM_AREA) {
+			const int32_t s = sc->lum_shape[l];
+			if (s < 0 || s >= (int32_t) sc->n_shapes) return fail(c, MTSGPU_EINVAL, "luminaire %u: bad shape", l);
+			const uint32_t n = sc->shape_tri_offset[s + 1] - sc->shape_tri_offset[s];
+			if (shapeType((uint32_t) s) != MTSGPU_SHAPE_TRIMESH) {
+				if (sc->lum_cdf_offset[l + 1] != sc->lum_cdf_offset[l]) return fail(c, MTSGPU_EINVAL, "luminaire %u: a non-mesh emitter has no triangle CDF", l);
+			} else if (sc->lum_cdf_offset[l + 1] - sc->lum_cdf_offset[l] != n + 1) return fail(c, MTSGPU_EINVAL, "luminaire %u: CDF size mismatch", l);
+		} else if (sc->lum_type[l] == MTSGPU_LUM_ENVMAP) {
+			// everything env_triangle / env_pdf index with (envmap.cpp:123-193)
+			if ((int32_t) l != sc->background_lum) return fail(c, MTSGPU_EINVAL, "luminaire %u: the envmap must be the background luminaire", l);
+			const uint64_t np = (uint64_t) sc->env_pdf_width * sc->env_pdf_height;
+			if (!sc->env_pixels || !sc->env_pdf || !sc->env_cdf || sc->env_width == 0 || sc->env_height == 0 || np == 0
+			    || sc->env_width > 16384 || sc->env_height > 16384 || np > (1u << 26))
+				return fail(c, MTSGPU_EINVAL, "luminaire %u: missing or oversized environment map", l);
+			for (uint64_t i = 0; i < np; ++i)
+				if (!(sc->env_cdf[i] <= sc->env_cdf[i + 1]) || !(sc->env_pdf[i] >= 0.0f)) return fail(c, MTSGPU_EINVAL, "luminaire %u: the environment map's CDF is not monotone", l);
+			const float *LP = sc->lum_params + (size_t) MTSGPU_LUM_NPARAMS * l;
+			for (int i = 0; i < 25; ++i) if (!std::isfinite(LP[i])) return fail(c, MTSGPU_EINVAL, "luminaire %u: non-finite parameter", l);
+		} else if (sc->lum_type[l] == MTSGPU_LUM_SKY) {
+			const std::string why = checkSkyLuminaire(l, sc->lum_params + (size_t) MTSGPU_LUM_NPARAMS * l, sc->background_lum, skyDerived);
+			if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+		} else if (sc->lum_type[l] > MTSGPU_LUM_COLLIMATED) {
+			return fail(c, MTSGPU_EINVAL, "luminaire %u: unknown type", l);
+		}
+	}
+	if (sc->background_lum >= (int32_t) sc->n_lums) return fail(c, MTSGPU_EINVAL, "background luminaire out of range");
+
+	freeAll(c->sceneAllocs);
+	freeAll(c->colorAllocs);      // a new scene starts without vertex colours (mtsgpu_set_vertex_colors)
+	c->dcol = DColors{ nullptr, nullptr };
+	c->hostColorSlots.clear();
+	freeAll(c->texAllocs);        // ... and without uv textures (mtsgpu_set_uv_textures)
+	c->dtex = DTextures{ nullptr, nullptr, nullptr };
+	c->hostSlotTex.clear();
+	c->dtan = DTangents{ nullptr, nullptr };      // ... and its tangents go with the scene's arrays
+	c->haveScene = false;
+	DScene d{};
+	int rc = 0;
+	{
+		// Device node order.  The first trace_top_nodes() slots hold the root and the sibling pairs below it in
+		// breadth-first order: k_trace keeps the first half of that prefix in LDS (kernels.h: kTopNodes).  After it,
+		// 128-byte lines (16 nodes) are filled with breadth-first pieces of subtrees ("treelets") so that one L1 miss
+		// serves several consecutive traversal steps.
+		// The KDNode encoding is unchanged (siblings adjacent, relative offset to the left child,
+		// gkdtree.h:442-470); only where a node lives changes, which traversal results do not depend on.
+		const uint32_t N = sc->n_nodes;
+		const uint32_t topSlots = trace_top_nodes();
+		std::vector<uint32_t> newIndex(N, 0u);
+		std::vector<uint32_t> stack, cand;           // entries: old index of the left node of a sibling pair
+		auto leftOf = [&](uint32_t i) { return i + ((sc->kd_nodes[2 * (size_t) i] & 0x3FFFFFFCu) >> 2); };
+		auto isLeaf = [&](uint32_t i) { return (sc->kd_nodes[2 * (size_t) i] & 0x80000000u) != 0; };
+		uint32_t pos = 2;                            // slot 0 = root, slot 1 = padding
+		newIndex[0] = 0;
+		if (!isLeaf(0)) cand.push_back(leftOf(0));
+		size_t head = 0;
+		while (head < cand.size() || !stack.empty()) {
+			if (head == cand.size()) { cand.clear(); head = 0; cand.push_back(stack.back()); stack.pop_back(); }
+			const uint32_t l = cand[head++];
+			newIndex[l] = pos; newIndex[l + 1] = pos + 1;
+			pos += 2;
+			for (uint32_t k = 0; k < 2; ++k)
+				if (!isLeaf(l + k)) cand.push_back(leftOf(l + k));
+			const bool full = pos < topSlots ? false : (pos == topSlots || (pos & 15u) == 0u);
+			if (full) {
+				// region full: the remaining frontier becomes the roots of later treelets (depth-first order)
+				for (size_t k = cand.size(); k > head; --k) stack.push_back(cand[k - 1]);
+				cand.clear(); head = 0;
+			}
+		}
+		const uint32_t total = std::max<uint32_t>(pos, std::max(2u, topSlots));      // the LDS prefix is always there to copy
+		if (total >= (1u << 29)) return fail(c, MTSGPU_EINVAL, "kd-tree too large");      // absolute child indices; k_trace's stack words keep node index * 2 below bit 30
+		std::vector<uint32_t> dev(2 * (size_t) total, 0u);
+		dev[2] = 0x80000000u; dev[3] = 0u;           // padding slot: empty leaf, never referenced
+		for (uint32_t i = 0; i < N; ++i) {
+			const uint32_t a = sc->kd_nodes[2 * (size_t) i], b = sc->kd_nodes[2 * (size_t) i + 1];
+			uint32_t *o = &dev[2 * (size_t) newIndex[i]];
+			if (a & 0x80000000u) { o[0] = a; o[1] = b; }
+			else { o[0] = (a & 3u) | (newIndex[leftOf(i)] << 2); o[1] = b; }     // absolute left-child index (< 2^29)
+		}
+		rc |= upload(c, (const uint32_t **) &d.nodes, dev.data(), dev.size());
+	}
+	{
+		// TriAccel records re-laid out in leaf order (one contiguous run per leaf, no index
+		// indirection on the device); non-occluders are shapes without a BSDF
+		// (Shape::isOccluder, shape.h:324)
+		const size_t LS = 4 * (size_t) kLeafStride;                 // dwords per record slot
+		std::vector<uint32_t> ta(LS * ((size_t) sc->n_indices + 1), 0u);
+		for (uint32_t e = 0; e < sc->n_indices; ++e) {
+			const uint32_t prim = sc->kd_indices[e];
+			uint32_t *dst = &ta[LS * (size_t) e];
+			std::memcpy(dst, sc->triaccel + 12 * (size_t) prim, 48);
+			// dword 0 = k<<30 | non-occluder<<29 | primitive id (the head of the record decides everything
+			// up to the plane distance); dword 10 stays the shape index
+			if (prim >= (1u << 28)) return fail(c, MTSGPU_EINVAL, "more than 2^28 primitives");
+			const bool isShape = dst[0] == MTSGPU_KNOTRIANGLE;
+			dst[0] = (std::min(dst[0], 3u) << 30) | (sc->shape_bsdf[dst[10]] < 0 ? 0x20000000u : 0u) | prim;
+			dst[11] = 0;
+			if ((dst[0] >> 30) == 3u) {
+				// k == 3: a degenerate triangle (dword 1 = 0) or a non-triangle shape (dword 1 = shape type,
+				// dwords 4..7 = centre and radius of the sphere)
+				dst[1] = 0;
+				if (isShape) {
+					const float *SP = sc->shape_params + (size_t) MTSGPU_SHAPE_NPARAMS * dst[10];
+					dst[1] = shapeType(dst[10]);
+					std::memcpy(dst + 4, SP, 16);
+				}
+			}
+		}
+		rc |= upload(c, (const uint32_t **) &d.leaf_ta, ta.data(), ta.size());
+		// per-primitive position / normal records for the shading kernels
+		const size_t TS = 4 * (size_t) kTriStride;                    // floats per record (one 128-byte line)
+		std::vector<float> triRec(TS * ((size_t) sc->n_tris + 1), 0.0f);
+		for (uint32_t s = 0; s < sc->n_shapes; ++s)
+			for (uint32_t t = sc->shape_tri_offset[s]; t < sc->shape_tri_offset[s + 1]; ++t) {
+				float *P = &triRec[TS * (size_t) t], *Nn = P + 12;
+				if (shapeType(s) != MTSGPU_SHAPE_TRIMESH) {
+					// non-mesh shape: centre + radius, flag bit 31 (the rest comes from shape_params)
+					const uint32_t flags = sc->shape_flags[s] | 0x80000000u;
+					std::memcpy(P, sc->shape_params + (size_t) MTSGPU_SHAPE_NPARAMS * s, 16);
+					std::memcpy(P + 10, &s, 4); std::memcpy(P + 11, &flags, 4);
+					continue;
+				}
+				for (int k = 0; k < 3; ++k) {
+					const uint32_t v = sc->tri_idx[3 * (size_t) t + k];
+					std::memcpy(P + 3 * k, sc->vtx_pos + 3 * (size_t) v, 12);
+					std::memcpy(Nn + 3 * k, sc->vtx_nrm + 3 * (size_t) v, 12);
+				}
+				const uint32_t flags = sc->shape_flags[s];
+				std::memcpy(P + 10, &s, 4); std::memcpy(P + 11, &flags, 4);
+			}
+		rc |= upload(c, (const float **) &d.tri_pos, triRec.data(), triRec.size());
+		d.tri_nrm = d.tri_pos ? d.tri_pos + 3 : nullptr;
+	}
+	rc |= upload(c, &d.shape_bsdf, sc->shape_bsdf, sc->n_shapes);
+	rc |= upload(c, &d.shape_lum, sc->shape_lum, sc->n_shapes);
+	rc |= upload(c, &d.shape_flags, sc->shape_flags, sc->n_shapes);
+	{
+		std::vector<uint32_t> bin(sc->n_shapes + 1, (uint32_t) kNumBsdfTypes);
+		for (uint32_t sIdx = 0; sIdx < sc->n_shapes; ++sIdx)
+			if (sc->shape_bsdf[sIdx] >= 0) bin[sIdx] = sc->bsdf_type[sc->shape_bsdf[sIdx]] & 0xFFu;
+		rc |= upload(c, &d.shape_bin, bin.data(), bin.size());
+	}
+	{
+		std::vector<uint32_t> st(sc->n_shapes + 1, (uint32_t) MTSGPU_SHAPE_TRIMESH);
+		std::vector<float> sp((size_t) MTSGPU_SHAPE_NPARAMS * (sc->n_shapes + 1), 0.0f);
+		if (sc->shape_type) {
+			std::copy(sc->shape_type, sc->shape_type + sc->n_shapes, st.begin());
+			std::copy(sc->shape_params, sc->shape_params + (size_t) MTSGPU_SHAPE_NPARAMS * sc->n_shapes, sp.begin());
+		}
+		rc |= upload(c, &d.shape_type, st.data(), st.size());
+		rc |= upload(c, &d.shape_params, sp.data(), sp.size());
+	}
+	rc |= upload(c, &d.shape_tri_offset, sc->shape_tri_offset, (size_t) sc->n_shapes + 1);
+	rc |= upload(c, &d.bsdf_type, sc->bsdf_type, sc->n_bsdfs);
+	rc |= upload(c, &d.bsdf_params, sc->bsdf_params, (size_t) MTSGPU_BSDF_NPARAMS * sc->n_bsdfs);
+	rc |= upload(c, &d.lum_type, sc->lum_type, sc->n_lums);
+	rc |= upload(c, &d.lum_params, sc->lum_params, (size_t) MTSGPU_LUM_NPARAMS * sc->n_lums);
+	rc |= upload(c, &d.lum_shape, sc->lum_shape, sc->n_lums);
+	rc |= upload(c, &d.lum_inv_area, sc->lum_inv_area, sc->n_lums);
+	rc |= upload(c, &d.lum_cdf_offset, sc->lum_cdf_offset, (size_t) sc->n_lums + 1);
+	rc |= upload(c, &d.lum_tri_cdf, sc->lum_tri_cdf, sc->lum_cdf_offset[sc->n_lums]);
+	rc |= upload(c, &d.lum_sel_cdf, sc->lum_sel_cdf, (size_t) sc->n_lums + 1);
+	rc |= upload(c, &d.lum_sel_pdf, sc->lum_sel_pdf, sc->n_lums);
+	if (sc->background_lum >= 0 && sc->lum_type[sc->background_lum] == MTSGPU_LUM_ENVMAP) {
+		const size_t np = (size_t) sc->env_pdf_width * sc->env_pdf_height;
+		rc |= upload(c, &d.env_pixels, sc->env_pixels, 3 * (size_t) sc->env_width * sc->env_height);
+		rc |= upload(c, &d.env_pdf, sc->env_pdf, np);
+		rc |= upload(c, &d.env_cdf, sc->env_cdf, np + 1);
+		d.env_width = sc->env_width; d.env_height = sc->env_height;
+		d.env_pdf_width = sc->env_pdf_width; d.env_pdf_height = sc->env_pdf_height;
+	}
+	if (sc->background_lum >= 0 && sc->lum_type[sc->background_lum] == MTSGPU_LUM_SKY) {
+		// what SkyLuminaire::configure() derives (sky.cpp:139-179), once per scene
+		rc |= upload(c, (const float **) &d.sky, (const float *) skyDerived, (size_t) MTSGPU_SKY_NDERIVED);
+	}
+	const float *dDpdu = nullptr; const uint32_t *dHasTan = nullptr;
+	if (!triDpdu.empty()) {
+		rc |= upload(c, &dDpdu, triDpdu.data(), triDpdu.size());
+		rc |= upload(c, &dHasTan, hasTan.data(), hasTan.size());
+	}
+	if (rc) { freeAll(c->sceneAllocs); return rc; }
+	c->dtan = DTangents{ reinterpret_cast<const float4 *>(dDpdu), dHasTan };
+	d.lum_sel_sum = sc->lum_sel_sum; d.background_lum = sc->background_lum;
+	d.has_shapes = 0;
+	for (uint32_t s = 0; s < sc->n_shapes; ++s) if (shapeType(s) != MTSGPU_SHAPE_TRIMESH) d.has_shapes = 1;
+	d.n_lums = sc->n_lums; d.n_nodes = sc->n_nodes; d.n_tris = sc->n_tris; d.n_shapes = sc->n_shapes;
+	for (int a = 0; a < 3; ++a) { d.aabb_min[a] = sc->aabb_min[a]; d.aabb_max[a] = sc->aabb_max[a]; }
+	c->dsc = d; c->nTris = sc->n_tris;
+	{
+		mtsgpu_ctx::HostScene &h = c->host;
+		h.nVerts = sc->n_verts;
+		h.triIdx.assign(sc->tri_idx, sc->tri_idx + 3 * (size_t) sc->n_tris);
+		h.shapeTriOffset.assign(sc->shape_tri_offset, sc->shape_tri_offset + sc->n_shapes + 1);
+		h.shapeType.assign(sc->n_shapes, (uint32_t) MTSGPU_SHAPE_TRIMESH);
+		if (sc->shape_type) h.shapeType.assign(sc->shape_type, sc->shape_type + sc->n_shapes);
+		h.bsdfType.assign(sc->bsdf_type, sc->bsdf_type + sc->n_bsdfs);
+		h.bsdfParams.assign(sc->bsdf_params, sc->bsdf_params + (size_t) MTSGPU_BSDF_NPARAMS * sc->n_bsdfs);
+		h.shapeBsdf.assign(sc->shape_bsdf, sc->shape_bsdf + sc->n_shapes);
+		h.lumType.assign(sc->lum_type, sc->lum_type + sc->n_lums);
+	}
+	// material queues that can ever be non-empty: the BSDF types of shapes that have one, and the "terminal" bin
+	c->binMask = 1u << kNumBsdfTypes;
+	for (uint32_t sIdx = 0; sIdx < sc->n_shapes; ++sIdx)
+		if (sc->shape_bsdf[sIdx] >= 0) c->binMask |= 1u << (sc->bsdf_type[sc->shape_bsdf[sIdx]] & 0xFFu);
+	c->haveScene = true;
+	return 0;
+}
+
+int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) { return uploadScene(c, sc, nullptr, nullptr, false); }
+
+int mtsgpu_upload_scene_tangents(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_dpdu, const uint32_t *shape_has_tangents) {
+	if ((vtx_dpdu == nullptr) != (shape_has_tangents == nullptr))
+		return fail(c, MTSGPU_EINVAL, "vtx_dpdu and shape_has_tangents must both be given or both be NULL");
+	return uploadScene(c, sc, vtx_dpdu, shape_has_tangents, true);
+}
+
+// the slot tables of the host (host.h) and of the kernels (kernels.h) are one table
+constexpr bool colorSlotTablesAgree() {
+	for (int t = 0; t < MTSGPU_BSDF_NTYPES; ++t)
+		for (int k = 0; k < 2; ++k)
+			if (kBsdfColorSlotOffset[t][k] != bsdf_color_slot_offset(t, k)) return false;
+	return true;
+}
+static_assert(colorSlotTablesAgree(), "BSDF colour slot tables differ");
+
+int mtsgpu_set_vertex_colors(mtsgpu_ctx *c, const float *vtx_col, const uint32_t *shape_has_colors, const uint32_t *bsdf_color_slots) {
+	if (!c) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_set_vertex_colors before mtsgpu_upload_scene");
+	c->lastPass.valid = false;
+	HIPCHK(c, hipSetDevice(c->device));
+	// nothing may still read the arrays that go (the shading launches of a render that was not synchronised)
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
+	freeAll(c->colorAllocs);
+	c->dcol = DColors{ nullptr, nullptr };
+	c->hostColorSlots.clear();
+	if (!vtx_col && !shape_has_colors && !bsdf_color_slots) return 0;
+	if ((vtx_col == nullptr) != (shape_has_colors == nullptr))
+		return fail(c, MTSGPU_EINVAL, "vtx_col and shape_has_colors must both be given or both be NULL");
+	const mtsgpu_ctx::HostScene &h = c->host;
+	const uint32_t nShapes = (uint32_t) h.shapeBsdf.size(), nBsdfs = (uint32_t) h.bsdfType.size();
+	bool anySlot = false;
+	if (bsdf_color_slots) {
+		const std::string why = checkBsdfColorSlots(nBsdfs, h.bsdfType.data(), h.bsdfParams.data(), bsdf_color_slots);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+		if (!c->hostSlotTex.empty())      // a slot mtsgpu_set_uv_textures has given a texture
+			for (uint32_t b = 0; b < nBsdfs; ++b)
+				for (int s = 0; s < 2; ++s)
+					if (((bsdf_color_slots[b] >> s) & 1u) && c->hostSlotTex[2 * (size_t) b + s] >= 0)
+						return fail(c, MTSGPU_EINVAL, "BSDF %u: slot %d takes vertex colours and has a uv texture as well", b, s);
+		for (uint32_t s = 0; s < nShapes; ++s) {
+			const int32_t b = h.shapeBsdf[s];
+			if (b < 0 || !bsdf_color_slots[b]) continue;
+			if (h.shapeType[s] != MTSGPU_SHAPE_TRIMESH)
+				return fail(c, MTSGPU_EINVAL, "shape %u: BSDF %d takes vertex colours, but a sphere has none (its.color would be read unwritten, shape.h:162-163)", s, b);
+			if (!shape_has_colors || !shape_has_colors[s])
+				return fail(c, MTSGPU_EINVAL, "shape %u: BSDF %d takes vertex colours, but the mesh has none (its.color would be read unwritten, shape.h:162-163)", s, b);
+		}
+		for (uint32_t b = 0; b < nBsdfs; ++b) anySlot |= bsdf_color_slots[b] != 0;
+	}
+	if (!vtx_col) return 0;       // masks that are all zero and no colours: nothing to keep
+	// the gather array: the colours of the three vertices of every primitive of a coloured mesh, zero elsewhere
+	std::vector<float> triCol(4 * (size_t) kTriColStride * ((size_t) c->nTris + 1), 0.0f);
+	bool anyColors = false;
+	for (uint32_t s = 0; s < nShapes; ++s) {
+		if (!shape_has_colors[s]) continue;
+		if (h.shapeType[s] != MTSGPU_SHAPE_TRIMESH) return fail(c, MTSGPU_EINVAL, "shape %u: only a triangle mesh can carry vertex colours", s);
+		anyColors = true;
+		uint32_t v;
+		if (!gatherMeshRows(h.triIdx.data(), h.shapeTriOffset[s], h.shapeTriOffset[s + 1], vtx_col, 3, kTriColStride, triCol.data(), &v))
+			return fail(c, MTSGPU_EINVAL, "shape %u: non-finite colour at vertex %u", s, v);
+	}
+	if (!anyColors) return 0;
+	const float *dCol = nullptr; const uint32_t *dSlots = nullptr;
+	int rc = upload(c, &dCol, triCol.data(), triCol.size(), &c->colorAllocs);
+	if (!rc && anySlot) rc = upload(c, &dSlots, bsdf_color_slots, nBsdfs, &c->colorAllocs);
+	if (rc) { freeAll(c->colorAllocs); return rc; }
+	c->dcol = DColors{ reinterpret_cast<const float4 *>(dCol), dSlots };
+	if (anySlot) c->hostColorSlots.assign(bsdf_color_slots, bsdf_color_slots + nBsdfs);
+	return 0;
+}
+
+static_assert(sizeof(mtsgpu_uv_texture) == sizeof(DTexture) && offsetof(mtsgpu_uv_texture, line_width) == offsetof(DTexture, line_width)
+              && offsetof(mtsgpu_uv_texture, bright) == offsetof(DTexture, bright), "mtsgpu_uv_texture and DTexture are one layout");
+static_assert(MTSGPU_TEX_CHECKERBOARD == (int) kTexCheckerboard && MTSGPU_TEX_GRID == (int) kTexGrid, "texture kinds differ");
+
+// 2 * uv' of texture t at texcoord (u, v) stays inside the range of the reference's (int) cast, with the margin the header states
+static bool uvCastInRange(const mtsgpu_uv_texture &t, float u, float v) {
+	const double lim = 2147483648.0 - 65536.0;
+	const double x = 2.0 * ((double) u * t.uscale + t.uoffset), y = 2.0 * ((double) v * t.vscale + t.voffset);
+	return std::fabs(x) < lim && std::fabs(y) < lim;
+}
+
+int mtsgpu_set_uv_textures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
+                           const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture) {
+	if (!c) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_set_uv_textures before mtsgpu_upload_scene");
+	c->lastPass.valid = false;
+	HIPCHK(c, hipSetDevice(c->device));
+	// nothing may still read the arrays that go (the shading launches of a render that was not synchronised)
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
+	freeAll(c->texAllocs);
+	c->dtex = DTextures{ nullptr, nullptr, nullptr };
+	c->hostSlotTex.clear();
+	if (!vtx_uv && !shape_has_uv && !textures && !bsdf_slot_texture) return 0;
+	if ((vtx_uv == nullptr) != (shape_has_uv == nullptr))
+		return fail(c, MTSGPU_EINVAL, "vtx_uv and shape_has_uv must both be given or both be NULL");
+	if (n_textures && !textures) return fail(c, MTSGPU_EINVAL, "n_textures without textures");
+	if (n_textures > (1u << 20)) return fail(c, MTSGPU_EINVAL, "at most 2^20 textures");
+	const mtsgpu_ctx::HostScene &h = c->host;
+	const uint32_t nShapes = (uint32_t) h.shapeBsdf.size(), nBsdfs = (uint32_t) h.bsdfType.size();
+	for (uint32_t k = 0; k < n_textures; ++k) {
+		const std::string why = checkUvTexture(textures[k]);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "texture %u: %s", k, why.c_str());
+	}
+	bool anySlot = false;
+	if (bsdf_slot_texture) {
+		const std::string why = checkBsdfSlotTextures(nBsdfs, h.bsdfType.data(), h.bsdfParams.data(), bsdf_slot_texture, n_textures,
+		                                              c->hostColorSlots.empty() ? nullptr : c->hostColorSlots.data());
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+		for (size_t i = 0; i < 2 * (size_t) nBsdfs; ++i) anySlot |= bsdf_slot_texture[i] >= 0;
+	}
+	// the gather array: the texcoords of the three vertices of every primitive of a mesh that has them, zero elsewhere
+	const size_t US = 4 * (size_t) kTriUvStride;
+	std::vector<float> triUv(US * ((size_t) c->nTris + 1), 0.0f);
+	for (uint32_t s = 0; s < nShapes; ++s) {
+		const bool hasUv = shape_has_uv && shape_has_uv[s];
+		const bool mesh = h.shapeType[s] == MTSGPU_SHAPE_TRIMESH;
+		if (hasUv && !mesh) return fail(c, MTSGPU_EINVAL, "shape %u: only a triangle mesh can carry texture coordinates", s);
+		uint32_t bad;
+		if (hasUv && !gatherMeshRows(h.triIdx.data(), h.shapeTriOffset[s], h.shapeTriOffset[s + 1], vtx_uv, 2, kTriUvStride, triUv.data(), &bad))
+			return fail(c, MTSGPU_EINVAL, "shape %u: non-finite texcoord at vertex %u", s, bad);
+		// the casts of the textures this shape is shaded with
+		const int32_t b = h.shapeBsdf[s];
+		if (b < 0 || !bsdf_slot_texture) continue;
+		for (int slot = 0; slot < 2; ++slot) {
+			const int32_t k = bsdf_slot_texture[2 * (size_t) b + slot];
+			if (k < 0) continue;
+			bool ok = true;
+			if (!mesh) ok = uvCastInRange(textures[k], 0.0f, 0.0f) && uvCastInRange(textures[k], 1.0f, 1.0f);
+			else if (!hasUv) ok = uvCastInRange(textures[k], 0.0f, 0.0f);
+			else
+				for (uint32_t t = h.shapeTriOffset[s]; ok && t < h.shapeTriOffset[s + 1]; ++t)
+					for (int v = 0; v < 3; ++v) ok = ok && uvCastInRange(textures[k], triUv[US * (size_t) t + 2 * v], triUv[US * (size_t) t + 2 * v + 1]);
+			if (!ok)
+				return fail(c, MTSGPU_EINVAL, "shape %u: texture %d maps a texcoord outside the range of the (int) cast (|2 uv'| >= 2^31 - 2^16)", s, k);
+		}
+	}
+	if (!anySlot && !vtx_uv) return 0;       // nothing to keep
+	const float *dUv = nullptr; const DTexture *dTex = nullptr; const int32_t *dSlots = nullptr;
+	int rc = upload(c, &dUv, triUv.data(), triUv.size(), &c->texAllocs);
+	if (!rc && anySlot) rc = upload(c, &dTex, reinterpret_cast<const DTexture *>(textures), n_textures, &c->texAllocs);
+	if (!rc && anySlot) rc = upload(c, &dSlots, bsdf_slot_texture, 2 * (size_t) nBsdfs, &c->texAllocs);
+	if (rc) { freeAll(c->texAllocs); return rc; }
+	c->dtex = DTextures{ reinterpret_cast<const float4 *>(dUv), dTex, dSlots };
+	if (anySlot) c->hostSlotTex.assign(bsdf_slot_texture, bsdf_slot_texture + 2 * (size_t) nBsdfs);
+	return 0;
+}
+
+} // extern "C"

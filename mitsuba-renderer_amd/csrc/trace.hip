@@ -165,7 +165,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 					if (lane < (uint32_t) kNumBins && cnt != 0u)
 						base = atomicAdd(&q.counters[(lane * kBinShards + shard) * kCounterStride], cnt);
 					base = __shfl(base, bin < 0 ? 0 : bin);
-					// a shard's segment holds its share of a statically dealt queue (api.cpp: ensurePaths); dynamic claims
+					// a shard's segment holds its share of a statically dealt queue (render.cpp: ensurePaths); dynamic claims
 					// can in principle exceed it: the entry is dropped then, the counter still counts it, and the host
 					// repeats the launch with static dealing when it sees a count above the capacity
 					const uint32_t pos = base + rank;

@@ -60,6 +60,11 @@ def test_hook_refusals(gpu_lib, mts, scenes):
     with pytest.raises(mts.MtsGpuError, match=r"operation.*code -1"):
         it.scene_lum_eval(3, q)
     assert it.scene_lum_eval(0, q[:0]).shape == (0, 16)
+    # the count is refused before a record is read, so the two records' memory stands in for 2^24 + 1 of them
+    A, out = mts.abi, np.zeros((2, 16), np.float32)
+    for op in range(3):
+        with pytest.raises(mts.MtsGpuError, match=r"at most 2\^24 query records per call.*code -1"):
+            it._chk(mts.lib().mtsgpu_scene_lum_eval(it._ctx, op, (1 << 24) + 1, A.ptr(q, A.f32p), A.ptr(out, A.f32p)), "scene_lum_eval")
     scene, it = _upload(mts, by_name["quad"])
     with pytest.raises(mts.MtsGpuError, match=r"no background luminaire.*code -1"):
         it.scene_lum_eval(2, q)

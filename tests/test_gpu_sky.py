@@ -114,6 +114,11 @@ def test_hook_refusals(device, mts):
     Q = P.copy(); Q[6] = 0
     with pytest.raises(mts.MtsGpuError, match="positive radius"):
         device.lum_eval(SKY, Q, 0, d)
+    # the count is refused before a record is read, so one record's memory stands in for 2^24 + 1 of them
+    A, block, q, out = mts.abi, np.zeros(mts.abi.LUM_NPARAMS, np.float32), np.zeros(6, np.float32), np.zeros(12, np.float32)
+    block[:len(P)] = P
+    with pytest.raises(mts.MtsGpuError, match=r"at most 2\^24 query records per call.*code -1"):
+        device._chk(mts.lib().mtsgpu_lum_eval(device._ctx, SKY, A.ptr(block, A.f32p), 0, (1 << 24) + 1, A.ptr(q, A.f32p), A.ptr(out, A.f32p)), "lum_eval")
 
 
 # --- 2. background pixels --------------------------------------------------------------------------------------------

@@ -73,6 +73,10 @@ def test_frame_hook_equals_the_mirror(gpu_lib, mts, mirrors, device_tree):
     assert same_bits_or_nan(a, b).all() and np.isfinite(a).mean() > 0.99
     with pytest.raises(mts.MtsGpuError, match="out of range"):
         it.shading_frame_eval([scene.sc.n_tris], [[0, 0, 0]])
+    # the count is refused before a record is read, so one record's memory stands in for 2^24 + 1 of them
+    A, p1, f9 = mts.abi, np.zeros(1, np.uint32), np.zeros(9, np.float32)
+    with pytest.raises(mts.MtsGpuError, match=r"at most 2\^24 query records per call.*code -1"):
+        it._chk(mts.lib().mtsgpu_shading_frame_eval(it._ctx, (1 << 24) + 1, A.ptr(p1, A.u32p), A.ptr(f9, A.f32p), A.ptr(f9, A.f32p)), "shading_frame_eval")
 
 
 # --- 2. the refusals of mtsgpu_upload_scene_tangents ----------------------------------------------------------------------

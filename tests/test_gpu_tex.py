@@ -84,6 +84,11 @@ def test_uv_and_texture_value_are_the_mirror_bit_for_bit(gpu_lib, mts, tree):
     bad = st.descriptor(); bad.kind = 2
     with pytest.raises(mts.MtsGpuError, match="unknown kind"):
         it.uv_texture_eval(bad, [0], [[0.1, 0.1, 0]])
+    # the count is refused before a record is read, so one record's memory stands in for 2^24 + 1 of them
+    A, p1, f5 = mts.abi, np.zeros(1, np.uint32), np.zeros(5, np.float32)
+    with pytest.raises(mts.MtsGpuError, match=r"at most 2\^24 query records per call.*code -1"):
+        it._chk(mts.lib().mtsgpu_uv_texture_eval(it._ctx, mts.uv_texture_array([st]), (1 << 24) + 1, A.ptr(p1, A.u32p), A.ptr(f5, A.f32p),
+                                                 A.ptr(f5, A.f32p)), "uv_texture_eval")
     # without texcoords every mesh reads (0, 0); the sphere does not care
     it.set_uv_textures()
     got = it.uv_texture_eval(st, [0, off[3]], [[0.3, 0.3, 0], pts[20]])
@@ -148,6 +153,11 @@ def test_slot_hook_refuses_the_composite(device, mts):
         device.bsdf_eval_slots(9, np.zeros(16), [0, 0], [1, 1, 1], np.zeros((2, 3)), 0, [[0, 0, 1]], [[0, 0, 1]])
     with pytest.raises(mts.MtsGpuError, match="bad BSDF type"):
         device.bsdf_eval_slots(0x200, np.zeros(16), [0, 0], [1, 1, 1], np.zeros((2, 3)), 0, [[0, 0, 1]], [[0, 0, 1]])
+    # the count is refused before a record is read, so one record's memory stands in for 2^24 + 1 of them
+    A, P, q, out, src = mts.abi, np.full(16, 0.5, np.float32), np.zeros(6, np.float32), np.zeros(8, np.float32), np.zeros(2, np.int32)
+    with pytest.raises(mts.MtsGpuError, match=r"at most 2\^24 query records per call.*code -1"):
+        device._chk(mts.lib().mtsgpu_bsdf_eval_slots(device._ctx, 0, A.ptr(P, A.f32p), A.ptr(src, A.i32p), A.ptr(q, A.f32p), A.ptr(q, A.f32p), 0,
+                                                     (1 << 24) + 1, A.ptr(q, A.f32p), A.ptr(out, A.f32p)), "bsdf_eval_slots")
 
 
 # --- 3. refusals -------------------------------------------------------------------------------------------------------

@@ -69,6 +69,10 @@ def test_interpolation_is_the_mirror_bit_for_bit(gpu_lib, mts, tree):
     # the hook's own refusals
     with pytest.raises(mts.MtsGpuError, match="out of range"):
         it.vertex_color_eval([n_prims], [[0.1, 0.1]])
+    # the count is refused before a record is read, so one record's memory stands in for 2^24 + 1 of them
+    A, p1, f3 = mts.abi, np.zeros(1, np.uint32), np.zeros(3, np.float32)
+    with pytest.raises(mts.MtsGpuError, match=r"at most 2\^24 query records per call.*code -1"):
+        it._chk(mts.lib().mtsgpu_vertex_color_eval(it._ctx, (1 << 24) + 1, A.ptr(p1, A.u32p), A.ptr(f3, A.f32p), A.ptr(f3, A.f32p)), "vertex_color_eval")
     it.set_vertex_colors()
     with pytest.raises(mts.MtsGpuError, match="no vertex colours"):
         it.vertex_color_eval([0], [[0.1, 0.1]])
@@ -133,6 +137,11 @@ def test_coloured_hook_refuses_the_composite(device, mts):
         device.bsdf_eval_colored(9, np.zeros(16), 0, [1, 1, 1], 0, [[0, 0, 1]], [[0, 0, 1]])
     with pytest.raises(mts.MtsGpuError, match="bad BSDF type"):
         device.bsdf_eval_colored(0x200, np.zeros(16), 0, [1, 1, 1], 0, [[0, 0, 1]], [[0, 0, 1]])
+    # the count is refused before a record is read, so one record's memory stands in for 2^24 + 1 of them
+    A, P, q, out = mts.abi, np.full(16, 0.5, np.float32), np.zeros(6, np.float32), np.zeros(8, np.float32)
+    with pytest.raises(mts.MtsGpuError, match=r"at most 2\^24 query records per call.*code -1"):
+        device._chk(mts.lib().mtsgpu_bsdf_eval_colored(device._ctx, 0, A.ptr(P, A.f32p), 1, A.ptr(q, A.f32p), 0, (1 << 24) + 1, A.ptr(q, A.f32p),
+                                                       A.ptr(out, A.f32p)), "bsdf_eval_colored")
 
 
 # --- 3. refusals -------------------------------------------------------------------------------------------------------

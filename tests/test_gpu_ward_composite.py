@@ -82,6 +82,20 @@ def test_single_block_call_refuses_a_composite(device, mts):
     with pytest.raises(mts.MtsGpuError) as e:
         device.bsdf_eval_table([0, 9], np.zeros((2, 16), dtype=np.float32), 1, 0, [0, 0, 1], [[0, 0, 1]])
     assert "between 1 and 7 children" in str(e.value)
+    for btype, op in ((0x200, 0), (11, 0), (0, 3), (0, -1)):
+        with pytest.raises(mts.MtsGpuError, match="bad BSDF type or operation"):
+            device.bsdf_eval(btype, [0.5, 0.5, 0.5], op, [0, 0, 1], [[0, 0, 1]])
+
+
+def test_both_calls_take_at_most_2_24_records(device, mts):
+    """the count is refused before a record is read, so one record's memory stands in for 2^24 + 1 of them"""
+    A, L, n = mts.abi, mts.lib(), (1 << 24) + 1
+    P, q, out, types = np.full(16, 0.5, np.float32), np.zeros(6, np.float32), np.zeros(8, np.float32), np.zeros(1, np.uint32)
+    with pytest.raises(mts.MtsGpuError, match=r"at most 2\^24 query records per call.*code -1"):
+        device._chk(L.mtsgpu_bsdf_eval(device._ctx, 0, A.ptr(P, A.f32p), 0, n, A.ptr(q, A.f32p), A.ptr(out, A.f32p)), "bsdf_eval")
+    with pytest.raises(mts.MtsGpuError, match=r"at most 2\^24 query records per call.*code -1"):
+        device._chk(L.mtsgpu_bsdf_eval_table(device._ctx, 1, A.ptr(types, A.u32p), A.ptr(P, A.f32p), 0, 0, n, A.ptr(q, A.f32p),
+                                             A.ptr(out, A.f32p)), "bsdf_eval_table")
 
 
 # --- 2. the reference's chi-square test on the device ----------------------------------------------------------------

@@ -381,6 +381,58 @@ typedef struct mtsgpu_uv_texture {
 int  mtsgpu_set_uv_textures(mtsgpu_ctx *ctx, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
                             const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture);
 
+/* --- unfiltered bitmap textures: `ldrtexture` with filterType = "none" --------------------------------------------------------
+ * With that filter type the MIPMap has one level and nothing is resampled, so the bitmap may have any size, and
+ * Texture2D::getValue(its) returns the same texel with or without uv partials (mipmap.cpp:228-231 and :296-299 are one
+ * expression): its.uv is all the lookup needs.  In binary32, integer after the two floors:
+ *   uv' as above;  xPos = (int) floorf(uv'.x * (float) width), yPos likewise with height            (mipmap.cpp:229-231)
+ *   MIPMap::getTexel (mipmap.cpp:203-225) AS WRITTEN: if (xPos <= 0 || yPos < 0 || xPos >= width || yPos >= height) the wrap
+ *     mode applies -- repeat: modulo(., size), the non-negative remainder (util.cpp:424-427); clamp: to [0, size - 1]; black:
+ *     return 0; white: return 1.  Column 0 therefore counts as out of range (sic): harmless under repeat and clamp, but under
+ *     black and white every lookup in column 0 returns the constant
+ *   the texel is texels[yPos][xPos]
+ * The filtered modes (trilinear, ewa: ray differentials, the pyramid) are not served.  The three floats of a slot with a bitmap
+ * should hold getAverage() = triangle(levels - 1, 0, 0) = that lookup at uv' = (0, 0): texel (0, 0) under repeat and clamp, 0
+ * under black, 1 under white; verifyEnergyConservation reads getMaximum(), the per-channel maximum over the texels, at least 1
+ * under white (mipmap.cpp:137-154).
+ * MTSGPU_TEX_BITMAP is a kind of mtsgpu_uv_texture that only the calls below take: kind and the four Texture2D floats count,
+ * the other seven words are ignored (the library keeps width, height, wrap mode and the pool index there). */
+enum { MTSGPU_TEX_BITMAP = 2 };
+/* the four modes of MIPMap::EWrapMode in the order of getTexel's switch -- not the enum's own numbering (mipmap.h:32-37: repeat,
+ * black, white, clamp), which integration/streamparse.h translates */
+enum { MTSGPU_WRAP_REPEAT = 0, MTSGPU_WRAP_CLAMP = 1, MTSGPU_WRAP_BLACK = 2, MTSGPU_WRAP_WHITE = 3 };
+typedef struct mtsgpu_bitmap {
+	uint32_t width, height;
+	uint32_t wrap_mode;                      /* MTSGPU_WRAP_*                                             */
+	uint32_t reserved;                       /* 0                                                         */
+	const float *texels;                     /* [height][width][3] linear RGB: what m_pyramid[0] holds    */
+} mtsgpu_bitmap;
+/* The texels of all bitmaps of one call together number at most MTSGPU_BITMAP_MAX_TEXELS: the device indexes the pool with
+ * one uint32 and a dimension is an int in the reference.  The pool costs 16 bytes per texel in HBM. */
+#define MTSGPU_BITMAP_MAX_TEXELS 2147483647u
+/* mtsgpu_set_uv_textures with bitmaps: a superset of that call, as mtsgpu_upload_scene_tangents is of the upload.  bitmaps
+ * [n_bitmaps]; texture_bitmap [n_textures] names the bitmap of each texture of kind MTSGPU_TEX_BITMAP (several may share one;
+ * ignored for the other kinds; may be NULL when no texture is a bitmap).  Same ownership: either call replaces what the other
+ * one set, everything NULL switches textures off.  With n_bitmaps = 0 it does what mtsgpu_set_uv_textures does.  The same
+ * checks, and MTSGPU_EINVAL as well, naming the index, for a bitmap with a zero dimension, an unknown wrap mode, a non-zero
+ * reserved word, no texels, or a texel that is negative or not finite (clampNegative has run in the reference,
+ * mipmap.cpp:169); more than MTSGPU_BITMAP_MAX_TEXELS texels in all; a bitmap texture whose texture_bitmap entry is out of
+ * range; and, for a bitmap texture some slot uses and a shape whose BSDF has that slot, uv' * width or uv' * height reaching
+ * 2^31 - 2^16 in magnitude at a vertex (on a sphere: at uv = 0 or 1), the range of the (int) cast with the margin of
+ * mtsgpu_set_uv_textures. */
+int  mtsgpu_set_uv_bitmap_textures(mtsgpu_ctx *ctx, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
+                                   const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture, uint32_t n_bitmaps,
+                                   const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap);
+/* LDRTexture::initializeFrom (ldrtexture.cpp:116-202) and MIPMap::fromBitmap (mipmap.cpp:156-177) on the host: the decoded
+ * file's bytes -> the texels an mtsgpu_bitmap takes.  data: height rows of width pixels of bpp bits -- 32 (r g b a), 24 (r g b),
+ * 16 (luminance a), 8 (luminance), 1 (bit pos % 8 of byte pos / 8, pos counting pixels without row padding; set = 255).  The
+ * 256-entry table: gamma == -1 is sRGB (v <= 0.04045 ? v / 12.92 : powf((v + 0.055) / 1.055, 2.4) at v = i / 255), anything else
+ * powf(i / 255, gamma), in binary32 as the reference computes it on its host.  Alpha is dropped, fromLinearRGB is the identity
+ * of an RGB build, clampNegative is applied.  out [height][width][3].  No context: errors go to mtsgpu_last_error(NULL).
+ * MTSGPU_EINVAL for a null argument, a zero dimension, and any other bit depth ("%i bpp images are currently not
+ * supported!", the reference's message). */
+int  mtsgpu_ldr_texels(int bpp, uint32_t width, uint32_t height, const uint8_t *data, float gamma, float *out);
+
 /* --- the hot path (replaces SampleIntegrator::render, integrator.cpp:87-120) */
 int  mtsgpu_render(mtsgpu_ctx *ctx, volatile const int *cancel);
 int  mtsgpu_sync(mtsgpu_ctx *ctx);
@@ -468,6 +520,11 @@ int  mtsgpu_group_set_vertex_colors(mtsgpu_group *g, const float *vtx_col, const
 /* mtsgpu_set_uv_textures on every member */
 int  mtsgpu_group_set_uv_textures(mtsgpu_group *g, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
                                   const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture);
+
+/* mtsgpu_set_uv_bitmap_textures on every member */
+int  mtsgpu_group_set_uv_bitmap_textures(mtsgpu_group *g, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
+                                         const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture, uint32_t n_bitmaps,
+                                         const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap);
 
 /* HBM triad a[i] = b[i] + s * c[i] over three arrays of `bytes` each on `device` (float4 lanes, best of `iters`
  * launches): the practical bandwidth roof next to the 8 TB/s specification.  GB/s in *gbs. */
@@ -584,6 +641,11 @@ int  mtsgpu_bsdf_eval_colored(mtsgpu_ctx *ctx, uint32_t bsdf_type, const float *
  * is checked like the textures of mtsgpu_set_uv_textures, but for the int range of the cast, which is the caller's to keep.
  * A test hook: it calls the device functions the shading kernels call. */
 int  mtsgpu_uv_texture_eval(mtsgpu_ctx *ctx, const mtsgpu_uv_texture *tex, uint32_t n, const uint32_t *prim, const float *rec, float *out);
+/* mtsgpu_uv_texture_eval for a bitmap: tex of kind MTSGPU_TEX_BITMAP with its Texture2D floats, *bitmap checked like those of
+ * mtsgpu_set_uv_bitmap_textures and uploaded for this call alone; same records, same out [n][5].  mtsgpu_uv_texture_eval itself
+ * keeps refusing the kind.  A test hook: it calls the device functions the shading kernels call. */
+int  mtsgpu_bitmap_texture_eval(mtsgpu_ctx *ctx, const mtsgpu_uv_texture *tex, const mtsgpu_bitmap *bitmap, uint32_t n, const uint32_t *prim,
+                                const float *rec, float *out);
 /* mtsgpu_bsdf_eval_colored for scenes with uv textures: slot s takes nothing (slot_source[s] = 0), color[3] (1) or
  * values[s][3] (2, the texture's value at the hit).  Same ops, query and output layout; evaluated through the device function
  * that builds the per-hit block for the texture kernels, so it returns what mtsgpu_bsdf_eval returns for the block with

@@ -131,6 +131,12 @@ struct FlatScene {
 	std::vector<mtsgpu_uv_texture> uvTextures;
 	std::vector<int32_t> bsdfSlotTexture;
 	bool anyUv;
+	/* the `ldrtexture` instances with filterType none among them: what the stream says about each, its texels as
+	 * LDRTexture::initializeFrom leaves them (mtsgpu_ldr_texels over Mitsuba's own decoder), and its size -- what
+	 * mtsgpu_group_set_uv_bitmap_textures takes on top */
+	std::vector<mtsgpu_stream::LdrTexture> ldrTextures;
+	std::vector<std::vector<float> > ldrTexels;
+	std::vector<uint32_t> ldrWidth, ldrHeight;
 	/* vertex tangents (TriMesh::getVertexTangents, trimesh.h:136-140: TriMesh::configure computes them for a mesh whose BSDF is
 	 * anisotropic, trimesh.cpp:288-290): dpdu in the order of vtxPos, one flag per shape -- what
 	 * mtsgpu_group_upload_scene_tangents takes */
@@ -149,8 +155,19 @@ struct FlatScene {
 	 * without texcoords is then shaded with uv = (0, 0), as in the reference) */
 	int setUvTextures(mtsgpu_group *group) const {
 		if (uvTextures.empty()) return MTSGPU_OK;
-		return mtsgpu_group_set_uv_textures(group, anyUv ? ptr(vtxUv) : NULL, anyUv ? ptr(shapeHasUv) : NULL, (uint32_t) uvTextures.size(),
-			&uvTextures[0], ptr(bsdfSlotTexture));
+		if (ldrTextures.empty())      /* no bitmap: the call such a scene has always taken */
+			return mtsgpu_group_set_uv_textures(group, anyUv ? ptr(vtxUv) : NULL, anyUv ? ptr(shapeHasUv) : NULL, (uint32_t) uvTextures.size(),
+				&uvTextures[0], ptr(bsdfSlotTexture));
+		std::vector<mtsgpu_bitmap> bitmaps(ldrTextures.size());
+		std::vector<int32_t> textureBitmap(uvTextures.size(), -1);
+		for (size_t k = 0; k < ldrTextures.size(); ++k) {
+			bitmaps[k].width = ldrWidth[k]; bitmaps[k].height = ldrHeight[k];
+			bitmaps[k].wrap_mode = ldrTextures[k].wrapMode; bitmaps[k].reserved = 0;
+			bitmaps[k].texels = &ldrTexels[k][0];
+			textureBitmap[ldrTextures[k].texture] = (int32_t) k;
+		}
+		return mtsgpu_group_set_uv_bitmap_textures(group, anyUv ? ptr(vtxUv) : NULL, anyUv ? ptr(shapeHasUv) : NULL, (uint32_t) uvTextures.size(),
+			&uvTextures[0], ptr(bsdfSlotTexture), (uint32_t) bitmaps.size(), &bitmaps[0], &textureBitmap[0]);
 	}
 
 	/* after upload(): hands the colours over when a mesh has some or a BSDF slot asks for them (then the
@@ -423,6 +440,33 @@ private:
 		envCdf[n] = 1.0f;
 	}
 
+	/* An unfiltered `ldrtexture` the parser met in `st`: the encoded file goes through Mitsuba's own decoder, as
+	 * LDRTexture(Stream *, InstanceManager *) does (ldrtexture.cpp:98-103), the decoded bytes through mtsgpu_ldr_texels, and
+	 * the slots of the table entries from `firstEntry` on that show this texture receive its getAverage() = triangle(0, 0, 0)
+	 * (ldrtexture.cpp:206): texel (0, 0) under repeat and clamp, and -- column 0 counts as out of range, mipmap.cpp:207 -- 0
+	 * under black, 1 under white.  getMaximum() is not needed here: verifyEnergyConservation has run inside Mitsuba, and the
+	 * kd / ks of the stream are its result. */
+	void decodeLdrTexture(MemoryStream *st, const mtsgpu_stream::LdrTexture &t, size_t firstEntry) {
+		ref<MemoryStream> file = new MemoryStream(t.size);
+		file->write(st->getData() + t.offset, t.size);
+		file->setPos(0);
+		ref<Bitmap> bitmap = new Bitmap(static_cast<Bitmap::EFileFormat>(t.format), file);
+		const uint32_t w = (uint32_t) bitmap->getWidth(), h = (uint32_t) bitmap->getHeight();
+		std::vector<float> texels(3 * (size_t) w * h);
+		if (w == 0 || h == 0 || mtsgpu_ldr_texels(bitmap->getBitsPerPixel(), w, h, bitmap->getData(), t.gamma, &texels[0]) != MTSGPU_OK)
+			SLog(EError, "gpupath: texture \"%s\": %s", t.filename.c_str(), (w == 0 || h == 0) ? "empty bitmap" : mtsgpu_last_error(NULL));
+		float average[3] = { texels[0], texels[1], texels[2] };
+		if (t.wrapMode == MTSGPU_WRAP_BLACK || t.wrapMode == MTSGPU_WRAP_WHITE)
+			average[0] = average[1] = average[2] = t.wrapMode == MTSGPU_WRAP_WHITE ? 1.0f : 0.0f;
+		for (size_t b = firstEntry; b < bsdfType.size(); ++b)
+			for (int slot = 0; slot < 2; ++slot) {
+				const int o = mtsgpu_stream::bsdfSlotOffset(bsdfType[b], slot);
+				if (bsdfSlotTexture[2 * b + slot] == t.texture && o >= 0)
+					memcpy(&bsdfParams[MTSGPU_BSDF_NPARAMS * b + o], average, sizeof(average));
+			}
+		ldrTexels.push_back(texels); ldrWidth.push_back(w); ldrHeight.push_back(h);
+	}
+
 	/* BSDF parameter block of one BSDF instance (shared instances are stored once) */
 	int bsdfOf(const BSDF *bsdf) {
 		if (!bsdf) return -1;
@@ -431,9 +475,13 @@ private:
 		/* one entry, or for a composite its children first and then the composite itself, whose block points at them */
 		ref<MemoryStream> st = serializedBSDF(bsdf);
 		std::string err;
-		const int index = mtsgpu_stream::parseBSDFTable<Float>(st->getData(), st->getSize(), bsdfType, bsdfParams, &err, &bsdfColorSlots, &uvTextures, &bsdfSlotTexture);
+		const size_t firstEntry = bsdfType.size(), firstLdr = ldrTextures.size();
+		const int index = mtsgpu_stream::parseBSDFTable<Float>(st->getData(), st->getSize(), bsdfType, bsdfParams, &err, &bsdfColorSlots, &uvTextures, &bsdfSlotTexture,
+			&ldrTextures);
 		if (index < 0)
 			SLog(EError, "gpupath: %s", err.c_str());
+		for (size_t k = firstLdr; k < ldrTextures.size(); ++k)
+			decodeLdrTexture(st.get(), ldrTextures[k], firstEntry);
 		for (size_t b = 0; b < bsdfColorSlots.size(); ++b) if (bsdfColorSlots[b]) anyColorSlots = true;
 		bsdfIndex[bsdf] = index;
 		return index;

@@ -86,6 +86,28 @@ template <typename FloatT> inline void copy3x4(float *dst, const Matrix44<FloatT
  * BSDFs.  What <BSDF class>::serialize wrote -- the only access to the plugins' private parameters.  BSDFs have no parent
  * (BSDF::setParent is empty, bsdf.cpp:55-57) and their only children are textures.
  * ---------------------------------------------------------------------------------------------------------------- */
+/* First float of texture slot `slot` (0, 1) of BSDF type `type` inside its parameter block, -1 = the type has no such slot: the
+ * table of include/mtsgpu.h (mtsgpu_set_vertex_colors), for callers that write a slot's floats after parsing. */
+inline int bsdfSlotOffset(uint32_t type, int slot) {
+	static const int table[MTSGPU_BSDF_NTYPES][2] = { { 0, -1 }, { 2, 5 }, { 7, -1 }, { 5, 8 }, { 0, -1 }, { 5, 8 }, { 4, 7 }, { 0, -1 }, { 7, 10 }, { -1, -1 } };
+	type &= 0xFFu;
+	return (type < (uint32_t) MTSGPU_BSDF_NTYPES && (slot == 0 || slot == 1)) ? table[type][slot] : -1;
+}
+
+/* What LDRTexture::serialize wrote (src/textures/ldrtexture.cpp:210-228), as far as a parser without an image decoder can go:
+ * the fields, and where the bytes of the encoded file lie in the stream the caller handed over.  wrapMode is translated to
+ * MTSGPU_WRAP_* (MIPMap::EWrapMode numbers repeat, black, white, clamp: mipmap.h:32-37). */
+struct LdrTexture {
+	int32_t texture;             /* index of the texture's descriptor in the caller's mtsgpu_uv_texture list */
+	std::string filename;
+	float gamma;                 /* -1: sRGB */
+	int32_t format;              /* Bitmap::EFileFormat */
+	int32_t filterType;          /* MIPMap::EFilterType: always ENone = 2 here, the others are refused */
+	uint32_t wrapMode;           /* MTSGPU_WRAP_* */
+	float maxAnisotropy;
+	size_t offset; uint32_t size;      /* the encoded file: bytes [offset, offset + size) of the stream */
+};
+
 template <typename FloatT> class BSDFStream {
 public:
 	BSDFStream(const uint8_t *data, size_t size) : r(data, size) {
@@ -133,6 +155,49 @@ public:
 			m_uvTexIds[id] = cls;
 			return;
 		}
+		if (cls == "LDRTexture" && slot >= 0 && m_uvTextures && m_bitmaps) {
+			/* Texture2D::serialize, filename, gamma, format, filterType, wrapMode, maxAnisotropy, a uint32 size and that many
+			 * bytes of the encoded file.  Nothing is decoded here: the block's slot stays (0, 0, 0) until the caller, who has
+			 * the decoder, writes the texture's getAverage() there. */
+			skipReference();
+			mtsgpu_uv_texture t;
+			memset(&t, 0, sizeof(t));
+			t.kind = MTSGPU_TEX_BITMAP;
+			t.uoffset = (float) r.readFloat(); t.voffset = (float) r.readFloat();
+			t.uscale = (float) r.readFloat(); t.vscale = (float) r.readFloat();
+			LdrTexture b;
+			b.texture = (int32_t) m_uvTextures->size();
+			b.filename = r.readString();
+			b.gamma = (float) r.readFloat();
+			b.format = r.readInt();
+			b.filterType = r.readInt();
+			const uint32_t wrap = r.readUInt();
+			b.maxAnisotropy = (float) r.readFloat();
+			b.size = r.readUInt();
+			b.offset = r.pos();
+			b.wrapMode = 0;
+			if (!r.ok()) return;
+			if (b.filterType != 2) {                                                             /* MIPMap::ENone */
+				const char *filter = b.filterType == 0 ? "ewa" : b.filterType == 1 ? "trilinear" : "unknown";
+				r.fail(std::string(what) + " of " + m_className + " is an LDRTexture with filterType \"" + filter + "\": a filtered lookup needs ray "
+				       "differentials (the uv partials of every hit), which this path does not trace; set filterType to \"none\" for the unfiltered texel");
+				return;
+			}
+			static const uint32_t wrapOf[4] = { MTSGPU_WRAP_REPEAT, MTSGPU_WRAP_BLACK, MTSGPU_WRAP_WHITE, MTSGPU_WRAP_CLAMP };
+			if (wrap > 3) { r.fail(std::string(what) + " of " + m_className + " is an LDRTexture with unknown wrap mode " + std::to_string((unsigned long long) wrap)); return; }
+			b.wrapMode = wrapOf[wrap];
+			if (b.size > r.size() - b.offset) {
+				r.fail(std::string(what) + " of " + m_className + " is an LDRTexture whose encoded file (" + std::to_string((unsigned long long) b.size) + " bytes) is truncated");
+				return;
+			}
+			r.setPos(b.offset + b.size);
+			rgb[0] = rgb[1] = rgb[2] = 0.0f;
+			m_slotTextures[slot] = b.texture;
+			m_uvTextures->push_back(t);
+			m_bitmaps->push_back(b);
+			m_uvTexIds[id] = cls;
+			return;
+		}
 		if (cls == "VertexColors" && slot >= 0) {
 			skipReference();
 			rgb[0] = rgb[1] = rgb[2] = 1.0f;
@@ -154,6 +219,9 @@ public:
 	/* the list that receives the Checkerboard / GridTexture descriptors (what mtsgpu_set_uv_textures takes as `textures`);
 	 * without it these classes are refused like every non-constant texture */
 	void takeUvTextures(std::vector<mtsgpu_uv_texture> *list) { m_uvTextures = list; }
+	/* the list that receives one LdrTexture per unfiltered LDRTexture met (next to takeUvTextures, which receives its
+	 * descriptor); without it the class is refused like every non-constant texture */
+	void takeBitmaps(std::vector<LdrTexture> *list) { m_bitmaps = list; }
 	/* per slot of the block read since the last resetColorSlots(): the index of its texture in that list, or -1 */
 	const int32_t *slotTextures() const { return m_slotTextures; }
 	bool hasSlotTexture() const { return m_slotTextures[0] >= 0 || m_slotTextures[1] >= 0; }
@@ -164,7 +232,7 @@ public:
 		m_seen.insert(id);
 		const std::string cls = r.readString();
 		if (cls == "VertexColors") { r.fail(std::string(what) + " of " + m_className + " is a VertexColors texture: vertex colours are a spectrum, this slot takes a float texture; not supported"); return 0; }
-		if (cls == "Checkerboard" || cls == "GridTexture") { r.fail(std::string(what) + " of " + m_className + " is a " + cls + " texture: uv textures are supported in spectrum slots only, this slot takes a float texture; not supported"); return 0; }
+		if (cls == "Checkerboard" || cls == "GridTexture" || cls == "LDRTexture") { r.fail(std::string(what) + " of " + m_className + " is a " + cls + " texture: uv textures are supported in spectrum slots only, this slot takes a float texture; not supported"); return 0; }
 		if (cls != "ConstantFloatTexture") { r.fail(std::string(what) + " of " + m_className + " is a " + cls + "; only constant values are supported"); return 0; }
 		skipReference();
 		return r.readFloat();
@@ -196,6 +264,7 @@ private:
 	std::set<uint32_t> m_seen, m_colorIds;
 	std::map<uint32_t, std::string> m_uvTexIds;
 	std::vector<mtsgpu_uv_texture> *m_uvTextures = NULL;
+	std::vector<LdrTexture> *m_bitmaps = NULL;
 	int32_t m_slotTextures[2] = { -1, -1 };
 	uint32_t m_colorSlots = 0;
 	std::map<uint32_t, RGB> m_values;
@@ -289,12 +358,17 @@ template <typename FloatT> inline bool parseBSDF(const uint8_t *data, size_t siz
  * uvTextures, and slotTextures receives two entries per appended table entry, the index of the slot's texture in uvTextures
  * or -1 (what mtsgpu_set_uv_textures takes as `textures` and `bsdf_slot_texture`).  A composite child with a textured slot
  * is refused with the child's number.  Without them a Checkerboard or GridTexture is refused like any other texture. */
+/* bitmaps (optional, with uvTextures and slotTextures): one LdrTexture per LDRTexture with filterType none, whose descriptor
+ * (kind MTSGPU_TEX_BITMAP) goes to uvTextures; offset counts from `data`.  The slot's floats in the block are left 0: the
+ * caller decodes the file and writes getAverage() there.  Without the list an LDRTexture is refused like any other texture. */
 template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t size, std::vector<uint32_t> &types, std::vector<float> &params,
                                                      std::string *err, std::vector<uint32_t> *colorSlots = NULL,
-                                                     std::vector<mtsgpu_uv_texture> *uvTextures = NULL, std::vector<int32_t> *slotTextures = NULL) {
+                                                     std::vector<mtsgpu_uv_texture> *uvTextures = NULL, std::vector<int32_t> *slotTextures = NULL,
+                                                     std::vector<LdrTexture> *bitmaps = NULL) {
 	BSDFStream<FloatT> rd(data, size);
-	const size_t first = types.size(), firstTex = uvTextures ? uvTextures->size() : 0;
+	const size_t first = types.size(), firstTex = uvTextures ? uvTextures->size() : 0, firstBmp = bitmaps ? bitmaps->size() : 0;
 	if (uvTextures && slotTextures) rd.takeUvTextures(uvTextures);
+	if (uvTextures && slotTextures && bitmaps) rd.takeBitmaps(bitmaps);
 	uint32_t flags = 0;
 	if (rd.className() == "TwoSidedBRDF") { flags |= MTSGPU_BSDF_TWOSIDED; rd.enterNestedBSDF(); }
 	int own = -1;
@@ -345,6 +419,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 		if (colorSlots) colorSlots->resize(first);
 		if (slotTextures) slotTextures->resize(2 * first);
 		if (uvTextures) uvTextures->resize(firstTex);
+		if (bitmaps) bitmaps->resize(firstBmp);
 		if (err) *err = rd.r.error() + " (while reading a " + rd.className() + ")";
 		return -1;
 	}

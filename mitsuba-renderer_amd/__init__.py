@@ -42,6 +42,7 @@ EXPORTS = [
     "mtsgpu_flat_scene_shape_has_texcoords", "mtsgpu_loaded_mesh_texcoords", "mtsgpu_uv_texture_eval", "mtsgpu_bsdf_eval_slots",
     "mtsgpu_flatten_tangents", "mtsgpu_flat_scene_vertex_tangents", "mtsgpu_flat_scene_shape_has_tangents", "mtsgpu_upload_scene_tangents",
     "mtsgpu_group_upload_scene_tangents", "mtsgpu_shading_frame_eval", "mtsgpu_bin_entries",
+    "mtsgpu_set_uv_bitmap_textures", "mtsgpu_group_set_uv_bitmap_textures", "mtsgpu_bitmap_texture_eval", "mtsgpu_ldr_texels",
 ]
 
 
@@ -234,6 +235,11 @@ def lib():
     L.mtsgpu_upload_scene_tangents.argtypes = [vp, C.POINTER(abi.Scene), f32p, u32p]
     L.mtsgpu_group_upload_scene_tangents.argtypes = [vp, C.POINTER(abi.Scene), f32p, u32p]
     L.mtsgpu_shading_frame_eval.argtypes = [vp, C.c_uint32, u32p, f32p, f32p]
+    bmpp = C.POINTER(abi.Bitmap)
+    L.mtsgpu_set_uv_bitmap_textures.argtypes = [vp, f32p, u32p, C.c_uint32, texp, abi.i32p, C.c_uint32, bmpp, abi.i32p]
+    L.mtsgpu_group_set_uv_bitmap_textures.argtypes = [vp, f32p, u32p, C.c_uint32, texp, abi.i32p, C.c_uint32, bmpp, abi.i32p]
+    L.mtsgpu_bitmap_texture_eval.argtypes = [vp, texp, bmpp, C.c_uint32, u32p, f32p, f32p]
+    L.mtsgpu_ldr_texels.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_float, f32p]
     _lib = L
     return L
 
@@ -246,6 +252,47 @@ def uv_texture_array(textures):
     """a ctypes array of mtsgpu_uv_texture from scenes.Checkerboard / GridTexture objects (or abi.UvTexture values)"""
     items = [t if isinstance(t, abi.UvTexture) else t.descriptor() for t in textures]
     return (abi.UvTexture * max(len(items), 1))(*items) if items else (abi.UvTexture * 1)()
+
+
+def bitmap_array(bitmaps):
+    """a ctypes array of mtsgpu_bitmap from scenes.BitmapTexture objects (or abi.Bitmap values)"""
+    items = [b if isinstance(b, abi.Bitmap) else b.bitmap() for b in bitmaps]
+    return (abi.Bitmap * max(len(items), 1))(*items) if items else (abi.Bitmap * 1)()
+
+
+def bitmap_table(textures):
+    """(bitmaps, texture_bitmap) for a list of texture objects: one entry of `bitmaps` per distinct (texels array, wrap mode)
+    among the scenes.BitmapTexture objects, and for every texture the index of its bitmap, -1 for the other kinds"""
+    bitmaps, index = [], []
+    for t in textures:
+        if getattr(t, "kind", None) != abi.TEX_BITMAP or isinstance(t, abi.UvTexture):
+            index.append(-1)
+            continue
+        hit = [i for i, b in enumerate(bitmaps) if b.texels is t.texels and b.wrap == t.wrap]
+        if not hit:
+            bitmaps.append(t)
+        index.append(hit[0] if hit else len(bitmaps) - 1)
+    return bitmaps, np.asarray(index, dtype=np.int32)
+
+
+def ldr_texels(pixels, gamma=-1.0, bpp=None, width=None, height=None):
+    """mtsgpu_ldr_texels: the bytes of a decoded LDR file -> [height][width][3] linear RGB float32, as LDRTexture::initializeFrom
+    and MIPMap::fromBitmap leave them.  pixels: uint8 [height][width] (8 bpp) or [height][width][2 | 3 | 4] (16, 24, 32); or
+    flat bytes with bpp, width and height given (the only way to 1 bpp)"""
+    a = np.ascontiguousarray(pixels, dtype=np.uint8)
+    if bpp is None:
+        if a.ndim not in (2, 3):
+            raise ValueError("ldr_texels: pixels are [height][width] or [height][width][channels]")
+        height, width = a.shape[:2]
+        bpp = 8 * (a.shape[2] if a.ndim == 3 else 1)
+    width, height, bpp = int(width), int(height), int(bpp)
+    if bpp in (1, 8, 16, 24, 32) and a.size < (width * height * bpp + 7) // 8:
+        raise ValueError("ldr_texels: %d bytes for %d x %d pixels of %d bits" % (a.size, width, height, bpp))
+    out = np.zeros((height, width, 3), dtype=np.float32)
+    rc = lib().mtsgpu_ldr_texels(bpp, width, height, a.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_float(gamma), abi.ptr(out, abi.f32p))
+    if rc != 0:
+        raise MtsGpuError("mtsgpu_ldr_texels: %s" % lib().mtsgpu_last_error(None).decode())
+    return out
 
 
 class Scene:
@@ -291,6 +338,9 @@ class Scene:
                 if rc != 0:
                     raise MtsGpuError("mtsgpu_flat_scene_set_mesh_texcoords: %s" % lib().mtsgpu_last_error(None).decode())
         self.textures = uv_texture_array(getattr(description, "textures", []))
+        # the bitmaps behind the BitmapTexture objects among them (none: the scene takes mtsgpu_set_uv_textures as ever)
+        self._bitmap_objects, self.texture_bitmap = bitmap_table(getattr(description, "textures", []))
+        self.bitmaps = bitmap_array(self._bitmap_objects)
         table = np.asarray(getattr(description, "bsdf_slot_texture", []), dtype=np.int32).reshape(-1, 2)
         self.bsdf_slot_texture = np.ascontiguousarray(table) if (table >= 0).any() else None
 
@@ -315,6 +365,14 @@ class Scene:
         uv = lib().mtsgpu_flat_scene_vertex_texcoords(self._h)
         has = lib().mtsgpu_flat_scene_shape_has_texcoords(self._h)
         return (uv if uv else None, has if has else None, len(self.textures), self.textures, abi.ptr(self.bsdf_slot_texture, abi.i32p))
+
+    def uv_bitmap_texture_args(self):
+        """what mtsgpu_set_uv_bitmap_textures takes for this scene: uv_texture_args() and (n_bitmaps, bitmaps, texture_bitmap), or
+        None when no texture in a slot of the scene is a bitmap -- such a scene takes mtsgpu_set_uv_textures"""
+        ut = self.uv_texture_args()
+        if ut is None or not self._bitmap_objects:
+            return None
+        return ut + (len(self._bitmap_objects), self.bitmaps, abi.ptr(self.texture_bitmap, abi.i32p))
 
     def vertex_tangents(self):
         """(pool [n_verts][6] float32 = dpdu, dpdv; flags [n_shapes] uint32) of the flat scene, or (None, None) when no mesh has
@@ -461,7 +519,10 @@ class MIPathTracer:
         if vc is not None:
             self._chk(lib().mtsgpu_set_vertex_colors(self._ctx, *vc), "set_vertex_colors")
         ut = scene.uv_texture_args() if isinstance(scene, Scene) else None
-        if ut is not None:
+        ub = scene.uv_bitmap_texture_args() if isinstance(scene, Scene) else None
+        if ub is not None:
+            self._chk(lib().mtsgpu_set_uv_bitmap_textures(self._ctx, *ub), "set_uv_bitmap_textures")
+        elif ut is not None:
             self._chk(lib().mtsgpu_set_uv_textures(self._ctx, *ut), "set_uv_textures")
         self.camera = camera
         self._chk(lib().mtsgpu_set_camera(self._ctx, C.byref(camera.c if hasattr(camera, "c") else camera)), "set_camera")
@@ -649,6 +710,34 @@ class MIPathTracer:
         self._chk(lib().mtsgpu_set_uv_textures(self._ctx, abi.ptr(a, abi.f32p), abi.ptr(b, abi.u32p), 0 if t is None else len(t), t,
                                                abi.ptr(s, abi.i32p)), "set_uv_textures")
 
+    def set_uv_bitmap_textures(self, vtx_uv=None, shape_has_uv=None, textures=None, bsdf_slot_texture=None, bitmaps=None, texture_bitmap=None):
+        """mtsgpu_set_uv_bitmap_textures on the uploaded scene: set_uv_textures() with bitmaps (scenes.BitmapTexture objects or
+        abi.Bitmap) and the bitmap index per texture.  With bitmaps and texture_bitmap both None they are derived from the
+        BitmapTexture objects among `textures` (none: n_bitmaps = 0)"""
+        a = None if vtx_uv is None else np.ascontiguousarray(vtx_uv, dtype=np.float32)
+        b = None if shape_has_uv is None else np.ascontiguousarray(shape_has_uv, dtype=np.uint32)
+        if bitmaps is None and texture_bitmap is None and textures is not None:
+            bitmaps, texture_bitmap = bitmap_table(textures)
+        t = None if textures is None else uv_texture_array(textures)
+        s = None if bsdf_slot_texture is None else np.ascontiguousarray(bsdf_slot_texture, dtype=np.int32)
+        bm = None if not bitmaps else bitmap_array(bitmaps)
+        tb = None if texture_bitmap is None else np.ascontiguousarray(texture_bitmap, dtype=np.int32)
+        self._chk(lib().mtsgpu_set_uv_bitmap_textures(self._ctx, abi.ptr(a, abi.f32p), abi.ptr(b, abi.u32p), 0 if t is None else len(t), t,
+                                                      abi.ptr(s, abi.i32p), 0 if bm is None else len(bitmaps), bm, abi.ptr(tb, abi.i32p)),
+                  "set_uv_bitmap_textures")
+
+    def bitmap_texture_eval(self, texture, prim, rec, bitmap=None):
+        """uv_texture_eval() for a scenes.BitmapTexture (or an abi.UvTexture of kind TEX_BITMAP with an abi.Bitmap)
+        (mtsgpu_bitmap_texture_eval) -> [n][5] = uv, rgb"""
+        p = np.ascontiguousarray(prim, dtype=np.uint32).reshape(-1)
+        q = np.ascontiguousarray(rec, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((len(p), 5), dtype=np.float32)
+        t = uv_texture_array([texture])
+        bm = bitmap_array([texture if bitmap is None else bitmap])
+        self._chk(lib().mtsgpu_bitmap_texture_eval(self._ctx, t, bm, len(p), abi.ptr(p, abi.u32p), abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)),
+                  "bitmap_texture_eval")
+        return out
+
     def uv_texture_eval(self, texture, prim, rec):
         """its.uv and the texture's value on the device for records (primitive, (u, v, -) | world point) of the uploaded scene
         (mtsgpu_uv_texture_eval) -> [n][5] = uv, rgb"""
@@ -801,7 +890,10 @@ class DeviceGroup:
         if vc is not None:
             self._chk(lib().mtsgpu_group_set_vertex_colors(self._g, *vc), "set_vertex_colors")
         ut = scene.uv_texture_args() if isinstance(scene, Scene) else None
-        if ut is not None:
+        ub = scene.uv_bitmap_texture_args() if isinstance(scene, Scene) else None
+        if ub is not None:
+            self._chk(lib().mtsgpu_group_set_uv_bitmap_textures(self._g, *ub), "set_uv_bitmap_textures")
+        elif ut is not None:
             self._chk(lib().mtsgpu_group_set_uv_textures(self._g, *ut), "set_uv_textures")
         self.camera = camera
         self._chk(lib().mtsgpu_group_set_camera(self._g, C.byref(camera.c)), "set_camera")

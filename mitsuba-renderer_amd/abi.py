@@ -14,6 +14,9 @@ COMPOSITE_MAX = 7
 BSDF_COLOR_SLOTS = {0: (0,), 1: (2, 5), 2: (7,), 3: (5, 8), 4: (0,), 5: (5, 8), 6: (4, 7), 7: (0,), 8: (7, 10), 9: ()}
 BSDF_NPARAMS = 16
 TEX_CHECKERBOARD, TEX_GRID = 0, 1
+TEX_BITMAP = 2
+WRAP_REPEAT, WRAP_CLAMP, WRAP_BLACK, WRAP_WHITE = 0, 1, 2, 3      # MTSGPU_WRAP_* (not the numbering of MIPMap::EWrapMode)
+BITMAP_MAX_TEXELS = 2147483647
 LUM_AREA, LUM_CONSTANT, LUM_POINT, LUM_DIRECTIONAL, LUM_SPOT, LUM_ENVMAP, LUM_COLLIMATED, LUM_SKY = 0, 1, 2, 3, 4, 5, 6, 7
 LUM_NPARAMS = 32
 SKY_NDERIVED = 24
@@ -32,6 +35,11 @@ class UvTexture(C.Structure):
     """mtsgpu_uv_texture"""
     _fields_ = [("kind", C.c_uint32), ("uoffset", C.c_float), ("voffset", C.c_float), ("uscale", C.c_float), ("vscale", C.c_float),
                 ("bright", C.c_float * 3), ("dark", C.c_float * 3), ("line_width", C.c_float)]
+
+
+class Bitmap(C.Structure):
+    """mtsgpu_bitmap"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("wrap_mode", C.c_uint32), ("reserved", C.c_uint32), ("texels", f32p)]
 
 
 class Scene(C.Structure):

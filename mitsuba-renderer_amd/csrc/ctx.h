@@ -40,7 +40,7 @@ struct mtsgpu_ctx {
 	// mtsgpu_set_uv_textures: DTextures' arrays, owned like the colours', and host copies of the two slot tables in force
 	// (empty = none), so that each of the two calls can refuse a slot the other one has taken
 	std::vector<void *> texAllocs;
-	mg::DTextures dtex{ nullptr, nullptr, nullptr };
+	mg::DTextures dtex{ nullptr, nullptr, nullptr, nullptr };
 	// mtsgpu_upload_scene_tangents: DTangents' arrays, owned with the scene (sceneAllocs); NULL, NULL without a tangent mesh
 	mg::DTangents dtan{ nullptr, nullptr };
 	std::vector<uint32_t> hostColorSlots;
@@ -172,7 +172,9 @@ int ensureFilm(mtsgpu_ctx *c);
 int ensureFilmStats(mtsgpu_ctx *c);
 
 // scene_upload.cpp
-std::string checkUvTexture(const mtsgpu_uv_texture &t);
+std::string checkUvTexture(const mtsgpu_uv_texture &t, bool bitmaps = false);
+std::string checkBitmap(const mtsgpu_bitmap &b, uint64_t *total);
+void packBitmapTexels(const mtsgpu_bitmap &b, float *dst);
 
 // render.cpp
 void applyTuning(mtsgpu_ctx *c);

@@ -457,6 +457,20 @@ int mtsgpu_group_set_uv_textures(mtsgpu_group *g, const float *vtx_uv, const uin
 	return 0;
 }
 
+int mtsgpu_group_set_uv_bitmap_textures(mtsgpu_group *g, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
+                                        const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture, uint32_t n_bitmaps,
+                                        const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap) {
+	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
+	for (size_t i = 0; i < g->members.size(); ++i)
+		if (int r = mtsgpu_set_uv_bitmap_textures(g->members[i], vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture, n_bitmaps, bitmaps,
+		                                          texture_bitmap)) {
+			const std::string why = mtsgpu_last_error(g->members[i]);
+			for (size_t k = 0; k < i; ++k) (void) mtsgpu_set_uv_textures(g->members[k], nullptr, nullptr, 0, nullptr, nullptr);
+			return gfail(g, r, "set_uv_bitmap_textures: %s", why.c_str());
+		}
+	return 0;
+}
+
 int mtsgpu_hbm_triad(int device, size_t bytes, int iters, double *gbs) {
 	if (!gbs || bytes < 4096 || iters <= 0) return gfail(nullptr, MTSGPU_EINVAL, "bad triad arguments");
 	*gbs = 0;

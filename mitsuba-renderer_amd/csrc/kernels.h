@@ -137,23 +137,37 @@ constexpr int bsdf_color_slot_offset(int bt, int s) {
 	     : bt == 4 ? (s == 0 ? 0 : -1) : bt == 5 ? (s == 0 ? 5 : 8) : bt == 6 ? (s == 0 ? 4 : 7) : bt == 7 ? (s == 0 ? 0 : -1)
 	     : bt == 8 ? (s == 0 ? 7 : 10) : -1;
 }
-// The procedural uv textures (mtsgpu_set_uv_textures), all NULL without them.  Like DColors an argument of kernels of its own
-// (k_shade_tex, k_shade_all_tex) only.  tri_uv: a gather array in primitive order, kTriUvStride float4 per primitive =
-// t0.uv t1.uv | t2.uv - - (32 bytes, two aligned 16-byte loads; zero for spheres and for meshes without texcoords).
+// The uv textures (mtsgpu_set_uv_textures, mtsgpu_set_uv_bitmap_textures), all NULL without them.  Like DColors an argument of
+// kernels of its own (k_shade_tex, k_shade_all_tex) only.  tri_uv: a gather array in primitive order, kTriUvStride float4 per
+// primitive = t0.uv t1.uv | t2.uv - - (32 bytes, two aligned 16-byte loads; zero for spheres and for meshes without texcoords).
 // textures[n_textures]: one descriptor each.  bsdf_slot_texture[n_bsdfs][2]: the texture of slot s of the BSDF, -1 = none;
-// non-NULL only while some slot has one, and the shading launches pick their texture kernels by it
+// non-NULL only while some slot has one, and the shading launches pick their texture kernels by it.  texels: the pool of the
+// bitmaps, one float4 (r, g, b, unused) per texel, each bitmap row-major as [y][x] from DTexture::first on: a lookup is one
+// aligned 16-byte gather.  NULL while no texture is a bitmap
 struct DTexture {
-	uint32_t kind;                          // MTSGPU_TEX_CHECKERBOARD, MTSGPU_TEX_GRID
+	uint32_t kind;                          // MTSGPU_TEX_CHECKERBOARD, MTSGPU_TEX_GRID, MTSGPU_TEX_BITMAP
 	float uoffset, voffset, uscale, vscale; // Texture2D (texture.cpp:43-52)
-	float bright[3], dark[3];
-	float line_width;                       // gridtexture only
+	union {
+		struct {
+			float bright[3], dark[3];
+			float line_width;               // gridtexture only
+		};
+		struct {                            // kTexBitmap: level 0 of the MIPMap (filterType none: the only level)
+			uint32_t width, height;
+			uint32_t wrap;                  // kWrap*
+			uint32_t first;                 // index of texel (0, 0) in DTextures::texels
+			uint32_t reserved[3];
+		};
+	};
 };
 struct DTextures {
 	const float4   *tri_uv;
 	const DTexture *textures;
 	const int32_t  *bsdf_slot_texture;
+	const float4   *texels;
 };
-constexpr uint32_t kTexCheckerboard = 0, kTexGrid = 1;      // DTexture::kind = MTSGPU_TEX_*
+constexpr uint32_t kTexCheckerboard = 0, kTexGrid = 1, kTexBitmap = 2;      // DTexture::kind = MTSGPU_TEX_*
+constexpr uint32_t kWrapRepeat = 0, kWrapClamp = 1, kWrapBlack = 2, kWrapWhite = 3;      // DTexture::wrap = MTSGPU_WRAP_*
 constexpr int kTriUvStride = 2;       // float4 per primitive of DTextures::tri_uv
 // The vertex tangents of the meshes whose BSDF is anisotropic (mtsgpu_upload_scene_tangents), both NULL without such a mesh.
 // Like DColors and DTextures an argument of kernels of its own (k_shade_tan, k_shade_all_tan) only.  tri_dpdu: a gather array
@@ -406,6 +420,9 @@ void launch_bsdf_eval_slots(hipStream_t s, uint32_t type, const float *params, c
 // (u, v, -) on a triangle, the world-space hit point on a sphere; out [n][5] = uv, rgb
 void launch_uv_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, uint32_t n, const uint32_t *prim,
                             const float *rec, float *out);
+// mtsgpu_bitmap_texture_eval: the same for a bitmap descriptor (kTexBitmap) whose texels lie at texels[tex.first ...]
+void launch_bitmap_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, const float4 *texels, uint32_t n,
+                                const uint32_t *prim, const float *rec, float *out);
 // mtsgpu_shading_frame_eval: the shading frame of fill_its_tan for n records of the uploaded scene; rec as for
 // launch_uv_texture_eval; tan.shape_has_tan must be readable (all zero without tangents); out [n][9] = s, t, n
 void launch_shading_frame_eval(hipStream_t s, const DScene &sc, const DTangents &tan, uint32_t n, const uint32_t *prim, const float *rec, float *out);
@@ -433,12 +450,12 @@ struct BinView { uint32_t prefix[kBinShards + 1]; };
 void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                   const DQueues &q, const BinView &view, const BinView *views_dev = nullptr, uint32_t n_bound = 0,
                   const uint32_t *bin_ids = nullptr, const DColors &col = DColors{ nullptr, nullptr },
-                  const DTextures &tex = DTextures{ nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr });
+                  const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr });
 // device-driven bounces, path integrator / one-sample direct integrator: all bins of bin_mask in one launch; views_dev as
 // above, n_bound bounds the sum of the bin sizes
 void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,
                       const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound, const DColors &col = DColors{ nullptr, nullptr },
-                      const DTextures &tex = DTextures{ nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr });
+                      const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr });
 // device-driven bounces: per-bin views from the shard counters of the closest-hit launch that just ran (`cur`), and
 // the counter set of the next bounce zeroed
 void launch_prep(hipStream_t s, const uint32_t *cur, uint32_t *next_set, BinView *views_dev, uint32_t bin_seg_cap,

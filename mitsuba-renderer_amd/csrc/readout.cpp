@@ -357,6 +357,39 @@ int mtsgpu_uv_texture_eval(mtsgpu_ctx *c, const mtsgpu_uv_texture *tex, uint32_t
 	return s.finish("uv-texture read-out");
 }
 
+int mtsgpu_bitmap_texture_eval(mtsgpu_ctx *c, const mtsgpu_uv_texture *tex, const mtsgpu_bitmap *bitmap, uint32_t n, const uint32_t *prim,
+                               const float *rec, float *out) {
+	if (!c || !tex || !bitmap || !prim || !rec || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_bitmap_texture_eval before mtsgpu_upload_scene");
+	if (tex->kind != (uint32_t) MTSGPU_TEX_BITMAP) return fail(c, MTSGPU_EINVAL, "texture: kind %u is not a bitmap", tex->kind);
+	std::string why = checkUvTexture(*tex, true);
+	if (!why.empty()) return fail(c, MTSGPU_EINVAL, "texture: %s", why.c_str());
+	uint64_t nTexels = 0;
+	why = checkBitmap(*bitmap, &nTexels);
+	if (!why.empty()) return fail(c, MTSGPU_EINVAL, "bitmap: %s", why.c_str());
+	if (int rc = checkRecordCount(c, n)) return rc;
+	if (int rc = checkPrimitives(c, n, prim)) return rc;
+	if (n == 0) return 0;
+	std::vector<float> pool(4 * (size_t) nTexels);
+	packBitmapTexels(*bitmap, pool.data());
+	Scratch s(c);
+	const uint32_t *dP = s.put(prim, n);
+	const float *dRec = s.put(rec, (size_t) n * 3);
+	const float *dTexels = s.put(pool.data(), pool.size());
+	float *dOut = s.alloc<float>((size_t) n * 5);
+	const float4 *triUv = c->dtex.tri_uv;
+	if (!triUv) triUv = s.zeros<float4>(kTriUvStride * ((size_t) c->nTris + 1));      // no texcoords set: every mesh reads zero rows
+	if (s.ok()) {
+		DTexture t;
+		std::memcpy(&t, tex, sizeof t);
+		t.width = bitmap->width; t.height = bitmap->height; t.wrap = bitmap->wrap_mode; t.first = 0u;
+		t.reserved[0] = t.reserved[1] = t.reserved[2] = 0u;
+		launch_bitmap_texture_eval(c->stream, c->dsc, triUv, t, reinterpret_cast<const float4 *>(dTexels), n, dP, dRec, dOut);
+	}
+	s.get(out, dOut, (size_t) n * 5);
+	return s.finish("bitmap-texture read-out");
+}
+
 int mtsgpu_shading_frame_eval(mtsgpu_ctx *c, uint32_t n, const uint32_t *prim, const float *rec, float *out) {
 	if (!c || !prim || !rec || !out) return fail(c, MTSGPU_EINVAL, "null argument");
 	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_shading_frame_eval before mtsgpu_upload_scene");

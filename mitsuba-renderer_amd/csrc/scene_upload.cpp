@@ -8,11 +8,38 @@
 using namespace mg;
 
 // what mtsgpu_set_uv_textures and mtsgpu_uv_texture_eval require of one descriptor; the reason, or an empty string
-std::string mg::checkUvTexture(const mtsgpu_uv_texture &t) {
-	if (t.kind >= (uint32_t) MTSGPU_TEX_NKINDS) return "unknown kind " + std::to_string(t.kind);
+// (bitmaps: a call that takes MTSGPU_TEX_BITMAP, of which only the four Texture2D floats count)
+std::string mg::checkUvTexture(const mtsgpu_uv_texture &t, bool bitmaps) {
+	const bool bitmap = bitmaps && t.kind == (uint32_t) MTSGPU_TEX_BITMAP;
+	if (t.kind >= (uint32_t) MTSGPU_TEX_NKINDS && !bitmap) return "unknown kind " + std::to_string(t.kind);
 	const float *f = &t.uoffset;      // the eleven floats behind the kind
-	for (int i = 0; i < 11; ++i) if (!std::isfinite(f[i])) return "non-finite parameter";
+	for (int i = 0; i < (bitmap ? 4 : 11); ++i) if (!std::isfinite(f[i])) return "non-finite parameter";
 	return std::string();
+}
+
+// what mtsgpu_set_uv_bitmap_textures and mtsgpu_bitmap_texture_eval require of one bitmap; the reason, or an empty string.
+// *total counts the texels so far and is checked before any texel is read
+std::string mg::checkBitmap(const mtsgpu_bitmap &b, uint64_t *total) {
+	if (b.width == 0 || b.height == 0) return "zero dimension (" + std::to_string(b.width) + " x " + std::to_string(b.height) + ")";
+	if (b.wrap_mode > (uint32_t) MTSGPU_WRAP_WHITE) return "unknown wrap mode " + std::to_string(b.wrap_mode);
+	if (b.reserved != 0) return "reserved word is not zero";
+	*total += (uint64_t) b.width * b.height;
+	if (*total > (uint64_t) MTSGPU_BITMAP_MAX_TEXELS)
+		return "more than " + std::to_string(MTSGPU_BITMAP_MAX_TEXELS) + " texels in all (the pool is indexed with one uint32)";
+	if (!b.texels) return "no texels";
+	const size_t n = 3 * (size_t) b.width * b.height;
+	for (size_t i = 0; i < n; ++i)
+		if (!std::isfinite(b.texels[i]) || b.texels[i] < 0.0f)
+			return "texel (" + std::to_string((i / 3) % b.width) + ", " + std::to_string((i / 3) / b.width) + ") is negative or not finite";
+	return std::string();
+}
+
+// the texels of one bitmap as the pool holds them: one float4 (r, g, b, unused) each, row-major
+void mg::packBitmapTexels(const mtsgpu_bitmap &b, float *dst) {
+	const size_t n = (size_t) b.width * b.height;
+	for (size_t i = 0; i < n; ++i) {
+		dst[4 * i] = b.texels[3 * i]; dst[4 * i + 1] = b.texels[3 * i + 1]; dst[4 * i + 2] = b.texels[3 * i + 2]; dst[4 * i + 3] = 0.0f;
+	}
 }
 
 namespace {
@@ -179,8 +206,8 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 	freeAll(c->colorAllocs);      // a new scene starts without vertex colours (mtsgpu_set_vertex_colors)
 	c->dcol = DColors{ nullptr, nullptr };
 	c->hostColorSlots.clear();
-	freeAll(c->texAllocs);        // ... and without uv textures (mtsgpu_set_uv_textures)
-	c->dtex = DTextures{ nullptr, nullptr, nullptr };
+	freeAll(c->texAllocs);        // ... and without uv textures (mtsgpu_set_uv_textures, mtsgpu_set_uv_bitmap_textures)
+	c->dtex = DTextures{ nullptr, nullptr, nullptr, nullptr };
 	c->hostSlotTex.clear();
 	c->dtan = DTangents{ nullptr, nullptr };      // ... and its tangents go with the scene's arrays
 	c->haveScene = false;
@@ -433,36 +460,65 @@ int mtsgpu_set_vertex_colors(mtsgpu_ctx *c, const float *vtx_col, const uint32_t
 static_assert(sizeof(mtsgpu_uv_texture) == sizeof(DTexture) && offsetof(mtsgpu_uv_texture, line_width) == offsetof(DTexture, line_width)
               && offsetof(mtsgpu_uv_texture, bright) == offsetof(DTexture, bright), "mtsgpu_uv_texture and DTexture are one layout");
 static_assert(MTSGPU_TEX_CHECKERBOARD == (int) kTexCheckerboard && MTSGPU_TEX_GRID == (int) kTexGrid, "texture kinds differ");
+static_assert(MTSGPU_TEX_BITMAP == (int) kTexBitmap && offsetof(DTexture, width) == offsetof(mtsgpu_uv_texture, bright)
+              && offsetof(DTexture, reserved) + sizeof(DTexture::reserved) == sizeof(DTexture), "the bitmap words are the seven behind vscale");
+static_assert(MTSGPU_WRAP_REPEAT == (int) kWrapRepeat && MTSGPU_WRAP_CLAMP == (int) kWrapClamp && MTSGPU_WRAP_BLACK == (int) kWrapBlack
+              && MTSGPU_WRAP_WHITE == (int) kWrapWhite, "wrap modes differ");
 
 // 2 * uv' of texture t at texcoord (u, v) stays inside the range of the reference's (int) cast, with the margin the header states
-static bool uvCastInRange(const mtsgpu_uv_texture &t, float u, float v) {
+// (a bitmap of sx x sy texels: uv' * (sx, sy), mipmap.cpp:229-230)
+static bool uvCastInRange(const mtsgpu_uv_texture &t, float u, float v, double sx = 2.0, double sy = 2.0) {
 	const double lim = 2147483648.0 - 65536.0;
-	const double x = 2.0 * ((double) u * t.uscale + t.uoffset), y = 2.0 * ((double) v * t.vscale + t.voffset);
+	const double x = sx * ((double) u * t.uscale + t.uoffset), y = sy * ((double) v * t.vscale + t.voffset);
 	return std::fabs(x) < lim && std::fabs(y) < lim;
 }
 
-int mtsgpu_set_uv_textures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
-                           const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture) {
+// mtsgpu_set_uv_textures (withBitmaps = false: no bitmaps, and kind MTSGPU_TEX_BITMAP is unknown) and mtsgpu_set_uv_bitmap_textures
+static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
+                         const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture, uint32_t n_bitmaps,
+                         const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap, bool withBitmaps) {
+	const char *me = withBitmaps ? "mtsgpu_set_uv_bitmap_textures" : "mtsgpu_set_uv_textures";
 	if (!c) return fail(c, MTSGPU_EINVAL, "null argument");
-	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_set_uv_textures before mtsgpu_upload_scene");
+	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "%s before mtsgpu_upload_scene", me);
 	c->lastPass.valid = false;
 	HIPCHK(c, hipSetDevice(c->device));
 	// nothing may still read the arrays that go (the shading launches of a render that was not synchronised)
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
 	freeAll(c->texAllocs);
-	c->dtex = DTextures{ nullptr, nullptr, nullptr };
+	c->dtex = DTextures{ nullptr, nullptr, nullptr, nullptr };
 	c->hostSlotTex.clear();
-	if (!vtx_uv && !shape_has_uv && !textures && !bsdf_slot_texture) return 0;
+	if (!vtx_uv && !shape_has_uv && !textures && !bsdf_slot_texture && !bitmaps && !texture_bitmap) return 0;
 	if ((vtx_uv == nullptr) != (shape_has_uv == nullptr))
 		return fail(c, MTSGPU_EINVAL, "vtx_uv and shape_has_uv must both be given or both be NULL");
 	if (n_textures && !textures) return fail(c, MTSGPU_EINVAL, "n_textures without textures");
 	if (n_textures > (1u << 20)) return fail(c, MTSGPU_EINVAL, "at most 2^20 textures");
+	if (n_bitmaps && !bitmaps) return fail(c, MTSGPU_EINVAL, "n_bitmaps without bitmaps");
+	if (n_bitmaps > (1u << 20)) return fail(c, MTSGPU_EINVAL, "at most 2^20 bitmaps");
 	const mtsgpu_ctx::HostScene &h = c->host;
 	const uint32_t nShapes = (uint32_t) h.shapeBsdf.size(), nBsdfs = (uint32_t) h.bsdfType.size();
 	for (uint32_t k = 0; k < n_textures; ++k) {
-		const std::string why = checkUvTexture(textures[k]);
+		const std::string why = checkUvTexture(textures[k], withBitmaps);
 		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "texture %u: %s", k, why.c_str());
+	}
+	// the bitmaps, the place of each in the pool, and the descriptors of the textures that show one
+	std::vector<uint32_t> first(n_bitmaps, 0u);
+	uint64_t nTexels = 0;
+	for (uint32_t b = 0; b < n_bitmaps; ++b) {
+		first[b] = (uint32_t) nTexels;
+		const std::string why = checkBitmap(bitmaps[b], &nTexels);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "bitmap %u: %s", b, why.c_str());
+	}
+	std::vector<DTexture> desc(n_textures);
+	bool anyBitmap = false;
+	for (uint32_t k = 0; k < n_textures; ++k) {
+		std::memcpy(&desc[k], &textures[k], sizeof(DTexture));
+		if (textures[k].kind != (uint32_t) MTSGPU_TEX_BITMAP) continue;
+		const int32_t b = texture_bitmap ? texture_bitmap[k] : -1;
+		if (b < 0 || (uint32_t) b >= n_bitmaps) return fail(c, MTSGPU_EINVAL, "texture %u: bitmap index %d out of range (%u bitmaps)", k, b, n_bitmaps);
+		desc[k].width = bitmaps[b].width; desc[k].height = bitmaps[b].height; desc[k].wrap = bitmaps[b].wrap_mode; desc[k].first = first[b];
+		desc[k].reserved[0] = desc[k].reserved[1] = desc[k].reserved[2] = 0u;
+		anyBitmap = true;
 	}
 	bool anySlot = false;
 	if (bsdf_slot_texture) {
@@ -488,23 +544,75 @@ int mtsgpu_set_uv_textures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *s
 			const int32_t k = bsdf_slot_texture[2 * (size_t) b + slot];
 			if (k < 0) continue;
 			bool ok = true;
-			if (!mesh) ok = uvCastInRange(textures[k], 0.0f, 0.0f) && uvCastInRange(textures[k], 1.0f, 1.0f);
-			else if (!hasUv) ok = uvCastInRange(textures[k], 0.0f, 0.0f);
+			const bool bitmap = textures[k].kind == (uint32_t) MTSGPU_TEX_BITMAP;
+			const double sx = bitmap ? (double) desc[k].width : 2.0, sy = bitmap ? (double) desc[k].height : 2.0;
+			if (!mesh) ok = uvCastInRange(textures[k], 0.0f, 0.0f, sx, sy) && uvCastInRange(textures[k], 1.0f, 1.0f, sx, sy);
+			else if (!hasUv) ok = uvCastInRange(textures[k], 0.0f, 0.0f, sx, sy);
 			else
 				for (uint32_t t = h.shapeTriOffset[s]; ok && t < h.shapeTriOffset[s + 1]; ++t)
-					for (int v = 0; v < 3; ++v) ok = ok && uvCastInRange(textures[k], triUv[US * (size_t) t + 2 * v], triUv[US * (size_t) t + 2 * v + 1]);
+					for (int v = 0; v < 3; ++v)
+						ok = ok && uvCastInRange(textures[k], triUv[US * (size_t) t + 2 * v], triUv[US * (size_t) t + 2 * v + 1], sx, sy);
+			if (!ok && bitmap)
+				return fail(c, MTSGPU_EINVAL, "shape %u: texture %d maps a texcoord outside the range of the (int) cast (|uv' * size| >= 2^31 - 2^16)", s, k);
 			if (!ok)
 				return fail(c, MTSGPU_EINVAL, "shape %u: texture %d maps a texcoord outside the range of the (int) cast (|2 uv'| >= 2^31 - 2^16)", s, k);
 		}
 	}
 	if (!anySlot && !vtx_uv) return 0;       // nothing to keep
-	const float *dUv = nullptr; const DTexture *dTex = nullptr; const int32_t *dSlots = nullptr;
+	const float *dUv = nullptr, *dTexels = nullptr; const DTexture *dTex = nullptr; const int32_t *dSlots = nullptr;
 	int rc = upload(c, &dUv, triUv.data(), triUv.size(), &c->texAllocs);
-	if (!rc && anySlot) rc = upload(c, &dTex, reinterpret_cast<const DTexture *>(textures), n_textures, &c->texAllocs);
+	if (!rc && anySlot) rc = upload(c, &dTex, desc.data(), n_textures, &c->texAllocs);
 	if (!rc && anySlot) rc = upload(c, &dSlots, bsdf_slot_texture, 2 * (size_t) nBsdfs, &c->texAllocs);
+	if (!rc && anySlot && anyBitmap) {
+		// the pool: the bitmaps one behind the other, 16 bytes per texel
+		std::vector<float> pool(4 * (size_t) nTexels);
+		for (uint32_t b = 0; b < n_bitmaps; ++b) packBitmapTexels(bitmaps[b], &pool[4 * (size_t) first[b]]);
+		rc = upload(c, &dTexels, pool.data(), pool.size(), &c->texAllocs);
+	}
 	if (rc) { freeAll(c->texAllocs); return rc; }
-	c->dtex = DTextures{ reinterpret_cast<const float4 *>(dUv), dTex, dSlots };
+	c->dtex = DTextures{ reinterpret_cast<const float4 *>(dUv), dTex, dSlots, reinterpret_cast<const float4 *>(dTexels) };
 	if (anySlot) c->hostSlotTex.assign(bsdf_slot_texture, bsdf_slot_texture + 2 * (size_t) nBsdfs);
+	return 0;
+}
+
+int mtsgpu_set_uv_textures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
+                           const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture) {
+	return setUvTextures(c, vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture, 0, nullptr, nullptr, false);
+}
+
+int mtsgpu_set_uv_bitmap_textures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
+                                  const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture, uint32_t n_bitmaps,
+                                  const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap) {
+	return setUvTextures(c, vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture, n_bitmaps, bitmaps, texture_bitmap, true);
+}
+
+// LDRTexture::initializeFrom (ldrtexture.cpp:116-202) and MIPMap::fromBitmap (mipmap.cpp:156-177)
+int mtsgpu_ldr_texels(int bpp, uint32_t width, uint32_t height, const uint8_t *data, float gamma, float *out) {
+	if (!data || !out) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	if (width == 0 || height == 0) return fail(nullptr, MTSGPU_EINVAL, "zero dimension (%u x %u)", width, height);
+	if (bpp != 1 && bpp != 8 && bpp != 16 && bpp != 24 && bpp != 32)
+		return fail(nullptr, MTSGPU_EINVAL, "%i bpp images are currently not supported!", bpp);
+	float tbl[256];
+	if (gamma == -1.0f) {
+		for (int i = 0; i < 256; ++i) {      // fromSRGBComponent (:116-121)
+			const float value = (float) i / 255.0f;
+			tbl[i] = value <= 0.04045f ? value / 12.92f : std::pow((value + 0.055f) / (float) (1.0 + 0.055), 2.4f);
+		}
+	} else {
+		for (int i = 0; i < 256; ++i) tbl[i] = std::pow((float) i / 255.0f, gamma);
+	}
+	for (int i = 0; i < 256; ++i) tbl[i] = std::max(tbl[i], 0.0f);      // clampNegative (a NaN of pow stays one: the upload refuses it)
+	const size_t n = (size_t) width * height;
+	for (size_t pos = 0; pos < n; ++pos) {
+		float *o = out + 3 * pos;
+		if (bpp == 32 || bpp == 24) {
+			const uint8_t *p = data + (size_t) (bpp / 8) * pos;
+			o[0] = tbl[p[0]]; o[1] = tbl[p[1]]; o[2] = tbl[p[2]];
+		} else {
+			const int value = bpp == 16 ? data[2 * pos] : bpp == 8 ? data[pos] : (data[pos / 8] & (1 << (pos % 8))) ? 255 : 0;
+			o[0] = o[1] = o[2] = tbl[value];
+		}
+	}
 	return 0;
 }
 

@@ -143,11 +143,35 @@ __device__ __forceinline__ void its_uv(const DScene &sc, const float4 *tri_uv, u
 		uvy = a.y * bx + a.w * by + c.y * bz;
 	}
 }
-// Texture2D::getValue(its) (texture.cpp:73-82) of a checkerboard (checkerboard.cpp:48-56) or a grid texture
-// (gridtexture.cpp:51-64) at its.uv = (uvx, uvy).  The casts truncate towards zero as the reference's (int) does; the host
-// has checked that they stay inside the int range for every texcoord of the scene (mtsgpu_set_uv_textures).
-__device__ __forceinline__ V3 tex_eval(const DTexture &t, float uvx, float uvy) {
+// MIPMap::triangle with filterType none (mipmap.cpp:228-231) and MIPMap::getTexel (:203-225) as written: the texel that holds
+// uv' = (x, y), floors in binary32, integers from there on.  The out-of-range test has `x <= 0`, so column 0 counts as outside:
+// harmless under repeat and clamp (modulo(0, w) = clamp(0, 0, w - 1) = 0), the constant under black and white.  modulo is the
+// non-negative remainder (util.cpp:424-427).  The host has checked that the casts stay inside the int range.
+__device__ __forceinline__ V3 bitmap_eval(const DTexture &t, const float4 *texels, float x, float y) {
+	const int w = (int) t.width, h = (int) t.height;
+	int xPos = (int) floorf(x * (float) w), yPos = (int) floorf(y * (float) h);
+	if (xPos <= 0 || yPos < 0 || xPos >= w || yPos >= h) {
+		if (t.wrap == kWrapRepeat) {
+			xPos = xPos - (xPos / w) * w; if (xPos < 0) xPos += w;
+			yPos = yPos - (yPos / h) * h; if (yPos < 0) yPos += h;
+		} else if (t.wrap == kWrapClamp) {
+			xPos = xPos < 0 ? 0 : xPos > w - 1 ? w - 1 : xPos;
+			yPos = yPos < 0 ? 0 : yPos > h - 1 ? h - 1 : yPos;
+		} else {
+			const float c = t.wrap == kWrapBlack ? 0.0f : 1.0f;
+			return V3(c, c, c);
+		}
+	}
+	const float4 v = texels[(size_t) t.first + (size_t) xPos + (size_t) w * (size_t) yPos];
+	return V3(v.x, v.y, v.z);
+}
+// Texture2D::getValue(its) (texture.cpp:73-82) of a checkerboard (checkerboard.cpp:48-56), a grid texture
+// (gridtexture.cpp:51-64) or an unfiltered bitmap (ldrtexture.cpp:230-232) at its.uv = (uvx, uvy).  The casts truncate towards
+// zero as the reference's (int) does; the host has checked that they stay inside the int range for every texcoord of the scene
+// (mtsgpu_set_uv_textures, mtsgpu_set_uv_bitmap_textures).  texels: DTextures::texels, read for a bitmap only.
+__device__ __forceinline__ V3 tex_eval(const DTexture &t, const float4 *texels, float uvx, float uvy) {
 	const float x = uvx * t.uscale + t.uoffset, y = uvy * t.vscale + t.voffset;
+	if (t.kind == kTexBitmap) return bitmap_eval(t, texels, x, y);
 	bool bright;
 	if (t.kind == kTexCheckerboard) {
 		// 2 * modulo(i, 2) - 1 with the non-negative remainder: +1 for an odd i, -1 for an even one

@@ -141,7 +141,21 @@ __global__ void k_uv_texture_eval(DScene sc, const float4 *tri_uv, DTexture tex,
 	const float *r = rec + 3 * (size_t) i;
 	float uvx, uvy;
 	its_uv(sc, tri_uv, prim[i], shape, r[0], r[1], V3(r[0], r[1], r[2]), uvx, uvy);
-	const V3 c = tex_eval(tex, uvx, uvy);
+	const V3 c = tex_eval(tex, nullptr, uvx, uvy);      // the host refuses a bitmap here
+	float *o = out + 5 * (size_t) i;
+	o[0] = uvx; o[1] = uvy; o[2] = c.x; o[3] = c.y; o[4] = c.z;
+}
+
+// mtsgpu_bitmap_texture_eval: the same for a bitmap descriptor, whose texels lie at texels[tex.first ...]
+__global__ void k_bitmap_texture_eval(DScene sc, const float4 *tri_uv, DTexture tex, const float4 *texels, uint32_t n, const uint32_t *prim,
+                                      const float *rec, float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t shape = __float_as_uint(sc.tri_pos[kTriStride * (size_t) prim[i] + 2].z);
+	const float *r = rec + 3 * (size_t) i;
+	float uvx, uvy;
+	its_uv(sc, tri_uv, prim[i], shape, r[0], r[1], V3(r[0], r[1], r[2]), uvx, uvy);
+	const V3 c = tex_eval(tex, texels, uvx, uvy);
 	float *o = out + 5 * (size_t) i;
 	o[0] = uvx; o[1] = uvy; o[2] = c.x; o[3] = c.y; o[4] = c.z;
 }
@@ -259,6 +273,11 @@ void launch_bsdf_eval_slots(hipStream_t s, uint32_t type, const float *params, c
 void launch_uv_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, uint32_t n, const uint32_t *prim,
                             const float *rec, float *out) {
 	if (n) hipLaunchKernelGGL(k_uv_texture_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, tri_uv, tex, n, prim, rec, out);
+}
+
+void launch_bitmap_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, const float4 *texels, uint32_t n,
+                                const uint32_t *prim, const float *rec, float *out) {
+	if (n) hipLaunchKernelGGL(k_bitmap_texture_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, tri_uv, tex, texels, n, prim, rec, out);
 }
 
 void launch_shading_frame_eval(hipStream_t s, const DScene &sc, const DTangents &tan, uint32_t n, const uint32_t *prim, const float *rec, float *out) {

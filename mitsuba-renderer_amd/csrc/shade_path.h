@@ -151,7 +151,7 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			const float *BP = sc.bsdf_params + 16 * (size_t) bsdfIdx;
 			float colouredBlock[kBsdfNParams];
 			if (VCOL == kSlotTexture && BT < 9) {
-				// a checkerboard or grid texture in a slot of this BSDF: that slot holds the texture's value at its.uv; a
+				// a checkerboard, a grid texture or a bitmap in a slot of this BSDF: that slot holds the texture's value at its.uv; a
 				// `vertexcolors` texture in the other one its.color
 				// (a scene that is here for its tangents alone has no texture table)
 				const bool noTex = TAN && tex.bsdf_slot_texture == nullptr;
@@ -165,13 +165,13 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				bsdf_block_with_slots<BT>(BP, kSlotBlock, kSlotBlock, zero, zero, zero, colouredBlock);
 				{
 					const int src = k0 >= 0 ? kSlotTexture : (slots & 1u) ? kSlotColor : kSlotBlock;
-					const V3 w = src == kSlotTexture ? tex_eval(tex.textures[k0], uvx, uvy)
+					const V3 w = src == kSlotTexture ? tex_eval(tex.textures[k0], tex.texels, uvx, uvy)
 					           : src == kSlotColor ? its_color(col.tri_col, h.w, __uint_as_float(h.y), __uint_as_float(h.z)) : zero;
 					bsdf_block_set_slot<BT, 0>(colouredBlock, src, w);
 				}
 				{
 					const int src = k1 >= 0 ? kSlotTexture : (slots & 2u) ? kSlotColor : kSlotBlock;
-					const V3 w = src == kSlotTexture ? tex_eval(tex.textures[k1], uvx, uvy)
+					const V3 w = src == kSlotTexture ? tex_eval(tex.textures[k1], tex.texels, uvx, uvy)
 					           : src == kSlotColor ? its_color(col.tri_col, h.w, __uint_as_float(h.y), __uint_as_float(h.z)) : zero;
 					bsdf_block_set_slot<BT, 1>(colouredBlock, src, w);
 				}
@@ -287,7 +287,7 @@ struct ShadeShared {
 template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false>
 __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const uint32_t *prefix,
                                             const uint32_t *bin_ids, const uint32_t block, ShadeShared &sh, const DColors &col,
-                                            const DTextures &tex = DTextures{ nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr }) {
+                                            const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr }) {
 	uint32_t (&s_cnt)[2][kShadeBlock / 64] = sh.cnt;
 	uint32_t (&s_base)[2] = sh.base;
 	float4 (&s_rows)[kShadeBlock / 64][64 * kRowStride] = sh.rows;
@@ -464,7 +464,7 @@ __global__ MG_SHADE_BOUNDS void k_shade_tan(DScene sc, DPaths ps, DConfig cfg, D
 // BSDF slot; the bins that cannot have one (composite, terminal) run the same code either way
 template <bool SKY, int VCOL, bool TAN = false>
 __device__ __forceinline__ void shade_all(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const BinView *views_dev, uint32_t bin_mask,
-                                          ShadeShared &sh, const DColors &col, const DTextures &tex = DTextures{ nullptr, nullptr, nullptr },
+                                          ShadeShared &sh, const DColors &col, const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr },
                                           const DTangents &tan = DTangents{ nullptr, nullptr }) {
 	uint32_t block = blockIdx.x;
 	int bin = -1;

@@ -65,6 +65,57 @@ class GridTexture(_UvTexture):
         return self.bright.copy()
 
 
+WRAP_MODES = {"repeat": abi.WRAP_REPEAT, "clamp": abi.WRAP_CLAMP, "black": abi.WRAP_BLACK, "white": abi.WRAP_WHITE}
+
+
+class BitmapTexture(_UvTexture):
+    """the `ldrtexture` texture (src/textures/ldrtexture.cpp) with filterType = "none": the texel that holds uv', no
+    filtering; pass it where a BSDF constructor of SceneDescription takes a reflectance or transmittance.  texels: [height]
+    [width][3] linear RGB float32, what the MIPMap's level 0 holds -- or pixels: the decoded file as a uint8 array [height]
+    [width] (8 bpp), [height][width][2] (16), [..][3] (24) or [..][4] (32), converted with `gamma` (-1 = sRGB) by
+    mtsgpu_ldr_texels, the restatement of LDRTexture::initializeFrom.  wrap: repeat, clamp, black or white.  Two textures that
+    are given the same texels array and wrap mode share one bitmap on the device."""
+    kind = abi.TEX_BITMAP
+
+    def __init__(self, texels=None, pixels=None, gamma=-1.0, wrap="repeat", uoffset=0.0, voffset=0.0, uscale=1.0, vscale=1.0):
+        _UvTexture.__init__(self, 0.0, 0.0, uoffset, voffset, uscale, vscale)
+        if (texels is None) == (pixels is None):
+            raise ValueError("BitmapTexture: give texels or pixels")
+        if pixels is not None:
+            from . import ldr_texels
+            texels = ldr_texels(pixels, gamma)
+        if not (isinstance(texels, np.ndarray) and texels.dtype == np.float32 and texels.flags["C_CONTIGUOUS"]):
+            texels = np.ascontiguousarray(texels, dtype=np.float32)
+        if texels.ndim != 3 or texels.shape[2] != 3 or texels.size == 0:
+            raise ValueError("BitmapTexture: texels are [height][width][3]")
+        self.texels = texels
+        self.height, self.width = texels.shape[:2]
+        self.wrap_name = wrap
+        self.wrap = WRAP_MODES[wrap]
+
+    def average(self):
+        """m_average = triangle(levels - 1, 0, 0) with one level (ldrtexture.cpp:206): getTexel(0, 0, 0), and column 0 counts as
+        out of range there (mipmap.cpp:207) -- texel (0, 0) under repeat and clamp, the constant under black and white"""
+        if self.wrap == abi.WRAP_BLACK:
+            return np.zeros(3, dtype=np.float32)
+        if self.wrap == abi.WRAP_WHITE:
+            return np.ones(3, dtype=np.float32)
+        return self.texels[0, 0].copy()
+
+    def maximum(self):
+        """MIPMap::getMaximum (mipmap.cpp:137-154): per channel over the texels, at least 1 under white"""
+        m = self.texels.reshape(-1, 3).max(axis=0)
+        return np.maximum(m, F(1.0)) if self.wrap == abi.WRAP_WHITE else m
+
+    def descriptor(self):
+        """the twelve words of mtsgpu_uv_texture: kind and Texture2D's four floats count, the library fills the rest"""
+        return abi.UvTexture(self.kind, self.uoffset, self.voffset, self.uscale, self.vscale)
+
+    def bitmap(self):
+        """mtsgpu_bitmap over this texture's texels (which must outlive it)"""
+        return abi.Bitmap(self.width, self.height, self.wrap, 0, abi.ptr(self.texels, abi.f32p))
+
+
 def _slot_average(v):
     """what a texture-typed argument of a BSDF leaves in the block: Texture::getAverage() (a constant: itself)"""
     return v.average() if isinstance(v, _UvTexture) else F(1.0) if v is VERTEX_COLORS else v
@@ -114,7 +165,7 @@ class SceneDescription:
         self.bsdf_type = []
         self.bsdf_params = []
         self.bsdf_color_slots = []  # per BSDF: bit s = its s-th texture slot takes its.color (include/mtsgpu.h)
-        self.textures = []          # the Checkerboard / GridTexture objects in use (what mtsgpu_set_uv_textures takes)
+        self.textures = []          # the Checkerboard / GridTexture / BitmapTexture objects in use (what mtsgpu_set_uv_textures takes)
         self.bsdf_slot_texture = [] # per BSDF: [index into textures or -1] for its two texture slots
         self._slot_textures = ()
         self.lum_type = []
@@ -885,6 +936,17 @@ def cornell_tex(sky=False):
     return sd
 
 
+def cornell_bmp(sky=False, wrap="repeat"):
+    """cornell_tex with an unfiltered 5 x 3 bitmap in place of the sphere's checkerboard: a bitmap, a checkerboard (the mesh
+    without texcoords), a grid texture and vertex colours (the sheet's two slots) on different slots of one scene"""
+    sd = cornell_tex(sky)
+    sd.name = "cornell_bmp_sky" if sky else "cornell_bmp"
+    texels = np.random.RandomState(9).uniform(0.05, 0.9, (3, 5, 3)).astype(np.float32)
+    bmp = BitmapTexture(texels=texels, wrap=wrap, uscale=6.0, vscale=-3.0, uoffset=0.25)
+    sd.meshes[[m.name for m in sd.meshes].index("sphere")].bsdf = sd.lambertian(bmp)
+    return sd
+
+
 def by_name(name, **kw):
     return {"c1": cornell_c1, "c3": cornell_c3, "c5": cornell_c5, "next": next_rows, "spheres": spheres, "envlit": envlit,
-            "vcol_grid": vcol_grid, "vcol": cornell_vcol, "tex": cornell_tex}[name](**kw)
+            "vcol_grid": vcol_grid, "vcol": cornell_vcol, "tex": cornell_tex, "bmp": cornell_bmp}[name](**kw)

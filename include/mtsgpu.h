@@ -670,6 +670,20 @@ int  mtsgpu_li_samples(mtsgpu_ctx *ctx, const uint32_t *pix_samples, uint32_t n,
  * mtsgpu_li_samples or mtsgpu_trace_rays since), MTSGPU_EINVAL past its end.  A test hook: tests/ref64_film.py restates
  * ImageBlock::putSample in binary64 over these records and the film must agree. */
 int  mtsgpu_pass_samples(mtsgpu_ctx *ctx, uint32_t first, uint32_t n, float *out);
+/* The camera records as the camera kernel leaves them, before any bounce overwrites their ray: one launch of that kernel and
+ * nothing else.  out [n][14] f32 = ray origin xyz, mint, ray direction xyz, maxt, raster x, raster y, and as bit patterns
+ * (u32) the sampler's 1D and 2D counters after generation, the record's pixel key (as for mtsgpu_pass_samples) and its
+ * sample index.  Two modes:
+ *   pix_samples != NULL: explicit samples, in [n][3] i32 = pixel x, y of the crop window, sample index; first must be 0.  The
+ *     sampler tables and arrays are built as mtsgpu_li_samples builds them, the keys lie in the grid mtsgpu_render uses, so
+ *     with highQualityEdges the pixels of the filter border are there: x in [-border, width + border), y likewise.
+ *   pix_samples == NULL: the pass mtsgpu_render rendered last is generated once more from its saved configuration, pixel list
+ *     and sampler tables (as mtsgpu_replay_roof kind 1 does) and records first .. first + n are returned, in the order of
+ *     mtsgpu_pass_samples.  MTSGPU_ESTATE when there is no valid last pass.
+ * Either mode takes the path records: the last pass is invalid afterwards.  MTSGPU_EINVAL for a pixel or sample index out of
+ * range, records past the end of the pass, more than 2^24 records.  A test hook: tests/ref64_camera.py restates
+ * PerspectiveCameraImpl::generateRay and OrthographicCamera::generateRay in binary64 and the rays must agree. */
+int  mtsgpu_camera_rays(mtsgpu_ctx *ctx, const int32_t *pix_samples, uint32_t first, uint32_t n, float *out);
 /* How many entries the closest-hit launches of the last mtsgpu_render / mtsgpu_li_samples appended to every material queue,
  * summed over the bounces: out [MTSGPU_BSDF_NTYPES + 1] u64, entry t = hits on shapes whose BSDF has type t, the last one the
  * terminal queue (hits on shapes without a BSDF and -- in frames that shade their misses: scenes with a background luminaire,

@@ -43,6 +43,7 @@ EXPORTS = [
     "mtsgpu_flatten_tangents", "mtsgpu_flat_scene_vertex_tangents", "mtsgpu_flat_scene_shape_has_tangents", "mtsgpu_upload_scene_tangents",
     "mtsgpu_group_upload_scene_tangents", "mtsgpu_shading_frame_eval", "mtsgpu_bin_entries",
     "mtsgpu_set_uv_bitmap_textures", "mtsgpu_group_set_uv_bitmap_textures", "mtsgpu_bitmap_texture_eval", "mtsgpu_ldr_texels",
+    "mtsgpu_camera_rays",
 ]
 
 
@@ -172,6 +173,7 @@ def lib():
     L.mtsgpu_ld_tables.argtypes = [vp, C.c_uint32, f32p, f32p]
     L.mtsgpu_li_samples.argtypes = [vp, u32p, C.c_uint32, f32p]
     L.mtsgpu_pass_samples.argtypes = [vp, C.c_uint32, C.c_uint32, f32p]
+    L.mtsgpu_camera_rays.argtypes = [vp, abi.i32p, C.c_uint32, C.c_uint32, f32p]
     L.mtsgpu_bin_entries.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.mtsgpu_flatten.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.KdParams), C.POINTER(vp)]
     L.mtsgpu_flat_scene_get.argtypes = [vp]; L.mtsgpu_flat_scene_get.restype = C.POINTER(abi.Scene)
@@ -841,6 +843,22 @@ class MIPathTracer:
         float32 laid out like li_samples(), the pixel key as a bit pattern in column 7.  n = None: up to the end of the pass
         (camera_samples of the last render when it took one pass)"""
         return _pass_samples(self._ctx, first, self.stats()["camera_samples"] - int(first) if n is None else n)
+
+    def camera_rays(self, pix_samples=None, first=0, n=None):
+        """the camera records as the camera kernel leaves them (mtsgpu_camera_rays): [n][14] float32 = o, mint, d, maxt, raster
+        x, y, then as bit patterns the sampler counters d1, d2, the pixel key and the sample index.  pix_samples [n][3] int32
+        (pixel x, y of the crop window -- the border pixels of highQualityEdges at negative coordinates included -- and the
+        sample index), or None for records first .. first + n of the pass rendered last, generated once more.  Either way
+        the last pass is invalid afterwards"""
+        if pix_samples is None:
+            ps, count = None, int(n)
+        else:
+            ps = np.ascontiguousarray(pix_samples, dtype=np.int32).reshape(-1, 3)
+            count = ps.shape[0]
+        out = np.zeros((count, abi.CAMERA_RAY_FLOATS), dtype=np.float32)
+        self._chk(lib().mtsgpu_camera_rays(self._ctx, None if ps is None else abi.ptr(ps, abi.i32p), int(first), count, abi.ptr(out, abi.f32p)),
+                  "camera_rays")
+        return out
 
     def close(self):
         if self._ctx and _lib is not None:

@@ -25,6 +25,7 @@ SHAPE_HAS_NORMALS = 1
 SHAPE_TRIMESH, SHAPE_SPHERE = 0, 1
 SHAPE_NPARAMS = 24
 KNOTRIANGLE = 0xFFFFFFFF
+CAMERA_RAY_FLOATS = 14          # a row of mtsgpu_camera_rays: o, mint, d, maxt, raster x, y | u32: d1, d2, pixel key, sample index
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)

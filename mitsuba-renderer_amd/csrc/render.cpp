@@ -1,6 +1,7 @@
 // render.cpp -- the wavefront engine behind mtsgpu_render (include/mtsgpu.h): the per-pass buffers, the host loops that
 // drive the traversal and shading stages per bounce, and the entry points that run them (mtsgpu_render, mtsgpu_trace_rays,
-// mtsgpu_li_samples) or read their records back (mtsgpu_pass_samples, mtsgpu_bin_entries).
+// mtsgpu_li_samples), run their first stage alone (mtsgpu_camera_rays) or read their records back (mtsgpu_pass_samples,
+// mtsgpu_bin_entries).
 #include "ctx.h"
 #include <algorithm>
 #include <cstdio>
@@ -599,6 +600,32 @@ int readSampleRows(mtsgpu_ctx *c, size_t first, uint32_t n, bool withKey, float 
 	return 0;
 }
 
+// The 14-float rows of mtsgpu_camera_rays for the n path records from `first` on, as k_generate left them: ray_o (o, mint),
+// ray_d (d, maxt), the sample position, the sampler's counters from the flags word, the pixel key and the sample index.
+int readCameraRows(mtsgpu_ctx *c, size_t first, uint32_t n, float *out) {
+	std::vector<float> ro(4 * (size_t) n), rd(4 * (size_t) n), Li(4 * (size_t) n), misc(4 * (size_t) n), spos(4 * (size_t) n);
+	const size_t pitch = kPathSlots * sizeof(float4);
+	const float4 *rec = c->paths.base + first * kPathSlots;
+	HIPCHK(c, hipMemcpy2DAsync(ro.data(), 16, rec + 0, pitch, 16, n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpy2DAsync(rd.data(), 16, rec + 1, pitch, 16, n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpy2DAsync(Li.data(), 16, rec + 4, pitch, 16, n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpy2DAsync(misc.data(), 16, rec + 6, pitch, 16, n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpy2DAsync(spos.data(), 16, rec + 7, pitch, 16, n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	for (size_t i = 0; i < n; ++i) {
+		uint32_t flags;
+		std::memcpy(&flags, &Li[4 * i + 3], 4);
+		float *o = out + 14 * i;
+		std::memcpy(o, &ro[4 * i], 16); std::memcpy(o + 4, &rd[4 * i], 16);
+		o[8] = spos[4 * i]; o[9] = spos[4 * i + 1];
+		const uint32_t words[4] = { (flags >> F_D1_SHIFT) & 0xFFu, (flags >> F_D2_SHIFT) & 0xFFu, 0u, 0u };
+		std::memcpy(o + 10, words, 8);
+		std::memcpy(o + 12, &misc[4 * i + 3], 4);             // the pixel key
+		std::memcpy(o + 13, &misc[4 * i + 2], 4);             // the sample index
+	}
+	return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -841,6 +868,69 @@ int mtsgpu_pass_samples(mtsgpu_ctx *c, uint32_t first, uint32_t n, float *out) {
 	if (n == 0) return 0;
 	if (!out) return fail(c, MTSGPU_EINVAL, "null output");
 	return readSampleRows(c, first, n, true, out);
+}
+
+// The camera records as k_generate leaves them (include/mtsgpu.h): one launch of the product's kernel and no bounce, for
+// explicit samples (sampler state built as mtsgpu_li_samples builds it, keys in the grid mtsgpu_render uses) or for the pass
+// rendered last once more (as mtsgpu_replay_roof kind 1 regenerates it).
+int mtsgpu_camera_rays(mtsgpu_ctx *c, const int32_t *pix_samples, uint32_t first, uint32_t n, float *out) {
+	int rc = checkReady(c); if (rc) return rc;
+	if (n > (1u << 24)) return fail(c, MTSGPU_EINVAL, "at most 2^24 camera records per call");
+	if (!pix_samples) {
+		const mtsgpu_ctx::LastPass lp = c->lastPass;
+		if (!lp.valid) return fail(c, MTSGPU_ESTATE, "no pass to regenerate: render first (setters, mtsgpu_li_samples, mtsgpu_trace_rays and this call invalidate the last pass)");
+		if ((uint64_t) first + n > lp.nPaths || lp.nPaths > c->pathCap)
+			return fail(c, MTSGPU_EINVAL, "records %u .. %llu lie past the end of the last pass (%u records)", first, (unsigned long long) first + n, lp.nPaths);
+		if (n == 0) return 0;
+		if (!out) return fail(c, MTSGPU_EINVAL, "null output");
+		rayQueues(c, nullptr, nullptr);
+		// its sampler tables and its part of the pixel list are still in place
+		launch_generate(c->stream, c->dsc, c->paths, lp.cfg, c->pixelList + lp.base, lp.nSlots, nullptr, lp.nPaths, c->queueA);
+		HIPCHK(c, hipGetLastError());
+		c->lastPass.valid = false;             // the path records no longer hold that pass
+		return readCameraRows(c, first, n, out);
+	}
+	if (first != 0) return fail(c, MTSGPU_EINVAL, "explicit samples start at record 0");
+	if (n == 0) return 0;
+	if (!out) return fail(c, MTSGPU_EINVAL, "null output");
+	const uint32_t spp = effectiveSpp(c);
+	// the grid of mtsgpu_render's keys: the full film, grown by the filter border with highQualityEdges
+	const int border = c->hqEdges ? c->filtBorder : 0;
+	const uint32_t keyW = (uint32_t) (filmWidth(c) + 2 * border);
+	if ((uint64_t) keyW * (uint64_t) (filmHeight(c) + 2 * border) > 0xFFFFFFFFull) return fail(c, MTSGPU_EINVAL, "film too large");
+	std::vector<uint32_t> keys(n), samples(3 * (size_t) n);
+	for (uint32_t i = 0; i < n; ++i) {
+		const int32_t x = pix_samples[3 * (size_t) i], y = pix_samples[3 * (size_t) i + 1], j = pix_samples[3 * (size_t) i + 2];
+		if (x < -border || y < -border || x >= c->cam.width + border || y >= c->cam.height + border || j < 0 || (uint32_t) j >= spp)
+			return fail(c, MTSGPU_EINVAL, "sample %u: pixel or sample index out of range", i);
+		// k_generate adds the crop offset and forms the key; cfg.pix_off takes the border off again
+		samples[3 * (size_t) i] = (uint32_t) (x + border); samples[3 * (size_t) i + 1] = (uint32_t) (y + border); samples[3 * (size_t) i + 2] = (uint32_t) j;
+		keys[i] = ((uint32_t) (y + border) + (uint32_t) c->cam.crop_offset_y) * keyW + (uint32_t) (x + border) + (uint32_t) c->cam.crop_offset_x;
+	}
+	rc = ensurePaths(c, n); if (rc) return rc;
+	rc = ensureBuf(c, &c->explicitSamples, &c->explicitCap, 3 * (size_t) n); if (rc) return rc;
+	c->renderListValid = false; c->lastPass.valid = false;
+	rc = ensureBuf(c, &c->pixelList, &c->pixelListCap, n); if (rc) return rc;
+	HIPCHK(c, hipMemcpyAsync(c->explicitSamples, samples.data(), 3 * (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	HIPCHK(c, hipMemcpyAsync(c->pixelList, keys.data(), (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	if (samplerHasTables(c)) {
+		rc = ensureBuf(c, &c->ldScr, &c->ldScrCap, (size_t) n * 3 * c->ldDepth); if (rc) return rc;
+		rc = ensureBuf(c, &c->ldPerm, &c->ldPermCap, (size_t) n * 2 * c->ldDepth * spp); if (rc) return rc;
+		rc = ensureTableWork(c, n, spp); if (rc) return rc;
+	}
+	rc = ensureSampleArrays(c, n, n); if (rc) return rc;
+	DConfig cfg = makeConfig(c, true);
+	cfg.pix_w = (int) keyW; cfg.pix_off = -border;
+	if (samplerHasTables(c)) {
+		launch_ld_tables(c->stream, cfg, c->pixelList, n, c->ldScr, c->ldPerm, c->ldState, c->ldScratch);
+		launch_sample_arrays(c->stream, cfg, n, c->ldState);
+	}
+	rayQueues(c, nullptr, c->queueA);
+	launch_generate(c->stream, c->dsc, c->paths, cfg, c->pixelList, n, c->explicitSamples, n, c->queueA);
+	rayQueues(c, nullptr, nullptr);
+	HIPCHK(c, hipGetLastError());
+	// `samples` and `keys` live on this stack; the read-back below waits for the stream
+	return readCameraRows(c, 0, n, out);
 }
 
 int mtsgpu_bin_entries(mtsgpu_ctx *c, uint64_t *out) {

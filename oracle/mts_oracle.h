@@ -135,6 +135,9 @@ void orc_sampler_values(const orc_render_params *p, uint32_t pixel_key, uint32_t
 /* MIPathTracer::Li for explicit (pixel, sample) pairs; same contract as mtsgpu_li_samples */
 void orc_li_samples(const mtsgpu_scene *sc, const mtsgpu_camera *cam, const orc_render_params *p,
                     const uint32_t *pix_samples, uint32_t n, float *out);
+/* Camera::generateRay for n given samples: in [n][4] = raster x, y, lens sample x, y; out [n][14] laid out like
+ * mtsgpu_camera_rays (o, mint, d, maxt, raster x, y; the four words of the sampler and the key are left 0) */
+void orc_camera_rays(const mtsgpu_camera *cam, uint32_t n, const float *samples, float *out);
 /* The reference's own sequential sampling (one MT19937-64 stream, scanline pixel
  * order inside the rectangle): kind 0 = independent.cpp, 1 = ldsampler.cpp. */
 void orc_render_rect_mt(const mtsgpu_scene *sc, const mtsgpu_camera *cam, const orc_render_params *p,

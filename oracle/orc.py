@@ -104,6 +104,7 @@ def lib():
                                   C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.POINTER(abi.Stats)]
     L.orc_li_samples.argtypes = [C.POINTER(abi.Scene), C.POINTER(abi.Camera), C.POINTER(RenderParams),
                                  u32p, C.c_uint32, f32p]
+    L.orc_camera_rays.argtypes = [C.POINTER(abi.Camera), C.c_uint32, f32p, f32p]; L.orc_camera_rays.restype = None
     L.orc_sampler_values.argtypes = [C.POINTER(RenderParams), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, f32p]
     L.orc_render_rect_mt.argtypes = [C.POINTER(abi.Scene), C.POINTER(abi.Camera), C.POINTER(RenderParams),
                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]
@@ -215,6 +216,14 @@ def li_samples(scene_ptr, cam, params, pix_samples):
     ps = np.ascontiguousarray(pix_samples, dtype=np.uint32).reshape(-1, 3)
     out = np.zeros((ps.shape[0], 8), dtype=np.float32)
     lib().orc_li_samples(scene_ptr, C.byref(cam), C.byref(params), abi.ptr(ps, abi.u32p), ps.shape[0], abi.ptr(out, abi.f32p))
+    return out
+
+
+def camera_rays(cam, samples):
+    """Camera::generateRay for samples [n][4] = raster x, y, lens x, y; rows laid out like mtsgpu_camera_rays: [n][14]"""
+    s = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1, 4)
+    out = np.zeros((s.shape[0], 14), dtype=np.float32)
+    lib().orc_camera_rays(C.byref(cam), s.shape[0], abi.ptr(s, abi.f32p), abi.ptr(out, abi.f32p))
     return out
 
 

@@ -2122,6 +2122,19 @@ void orc_li_samples(const mtsgpu_scene *sc, const mtsgpu_camera *cam, const orc_
 	free(scr); free(perm); arrays_free(&arrays);
 }
 
+void orc_camera_rays(const mtsgpu_camera *cam, uint32_t n, const float *samples, float *out) {
+	for (uint32_t i = 0; i < n; ++i) {
+		const float *s = samples + 4 * (size_t) i;
+		ray_t ray;
+		camera_generate_ray(cam, s, s + 2, &ray);
+		float *o = out + 14 * (size_t) i;
+		o[0] = ray.o[0]; o[1] = ray.o[1]; o[2] = ray.o[2]; o[3] = ray.mint;
+		o[4] = ray.d[0]; o[5] = ray.d[1]; o[6] = ray.d[2]; o[7] = ray.maxt;
+		o[8] = s[0]; o[9] = s[1];
+		o[10] = o[11] = o[12] = o[13] = 0.0f;
+	}
+}
+
 /* The reference's own sequential sampling: one Random (default seed 5489, the
  * un-cloned sampler), scanline order inside the rectangle (integrator.cpp:204-226) */
 void orc_render_rect_mt(const mtsgpu_scene *sc, const mtsgpu_camera *cam, const orc_render_params *prm,

@@ -55,27 +55,23 @@ int ensureFilm(mtsgpu_ctx *c) {
 	const size_t px = (size_t) c->cam.width * c->cam.height;
 	if (c->film && !c->ownFilm) return 0;
 	if (c->film && c->filmPixels == px) return 0;
-	if (c->film) (void) hipFree(c->film);
-	c->film = nullptr;
-	HIPCHK(c, hipMalloc((void **) &c->film, px * 5 * sizeof(float)));
-	HIPCHK(c, hipMemset(c->film, 0, px * 5 * sizeof(float)));
-	c->ownFilm = true; c->filmPixels = px;
+	// a film of another size is a new film, zeroed: released first, so that the buffer is not merely grown into
+	c->film = nullptr; c->ownedFilm.release();
+	if (int rc = c->ownedFilm.ensure(c, px * 5)) return rc;
+	HIPCHK(c, hipMemset(c->ownedFilm, 0, px * 5 * sizeof(float)));
+	c->film = c->ownedFilm; c->ownFilm = true; c->filmPixels = px;
 	return 0;
 }
 
 // the statistics buffers of the test-case mode, zeroed when (re)allocated: sized like the film, owned by the context
-static void freeFilmStats(mtsgpu_ctx *c) {
-	if (c->statVar) (void) hipFree(c->statVar);
-	if (c->statN) (void) hipFree(c->statN);
-	c->statVar = nullptr; c->statN = nullptr; c->statPixels = 0;
-}
+static void freeFilmStats(mtsgpu_ctx *c) { c->statVar.release(); c->statN.release(); c->statPixels = 0; }
 int ensureFilmStats(mtsgpu_ctx *c) {
 	const size_t px = (size_t) c->cam.width * c->cam.height;
 	if (c->statVar && c->statN && c->statPixels == px) return 0;
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	freeFilmStats(c);
-	HIPCHK(c, hipMalloc((void **) &c->statVar, px * 3 * sizeof(float)));
-	HIPCHK(c, hipMalloc((void **) &c->statN, px * sizeof(uint32_t)));
+	if (int rc = c->statVar.ensure(c, px * 3)) return rc;
+	if (int rc = c->statN.ensure(c, px)) return rc;
 	HIPCHK(c, hipMemset(c->statVar, 0, px * 3 * sizeof(float)));
 	HIPCHK(c, hipMemset(c->statN, 0, px * sizeof(uint32_t)));
 	c->statPixels = px;
@@ -118,21 +114,20 @@ int mtsgpu_create(int device, mtsgpu_ctx **out) {
 	mtsgpu_ctx *c = new mtsgpu_ctx();
 	c->device = device;
 	c->nCUs = (uint32_t) std::max(1, prop.multiProcessorCount);
-	if (hipStreamCreate(&c->stream) != hipSuccess) { delete c; return fail(nullptr, MTSGPU_EHIP, "hipStreamCreate failed"); }
+	// from here on every failure goes through mtsgpu_destroy: whatever exists by then has its owner in the context
+	auto give_up = [&](const char *what) { mtsgpu_destroy(c); return fail(nullptr, MTSGPU_EHIP, "%s failed", what); };
+	if (hipStreamCreate(&c->stream) != hipSuccess) return give_up("hipStreamCreate");
 	c->ownStream = true;
 	{
 		bool ok = hipStreamCreate(&c->stream2) == hipSuccess && hipEventCreateWithFlags(&c->evCount, hipEventDisableTiming) == hipSuccess;
 		for (int i = 0; i < 2 && ok; ++i)
 			ok = hipEventCreateWithFlags(&c->evShade[i], kOrderEventFlags) == hipSuccess
 			  && hipEventCreateWithFlags(&c->evShadow[i], kOrderEventFlags) == hipSuccess;
-		if (!ok) { mtsgpu_destroy(c); return fail(nullptr, MTSGPU_EHIP, "stream / event creation failed"); }
+		if (!ok) return give_up("stream / event creation");
 	}
-	if (hipHostMalloc((void **) &c->hostCounters, (kNumCounters * kCounterStride + 4) * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
-		(void) hipStreamDestroy(c->stream); delete c; return fail(nullptr, MTSGPU_EHIP, "hipHostMalloc failed");
-	}
-	if (hipMalloc((void **) &c->pathLen, sizeof(unsigned long long)) != hipSuccess) {
-		mtsgpu_destroy(c); return fail(nullptr, MTSGPU_EHIP, "hipMalloc failed");
-	}
+	if (hipHostMalloc((void **) &c->hostCounters, kHostCounterWords * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+		return give_up("hipHostMalloc");
+	if (c->pathLen.ensure(c, 1)) return give_up("hipMalloc");
 	{
 		// the first 1000 primes (primeTable, src/libcore/util.cpp:64-122) for the halton / hammersley samplers
 		std::vector<uint16_t> primes;
@@ -141,10 +136,9 @@ int mtsgpu_create(int device, mtsgpu_ctx **out) {
 			for (uint32_t d = 2; d * d <= v; ++d) if (v % d == 0) { isPrime = false; break; }
 			if (isPrime) primes.push_back((uint16_t) v);
 		}
-		if (hipMalloc((void **) &c->primes, primes.size() * sizeof(uint16_t)) != hipSuccess
-		    || hipMemcpy(c->primes, primes.data(), primes.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) {
-			mtsgpu_destroy(c); return fail(nullptr, MTSGPU_EHIP, "prime table upload failed");
-		}
+		if (c->primes.ensure(c, primes.size())
+		    || hipMemcpy(c->primes, primes.data(), primes.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess)
+			return give_up("prime table upload");
 	}
 	*out = c;
 	return 0;
@@ -152,35 +146,9 @@ int mtsgpu_create(int device, mtsgpu_ctx **out) {
 
 void mtsgpu_destroy(mtsgpu_ctx *c) {
 	if (!c) return;
-	(void) hipSetDevice(c->device);
-	(void) hipDeviceSynchronize();
-	freeAll(c->sceneAllocs); freeAll(c->colorAllocs); freeAll(c->texAllocs); freeAll(c->pathAllocs);
-	if (c->ownFilm && c->film) (void) hipFree(c->film);
-	if (c->pixelList) (void) hipFree(c->pixelList);
-	if (c->ldScr) (void) hipFree(c->ldScr);
-	if (c->ldPerm) (void) hipFree(c->ldPerm);
-	if (c->ldState) (void) hipFree(c->ldState);
-	if (c->ldScratch) (void) hipFree(c->ldScratch);
-	if (c->arrScr) (void) hipFree(c->arrScr);
-	if (c->arrPerm) (void) hipFree(c->arrPerm);
-	if (c->arrPts) (void) hipFree(c->arrPts);
-	if (c->primSave) (void) hipFree(c->primSave);
-	if (c->shqNee) (void) hipFree(c->shqNee);
-	if (c->primes) (void) hipFree(c->primes);
-	if (c->pathLen) (void) hipFree(c->pathLen);
-	if (c->explicitSamples) (void) hipFree(c->explicitSamples);
-	if (c->filtValues) (void) hipFree(c->filtValues);
-	if (c->statVar) (void) hipFree(c->statVar);
-	if (c->statN) (void) hipFree(c->statN);
-	if (c->tileMeta) (void) hipFree(c->tileMeta);
-	if (c->blocks) (void) hipFree(c->blocks);
-	if (c->hostCounters) (void) hipHostFree(c->hostCounters);
-	for (auto &e : c->traceEvents) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
-	for (auto &e : c->shadeEvents) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
-	if (c->ownStream && c->stream) (void) hipStreamDestroy(c->stream);
-	if (c->stream2) (void) hipStreamDestroy(c->stream2);
-	for (hipEvent_t e : { c->evShade[0], c->evShade[1], c->evShadow[0], c->evShadow[1], c->evCount }) if (e) (void) hipEventDestroy(e);
-	delete c;
+	(void) hipSetDevice(c->device);       // memory is freed with the context's device current ...
+	(void) hipDeviceSynchronize();        // ... and idle
+	delete c;                             // ~mtsgpu_ctx and the DevBuf members release what the context owns
 }
 
 int mtsgpu_set_stream(mtsgpu_ctx *c, void *hip_stream) {
@@ -256,7 +224,7 @@ int mtsgpu_set_rfilter(mtsgpu_ctx *c, float size_x, float size_y, const float *v
 	if (!values) { c->filtSizeX = c->filtSizeY = 0.5f; c->filtBorder = 0; return 0; }
 	if (!(size_x > 0) || !(size_y > 0) || size_x > 8 || size_y > 8) return fail(c, MTSGPU_EINVAL, "bad filter size");
 	HIPCHK(c, hipSetDevice(c->device));
-	if (!c->filtValues) HIPCHK(c, hipMalloc((void **) &c->filtValues, 256 * sizeof(float)));
+	if (int rc = c->filtValues.ensure(c, 256)) return rc;
 	HIPCHK(c, hipMemcpy(c->filtValues, values, 256 * sizeof(float), hipMemcpyHostToDevice));
 	c->filtSizeX = size_x; c->filtSizeY = size_y;
 	c->filtBorder = (int) std::ceil(std::max(size_x, size_y) - 0.5f);       // renderproc.cpp:143-144
@@ -306,7 +274,7 @@ int mtsgpu_tabulate_filter(int kind, float half_size, float p0, float p1, float 
 
 int mtsgpu_set_film_buffer(mtsgpu_ctx *c, void *device_ptr) {
 	if (!c) return fail(nullptr, MTSGPU_EINVAL, "null context");
-	if (c->ownFilm && c->film) (void) hipFree(c->film);
+	c->ownedFilm.release();
 	c->film = (float *) device_ptr; c->ownFilm = false; c->filmPixels = 0;
 	return 0;
 }

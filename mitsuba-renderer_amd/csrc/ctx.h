@@ -1,5 +1,7 @@
 // ctx.h -- the context behind the C ABI (include/mtsgpu.h) and the helpers its translation units share: api.cpp (context,
 // setters, film), scene_upload.cpp, render.cpp (the wavefront engine), readout.cpp (test and measurement hooks), group.cpp.
+// Device memory of a context has one owner per buffer: a DevBuf (grow-only, freed by its destructor) or one of the *Allocs
+// lists; ~mtsgpu_ctx releases the lists, the pinned words, the events and the streams, so mtsgpu_destroy names no buffer.
 #pragma once
 #include "host.h"
 #include "kernels.h"
@@ -9,7 +11,60 @@
 #include <utility>
 #include <vector>
 
+namespace mg {
+extern thread_local std::string g_lastError;
+// records the message (thread-local and in the context) and returns `code`
+int fail(mtsgpu_ctx *ctx, int code, const char *fmt, ...);
+}
+
+#define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
+	return mg::fail(ctx, MTSGPU_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+
+namespace mg {
+// A device buffer with one owner.  ensure() only ever grows it (the contents are lost when it does); the destructor frees
+// it, with the owner's device current (mtsgpu_destroy, mtsgpu_group_destroy).  Reads as the pointer it holds.
+template <typename T> struct DevBuf {
+	T *p = nullptr; size_t cap = 0;
+	DevBuf() = default;
+	DevBuf(const DevBuf &) = delete;
+	DevBuf &operator=(const DevBuf &) = delete;
+	~DevBuf() { release(); }
+	operator T *() const { return p; }
+	void release() { if (p) (void) hipFree(p); p = nullptr; cap = 0; }
+	int ensure(mtsgpu_ctx *c, size_t need) {
+		if (need <= cap) return 0;
+		release();
+		void *raw = nullptr;
+		HIPCHK(c, hipMalloc(&raw, need * sizeof(T)));
+		p = static_cast<T *>(raw); cap = need;
+		return 0;
+	}
+};
+
+// The pinned words of a context (mtsgpu_ctx::hostCounters): the counter set readCounters() fetches, then two scratch values
+// behind it: the path-length sum of a frame (64 bits) and the queue size a chunk of device-driven bounces ends with
+constexpr size_t kHostPathLenWord = (size_t) kNumCounters * kCounterStride;
+constexpr size_t kHostNextWord = kHostPathLenWord + 2;
+constexpr size_t kHostCounterWords = kHostPathLenWord + 4;
+// bytes of one counter set (kCounterSets of them alternate between bounces)
+constexpr size_t kCounterSetBytes = (size_t) kNumCounters * kCounterStride * sizeof(uint32_t);
+
+using EventPool = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
+inline void freeAll(std::vector<void *> &v) { for (void *p : v) (void) hipFree(p); v.clear(); }
+}
+
 struct mtsgpu_ctx {
+	// with `device` current and idle (mtsgpu_destroy): everything no DevBuf member owns.  A caller's stream or film is not ours.
+	~mtsgpu_ctx() {
+		for (auto *list : { &sceneAllocs, &colorAllocs, &texAllocs, &pathAllocs }) mg::freeAll(*list);
+		if (hostCounters) (void) hipHostFree(hostCounters);
+		for (auto *pool : { &traceEvents, &shadeEvents })
+			for (auto &e : *pool) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
+		for (hipEvent_t e : { evShade[0], evShade[1], evShadow[0], evShadow[1], evCount }) if (e) (void) hipEventDestroy(e);
+		if (ownStream && stream) (void) hipStreamDestroy(stream);
+		if (stream2) (void) hipStreamDestroy(stream2);
+	}
+
 	int device = 0;
 	uint32_t nCUs = 256;                   // hipDeviceProp_t::multiProcessorCount
 	hipStream_t stream = nullptr;
@@ -57,18 +112,19 @@ struct mtsgpu_ctx {
 	std::map<std::string, long> tuning;      // mtsgpu_set_tuning
 
 	// film
-	float *film = nullptr; bool ownFilm = false; size_t filmPixels = 0;
+	float *film = nullptr;                 // the film in use: ownedFilm's, or the caller's (mtsgpu_set_film_buffer), never freed here
+	mg::DevBuf<float> ownedFilm; bool ownFilm = false; size_t filmPixels = 0;
 	float filtSizeX = 0.5f, filtSizeY = 0.5f; int filtBorder = 0;
 	bool hqEdges = false;
 	int integrator = 0, nLumSamples = 1, nBsdfSamples = 1;
-	float *filtValues = nullptr;           // device [16][16]
+	mg::DevBuf<float> filtValues;          // device [16][16]
 	// test-case mode (mtsgpu_set_film_statistics): per-pixel variance [H][W][3] and sample count [H][W], allocated only while
 	// the mode is on; statsForm = the form of the variance kernel the last pass ran (0 lane, 1 wave, -1 none)
 	bool filmStats = false;
-	float *statVar = nullptr; uint32_t *statN = nullptr; size_t statPixels = 0;
+	mg::DevBuf<float> statVar; mg::DevBuf<uint32_t> statN; size_t statPixels = 0;
 	int statsForm = -1;
-	mg::TileMeta *tileMeta = nullptr; size_t tileMetaCap = 0;
-	float *blocks = nullptr; size_t blocksCap = 0;
+	mg::DevBuf<mg::TileMeta> tileMeta;
+	mg::DevBuf<float> blocks;
 
 	// per-pass buffers
 	size_t pathCap = 0;
@@ -77,29 +133,29 @@ struct mtsgpu_ctx {
 	uint32_t *queueA = nullptr, *queueB = nullptr;
 	float4 *rayqA[2] = { nullptr, nullptr }, *rayqB[2] = { nullptr, nullptr };      // the rays of queueA / queueB in queue order (o, d)
 	uint4 *binHits = nullptr;               // DQueues::bin_hits: the hits of binned paths, next to their ids
-	uint32_t *pixelList = nullptr; size_t pixelListCap = 0;
+	mg::DevBuf<uint32_t> pixelList;
 	// The work units of a frame (pixel keys in tile order + tile rectangles) depend on the film geometry and the tile
 	// sharding only: they are kept from frame to frame (a 1-spp frame spent 0.55 of its 10.6 ms rebuilding and uploading
 	// them).  renderKey is what they were built for; the test hooks that borrow pixelList clear renderListValid.
 	std::vector<uint32_t> renderPixels; std::vector<mg::TileMeta> renderTiles;
 	std::vector<long long> renderKey; bool renderListValid = false;
-	uint32_t *ldScr = nullptr; uint16_t *ldPerm = nullptr; size_t ldScrCap = 0, ldPermCap = 0;
-	uint16_t *ldScratch = nullptr; size_t ldScratchCap = 0;      // the tables of a pass while they are shuffled (kernels.h)
+	mg::DevBuf<uint32_t> ldScr; mg::DevBuf<uint16_t> ldPerm;
+	mg::DevBuf<uint16_t> ldScratch;        // the tables of a pass while they are shuffled (kernels.h)
 	// Sampler::request2DArray arrays of the direct integrator (per pass, like the tables above)
-	unsigned long long *ldState = nullptr; size_t ldStateCap = 0;
-	uint32_t *arrScr = nullptr; uint16_t *arrPerm = nullptr; float2 *arrPts = nullptr; size_t arrScrCap = 0, arrPermCap = 0, arrPtsCap = 0;
-	float4 *primSave = nullptr; size_t primSaveCap = 0;
-	float4 *shqNee = nullptr; size_t shqNeeCap = 0;      // DPaths::shq_nee, once a frame has run with DQueues::nee_parked == 0
-	uint16_t *primes = nullptr;        // primeTable (util.cpp:64-122) on the device
-	uint32_t *explicitSamples = nullptr; size_t explicitCap = 0;
-	uint32_t *hostCounters = nullptr;       // pinned
+	mg::DevBuf<unsigned long long> ldState;
+	mg::DevBuf<uint32_t> arrScr; mg::DevBuf<uint16_t> arrPerm; mg::DevBuf<float2> arrPts;
+	mg::DevBuf<float4> primSave;
+	mg::DevBuf<float4> shqNee;             // DPaths::shq_nee, once a frame has run with DQueues::nee_parked == 0
+	mg::DevBuf<uint16_t> primes;           // primeTable (util.cpp:64-122) on the device
+	mg::DevBuf<uint32_t> explicitSamples;
+	uint32_t *hostCounters = nullptr;       // pinned, kHostCounterWords words
 	uint32_t *counterSets = nullptr;        // kCounterSets x kNumCounters lines, used by alternate bounces
 	uint32_t *spillClosest = nullptr, *spillShadow = nullptr;   // the two traversal kernels run concurrently
 	mg::BinView *viewsDev = nullptr;        // device-driven bounces: per-bin views written by k_prep
 	unsigned long long *devStats = nullptr; // kStat* counters of a device-driven frame
 	bool devStatsUsed = false;              // a device-driven pass ran since the statistics were cleared
 	uint32_t binMask = 0x1FFu;              // bins that can be non-empty with the uploaded scene (BSDF types present + terminal)
-	unsigned long long *pathLen = nullptr;  // device: sum of the final path depths of a render (avgPathLength)
+	mg::DevBuf<unsigned long long> pathLen; // device: sum of the final path depths of a render (avgPathLength)
 	std::vector<void *> pathAllocs;
 
 	// stats
@@ -107,23 +163,15 @@ struct mtsgpu_ctx {
 	// entries the closest-hit launches of the last frame appended to every material queue (mtsgpu_bin_entries): counted by the
 	// host where it reads the shard counters back, by k_prep otherwise
 	uint64_t binEntries[mg::kNumBins] = {};
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> traceEvents, shadeEvents;
+	mg::EventPool traceEvents, shadeEvents; // the timing events of a frame with time_kernels on, kept from frame to frame
 	size_t traceEvUsed = 0, shadeEvUsed = 0;
 	std::vector<unsigned char> traceEvClass;      // per traversal launch: 0 closest-hit, 1 closest-hit of a pass's first bounce, 2 any-hit
+	bool debug = false;                     // MTSGPU_DEBUG was set when the frame began
 	// what mtsgpu_replay_roof needs to know about the pass rendered last: how to generate its camera rays again, and
 	// how many slots of the shadow queue hold rays (the largest shadow launch of the pass; 0 after device-driven bounces)
 	struct LastPass { bool valid = false; mg::DConfig cfg{}; size_t base = 0; uint32_t nSlots = 0, nPaths = 0, shadowMax = 0; } lastPass;
 };
 
-
-namespace mg {
-extern thread_local std::string g_lastError;
-// records the message (thread-local and in the context) and returns `code`
-int fail(mtsgpu_ctx *ctx, int code, const char *fmt, ...);
-}
-
-#define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-	return mg::fail(ctx, MTSGPU_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 // What the translation units behind the C ABI share besides the context.  Only what a second file uses is declared here;
 // everything else is local to its file.
@@ -144,18 +192,6 @@ template <typename T> int upload(mtsgpu_ctx *ctx, const T **dst, const T *src, s
 	if (rc) return rc;
 	if (count) HIPCHK(ctx, hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
 	*dst = p;
-	return 0;
-}
-
-inline void freeAll(std::vector<void *> &v) { for (void *p : v) (void) hipFree(p); v.clear(); }
-
-template <typename T> int ensureBuf(mtsgpu_ctx *c, T **p, size_t *cap, size_t need) {
-	if (need <= *cap) return 0;
-	if (*p) (void) hipFree(*p);
-	*p = nullptr; *cap = 0;
-	void *raw = nullptr;
-	HIPCHK(c, hipMalloc(&raw, need * sizeof(T)));
-	*p = static_cast<T *>(raw); *cap = need;
 	return 0;
 }
 

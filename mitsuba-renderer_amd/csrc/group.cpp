@@ -69,7 +69,7 @@ struct mtsgpu_group {
 	Rccl rccl;
 	std::vector<ncclComm_t> comms;         // one per member when RCCL is usable
 	std::string rcclNote;                  // why RCCL is not used, if it is not
-	float *staging = nullptr; size_t stagingFloats = 0;   // on members[0]'s device: a peer's film (ordered sum) / the RCCL result
+	DevBuf<float> staging;                 // on members[0]'s device: a peer's film (ordered sum) / the RCCL result
 	int lastReduceKind = 0;
 	int rcclRanks = 0;                     // ranks of the communicator that passed the self-check (0: none did)
 	std::string reduceNote;                // why the last frame fell back to the ordered sum ("" when it did not)
@@ -99,6 +99,20 @@ template <typename F> int forAll(mtsgpu_group *g, const char *what, F &&f) {
 		if (rc[i]) return gfail(g, rc[i], "%s, member %zu (device %d): %s", what, i, g->devices[i], mtsgpu_last_error(g->members[i]));
 	return 0;
 }
+
+// The same call on every member, in member order; the first failure ends it and is reported as "<what>: <the member's
+// message>".  undo: what takes the setting back off a member -- run on the members already set, so that no member keeps what
+// another one could not take (the group renders one scene)
+template <typename F, typename U> int forEach(mtsgpu_group *g, const char *what, F &&f, U &&undo) {
+	for (size_t i = 0; i < g->members.size(); ++i)
+		if (int rc = f(g->members[i])) {
+			const std::string why = mtsgpu_last_error(g->members[i]);
+			for (size_t k = 0; k < i; ++k) (void) undo(g->members[k]);
+			return gfail(g, rc, "%s: %s", what, why.c_str());
+		}
+	return 0;
+}
+template <typename F> int forEach(mtsgpu_group *g, const char *what, F &&f) { return forEach(g, what, f, [](mtsgpu_ctx *) { return 0; }); }
 
 bool selfCheckComms(mtsgpu_group *g, std::string &why) {
 	const int n = (int) g->members.size();
@@ -215,7 +229,8 @@ int mtsgpu_create_multi(int ndev, const int *devs, mtsgpu_group **out) {
 void mtsgpu_group_destroy(mtsgpu_group *g) {
 	if (!g) return;
 	for (ncclComm_t c : g->comms) if (c) (void) g->rccl.commDestroy(c);
-	if (g->staging && !g->devices.empty()) { (void) hipSetDevice(g->devices[0]); (void) hipFree(g->staging); }
+	if (!g->devices.empty()) (void) hipSetDevice(g->devices[0]);      // the staging buffer is freed with its device current
+	g->staging.release();
 	for (mtsgpu_ctx *c : g->members) mtsgpu_destroy(c);
 	// the RCCL handle stays loaded: unloading a library that owns device state is not safe at this point
 	delete g;
@@ -245,30 +260,22 @@ int mtsgpu_group_upload_scene_tangents(mtsgpu_group *g, const mtsgpu_scene *scen
 
 int mtsgpu_group_set_camera(mtsgpu_group *g, const mtsgpu_camera *cam) {
 	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
-	for (size_t i = 0; i < g->members.size(); ++i)
-		if (int rc = mtsgpu_set_camera(g->members[i], cam)) return gfail(g, rc, "set_camera: %s", mtsgpu_last_error(g->members[i]));
-	return 0;
+	return forEach(g, "set_camera", [&](mtsgpu_ctx *c) { return mtsgpu_set_camera(c, cam); });
 }
 
 int mtsgpu_group_set_integrator(mtsgpu_group *g, int max_depth, int rr_depth, int strict_normals) {
 	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
-	for (size_t i = 0; i < g->members.size(); ++i)
-		if (int rc = mtsgpu_set_integrator(g->members[i], max_depth, rr_depth, strict_normals)) return gfail(g, rc, "set_integrator: %s", mtsgpu_last_error(g->members[i]));
-	return 0;
+	return forEach(g, "set_integrator", [&](mtsgpu_ctx *c) { return mtsgpu_set_integrator(c, max_depth, rr_depth, strict_normals); });
 }
 
 int mtsgpu_group_set_sampler(mtsgpu_group *g, int kind, uint32_t spp, int ld_depth, uint64_t seed) {
 	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
-	for (size_t i = 0; i < g->members.size(); ++i)
-		if (int rc = mtsgpu_set_sampler(g->members[i], kind, spp, ld_depth, seed)) return gfail(g, rc, "set_sampler: %s", mtsgpu_last_error(g->members[i]));
-	return 0;
+	return forEach(g, "set_sampler", [&](mtsgpu_ctx *c) { return mtsgpu_set_sampler(c, kind, spp, ld_depth, seed); });
 }
 
 int mtsgpu_group_set_rfilter(mtsgpu_group *g, float size_x, float size_y, const float *values) {
 	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
-	for (size_t i = 0; i < g->members.size(); ++i)
-		if (int rc = mtsgpu_set_rfilter(g->members[i], size_x, size_y, values)) return gfail(g, rc, "set_rfilter: %s", mtsgpu_last_error(g->members[i]));
-	return 0;
+	return forEach(g, "set_rfilter", [&](mtsgpu_ctx *c) { return mtsgpu_set_rfilter(c, size_x, size_y, values); });
 }
 
 namespace {
@@ -281,12 +288,8 @@ struct DeviceGuard {
 };
 
 int ensureStaging(mtsgpu_group *g, size_t count) {
-	if (g->stagingFloats >= count) return 0;
 	GHIP(g, hipSetDevice(g->devices[0]));
-	if (g->staging) (void) hipFree(g->staging);
-	g->staging = nullptr; g->stagingFloats = 0;
-	GHIP(g, hipMalloc((void **) &g->staging, count * sizeof(float)));
-	g->stagingFloats = count;
+	if (int rc = g->staging.ensure(g->members[0], count)) return gfail(g, rc, "%s", mtsgpu_last_error(g->members[0]));
 	return 0;
 }
 
@@ -418,7 +421,7 @@ const char *mtsgpu_group_reduce_note(const mtsgpu_group *g) { return g ? g->redu
 int mtsgpu_group_set_tuning(mtsgpu_group *g, const char *key, long value) {
 	if (!g || !key) return gfail(g, MTSGPU_EINVAL, "null argument");
 	if (!strcmp(key, "rccl_fail")) { g->testFailReduce = value != 0; return 0; }
-	for (size_t i = 0; i < g->members.size(); ++i)
+	for (size_t i = 0; i < g->members.size(); ++i)      // this one's message names the member, not the call
 		if (int r = mtsgpu_set_tuning(g->members[i], key, value))
 			return gfail(g, r, "member %zu: %s", i, mtsgpu_last_error(g->members[i]));
 	return 0;
@@ -426,49 +429,32 @@ int mtsgpu_group_set_tuning(mtsgpu_group *g, const char *key, long value) {
 
 int mtsgpu_group_set_film_statistics(mtsgpu_group *g, int on) {
 	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
-	for (size_t i = 0; i < g->members.size(); ++i)
-		if (int r = mtsgpu_set_film_statistics(g->members[i], on))
-			return gfail(g, r, "set_film_statistics: %s", mtsgpu_last_error(g->members[i]));
-	return 0;
+	return forEach(g, "set_film_statistics", [&](mtsgpu_ctx *c) { return mtsgpu_set_film_statistics(c, on); });
 }
 
 int mtsgpu_group_set_vertex_colors(mtsgpu_group *g, const float *vtx_col, const uint32_t *shape_has_colors, const uint32_t *bsdf_color_slots) {
 	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
-	for (size_t i = 0; i < g->members.size(); ++i)
-		if (int r = mtsgpu_set_vertex_colors(g->members[i], vtx_col, shape_has_colors, bsdf_color_slots)) {
-			const std::string why = mtsgpu_last_error(g->members[i]);
-			// no member keeps colours another one could not take: the group renders one scene
-			for (size_t k = 0; k < i; ++k) (void) mtsgpu_set_vertex_colors(g->members[k], nullptr, nullptr, nullptr);
-			return gfail(g, r, "set_vertex_colors: %s", why.c_str());
-		}
-	return 0;
+	return forEach(g, "set_vertex_colors", [&](mtsgpu_ctx *c) { return mtsgpu_set_vertex_colors(c, vtx_col, shape_has_colors, bsdf_color_slots); },
+	               [](mtsgpu_ctx *c) { return mtsgpu_set_vertex_colors(c, nullptr, nullptr, nullptr); });
 }
+
+// both texture setters are undone by the first one without textures
+static int clearUvTextures(mtsgpu_ctx *c) { return mtsgpu_set_uv_textures(c, nullptr, nullptr, 0, nullptr, nullptr); }
 
 int mtsgpu_group_set_uv_textures(mtsgpu_group *g, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
                                  const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture) {
 	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
-	for (size_t i = 0; i < g->members.size(); ++i)
-		if (int r = mtsgpu_set_uv_textures(g->members[i], vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture)) {
-			const std::string why = mtsgpu_last_error(g->members[i]);
-			// no member keeps textures another one could not take: the group renders one scene
-			for (size_t k = 0; k < i; ++k) (void) mtsgpu_set_uv_textures(g->members[k], nullptr, nullptr, 0, nullptr, nullptr);
-			return gfail(g, r, "set_uv_textures: %s", why.c_str());
-		}
-	return 0;
+	return forEach(g, "set_uv_textures", [&](mtsgpu_ctx *c) { return mtsgpu_set_uv_textures(c, vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture); },
+	               clearUvTextures);
 }
 
 int mtsgpu_group_set_uv_bitmap_textures(mtsgpu_group *g, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
                                         const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture, uint32_t n_bitmaps,
                                         const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap) {
 	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
-	for (size_t i = 0; i < g->members.size(); ++i)
-		if (int r = mtsgpu_set_uv_bitmap_textures(g->members[i], vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture, n_bitmaps, bitmaps,
-		                                          texture_bitmap)) {
-			const std::string why = mtsgpu_last_error(g->members[i]);
-			for (size_t k = 0; k < i; ++k) (void) mtsgpu_set_uv_textures(g->members[k], nullptr, nullptr, 0, nullptr, nullptr);
-			return gfail(g, r, "set_uv_bitmap_textures: %s", why.c_str());
-		}
-	return 0;
+	return forEach(g, "set_uv_bitmap_textures", [&](mtsgpu_ctx *c) {
+		return mtsgpu_set_uv_bitmap_textures(c, vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture, n_bitmaps, bitmaps, texture_bitmap); },
+	               clearUvTextures);
 }
 
 int mtsgpu_hbm_triad(int device, size_t bytes, int iters, double *gbs) {
@@ -478,13 +464,13 @@ int mtsgpu_hbm_triad(int device, size_t bytes, int iters, double *gbs) {
 	if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) return gfail(nullptr, MTSGPU_ENODEV, "no such HIP device");
 	GHIP(nullptr, hipSetDevice(device));
 	const size_t n = bytes / sizeof(float4);
-	float4 *a = nullptr, *b = nullptr, *c = nullptr;
-	hipEvent_t e0 = nullptr, e1 = nullptr;
+	DevBuf<float4> a, b, c;                  // buffers and events are released on every way out
+	EventPair ev;
+	hipEvent_t &e0 = ev.a, &e1 = ev.b;
 	hipStream_t s = nullptr;
 	int rc = 0;
 	do {
-		if (hipMalloc((void **) &a, n * sizeof(float4)) != hipSuccess || hipMalloc((void **) &b, n * sizeof(float4)) != hipSuccess
-		    || hipMalloc((void **) &c, n * sizeof(float4)) != hipSuccess || hipStreamCreate(&s) != hipSuccess
+		if (a.ensure(nullptr, n) || b.ensure(nullptr, n) || c.ensure(nullptr, n) || hipStreamCreate(&s) != hipSuccess
 		    || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { rc = gfail(nullptr, MTSGPU_EHIP, "triad: allocation failed"); break; }
 		(void) hipMemsetAsync(b, 0, n * sizeof(float4), s); (void) hipMemsetAsync(c, 0, n * sizeof(float4), s);
 		launch_triad(s, a, b, c, 0.5f, n);                                  // warm-up
@@ -506,12 +492,7 @@ int mtsgpu_hbm_triad(int device, size_t bytes, int iters, double *gbs) {
 		}
 		if (!rc && best < 1e29f) *gbs = 3.0 * (double) (n * sizeof(float4)) / (best * 1e-3) / 1e9;
 	} while (false);
-	if (e0) (void) hipEventDestroy(e0);
-	if (e1) (void) hipEventDestroy(e1);
 	if (s) (void) hipStreamDestroy(s);
-	if (a) (void) hipFree(a);
-	if (b) (void) hipFree(b);
-	if (c) (void) hipFree(c);
 	return rc;
 }
 
@@ -526,11 +507,12 @@ int mtsgpu_gather_roof(int device, size_t footprint_bytes, double *lane_requests
 	GHIP(nullptr, hipGetDeviceProperties(&prop, device));
 	const unsigned blocks = (unsigned) prop.multiProcessorCount * 7u;
 	const int iters = 1000;
-	uint4 *data = nullptr; uint32_t *sink = nullptr;
-	hipEvent_t e0 = nullptr, e1 = nullptr; hipStream_t s = nullptr;
+	DevBuf<uint4> data; DevBuf<uint32_t> sink;
+	EventPair ev;
+	hipEvent_t &e0 = ev.a, &e1 = ev.b; hipStream_t s = nullptr;
 	int rc = 0;
 	do {
-		if (hipMalloc((void **) &data, footprint_bytes) != hipSuccess || hipMalloc((void **) &sink, 4) != hipSuccess || hipStreamCreate(&s) != hipSuccess
+		if (data.ensure(nullptr, footprint_bytes / sizeof(uint4)) || sink.ensure(nullptr, 1) || hipStreamCreate(&s) != hipSuccess
 		    || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { rc = gfail(nullptr, MTSGPU_EHIP, "gather roof: allocation failed"); break; }
 		(void) hipMemsetAsync(data, 1, footprint_bytes, s);
 		const uint32_t mask = (uint32_t) (footprint_bytes / 16 - 1);
@@ -546,11 +528,7 @@ int mtsgpu_gather_roof(int device, size_t footprint_bytes, double *lane_requests
 		}
 		if (!rc && best < 1e29f) *lane_requests_per_s = (double) blocks * 256.0 * iters / (best * 1e-3);
 	} while (false);
-	if (e0) (void) hipEventDestroy(e0);
-	if (e1) (void) hipEventDestroy(e1);
 	if (s) (void) hipStreamDestroy(s);
-	if (data) (void) hipFree(data);
-	if (sink) (void) hipFree(sink);
 	return rc;
 }
 

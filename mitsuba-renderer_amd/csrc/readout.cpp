@@ -104,7 +104,6 @@ int mtsgpu_replay_roof(mtsgpu_ctx *c, int kind, uint32_t n, uint32_t stride, int
 	if (!scratch.ok()) return scratch.finish("replay roof allocation");
 	EventPair ev;
 	HIPCHK(c, hipEventCreate(&ev.a)); HIPCHK(c, hipEventCreate(&ev.b));
-	const size_t counterBytes = kNumCounters * kCounterStride * sizeof(uint32_t);
 	c->q.counters = c->counterSets; c->q.spill = mode == 1 ? c->spillShadow : c->spillClosest; c->q.dev_stats = nullptr;
 	c->q.next = c->queueB;
 	// the rays of the sample
@@ -137,7 +136,7 @@ int mtsgpu_replay_roof(mtsgpu_ctx *c, int kind, uint32_t n, uint32_t stride, int
 	// 1. the counting kernel records what every ray asks for
 	HIPCHK(c, hipMemsetAsync(recLen, 0, (size_t) n * 4, s));
 	HIPCHK(c, hipMemsetAsync(c->q.trace_counts, 0, kNumTraceCounts * sizeof(unsigned long long), s));
-	HIPCHK(c, hipMemsetAsync(c->q.counters, 0, counterBytes, s));
+	HIPCHK(c, hipMemsetAsync(c->q.counters, 0, kCounterSetBytes, s));
 	c->q.rec = rec; c->q.rec_len = recLen; c->q.rec_cap = cap;
 	launch_trace(s, mode, true, bin, c->dsc, c->paths, c->q, queue, n, coherent);
 	c->q.rec = c->q.rec_len = nullptr; c->q.rec_cap = 0;
@@ -159,7 +158,7 @@ int mtsgpu_replay_roof(mtsgpu_ctx *c, int kind, uint32_t n, uint32_t stride, int
 	// 3. the product kernel and the replay on the same rays, best of `reps`
 	float prodMs = 1e30f, replayMs = 1e30f;
 	for (int i = 0; i <= reps; ++i) {            // round 0 warms up
-		HIPCHK(c, hipMemsetAsync(c->q.counters, 0, counterBytes, s));
+		HIPCHK(c, hipMemsetAsync(c->q.counters, 0, kCounterSetBytes, s));
 		HIPCHK(c, hipEventRecord(ev.a, s));
 		launch_trace(s, mode, false, bin, c->dsc, c->paths, c->q, queue, n, coherent);
 		HIPCHK(c, hipEventRecord(ev.b, s));
@@ -186,11 +185,11 @@ int mtsgpu_ld_tables(mtsgpu_ctx *c, uint32_t pixel_key, float *out1d, float *out
 	HIPCHK(c, hipSetDevice(c->device));
 	const uint32_t spp = effectiveSpp(c);
 	const int depth = c->ldDepth;
-	int rc = ensureBuf(c, &c->ldScr, &c->ldScrCap, (size_t) 3 * depth); if (rc) return rc;
-	rc = ensureBuf(c, &c->ldPerm, &c->ldPermCap, (size_t) 2 * depth * spp); if (rc) return rc;
+	int rc = c->ldScr.ensure(c, (size_t) 3 * depth); if (rc) return rc;
+	rc = c->ldPerm.ensure(c, (size_t) 2 * depth * spp); if (rc) return rc;
 	rc = ensureTableWork(c, 1, spp); if (rc) return rc;
 	c->renderListValid = false; c->lastPass.valid = false;
-	rc = ensureBuf(c, &c->pixelList, &c->pixelListCap, 1); if (rc) return rc;
+	rc = c->pixelList.ensure(c, 1); if (rc) return rc;
 	HIPCHK(c, hipMemcpyAsync(c->pixelList, &pixel_key, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
 	DConfig cfg{};
 	cfg.spp = spp; cfg.ld_depth = depth; cfg.seed = c->seed; cfg.sampler_kind = 1;
@@ -230,11 +229,11 @@ int mtsgpu_sampler_values(mtsgpu_ctx *c, uint32_t pixel_key, uint32_t sample_ind
 	if (n > 4096u || sample_index >= spp) return fail(c, MTSGPU_EINVAL, "sample index or count out of range");
 	HIPCHK(c, hipSetDevice(c->device));
 	c->renderListValid = false; c->lastPass.valid = false;
-	int rc = ensureBuf(c, &c->pixelList, &c->pixelListCap, 1); if (rc) return rc;
+	int rc = c->pixelList.ensure(c, 1); if (rc) return rc;
 	HIPCHK(c, hipMemcpyAsync(c->pixelList, &pixel_key, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
 	if (samplerHasTables(c)) {
-		rc = ensureBuf(c, &c->ldScr, &c->ldScrCap, (size_t) 3 * c->ldDepth); if (rc) return rc;
-		rc = ensureBuf(c, &c->ldPerm, &c->ldPermCap, (size_t) 2 * c->ldDepth * spp); if (rc) return rc;
+		rc = c->ldScr.ensure(c, (size_t) 3 * c->ldDepth); if (rc) return rc;
+		rc = c->ldPerm.ensure(c, (size_t) 2 * c->ldDepth * spp); if (rc) return rc;
 		rc = ensureTableWork(c, 1, spp); if (rc) return rc;
 	}
 	const int integratorSaved = c->integrator;

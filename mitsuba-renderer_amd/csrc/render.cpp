@@ -35,7 +35,7 @@ long tuningOr(const mtsgpu_ctx *c, const char *key, long dflt) {
 
 // scheduling parameters of k_trace: the defaults, or what mtsgpu_set_tuning asked for
 void mg::applyTuning(mtsgpu_ctx *c) {
-	auto get = [&](const char *key, long dflt) { auto it = c->tuning.find(key); return it == c->tuning.end() ? dflt : it->second; };
+	const auto get = [&](const char *key, long dflt) { return tuningOr(c, key, dflt); };
 	c->q.refill_min = (uint32_t) get("refill_min", 32);
 	c->q.desc_min = (uint32_t) get("desc_min", 8);
 	c->q.leaf_min = (uint32_t) get("leaf_min", 8);
@@ -56,8 +56,8 @@ bool mg::samplerHasTables(const mtsgpu_ctx *c) {
 // what launch_ld_tables needs besides the tables: one stream word per slot and, above 512 samples per pixel, the scratch
 // copy the tables are shuffled in
 int mg::ensureTableWork(mtsgpu_ctx *c, size_t nSlots, uint32_t spp) {
-	int rc = ensureBuf(c, &c->ldState, &c->ldStateCap, nSlots); if (rc) return rc;
-	return ensureBuf(c, &c->ldScratch, &c->ldScratchCap, ld_table_scratch_entries((uint32_t) nSlots, spp, c->ldDepth));
+	int rc = c->ldState.ensure(c, nSlots); if (rc) return rc;
+	return c->ldScratch.ensure(c, ld_table_scratch_entries((uint32_t) nSlots, spp, c->ldDepth));
 }
 
 DConfig mg::makeConfig(const mtsgpu_ctx *c, bool slotPerPath) {
@@ -91,11 +91,8 @@ DConfig mg::makeConfig(const mtsgpu_ctx *c, bool slotPerPath) {
 	// Without a background luminaire a ray that leaves the scene ends its path and adds nothing: the records are kept so that
 	// such a ray needs no shading (kernels.h: DConfig::miss_settled).  The rounds of MIDirectIntegrator keep the shaded route,
 	// and so does the "miss_shaded" knob at 1 (A/B runs, tests)
-	{
-		const auto it = c->tuning.find("miss_shaded");
-		const bool rounds = c->integrator == 1 && (c->nLumSamples > 1 || c->nBsdfSamples > 1);
-		cfg.miss_settled = (c->dsc.background_lum < 0 && !rounds && !(it != c->tuning.end() && it->second == 1)) ? 1 : 0;
-	}
+	const bool rounds = c->integrator == 1 && (c->nLumSamples > 1 || c->nBsdfSamples > 1);
+	cfg.miss_settled = (c->dsc.background_lum < 0 && !rounds && tuningOr(c, "miss_shaded", 0) != 1) ? 1 : 0;
 	return cfg;
 }
 
@@ -172,15 +169,6 @@ int ensurePaths(mtsgpu_ctx *c, size_t cap) {
 	return 0;
 }
 
-// The direct-light terms of the shadow queue (DPaths::shq_nee), for a frame that runs with DQueues::nee_parked == 0: the
-// rounds of MIDirectIntegrator and the "nee_parked" knob at 0.  Every other frame parks the terms in the path records and
-// does without the 16 bytes per path.
-int ensureNeeQueue(mtsgpu_ctx *c) {
-	int rc = ensureBuf(c, &c->shqNee, &c->shqNeeCap, c->pathCap);
-	c->paths.shq_nee = c->shqNee;
-	return rc;
-}
-
 // buffers of the sample arrays for nSlots sampler slots (and of the saved camera hits for nPaths paths)
 int ensureSampleArrays(mtsgpu_ctx *c, size_t nSlots, size_t nPaths) {
 	if (c->integrator != 1 || (c->nLumSamples <= 1 && c->nBsdfSamples <= 1))
@@ -196,40 +184,56 @@ int ensureSampleArrays(mtsgpu_ctx *c, size_t nSlots, size_t nPaths) {
 			total += (size_t) spp * n; ++nArr;
 		}
 	int rc = 0;
-	if (c->nBsdfSamples > 1) { rc = ensureBuf(c, &c->primSave, &c->primSaveCap, 3 * nPaths); if (rc) return rc; }
+	if (c->nBsdfSamples > 1) { rc = c->primSave.ensure(c, 3 * nPaths); if (rc) return rc; }
 	c->paths.prim = c->primSave;
 	if (!samplerHasTables(c)) return 0;
-	rc = ensureBuf(c, &c->ldState, &c->ldStateCap, nSlots); if (rc) return rc;
+	rc = c->ldState.ensure(c, nSlots); if (rc) return rc;
 	if (c->samplerKind == MTSGPU_SAMPLER_LD_KEYED) {
-		rc = ensureBuf(c, &c->arrScr, &c->arrScrCap, nSlots * nArr * 2); if (rc) return rc;
-		rc = ensureBuf(c, &c->arrPerm, &c->arrPermCap, nSlots * total); if (rc) return rc;
+		rc = c->arrScr.ensure(c, nSlots * nArr * 2); if (rc) return rc;
+		rc = c->arrPerm.ensure(c, nSlots * total); if (rc) return rc;
 	} else {
-		rc = ensureBuf(c, &c->arrPts, &c->arrPtsCap, nSlots * total); if (rc) return rc;
+		rc = c->arrPts.ensure(c, nSlots * total); if (rc) return rc;
 	}
 	return 0;
 }
 
-hipEvent_t *nextEventPair(mtsgpu_ctx *c, std::vector<std::pair<hipEvent_t, hipEvent_t>> &pool, size_t &used) {
-	if (used == pool.size()) {
-		hipEvent_t a, b;
-		if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return nullptr;
-		pool.emplace_back(a, b);
-	}
-	return &pool[used++].first;
-}
+// What a timed launch is: a traversal launch of one of the classes of ctx.h's traceEvClass, or the shading of a bounce
+enum LaunchKind { kClosest = 0, kClosestFirst = 1, kAnyHit = 2, kShading = 3 };
 
-// an event pair for a traversal launch of class cls (ctx.h: traceEvClass)
-hipEvent_t *nextTraceEvents(mtsgpu_ctx *c, int cls) {
-	hipEvent_t *ev = nextEventPair(c, c->traceEvents, c->traceEvUsed);
-	if (ev) {
-		if (c->traceEvClass.size() < c->traceEvUsed) c->traceEvClass.resize(c->traceEvUsed);
-		c->traceEvClass[c->traceEvUsed - 1] = (unsigned char) cls;
+// The one way the engine launches a stage: `launch` (a kernel, or the kernels of one shading step) on stream s, then the
+// check that the device accepted it.  With time_kernels on the launch runs between a pair of events from the pool of its
+// kind, and a traversal launch files its class next to its pair (collectTimings sums the classes apart).  The host counts
+// the traversal launches of a frame that keeps no statistics on the device (device-driven bounces count theirs in k_prep).
+// An event that cannot be created is MTSGPU_EHIP: no launch goes untimed silently.
+template <typename F> int timedLaunch(mtsgpu_ctx *c, hipStream_t s, LaunchKind kind, F &&launch) {
+	const bool shading = kind == kShading;
+	std::pair<hipEvent_t, hipEvent_t> ev{ nullptr, nullptr };
+	if (c->timeKernels) {
+		EventPool &pool = shading ? c->shadeEvents : c->traceEvents;
+		size_t &used = shading ? c->shadeEvUsed : c->traceEvUsed;
+		if (used == pool.size()) {
+			if (hipEventCreate(&ev.first) != hipSuccess || hipEventCreate(&ev.second) != hipSuccess) {
+				if (ev.first) (void) hipEventDestroy(ev.first);
+				return fail(c, MTSGPU_EHIP, "hipEventCreate failed");
+			}
+			pool.push_back(ev);
+		}
+		if (!shading) {
+			if (c->traceEvClass.size() <= used) c->traceEvClass.resize(used + 1);
+			c->traceEvClass[used] = (unsigned char) kind;
+		}
+		ev = pool[used++];
+		HIPCHK(c, hipEventRecord(ev.first, s));
 	}
-	return ev;
+	launch();
+	if (ev.second) HIPCHK(c, hipEventRecord(ev.second, s));
+	HIPCHK(c, hipGetLastError());
+	if (!shading && !c->q.dev_stats) c->stats.trace_launches++;
+	return 0;
 }
 
 int readCounters(mtsgpu_ctx *c) {
-	HIPCHK(c, hipMemcpyAsync(c->hostCounters, c->q.counters, kNumCounters * kCounterStride * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpyAsync(c->hostCounters, c->q.counters, kCounterSetBytes, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	return 0;
 }
@@ -239,19 +243,16 @@ int readCounters(mtsgpu_ctx *c) {
 // the launch run again with static dealing: tracing a ray twice writes the same hit twice.
 int traceAndBin(mtsgpu_ctx *c, const uint32_t *queue, uint32_t n, bool coherent, BinView *views) {
 	hipStream_t s = c->stream;
-	const size_t counterBytes = kNumCounters * kCounterStride * sizeof(uint32_t);
+	const bool testRetry = tuningOr(c, "test_retry", 0) != 0;      // exercises the retry (tests)
 	for (int attempt = 0; attempt < 2; ++attempt) {
-		if (attempt) HIPCHK(c, hipMemsetAsync(c->q.counters, 0, counterBytes, s));
+		if (attempt) HIPCHK(c, hipMemsetAsync(c->q.counters, 0, kCounterSetBytes, s));
 		c->q.force_static = attempt ? 1u : 0u;
-		hipEvent_t *ev = c->timeKernels ? nextTraceEvents(c, coherent ? 1 : 0) : nullptr;
-		if (ev) HIPCHK(c, hipEventRecord(ev[0], s));
-		launch_trace(s, 0, c->countTraversal && attempt == 0, true, c->dsc, c->paths, c->q, queue, n, coherent);
-		if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
-		HIPCHK(c, hipGetLastError());
-		c->stats.trace_launches++;
-		int rc = readCounters(c); if (rc) { c->q.force_static = 0; return rc; }
+		int rc = timedLaunch(c, s, coherent ? kClosestFirst : kClosest, [&] {
+			launch_trace(s, 0, c->countTraversal && attempt == 0, true, c->dsc, c->paths, c->q, queue, n, coherent); });
+		if (!rc) rc = readCounters(c);
 		c->q.force_static = 0;
-		bool overflow = false;
+		if (rc) return rc;
+		bool overflow = attempt == 0 && testRetry;
 		for (int b = 0; b < kNumBins; ++b) {
 			uint32_t acc = 0;
 			for (int k = 0; k < kBinShards; ++k) {
@@ -262,7 +263,6 @@ int traceAndBin(mtsgpu_ctx *c, const uint32_t *queue, uint32_t n, bool coherent,
 			}
 			views[b].prefix[kBinShards] = acc;
 		}
-		if (attempt == 0 && c->tuning.count("test_retry") && c->tuning["test_retry"]) overflow = true;   // exercises the retry (tests)
 		if (!overflow) {
 			for (int b = 0; b < kNumBins; ++b) c->binEntries[b] += views[b].prefix[kBinShards];
 			return 0;
@@ -272,6 +272,60 @@ int traceAndBin(mtsgpu_ctx *c, const uint32_t *queue, uint32_t n, bool coherent,
 	return fail(c, MTSGPU_EHIP, "internal: bin segment overflow with static dealing");
 }
 
+// The any-hit step of a bounce: the shadow queue, with a spill area of its own (a closest-hit launch may run beside it).
+// n: the size of the queue, or, with `count`, a bound of the size the device keeps in that word.
+int traceShadows(mtsgpu_ctx *c, hipStream_t s, uint32_t n, bool coherent, const uint32_t *count = nullptr) {
+	DQueues q2 = c->q; q2.spill = c->spillShadow;
+	return timedLaunch(c, s, kAnyHit, [&] { launch_trace(s, 1, c->countTraversal, false, c->dsc, c->paths, q2, q2.shadow, n, coherent, count); });
+}
+
+// What every shading launch of a frame takes: the stream, the frame's configuration and, from the context at the moment of
+// the launch, the scene, the records, the queues and the three per-vertex families.
+struct Shader {
+	mtsgpu_ctx *c; hipStream_t s; DConfig cfg;
+	bool fused;                            // the "shade_fused" knob: one kernel for the bins of kShadeAllBins (device-driven bounces)
+	Shader(mtsgpu_ctx *c, hipStream_t s, const DConfig &cfg) : c(c), s(s), cfg(cfg), fused(tuningOr(c, "shade_fused", 1) != 0) {}
+	// Bin b: over the view the host read back, or (viewsDev) over the one k_prep wrote, with a grid for `bound` paths.
+	// ids: the queue to shade instead of the bin's (the ray queue, for the material-independent tail)
+	void bin(int b, const BinView &view, const BinView *viewsDev = nullptr, uint32_t bound = 0, const uint32_t *ids = nullptr) const {
+		launch_shade(s, b, c->dsc, c->paths, cfg, c->q, view, viewsDev, bound, ids, c->dcol, c->dtex, c->dtan);
+	}
+	// the first nBins bins of a bounce whose sizes the host has read
+	void bins(const BinView *views, int nBins = kNumBins) const { for (int b = 0; b < nBins; ++b) bin(b, views[b]); }
+	// The bins of a bounce whose sizes only the device knows: the fused kernel where it applies, and one launch for every
+	// other bin the scene can fill (the composite, which the fused kernel leaves out; every bin without it)
+	void binsOnDevice(uint32_t bound) const {
+		uint32_t each = c->binMask;
+		if (cfg.dr_mode == 0 && fused) {
+			launch_shade_all(s, c->dsc, c->paths, cfg, c->q, c->viewsDev, c->binMask & kShadeAllBins, bound, c->dcol, c->dtex, c->dtan);
+			each &= ~kShadeAllBins;
+		}
+		const BinView none{};
+		for (int b = 0; b < kNumBins; ++b)
+			if (each & (1u << b)) bin(b, none, c->viewsDev, bound);
+	}
+};
+
+// the rounds of MIDirectIntegrator with more than one sample per strategy (runDirectRounds)
+bool directRounds(const DConfig &cfg) { return cfg.integrator == 1 && (cfg.n_lum > 1 || cfg.n_bsdf > 1); }
+
+// The direct-light terms of the shadow queue (DPaths::shq_nee), for a frame that runs with DQueues::nee_parked == 0; every
+// other frame parks the terms in the path records and does without the 16 bytes per path
+int ensureNeeQueue(mtsgpu_ctx *c) {
+	const int rc = c->shqNee.ensure(c, c->pathCap);
+	c->paths.shq_nee = c->shqNee;
+	return rc;
+}
+
+// The queue flags of a frame, under the caller's RayQueuesOff: whether k_trace<closest> settles a miss (k_trace and k_shade
+// agree on who does), and whether a direct-light term is parked in its path's record -- not in the rounds, which add their
+// terms to Li one after the other, and not with the "nee_parked" knob at 0
+int beginQueues(mtsgpu_ctx *c, const DConfig &cfg) {
+	c->q.miss_settled = cfg.miss_settled ? 1u : 0u;
+	c->q.nee_parked = !directRounds(cfg) && tuningOr(c, "nee_parked", 1) != 0 ? 1u : 0u;
+	return c->q.nee_parked ? 0 : ensureNeeQueue(c);
+}
+
 // MIDirectIntegrator with more than one sample per strategy (direct.cpp:129-150,163-195): after the camera rays are
 // traced and sorted by material, the two sampling loops run as rounds over those queues -- round j of the first loop
 // shades with luminaire sample j and traces its shadow rays, round j of the second loop shades with BSDF sample j,
@@ -279,65 +333,47 @@ int traceAndBin(mtsgpu_ctx *c, const uint32_t *queue, uint32_t n, bool coherent,
 // (emission, luminaire samples 0.., BSDF samples 0..), which float addition needs for identical results.
 int runDirectRounds(mtsgpu_ctx *c, const DConfig &cfg0, uint32_t nPaths, volatile const int *cancel) {
 	hipStream_t s = c->stream;
-	DConfig cfg = cfg0;
-	const size_t counterBytes = kNumCounters * kCounterStride * sizeof(uint32_t);
-	auto timedTrace = [&](int mode, bool bin, const uint32_t *queue, uint32_t n, bool coherent) -> int {
-		hipEvent_t *ev = c->timeKernels ? nextTraceEvents(c, mode == 1 ? 2 : 0) : nullptr;
-		if (ev) HIPCHK(c, hipEventRecord(ev[0], s));
-		launch_trace(s, mode, c->countTraversal, bin, c->dsc, c->paths, c->q, queue, n, coherent);
-		if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
-		HIPCHK(c, hipGetLastError());
-		c->stats.trace_launches++;
-		return 0;
-	};
-	{ int rc = ensureNeeQueue(c); if (rc) return rc; }      // the rounds add their terms to Li one after the other: nothing is parked
-	HIPCHK(c, hipMemsetAsync(c->q.counters, 0, counterBytes, s));
+	Shader shade(c, s, cfg0);
+	RayQueuesOff rqOff{ c };
+	int rc = beginQueues(c, cfg0); if (rc) return rc;
+	HIPCHK(c, hipMemsetAsync(c->q.counters, 0, kCounterSetBytes, s));
 	c->q.next = c->queueB;
 	BinView views[kNumBins];
-	RayQueuesOff rqOff{ c };
 	rayQueues(c, c->queueA, nullptr);        // the camera rays; the rays of the sampling rounds are traced from the records
-	int rc = traceAndBin(c, c->queueA, nPaths, true, views); if (rc) return rc;
+	rc = traceAndBin(c, c->queueA, nPaths, true, views); if (rc) return rc;
 	rayQueues(c, nullptr, nullptr);
 	c->stats.rays_closest += nPaths;
-	auto shadeRound = [&](int mode, int index, bool withTerminal) -> int {
-		hipEvent_t *sev = c->timeKernels ? nextEventPair(c, c->shadeEvents, c->shadeEvUsed) : nullptr;
-		HIPCHK(c, hipMemsetAsync(c->q.counters, 0, counterBytes, s));     // the bins stay as they are; views[] holds their sizes
-		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
-		cfg.dr_mode = mode; cfg.dr_index = index;
-		for (int b = 0; b < (withTerminal ? kNumBins : kNumBsdfTypes); ++b)
-			launch_shade(s, b, c->dsc, c->paths, cfg, c->q, views[b], nullptr, 0, nullptr, c->dcol, c->dtex, c->dtan);
-		if (sev) HIPCHK(c, hipEventRecord(sev[1], s));
-		HIPCHK(c, hipGetLastError());
-		return readCounters(c);
+	auto shadeRound = [&](int mode, int index, int nBins) -> int {
+		HIPCHK(c, hipMemsetAsync(c->q.counters, 0, kCounterSetBytes, s));     // the bins stay as they are; views[] holds their sizes
+		shade.cfg.dr_mode = mode; shade.cfg.dr_index = index;
+		const int rc = timedLaunch(c, s, kShading, [&] { shade.bins(views, nBins); });
+		return rc ? rc : readCounters(c);
 	};
 	// direct.cpp:122-150
 	for (int j = 0; j < std::max(1, c->nLumSamples); ++j) {
 		if (cancel && *cancel) return fail(c, MTSGPU_ECANCEL, "render cancelled");
-		rc = shadeRound(1, j, j == 0); if (rc) return rc;
+		rc = shadeRound(1, j, j == 0 ? kNumBins : kNumBsdfTypes); if (rc) return rc;      // the terminal bin once
 		const uint32_t nShadow = c->hostCounters[kShadowWord];
 		if (nShadow) {
-			rc = timedTrace(1, false, c->q.shadow, nShadow, true); if (rc) return rc;
+			rc = traceShadows(c, s, nShadow, true); if (rc) return rc;
 			c->stats.rays_shadow += nShadow;
 		}
 	}
 	// direct.cpp:152-195
 	for (int j = 0; j < std::max(1, c->nBsdfSamples); ++j) {
 		if (cancel && *cancel) return fail(c, MTSGPU_ECANCEL, "render cancelled");
-		rc = shadeRound(2, j, false); if (rc) return rc;
+		rc = shadeRound(2, j, kNumBsdfTypes); if (rc) return rc;
 		const uint32_t nNext = c->hostCounters[kNextWord];
 		if (!nNext) continue;
-		rc = timedTrace(0, false, c->queueB, nNext, false); if (rc) return rc;
+		rc = timedLaunch(c, s, kClosest, [&] { launch_trace(s, 0, c->countTraversal, false, c->dsc, c->paths, c->q, c->queueB, nNext, false); });
+		if (rc) return rc;
 		c->stats.rays_closest += nNext;
 		// what the sampled rays hit: the material-independent tail of the shading kernel over the ray queue
 		BinView tail;
 		tail.prefix[0] = 0;
 		for (int k = 1; k <= kBinShards; ++k) tail.prefix[k] = nNext;
-		hipEvent_t *sev = c->timeKernels ? nextEventPair(c, c->shadeEvents, c->shadeEvUsed) : nullptr;
-		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
-		cfg.dr_mode = 3; cfg.dr_index = j;
-		launch_shade(s, kNumBsdfTypes, c->dsc, c->paths, cfg, c->q, tail, nullptr, 0, c->queueB, c->dcol, c->dtex, c->dtan);
-		if (sev) HIPCHK(c, hipEventRecord(sev[1], s));
-		HIPCHK(c, hipGetLastError());
+		shade.cfg.dr_mode = 3; shade.cfg.dr_index = j;
+		rc = timedLaunch(c, s, kShading, [&] { shade.bin(kNumBsdfTypes, tail, nullptr, 0, c->queueB); }); if (rc) return rc;
 	}
 	return 0;
 }
@@ -352,8 +388,7 @@ uint32_t *counterSet(mtsgpu_ctx *c, int bounce) { return c->counterSets + (size_
 // frames keep the host-sized grids of runBounces.  The host looks at a queue size once per chunk of bounces, to stop.
 int runBouncesDevice(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile const int *cancel) {
 	hipStream_t s1 = c->stream, s2 = c->stream2;
-	const size_t setBytes = (size_t) kNumCounters * kCounterStride * sizeof(uint32_t);
-	HIPCHK(c, hipMemsetAsync(c->counterSets, 0, kCounterSets * setBytes, s1));
+	HIPCHK(c, hipMemsetAsync(c->counterSets, 0, kCounterSets * kCounterSetBytes, s1));
 	c->q.dev_stats = c->devStats;        // cleared by the caller (one frame may take several passes)
 	c->devStatsUsed = true;
 	// MIPathTracer traces at most maxDepth rays per path (path.cpp:87), the one-sample direct integrator two
@@ -375,17 +410,8 @@ int runBouncesDevice(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatil
 		}
 	} restore{ c, s2, shadowPending };
 	RayQueuesOff rqOff{ c };
-	c->q.nee_parked = tuningOr(c, "nee_parked", 1) != 0 ? 1u : 0u;
-	if (!c->q.nee_parked) { int rc = ensureNeeQueue(c); if (rc) return rc; }
-	c->q.miss_settled = cfg.miss_settled ? 1u : 0u;      // k_trace<closest> and k_shade agree on who settles a miss
-	// cls >= 0: a traversal launch of that class (ctx.h: traceEvClass)
-	auto timed = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>> &pool, size_t &used, hipStream_t s, int which, int cls = -1) -> int {
-		if (!c->timeKernels) return 0;
-		hipEvent_t *ev = which == 0 ? (cls >= 0 ? nextTraceEvents(c, cls) : nextEventPair(c, pool, used)) : &pool[used - 1].first;
-		if (!ev) return fail(c, MTSGPU_EHIP, "hipEventCreate failed");
-		HIPCHK(c, hipEventRecord(ev[which], s));
-		return 0;
-	};
+	{ int rc = beginQueues(c, cfg); if (rc) return rc; }
+	const Shader shade(c, s1, cfg);
 	while (b < limit && upper > 0) {
 		if (cancel && *cancel) return fail(c, MTSGPU_ECANCEL, "render cancelled");
 		const int end = (int) std::min<long long>((long long) b + chunk, limit);
@@ -393,44 +419,26 @@ int runBouncesDevice(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatil
 			uint32_t *set = counterSet(c, b), *prev = counterSet(c, b - 1);
 			c->q.counters = set; c->q.next = nxt; c->q.spill = c->spillClosest;
 			rayQueues(c, cur, nxt);
-			int rc = timed(c->traceEvents, c->traceEvUsed, s1, 0, b == 0 ? 1 : 0); if (rc) return rc;
-			launch_trace(s1, 0, c->countTraversal, true, c->dsc, c->paths, c->q, cur, upper, b == 0,
-			             b == 0 ? nullptr : prev + (size_t) kNextWord);
-			rc = timed(c->traceEvents, c->traceEvUsed, s1, 1); if (rc) return rc;
+			int rc = timedLaunch(c, s1, b == 0 ? kClosestFirst : kClosest, [&] {
+				launch_trace(s1, 0, c->countTraversal, true, c->dsc, c->paths, c->q, cur, upper, b == 0,
+				             b == 0 ? nullptr : prev + (size_t) kNextWord); });
+			if (rc) return rc;
 			// the shading of this bounce adds to Li after the shadow rays of the previous one have (path.cpp:124 before :80)
 			if (shadowPending) HIPCHK(c, hipStreamWaitEvent(s1, c->evShadow[(b - 1) & 1], 0));
-			rc = timed(c->shadeEvents, c->shadeEvUsed, s1, 0); if (rc) return rc;
-			launch_prep(s1, set, prev, c->viewsDev, c->q.bin_seg_cap, c->devStats);
-			if (cfg.dr_mode == 0 && tuningOr(c, "shade_fused", 1) != 0) {
-				launch_shade_all(s1, c->dsc, c->paths, cfg, c->q, c->viewsDev, c->binMask & kShadeAllBins, upper, c->dcol, c->dtex, c->dtan);
-				// the bins the fused kernel leaves out (the composite), one launch each, only when the scene has them
-				BinView none{};
-				for (int bin = 0; bin < kNumBins; ++bin)
-					if (c->binMask & ~kShadeAllBins & (1u << bin))
-						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper, nullptr, c->dcol, c->dtex, c->dtan);
-			} else {
-				BinView none{};
-				for (int bin = 0; bin < kNumBins; ++bin)
-					if (c->binMask & (1u << bin))
-						launch_shade(s1, bin, c->dsc, c->paths, cfg, c->q, none, c->viewsDev, upper, nullptr, c->dcol, c->dtex, c->dtan);
-			}
-			rc = timed(c->shadeEvents, c->shadeEvUsed, s1, 1); if (rc) return rc;
-			HIPCHK(c, hipGetLastError());
+			rc = timedLaunch(c, s1, kShading, [&] {
+				launch_prep(s1, set, prev, c->viewsDev, c->q.bin_seg_cap, c->devStats);
+				shade.binsOnDevice(upper); });
+			if (rc) return rc;
 			HIPCHK(c, hipEventRecord(c->evShade[b & 1], s1));
 			// shadow rays of this bounce on the second stream, next to the closest-hit launch of the next bounce
 			HIPCHK(c, hipStreamWaitEvent(s2, c->evShade[b & 1], 0));
-			DQueues q2 = c->q; q2.spill = c->spillShadow;
-			rc = timed(c->traceEvents, c->traceEvUsed, s2, 0, 2); if (rc) return rc;
-			launch_trace(s2, 1, c->countTraversal, false, c->dsc, c->paths, q2, c->q.shadow, upper, b == 0,
-			             set + (size_t) kShadowWord);
-			rc = timed(c->traceEvents, c->traceEvUsed, s2, 1); if (rc) return rc;
-			HIPCHK(c, hipGetLastError());
+			rc = traceShadows(c, s2, upper, b == 0, set + (size_t) kShadowWord); if (rc) return rc;
 			HIPCHK(c, hipEventRecord(c->evShadow[b & 1], s2));
 			shadowPending = true;
 			std::swap(cur, nxt);
 		}
 		// how many paths are left: the one read-back of the chunk
-		uint32_t *hostNext = &c->hostCounters[kNumCounters * kCounterStride + 2];
+		uint32_t *hostNext = &c->hostCounters[kHostNextWord];
 		HIPCHK(c, hipMemcpyAsync(hostNext, counterSet(c, b - 1) + (size_t) kNextWord, sizeof(uint32_t), hipMemcpyDeviceToHost, s1));
 		HIPCHK(c, hipEventRecord(c->evCount, s1));
 		HIPCHK(c, hipEventSynchronize(c->evCount));
@@ -455,10 +463,25 @@ int collectDeviceStats(mtsgpu_ctx *c) {
 	return 0;
 }
 
+// MTSGPU_DEBUG: what the launches of a host-driven bounce took, once they are done (tools/bounce_times.py)
+int printBounce(mtsgpu_ctx *c, uint32_t nClosest, uint32_t nShadow) {
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	float a = 0, b = 0, c2 = 0;
+	if (c->timeKernels) {
+		const size_t ti = c->traceEvUsed - (nShadow ? 2 : 1);
+		(void) hipEventElapsedTime(&a, c->traceEvents[ti].first, c->traceEvents[ti].second);
+		(void) hipEventElapsedTime(&b, c->shadeEvents[c->shadeEvUsed - 1].first, c->shadeEvents[c->shadeEvUsed - 1].second);
+		if (nShadow) (void) hipEventElapsedTime(&c2, c->traceEvents[ti + 1].first, c->traceEvents[ti + 1].second);
+	}
+	fprintf(stderr, "bounce: closest %u rays %.3f ms (%.2f Grays/s) | shade %.3f ms | shadow %u rays %.3f ms (%.2f Grays/s)\n",
+	        nClosest, a, a > 0 ? nClosest / a / 1e6 : 0.0, b, nShadow, c2, c2 > 0 ? nShadow / c2 / 1e6 : 0.0);
+	return 0;
+}
+
 // One wavefront pass: all bounces of the paths already generated into queueA[0..nPaths)
 int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile const int *cancel) {
 	c->q.counters = c->counterSets; c->q.spill = c->spillClosest; c->q.dev_stats = nullptr;
-	if (cfg.integrator == 1 && (cfg.n_lum > 1 || cfg.n_bsdf > 1))
+	if (directRounds(cfg))
 		return runDirectRounds(c, cfg, nPaths, cancel);
 	{
 		// frames of few paths are chains of launches too short to hide a host round trip
@@ -472,17 +495,15 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 	uint32_t *cur = c->queueA, *nxt = c->queueB;
 	bool first = true;       // camera rays and their shadow rays are coherent: plain 64-ray batches win there
 	hipStream_t s = c->stream;
-	const size_t setBytes = (size_t) kNumCounters * kCounterStride * sizeof(uint32_t);
 	RayQueuesOff rqOff{ c };
-	c->q.nee_parked = tuningOr(c, "nee_parked", 1) != 0 ? 1u : 0u;
-	if (!c->q.nee_parked) { int rc = ensureNeeQueue(c); if (rc) return rc; }
-	c->q.miss_settled = cfg.miss_settled ? 1u : 0u;      // k_trace<closest> and k_shade agree on who settles a miss
+	{ int rc = beginQueues(c, cfg); if (rc) return rc; }
+	const Shader shade(c, s, cfg);
 	for (int b = 0; nQ > 0; ++b) {
 		if (cancel && *cancel)
 			return fail(c, MTSGPU_ECANCEL, "render cancelled");
 		// the counter set of this bounce; its last users (bounce b - 2) are done: the shading of bounce b - 1 waited for them
 		c->q.counters = counterSet(c, b); c->q.spill = c->spillClosest;
-		HIPCHK(c, hipMemsetAsync(c->q.counters, 0, setBytes, s));
+		HIPCHK(c, hipMemsetAsync(c->q.counters, 0, kCounterSetBytes, s));
 		c->q.next = nxt;
 		rayQueues(c, cur, nxt);
 		// closest hit + material sort
@@ -490,38 +511,17 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 		int rc = traceAndBin(c, cur, nQ, first, views); if (rc) return rc;
 		c->stats.rays_closest += nQ;
 		// shade, one launch per BSDF type
-		hipEvent_t *sev = c->timeKernels ? nextEventPair(c, c->shadeEvents, c->shadeEvUsed) : nullptr;
-		if (sev) HIPCHK(c, hipEventRecord(sev[0], s));
-		for (int bin = 0; bin < kNumBins; ++bin)
-			launch_shade(s, bin, c->dsc, c->paths, cfg, c->q, views[bin], nullptr, 0, nullptr, c->dcol, c->dtex, c->dtan);
-		if (sev) HIPCHK(c, hipEventRecord(sev[1], s));
-		HIPCHK(c, hipGetLastError());
+		rc = timedLaunch(c, s, kShading, [&] { shade.bins(views); }); if (rc) return rc;
 		rc = readCounters(c); if (rc) return rc;
 		const uint32_t nNext = c->hostCounters[kNextWord], nShadow = c->hostCounters[kShadowWord];
 		// shadow rays of this bounce (they cancel the parked direct-light terms of the occluded ones -- or, unparked, add the others' --
 		// before the next bounce reads the records); the shading above has completed
 		if (nShadow) {
-			DQueues q2 = c->q; q2.spill = c->spillShadow;
 			c->lastPass.shadowMax = std::max(c->lastPass.shadowMax, nShadow);
-			hipEvent_t *ev2 = c->timeKernels ? nextTraceEvents(c, 2) : nullptr;
-			if (ev2) HIPCHK(c, hipEventRecord(ev2[0], s));
-			launch_trace(s, 1, c->countTraversal, false, c->dsc, c->paths, q2, q2.shadow, nShadow, first);
-			if (ev2) HIPCHK(c, hipEventRecord(ev2[1], s));
-			HIPCHK(c, hipGetLastError());
-			c->stats.rays_shadow += nShadow; c->stats.trace_launches++;
+			rc = traceShadows(c, s, nShadow, first); if (rc) return rc;
+			c->stats.rays_shadow += nShadow;
 		}
-		if (getenv("MTSGPU_DEBUG")) {
-			HIPCHK(c, hipStreamSynchronize(s));
-			float a = 0, b2 = 0, c2 = 0;
-			if (c->timeKernels) {
-				const size_t ti = c->traceEvUsed - (nShadow ? 2 : 1);
-				(void) hipEventElapsedTime(&a, c->traceEvents[ti].first, c->traceEvents[ti].second);
-				(void) hipEventElapsedTime(&b2, c->shadeEvents[c->shadeEvUsed - 1].first, c->shadeEvents[c->shadeEvUsed - 1].second);
-				if (nShadow) (void) hipEventElapsedTime(&c2, c->traceEvents[ti + 1].first, c->traceEvents[ti + 1].second);
-			}
-			fprintf(stderr, "bounce: closest %u rays %.3f ms (%.2f Grays/s) | shade %.3f ms | shadow %u rays %.3f ms (%.2f Grays/s)\n",
-			        nQ, a, a > 0 ? nQ / a / 1e6 : 0.0, b2, nShadow, c2, c2 > 0 ? nShadow / c2 / 1e6 : 0.0);
-		}
+		if (c->debug) { rc = printBounce(c, nQ, nShadow); if (rc) return rc; }
 		std::swap(cur, nxt);
 		nQ = nNext;
 		first = false;
@@ -564,10 +564,10 @@ int fetchTraceCounts(mtsgpu_ctx *c) {
 	c->stats.req_pair_global = h[kCntPairGlobal]; c->stats.req_pair_lds = h[kCntPairLds];
 	c->stats.req_node_global = h[kCntNodeGlobal]; c->stats.req_node_lds = h[kCntNodeLds];
 	c->stats.req_tail = h[kCntTail]; c->stats.req_spill = h[kCntSpill]; c->stats.req_head = h[kCntHead];
-	if (getenv("MTSGPU_DEBUG"))     // candidates whose tail was fetched with a plane distance outside the visited leaf's own interval
+	if (c->debug)     // candidates whose tail was fetched with a plane distance outside the visited leaf's own interval
 		fprintf(stderr, "[mtsgpu] record tails: %llu requests, %llu candidates of which %llu (%.3f) lie outside the leaf's interval\n",
 		        h[kCntTail], h[kCntTail] / 2, h[15], h[kCntTail] ? 2.0 * h[15] / h[kCntTail] : 0.0);
-	if (getenv("MTSGPU_DEBUG"))     // SIMD utilisation of the traversal loops: lane steps / lane slots issued
+	if (c->debug)     // SIMD utilisation of the traversal loops: lane steps / lane slots issued
 		fprintf(stderr, "[mtsgpu] lanes: inner %llu/%llu (%.3f)  leaf-prims %llu/%llu (%.3f)  outer %llu/%llu (%.3f)  batch slots %llu\n",
 		        h[0], h[4], h[4] ? (double) h[0] / h[4] : 0.0, h[2], h[5], h[5] ? (double) h[2] / h[5] : 0.0,
 		        h[1], h[6], h[6] ? (double) h[1] / h[6] : 0.0, h[7]);
@@ -626,97 +626,131 @@ int readCameraRows(mtsgpu_ctx *c, size_t first, uint32_t n, float *out) {
 	return 0;
 }
 
-} // namespace
+// A frame begins: statistics (bins: those of mtsgpu_bin_entries too), the timing events in use and the debug switch (read
+// here, not per bounce)
+void beginFrame(mtsgpu_ctx *c, bool bins = true) {
+	std::memset(&c->stats, 0, sizeof(c->stats));
+	if (bins) std::memset(c->binEntries, 0, sizeof(c->binEntries));
+	c->traceEvUsed = c->shadeEvUsed = 0;
+	c->debug = getenv("MTSGPU_DEBUG") != nullptr;
+}
 
-extern "C" {
-
-int mtsgpu_render(mtsgpu_ctx *c, volatile const int *cancel) {
-	int rc = checkReady(c); if (rc) return rc;
-	// refused before anything is touched: the context stays as it was
-	if (c->filmStats && c->filtBorder > 0)
-		return fail(c, MTSGPU_EINVAL, "film statistics need the box filter: the reference collects them only with a reconstruction "
-		            "filter no wider than a pixel (renderjob.cpp:96-99, mfilm.cpp:145); this filter has a border of %d", c->filtBorder);
-	rc = ensureFilm(c); if (rc) return rc;
-	c->statsForm = -1;
-	if (c->filmStats) { rc = ensureFilmStats(c); if (rc) return rc; }      // before defaultMaxPaths() asks for the free memory
-	const int W = c->cam.width, H = c->cam.height, bs = c->blockSize;
-	const uint32_t spp = effectiveSpp(c);
-	// ImageBlock work units (imageproc.cpp:43-78) owned by this context: tile (tx, ty) -> part morton(tx, ty) % n_parts
-	// Film::hasHighQualityEdges: the rendered rectangle grows by the filter border (renderproc.cpp:146-153)
-	const int off = c->hqEdges ? -c->filtBorder : 0;
+// The work units of a frame: ImageBlock tiles (imageproc.cpp:43-78) owned by this context, tile (tx, ty) -> part
+// morton(tx, ty) % n_parts, as pixel keys in tile order (renderPixels, and pixelList on the device) and tile rectangles
+// (renderTiles).  They depend on the film geometry and the tile sharding only (renderKey) and are kept from frame to frame;
+// the cached list holds while renderListValid (the hooks that borrow pixelList clear it) and pixelList still has its size.
+// *offOut, *keyWOut: the grid the keys index -- the full film (the crop window only moves the rendered rectangle in it),
+// grown by the filter border with Film::hasHighQualityEdges (renderproc.cpp:146-153)
+int ensureWorkUnits(mtsgpu_ctx *c, int *offOut, int *keyWOut) {
+	const int W = c->cam.width, H = c->cam.height, bs = c->blockSize, off = c->hqEdges ? -c->filtBorder : 0;
 	const int RW = W - 2 * off, RH = H - 2 * off;
 	const int tx = (RW + bs - 1) / bs, ty = (RH + bs - 1) / bs;
-	// keys: index of the raster pixel in the (full film + border) grid; the crop window only moves the rectangle
 	const int cx = c->cam.crop_offset_x, cy = c->cam.crop_offset_y;
 	const int keyW = filmWidth(c) - 2 * off;
 	if ((uint64_t) keyW * (uint64_t) (filmHeight(c) - 2 * off) > 0xFFFFFFFFull) return fail(c, MTSGPU_EINVAL, "film too large");
+	*offOut = off; *keyWOut = keyW;
 	std::vector<uint32_t> &pixels = c->renderPixels;
 	std::vector<TileMeta> &tiles = c->renderTiles;
 	const std::vector<long long> key = { W, H, bs, off, cx, cy, keyW, c->nParts, c->part };
-	const bool reuse = c->renderListValid && key == c->renderKey && c->pixelList && c->pixelListCap >= pixels.size();
-	if (!reuse) {
-		pixels.clear(); tiles.clear();
-		for (int t = 0; t < tx * ty; ++t) {
-			if (tileMorton((uint32_t) (t % tx), (uint32_t) (t / tx)) % (uint32_t) c->nParts != (uint32_t) c->part) continue;
-			const int x0 = off + (t % tx) * bs, y0 = off + (t / tx) * bs;            // inside the crop window
-			TileMeta tm{};
-			tm.x0 = x0 + cx; tm.y0 = y0 + cy; tm.w = std::min(bs, off + RW - x0); tm.h = std::min(bs, off + RH - y0);
-			tm.slot_base = (uint32_t) pixels.size(); tm.block_index = (uint32_t) tiles.size();
-			tm.colour = (uint32_t) (((t % tx) & 1) + 2 * ((t / tx) & 1));
-			tiles.push_back(tm);
-			for (int y = tm.y0; y < tm.y0 + tm.h; ++y)
-				for (int x = tm.x0; x < tm.x0 + tm.w; ++x)
-					pixels.push_back((uint32_t) (y - off) * (uint32_t) keyW + (uint32_t) (x - off));
-		}
-		c->renderKey = key; c->renderListValid = false;
+	if (c->renderListValid && key == c->renderKey && c->pixelList && c->pixelList.cap >= pixels.size()) return 0;
+	pixels.clear(); tiles.clear();
+	for (int t = 0; t < tx * ty; ++t) {
+		if (tileMorton((uint32_t) (t % tx), (uint32_t) (t / tx)) % (uint32_t) c->nParts != (uint32_t) c->part) continue;
+		const int x0 = off + (t % tx) * bs, y0 = off + (t / tx) * bs;            // inside the crop window
+		TileMeta tm{};
+		tm.x0 = x0 + cx; tm.y0 = y0 + cy; tm.w = std::min(bs, off + RW - x0); tm.h = std::min(bs, off + RH - y0);
+		tm.slot_base = (uint32_t) pixels.size(); tm.block_index = (uint32_t) tiles.size();
+		tm.colour = (uint32_t) (((t % tx) & 1) + 2 * ((t / tx) & 1));
+		tiles.push_back(tm);
+		for (int y = tm.y0; y < tm.y0 + tm.h; ++y)
+			for (int x = tm.x0; x < tm.x0 + tm.w; ++x)
+				pixels.push_back((uint32_t) (y - off) * (uint32_t) keyW + (uint32_t) (x - off));
 	}
-	std::memset(&c->stats, 0, sizeof(c->stats));
-	std::memset(c->binEntries, 0, sizeof(c->binEntries));
-	c->traceEvUsed = c->shadeEvUsed = 0;
+	c->renderKey = key; c->renderListValid = false;
 	if (pixels.empty()) return 0;
-	if (!reuse) {
-		rc = ensureBuf(c, &c->pixelList, &c->pixelListCap, pixels.size()); if (rc) return rc;
-		HIPCHK(c, hipMemcpyAsync(c->pixelList, pixels.data(), pixels.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-		// valid only once the copy has landed: a frame that leaves early (cancel, an error) and a caller that then switches
-		// streams (mtsgpu_set_stream) must not find a list that is marked valid but not ordered before its next use
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		c->renderListValid = true;
-	}
+	int rc = c->pixelList.ensure(c, pixels.size()); if (rc) return rc;
+	HIPCHK(c, hipMemcpyAsync(c->pixelList, pixels.data(), pixels.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	// valid only once the copy has landed: a frame that leaves early (cancel, an error) and a caller that then switches
+	// streams (mtsgpu_set_stream) must not find a list that is marked valid but not ordered before its next use
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	c->renderListValid = true;
+	return 0;
+}
 
+// the sampler tables and sample arrays of nSlots sampler slots carrying nPaths paths (a pass, or the explicit samples of a hook)
+int ensureSamplerBuffers(mtsgpu_ctx *c, size_t nSlots, size_t nPaths) {
+	if (samplerHasTables(c)) {
+		const uint32_t spp = effectiveSpp(c);
+		int rc = c->ldScr.ensure(c, nSlots * 3 * c->ldDepth); if (rc) return rc;
+		rc = c->ldPerm.ensure(c, nSlots * 2 * c->ldDepth * spp); if (rc) return rc;
+		rc = ensureTableWork(c, nSlots, spp); if (rc) return rc;
+	}
+	return ensureSampleArrays(c, nSlots, nPaths);
+}
+
+// The buffers of a pass, and in *slotsPerPass how many sampler slots (pixels) one takes: the path records and queues, the
+// sampler's tables and, with a filter wider than a pixel, the tile records and blocks of the whole frame
+int ensurePassBuffers(mtsgpu_ctx *c, size_t *slotsPerPass) {
+	const int bs = c->blockSize;
+	const uint32_t spp = effectiveSpp(c);
 	const bool wideFilter = c->filtBorder > 0;
 	if (wideFilter && 2 * c->filtBorder > bs) return fail(c, MTSGPU_EINVAL, "filter border %d too wide for block size %d", c->filtBorder, bs);
 	const uint64_t maxPaths = c->maxPaths ? c->maxPaths : defaultMaxPaths(c);
-	size_t slotsPerPass = (size_t) std::max<uint64_t>(1, std::min<uint64_t>(pixels.size(), maxPaths / spp));
-	if (wideFilter) slotsPerPass = std::max<size_t>(slotsPerPass, (size_t) bs * bs);     // passes hold whole tiles
-	if ((uint64_t) slotsPerPass * spp > 0x7FFFFFFFull) return fail(c, MTSGPU_EINVAL, "pass too large");
-	rc = ensurePaths(c, slotsPerPass * spp); if (rc) return rc;
-	if (samplerHasTables(c)) {
-		rc = ensureBuf(c, &c->ldScr, &c->ldScrCap, slotsPerPass * 3 * c->ldDepth); if (rc) return rc;
-		rc = ensureBuf(c, &c->ldPerm, &c->ldPermCap, slotsPerPass * 2 * c->ldDepth * spp); if (rc) return rc;
-		rc = ensureTableWork(c, slotsPerPass, spp); if (rc) return rc;
-	}
-	rc = ensureSampleArrays(c, slotsPerPass, slotsPerPass * spp); if (rc) return rc;
-	if (c->countTraversal) HIPCHK(c, hipMemsetAsync(c->q.trace_counts, 0, kNumTraceCounts * sizeof(unsigned long long), c->stream));
-	DConfig cfg = makeConfig(c, false);
-	cfg.pix_w = keyW; cfg.pix_off = off;
-	HIPCHK(c, hipMemsetAsync(c->pathLen, 0, sizeof(unsigned long long), c->stream));
-	HIPCHK(c, hipMemsetAsync(c->devStats, 0, kNumDevStats * sizeof(unsigned long long), c->stream));
-	c->devStatsUsed = false;
-	const size_t fullBlock = (size_t) (bs + 2 * c->filtBorder) * (bs + 2 * c->filtBorder) * 5;
+	size_t slots = (size_t) std::max<uint64_t>(1, std::min<uint64_t>(c->renderPixels.size(), maxPaths / spp));
+	if (wideFilter) slots = std::max<size_t>(slots, (size_t) bs * bs);     // passes hold whole tiles
+	if ((uint64_t) slots * spp > 0x7FFFFFFFull) return fail(c, MTSGPU_EINVAL, "pass too large");
+	int rc = ensurePaths(c, slots * spp); if (rc) return rc;
+	rc = ensureSamplerBuffers(c, slots, slots * spp); if (rc) return rc;
 	if (wideFilter) {
-		rc = ensureBuf(c, &c->tileMeta, &c->tileMetaCap, tiles.size()); if (rc) return rc;
-		rc = ensureBuf(c, &c->blocks, &c->blocksCap, tiles.size() * fullBlock); if (rc) return rc;
+		const size_t fullBlock = (size_t) (bs + 2 * c->filtBorder) * (bs + 2 * c->filtBorder) * 5;
+		rc = c->tileMeta.ensure(c, c->renderTiles.size()); if (rc) return rc;
+		rc = c->blocks.ensure(c, c->renderTiles.size() * fullBlock); if (rc) return rc;
 	}
+	*slotsPerPass = slots;
+	return 0;
+}
 
+// The explicit samples of a hook on the device, one path each: n (x, y, sample index) triples and their pixel keys, which take
+// the place of the frame's work units (the cached list and the last pass are gone), and the buffers their paths need
+int putExplicitSamples(mtsgpu_ctx *c, const uint32_t *samples, const uint32_t *keys, uint32_t n) {
+	int rc = ensurePaths(c, n); if (rc) return rc;
+	rc = c->explicitSamples.ensure(c, 3 * (size_t) n); if (rc) return rc;
+	c->renderListValid = false; c->lastPass.valid = false;
+	rc = c->pixelList.ensure(c, n); if (rc) return rc;
+	HIPCHK(c, hipMemcpyAsync(c->explicitSamples, samples, 3 * (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	HIPCHK(c, hipMemcpyAsync(c->pixelList, keys, (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	return ensureSamplerBuffers(c, n, n);
+}
+
+// sampler state and camera rays of nSlots slots from pixelList + base on, into queueA
+int generatePaths(mtsgpu_ctx *c, const DConfig &cfg, size_t base, uint32_t nSlots, const uint32_t *explicitSamples, uint32_t nPaths) {
+	if (samplerHasTables(c)) {
+		launch_ld_tables(c->stream, cfg, c->pixelList + base, nSlots, c->ldScr, c->ldPerm, c->ldState, c->ldScratch);
+		launch_sample_arrays(c->stream, cfg, nSlots, c->ldState);
+	}
+	rayQueues(c, nullptr, c->queueA);
+	launch_generate(c->stream, c->dsc, c->paths, cfg, c->pixelList + base, nSlots, explicitSamples, nPaths, c->queueA);
+	rayQueues(c, nullptr, nullptr);
+	HIPCHK(c, hipGetLastError());
+	return 0;
+}
+
+// The passes of a frame over the work units: generate, bounce, add to the film (or, with a filter wider than a pixel, to the
+// tiles' blocks, which join the film when all passes are done).  Leaves total_ms and path_length_sum in the statistics.
+int renderPasses(mtsgpu_ctx *c, const DConfig &cfg, size_t slotsPerPass, volatile const int *cancel) {
+	const std::vector<uint32_t> &pixels = c->renderPixels;
+	std::vector<TileMeta> &tiles = c->renderTiles;
+	const int bs = c->blockSize;
+	const uint32_t spp = cfg.spp;
+	const bool wideFilter = c->filtBorder > 0;
 	// frame timing events, released on every way out of this function
 	EventPair frameEv;
 	HIPCHK(c, hipEventCreate(&frameEv.a)); HIPCHK(c, hipEventCreate(&frameEv.b));
-	const hipEvent_t t0 = frameEv.a, t1 = frameEv.b;
-	HIPCHK(c, hipEventRecord(t0, c->stream));
+	HIPCHK(c, hipEventRecord(frameEv.a, c->stream));
 	size_t tileCursor = 0;
 	for (size_t base = 0; base < pixels.size();) {
 		uint32_t nSlots;
-		size_t tileFirst = tileCursor;
+		const size_t tileFirst = tileCursor;
 		if (wideFilter) {
 			// whole tiles only: a block gathers from all samples of its tile
 			size_t acc = 0;
@@ -732,18 +766,10 @@ int mtsgpu_render(mtsgpu_ctx *c, volatile const int *cancel) {
 			nSlots = (uint32_t) std::min(slotsPerPass, pixels.size() - base);
 		}
 		const uint32_t nPaths = nSlots * spp;
-		if (samplerHasTables(c)) {
-			launch_ld_tables(c->stream, cfg, c->pixelList + base, nSlots, c->ldScr, c->ldPerm, c->ldState, c->ldScratch);
-			launch_sample_arrays(c->stream, cfg, nSlots, c->ldState);
-		}
-		rayQueues(c, nullptr, c->queueA);
-		launch_generate(c->stream, c->dsc, c->paths, cfg, c->pixelList + base, nSlots, nullptr, nPaths, c->queueA);
-		rayQueues(c, nullptr, nullptr);
-		HIPCHK(c, hipGetLastError());
+		int rc = generatePaths(c, cfg, base, nSlots, nullptr, nPaths); if (rc) return rc;
 		c->lastPass.valid = true; c->lastPass.cfg = cfg; c->lastPass.base = base;
 		c->lastPass.nSlots = nSlots; c->lastPass.nPaths = nPaths; c->lastPass.shadowMax = 0;
-		rc = runBounces(c, cfg, nPaths, cancel);
-		if (rc) return rc;
+		rc = runBounces(c, cfg, nPaths, cancel); if (rc) return rc;
 		if (wideFilter) {
 			const uint32_t nT = (uint32_t) (tileCursor - tileFirst);
 			HIPCHK(c, hipMemcpyAsync(c->tileMeta + tileFirst, tiles.data() + tileFirst, nT * sizeof(TileMeta), hipMemcpyHostToDevice, c->stream));
@@ -766,13 +792,42 @@ int mtsgpu_render(mtsgpu_ctx *c, volatile const int *cancel) {
 		for (uint32_t colour = 0; colour < 4; ++colour)
 			launch_add_blocks(c->stream, cfg, c->tileMeta, (uint32_t) tiles.size(), colour, bs, c->blocks, c->film);
 	HIPCHK(c, hipGetLastError());
-	HIPCHK(c, hipEventRecord(t1, c->stream));
-	HIPCHK(c, hipMemcpyAsync(&c->hostCounters[kNumCounters * kCounterStride], c->pathLen, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipEventRecord(frameEv.b, c->stream));
+	HIPCHK(c, hipMemcpyAsync(&c->hostCounters[kHostPathLenWord], c->pathLen, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	std::memcpy(&c->stats.path_length_sum, &c->hostCounters[kNumCounters * kCounterStride], sizeof(uint64_t));
+	std::memcpy(&c->stats.path_length_sum, &c->hostCounters[kHostPathLenWord], sizeof(uint64_t));
 	float ms = 0;
-	HIPCHK(c, hipEventElapsedTime(&ms, t0, t1));
+	HIPCHK(c, hipEventElapsedTime(&ms, frameEv.a, frameEv.b));
 	c->stats.total_ms = ms;
+	return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int mtsgpu_render(mtsgpu_ctx *c, volatile const int *cancel) {
+	int rc = checkReady(c); if (rc) return rc;
+	// refused before anything is touched: the context stays as it was
+	if (c->filmStats && c->filtBorder > 0)
+		return fail(c, MTSGPU_EINVAL, "film statistics need the box filter: the reference collects them only with a reconstruction "
+		            "filter no wider than a pixel (renderjob.cpp:96-99, mfilm.cpp:145); this filter has a border of %d", c->filtBorder);
+	rc = ensureFilm(c); if (rc) return rc;
+	c->statsForm = -1;
+	if (c->filmStats) { rc = ensureFilmStats(c); if (rc) return rc; }      // before defaultMaxPaths() asks for the free memory
+	int off = 0, keyW = 0;
+	rc = ensureWorkUnits(c, &off, &keyW); if (rc) return rc;
+	beginFrame(c);
+	if (c->renderPixels.empty()) return 0;
+	size_t slotsPerPass = 0;
+	rc = ensurePassBuffers(c, &slotsPerPass); if (rc) return rc;
+	if (c->countTraversal) HIPCHK(c, hipMemsetAsync(c->q.trace_counts, 0, kNumTraceCounts * sizeof(unsigned long long), c->stream));
+	DConfig cfg = makeConfig(c, false);
+	cfg.pix_w = keyW; cfg.pix_off = off;
+	HIPCHK(c, hipMemsetAsync(c->pathLen, 0, sizeof(unsigned long long), c->stream));
+	HIPCHK(c, hipMemsetAsync(c->devStats, 0, kNumDevStats * sizeof(unsigned long long), c->stream));
+	c->devStatsUsed = false;
+	rc = renderPasses(c, cfg, slotsPerPass, cancel); if (rc) return rc;
 	collectTimings(c);
 	rc = collectDeviceStats(c); if (rc) return rc;
 	if (c->countTraversal) { rc = fetchTraceCounts(c); if (rc) return rc; }
@@ -784,8 +839,7 @@ int mtsgpu_trace_rays(mtsgpu_ctx *c, const float *rays, uint32_t n, int shadow, 
 	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "no scene uploaded");
 	if (!rays || !hits) return fail(c, MTSGPU_EINVAL, "null argument");
 	HIPCHK(c, hipSetDevice(c->device));
-	std::memset(&c->stats, 0, sizeof(c->stats));
-	c->traceEvUsed = c->shadeEvUsed = 0;
+	beginFrame(c, false);
 	if (n == 0) return 0;
 	c->lastPass.valid = false;
 	int rc = ensurePaths(c, n); if (rc) return rc;
@@ -798,15 +852,12 @@ int mtsgpu_trace_rays(mtsgpu_ctx *c, const float *rays, uint32_t n, int shadow, 
 	}
 	launch_iota(c->stream, c->queueA, n);
 	if (c->countTraversal) HIPCHK(c, hipMemsetAsync(c->q.trace_counts, 0, kNumTraceCounts * sizeof(unsigned long long), c->stream));
-	hipEvent_t *ev = c->timeKernels ? nextTraceEvents(c, shadow ? 2 : 0) : nullptr;
-	if (ev) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-	HIPCHK(c, hipMemsetAsync(c->q.counters, 0, kNumCounters * kCounterStride * sizeof(uint32_t), c->stream));     // dynamic batch head
-	launch_trace(c->stream, shadow ? 2 : 0, c->countTraversal, false, c->dsc, c->paths, c->q, c->queueA, n, false);
-	if (ev) HIPCHK(c, hipEventRecord(ev[1], c->stream));
-	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipMemsetAsync(c->q.counters, 0, kCounterSetBytes, c->stream));     // dynamic batch head
+	rc = timedLaunch(c, c->stream, shadow ? kAnyHit : kClosest, [&] {
+		launch_trace(c->stream, shadow ? 2 : 0, c->countTraversal, false, c->dsc, c->paths, c->q, c->queueA, n, false); });
+	if (rc) return rc;
 	HIPCHK(c, hipMemcpy2DAsync(hits, 16, c->paths.base + 2, kPathSlots * sizeof(float4), 16, n, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	c->stats.trace_launches = 1;
 	if (shadow) c->stats.rays_shadow = n; else c->stats.rays_closest = n;
 	collectTimings(c);
 	if (c->countTraversal) { rc = fetchTraceCounts(c); if (rc) return rc; }
@@ -816,9 +867,7 @@ int mtsgpu_trace_rays(mtsgpu_ctx *c, const float *rays, uint32_t n, int shadow, 
 int mtsgpu_li_samples(mtsgpu_ctx *c, const uint32_t *pix_samples, uint32_t n, float *out) {
 	int rc = checkReady(c); if (rc) return rc;
 	if (!pix_samples || !out) return fail(c, MTSGPU_EINVAL, "null argument");
-	std::memset(&c->stats, 0, sizeof(c->stats));
-	std::memset(c->binEntries, 0, sizeof(c->binEntries));
-	c->traceEvUsed = c->shadeEvUsed = 0;
+	beginFrame(c);
 	if (n == 0) return 0;
 	const uint32_t spp = effectiveSpp(c);
 	std::vector<uint32_t> keys(n);
@@ -828,27 +877,9 @@ int mtsgpu_li_samples(mtsgpu_ctx *c, const uint32_t *pix_samples, uint32_t n, fl
 			return fail(c, MTSGPU_EINVAL, "sample %u: pixel or sample index out of range", i);
 		keys[i] = (y + (uint32_t) c->cam.crop_offset_y) * (uint32_t) filmWidth(c) + x + (uint32_t) c->cam.crop_offset_x;
 	}
-	rc = ensurePaths(c, n); if (rc) return rc;
-	rc = ensureBuf(c, &c->explicitSamples, &c->explicitCap, 3 * (size_t) n); if (rc) return rc;
-	c->renderListValid = false; c->lastPass.valid = false;
-	rc = ensureBuf(c, &c->pixelList, &c->pixelListCap, n); if (rc) return rc;
-	HIPCHK(c, hipMemcpyAsync(c->explicitSamples, pix_samples, 3 * (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-	HIPCHK(c, hipMemcpyAsync(c->pixelList, keys.data(), (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-	if (samplerHasTables(c)) {
-		rc = ensureBuf(c, &c->ldScr, &c->ldScrCap, (size_t) n * 3 * c->ldDepth); if (rc) return rc;
-		rc = ensureBuf(c, &c->ldPerm, &c->ldPermCap, (size_t) n * 2 * c->ldDepth * spp); if (rc) return rc;
-		rc = ensureTableWork(c, n, spp); if (rc) return rc;
-	}
-	rc = ensureSampleArrays(c, n, n); if (rc) return rc;
+	rc = putExplicitSamples(c, pix_samples, keys.data(), n); if (rc) return rc;
 	const DConfig cfg = makeConfig(c, true);
-	if (samplerHasTables(c)) {
-		launch_ld_tables(c->stream, cfg, c->pixelList, n, c->ldScr, c->ldPerm, c->ldState, c->ldScratch);
-		launch_sample_arrays(c->stream, cfg, n, c->ldState);
-	}
-	rayQueues(c, nullptr, c->queueA);
-	launch_generate(c->stream, c->dsc, c->paths, cfg, c->pixelList, n, c->explicitSamples, n, c->queueA);
-	rayQueues(c, nullptr, nullptr);
-	HIPCHK(c, hipGetLastError());
+	rc = generatePaths(c, cfg, 0, n, c->explicitSamples, n); if (rc) return rc;
 	HIPCHK(c, hipMemsetAsync(c->devStats, 0, kNumDevStats * sizeof(unsigned long long), c->stream));
 	c->devStatsUsed = false;
 	rc = runBounces(c, cfg, n, nullptr); if (rc) return rc;
@@ -907,28 +938,10 @@ int mtsgpu_camera_rays(mtsgpu_ctx *c, const int32_t *pix_samples, uint32_t first
 		samples[3 * (size_t) i] = (uint32_t) (x + border); samples[3 * (size_t) i + 1] = (uint32_t) (y + border); samples[3 * (size_t) i + 2] = (uint32_t) j;
 		keys[i] = ((uint32_t) (y + border) + (uint32_t) c->cam.crop_offset_y) * keyW + (uint32_t) (x + border) + (uint32_t) c->cam.crop_offset_x;
 	}
-	rc = ensurePaths(c, n); if (rc) return rc;
-	rc = ensureBuf(c, &c->explicitSamples, &c->explicitCap, 3 * (size_t) n); if (rc) return rc;
-	c->renderListValid = false; c->lastPass.valid = false;
-	rc = ensureBuf(c, &c->pixelList, &c->pixelListCap, n); if (rc) return rc;
-	HIPCHK(c, hipMemcpyAsync(c->explicitSamples, samples.data(), 3 * (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-	HIPCHK(c, hipMemcpyAsync(c->pixelList, keys.data(), (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-	if (samplerHasTables(c)) {
-		rc = ensureBuf(c, &c->ldScr, &c->ldScrCap, (size_t) n * 3 * c->ldDepth); if (rc) return rc;
-		rc = ensureBuf(c, &c->ldPerm, &c->ldPermCap, (size_t) n * 2 * c->ldDepth * spp); if (rc) return rc;
-		rc = ensureTableWork(c, n, spp); if (rc) return rc;
-	}
-	rc = ensureSampleArrays(c, n, n); if (rc) return rc;
+	rc = putExplicitSamples(c, samples.data(), keys.data(), n); if (rc) return rc;
 	DConfig cfg = makeConfig(c, true);
 	cfg.pix_w = (int) keyW; cfg.pix_off = -border;
-	if (samplerHasTables(c)) {
-		launch_ld_tables(c->stream, cfg, c->pixelList, n, c->ldScr, c->ldPerm, c->ldState, c->ldScratch);
-		launch_sample_arrays(c->stream, cfg, n, c->ldState);
-	}
-	rayQueues(c, nullptr, c->queueA);
-	launch_generate(c->stream, c->dsc, c->paths, cfg, c->pixelList, n, c->explicitSamples, n, c->queueA);
-	rayQueues(c, nullptr, nullptr);
-	HIPCHK(c, hipGetLastError());
+	rc = generatePaths(c, cfg, 0, n, c->explicitSamples, n); if (rc) return rc;
 	// `samples` and `keys` live on this stack; the read-back below waits for the stream
 	return readCameraRows(c, 0, n, out);
 }

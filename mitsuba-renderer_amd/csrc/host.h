@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/mtsgpu.h"
 #include "devmath.h"
+#include "kdtree.h"
 #include <cmath>
 #include <memory>
 #include <stdexcept>
@@ -9,18 +10,6 @@
 #include <vector>
 
 namespace mg {
-
-struct KdTree {
-	std::vector<uint32_t> nodes;      // 2 dwords per node
-	std::vector<uint32_t> indices;
-	float aabbMin[3] = { 0, 0, 0 }, aabbMax[3] = { 0, 0, 0 };
-	double stats[6] = { 0, 0, 0, 0, 0, 0 };
-};
-
-// genBox: [nTris][6] boxes, read for the primitives whose tri row is {MTSGPU_KNOTRIANGLE x 3}; may be NULL without such
-void buildKdTree(const float *vtx, const uint32_t *tri, uint32_t nTris, const float *genBox, const mtsgpu_kd_params *kp, KdTree &out);
-bool clippedTriangleBox(const float *p0, const float *p1, const float *p2, const float *bmin, const float *bmax,
-                        float *omin, float *omax);
 
 // Owns every array a mtsgpu_scene points to
 struct FlatScene {

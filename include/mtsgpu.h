@@ -317,7 +317,11 @@ int  mtsgpu_set_options(mtsgpu_ctx *ctx, uint64_t max_paths, int count_traversal
  *   test_retry (0/1)                          treat every first closest-hit launch as overflowed (exercises the retry)
  *   stats_wave (-1 rule, 0 lane, 1 wave)      form of the variance kernel of the test-case mode (below)
  *   miss_shaded (0/1, default 0)              1: a ray that leaves a scene without a background luminaire goes through the
- *                                             terminal queue and the shading kernel; 0: its path ends in the traversal kernel */
+ *                                             terminal queue and the shading kernel; 0: its path ends in the traversal kernel
+ *   lean_closest (0..7, default 3)            which closest-hit launches of host-driven frames run the kernel without the mailbox
+ *                                             (8 waves per SIMD; rays on which two primitives tie in t are traced again with the
+ *                                             mailbox): 1 the incoherent launches of at least plain_below rays, 2 the coherent
+ *                                             first launch, 4 the launches below plain_below */
 int  mtsgpu_set_tuning(mtsgpu_ctx *ctx, const char *key, long value);
 
 /* --- per-vertex colours and the `vertexcolors` texture (src/textures/vertexcolors.cpp: getValue(its) = its.color) -----

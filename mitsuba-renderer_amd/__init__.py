@@ -175,6 +175,7 @@ def lib():
     L.mtsgpu_pass_samples.argtypes = [vp, C.c_uint32, C.c_uint32, f32p]
     L.mtsgpu_camera_rays.argtypes = [vp, abi.i32p, C.c_uint32, C.c_uint32, f32p]
     L.mtsgpu_bin_entries.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.mtsgpu_hook_rays_redone.argtypes = [vp, C.POINTER(C.c_uint64)]      # a hook outside the ABI (csrc/ctx.h), not in EXPORTS
     L.mtsgpu_flatten.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.KdParams), C.POINTER(vp)]
     L.mtsgpu_flat_scene_get.argtypes = [vp]; L.mtsgpu_flat_scene_get.restype = C.POINTER(abi.Scene)
     L.mtsgpu_flat_scene_free.argtypes = [vp]; L.mtsgpu_flat_scene_free.restype = None
@@ -598,7 +599,11 @@ class MIPathTracer:
     def stats(self):
         st = abi.Stats()
         self._chk(lib().mtsgpu_get_stats(self._ctx, C.byref(st)), "get_stats")
-        return st.as_dict()
+        d = st.as_dict()
+        redone = C.c_uint64(0)      # not a field of mtsgpu_stats, whose layout is part of ABI version 8
+        self._chk(lib().mtsgpu_hook_rays_redone(self._ctx, C.byref(redone)), "rays_redone")
+        d["rays_redone"] = int(redone.value)
+        return d
 
     def bin_entries(self):
         """entries the closest-hit launches of the last frame appended to every material queue (mtsgpu_bin_entries): one count per

@@ -163,6 +163,8 @@ struct mtsgpu_ctx {
 	// entries the closest-hit launches of the last frame appended to every material queue (mtsgpu_bin_entries): counted by the
 	// host where it reads the shard counters back, by k_prep otherwise
 	uint64_t binEntries[mg::kNumBins] = {};
+	// closest-hit rays of the last frame that the lean kernel handed to the kernel with the mailbox (mtsgpu_hook_rays_redone)
+	uint64_t raysRedone = 0;
 	mg::EventPool traceEvents, shadeEvents; // the timing events of a frame with time_kernels on, kept from frame to frame
 	size_t traceEvUsed = 0, shadeEvUsed = 0;
 	std::vector<unsigned char> traceEvClass;      // per traversal launch: 0 closest-hit, 1 closest-hit of a pass's first bounce, 2 any-hit
@@ -224,3 +226,9 @@ struct RayQueuesOff { mtsgpu_ctx *c; ~RayQueuesOff() { rayQueues(c, nullptr, nul
 
 } // namespace mg
 #pragma GCC visibility pop
+
+// A measurement hook outside the C ABI of include/mtsgpu.h (ABI version 8 fixes mtsgpu_stats and the list of entry points): the
+// closest-hit rays of the last frame, or mtsgpu_trace_rays call, that were traced a second time, with the mailbox, because two
+// primitives tied in t on them (tuning key "lean_closest"; render.cpp: traceAndBin).  A redone ray counts once in rays_closest
+// and once in mtsgpu_bin_entries.
+extern "C" int mtsgpu_hook_rays_redone(mtsgpu_ctx *ctx, uint64_t *out);

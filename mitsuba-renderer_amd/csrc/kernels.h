@@ -20,11 +20,13 @@ constexpr int kNumBins = kNumBsdfTypes + 1;   // + "terminal" (miss / no BSDF)
 constexpr int kTraceBlock = MG_TRACE_BLOCK;
 static_assert(kTraceBlock % 256 == 0 && kTraceBlock <= 1024, "whole multiples of four waves");
 #ifdef MG_TRACE_WGS
-constexpr unsigned trace_blocks_per_cu(int) { return MG_TRACE_WGS; }
+constexpr unsigned trace_blocks_per_cu(int, bool = false) { return MG_TRACE_WGS; }
 #else
-constexpr unsigned trace_blocks_per_cu(int mode) { return (mode == 0 ? 24u : 32u) / (kTraceBlock / 64); }
+// lean: the closest-hit kernel without the mailbox and with one register of hit state (trace.hip: LEAN), which has the any-hit
+// kernel's footprint (64 VGPRs, 36 KB of LDS) and so its 4 workgroups per CU
+constexpr unsigned trace_blocks_per_cu(int mode, bool lean = false) { return (mode == 0 && !lean ? 24u : 32u) / (kTraceBlock / 64); }
 #endif
-constexpr unsigned trace_waves_per_simd(int mode) { return trace_blocks_per_cu(mode) * (kTraceBlock / 64) / 4; }
+constexpr unsigned trace_waves_per_simd(int mode, bool lean = false) { return trace_blocks_per_cu(mode, lean) * (kTraceBlock / 64) / 4; }
 constexpr unsigned kTraceBlocksPerCuMax = 2048 / kTraceBlock;      // largest persistent traversal grid: 32 waves per CU
 // LDS layout of the traversal kernels (trace.hip; k_replay of measure.hip keeps the same footprint)
 #ifndef MG_STACK_LDS
@@ -60,13 +62,13 @@ constexpr int kBinShards = 16;        // the closest-hit kernel appends to bins[
 // The bins k_shade_all shades.  The composite (bin 9) loops over its children and switches on their type: inside the fused
 // kernel that loop would raise the registers of every bin, so device-driven frames launch k_shade<9> next to it.
 constexpr uint32_t kShadeAllBins = ((1u << kNumBins) - 1u) & ~(1u << 9);
-constexpr int kNumCounters = kNumBins * kBinShards + 4;   // bins x shards, next, shadow, dynamic heads of the two traversal launches
+constexpr int kNumCounters = kNumBins * kBinShards + 5;   // bins x shards, next, shadow, dynamic heads of the two traversal launches, redo list
 // Two sets of counters, used by alternate bounces: the shadow rays of bounce b are traced (second stream) while the
 // closest-hit launch of bounce b + 1 already fills the next set
 constexpr int kCounterSets = 2;
-constexpr int kCntNext = kNumBins * kBinShards, kCntShadow = kCntNext + 1, kCntDynClosest = kCntNext + 2, kCntDynShadow = kCntNext + 3;
+constexpr int kCntNext = kNumBins * kBinShards, kCntShadow = kCntNext + 1, kCntDynClosest = kCntNext + 2, kCntDynShadow = kCntNext + 3, kCntRedo = kCntNext + 4;
 // word offsets of the two queue counters of k_shade inside a counter set (one 128-byte line each)
-constexpr int kNextWord = kCntNext * kCounterStride, kShadowWord = kCntShadow * kCounterStride;
+constexpr int kNextWord = kCntNext * kCounterStride, kShadowWord = kCntShadow * kCounterStride, kRedoWord = kCntRedo * kCounterStride;
 #ifndef MG_SHADE_BLOCK
 #define MG_SHADE_BLOCK 1024     // 512: two atomics-bound milliseconds more per 64-spp frame (one reservation per workgroup)
 #endif
@@ -334,6 +336,12 @@ struct DQueues {
 	// ended.  Same addition, same place in the path's order of sums.  Slot 2 is free for it: the hits of binned paths
 	// travel with the bins.
 	uint32_t nee_parked;
+	// Lean closest-hit launches (trace.hip: LEAN): 1 = this launch runs the kernel without the mailbox, 4 workgroups per CU -- set
+	// by launch_trace, read by trace_plan on both sides.  redo: the path ids of the rays on which two primitives tied in t, where the
+	// mailbox decides which one is reported: the lean kernel bins none of them and lists them here (count in counters[kCntRedo]),
+	// and the host runs the list through the kernel with the mailbox (render.cpp: traceAndBin)
+	uint32_t lean;
+	uint32_t *redo;
 };
 constexpr uint32_t kNeeTag = 0x4E454521u;      // not a primitive index (< 2^29) and not kNoPrim
 // the radiance of a path record with a parked direct-light term added (what every reader of a finished path sees)
@@ -355,7 +363,7 @@ struct TracePlan {
 __host__ __device__ inline TracePlan trace_plan(uint32_t n, int mode, const DQueues &q) {
 	TracePlan p;
 	const uint32_t wavesPerBlock = kTraceBlock / 64;
-	uint32_t perCu = trace_blocks_per_cu(mode);
+	uint32_t perCu = trace_blocks_per_cu(mode, q.lean != 0);
 	if (q.tune_blocks_per_cu && q.tune_blocks_per_cu < perCu) perCu = q.tune_blocks_per_cu;
 	const uint32_t maxBlocks = q.n_cus * perCu;
 	// rays per wave: 64, or the smallest power of two (>= 8) with which the launch still fits into one round of the
@@ -440,8 +448,12 @@ void launch_generate(hipStream_t s, const DScene &sc, const DPaths &ps, const DC
 // mode 2: any-hit over ps.ray_* (writes ps.hit.w = occluded) -- test/benchmark API
 // n_dev == NULL: n rays, grid sized for them.  n_dev != NULL: the count is read from device memory by the kernel and n
 // is only its upper bound (device-driven bounces: the host never learns the queue sizes)
+// lean: (mode 0 with bin, no counting, n_dev == NULL) the kernel without the mailbox, which lists tied rays in q.redo instead of binning them
 void launch_trace(hipStream_t s, int mode, bool count, bool bin, const DScene &sc, const DPaths &ps,
-                  const DQueues &q, const uint32_t *queue, uint32_t n, bool coherent, const uint32_t *n_dev = nullptr);
+                  const DQueues &q, const uint32_t *queue, uint32_t n, bool coherent, const uint32_t *n_dev = nullptr, bool lean = false);
+// the hits a closest-hit launch with the material sort appended to the bins (counts in q.counters), copied to the records of their
+// paths (mtsgpu_trace_rays); n bounds the entries of a segment
+void launch_unbin_hits(hipStream_t s, const DPaths &ps, const DQueues &q, uint32_t n);
 // prefix[s] = number of entries of the bin in segments < s (prefix[kBinShards] = total)
 struct BinView { uint32_t prefix[kBinShards + 1]; };
 // views_dev == NULL: the bin has view.prefix[kBinShards] entries.  Otherwise the view is views_dev[bin] (written by

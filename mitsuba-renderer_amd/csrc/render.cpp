@@ -26,6 +26,11 @@ uint32_t tileMorton(uint32_t tx, uint32_t ty) {
 	return m;
 }
 
+// The "lean_closest" knob when nobody set it (traceAndBin: which closest-hit launches run the kernel without the mailbox): the
+// incoherent launches of at least plainBelow rays and the coherent first launch, which measured faster with it; the launches
+// below plainBelow showed no difference and keep the kernel with the mailbox (profiles/r19_lean_closest_ab.txt)
+constexpr long kLeanClosestDefault = 3;
+
 long tuningOr(const mtsgpu_ctx *c, const char *key, long dflt) {
 	auto it = c->tuning.find(key);
 	return it == c->tuning.end() ? dflt : it->second;
@@ -108,9 +113,9 @@ namespace {
 
 // Device bytes ensurePaths() allocates per path of a pass: the 128-byte record, the shadow ray (2 x 16), the eleven material
 // bins sized for the all-in-one-bin case with a quarter of headroom (id 4 + hit 16 bytes per entry), the two next queues
-// (id 4 + ray 32 bytes each) and the shadow queue's ids -- about 515 bytes, 37 GB for the default pass of 72 M paths.
+// (id 4 + ray 32 bytes each), the shadow queue's ids and the redo list's -- about 519 bytes, 37 GB for the default pass of 72 M paths.
 // (A frame that does not park its direct-light terms adds 16 bytes per path for them: ensureNeeQueue.)
-constexpr size_t kBytesPerPath = kPathSlots * 16 + 2 * 16 + (size_t) (kNumBins * (4 + 16) * 5 / 4) + 2 * (4 + 32) + 4 + 4;
+constexpr size_t kBytesPerPath = kPathSlots * 16 + 2 * 16 + (size_t) (kNumBins * (4 + 16) * 5 / 4) + 2 * (4 + 32) + 4 + 4 + 4;
 // Paths per pass when the caller set none (mtsgpu_set_options max_paths == 0): 72 M, or what 60 % of the free device memory
 // holds if that is less (the sampler tables, the film and the scene of a later upload need room too)
 uint64_t defaultMaxPaths(mtsgpu_ctx *c) {
@@ -152,6 +157,7 @@ int ensurePaths(mtsgpu_ctx *c, size_t cap) {
 	rc |= devAlloc(c, &c->queueA, cap, o); rc |= devAlloc(c, &c->queueB, cap, o);
 	for (int k = 0; k < 2; ++k) { rc |= devAlloc(c, &c->rayqA[k], cap, o); rc |= devAlloc(c, &c->rayqB[k], cap, o); }
 	rc |= devAlloc(c, &c->q.shadow, cap, o);
+	rc |= devAlloc(c, &c->q.redo, cap, o);          // closest-hit rays on which two primitives tied (k_trace LEAN): traced again with the mailbox
 	rc |= devAlloc(c, &c->counterSets, (size_t) kCounterSets * kNumCounters * kCounterStride, o);
 	rc |= devAlloc(c, &c->viewsDev, kNumBins, o);
 	rc |= devAlloc(c, &c->devStats, kNumDevStats, o);
@@ -241,15 +247,43 @@ int readCounters(mtsgpu_ctx *c) {
 // Closest-hit launch over queue[0..n) with the material sort, then the per-bin segment sizes (one blocking read of the
 // counters).  A shard segment that overflowed (possible only with dynamically claimed batches, see ensurePaths) makes
 // the launch run again with static dealing: tracing a ray twice writes the same hit twice.
-int traceAndBin(mtsgpu_ctx *c, const uint32_t *queue, uint32_t n, bool coherent, BinView *views) {
+// With the "lean_closest" knob the launch runs the kernel without the mailbox (trace.hip: LEAN, 8 waves per SIMD).  The rays on
+// which two primitives tied come back as a list of path ids (q.redo) and go through the kernel with the mailbox, into the same
+// bins and counters: every ray is binned once, by one of the two.  The redo deals its rays statically, but it appends to
+// segments the first launch has filled already, so the proven bound of one static dealing (ensurePaths) does not cover the pair:
+// the overflow retry runs the whole queue through the kernel with the mailbox, one static launch, for which it holds.
+// Which launches (bits of the knob): 1 = the incoherent launches of at least plainBelow rays, 2 = the coherent first launch,
+// 4 = the launches below plainBelow (kernels.h: trace_plan).  Counting frames keep the mailbox (the oracle counts with it).
+bool leanClosest(const mtsgpu_ctx *c, uint32_t n, bool coherent) {
+	const long knob = tuningOr(c, "lean_closest", kLeanClosestDefault);
+	const uint32_t plainBelow = c->q.tune_plain_below ? c->q.tune_plain_below : 8u * (c->q.n_cus * kTraceBlocksPerCuMax) * kTraceBlock;
+	return (knob & (coherent ? 2 : (n < plainBelow ? 4 : 1))) != 0 && !c->countTraversal;
+}
+// launches (may be NULL): how many launches the call made (1; 2 with a redo; more with the retry)
+int traceAndBin(mtsgpu_ctx *c, const uint32_t *queue, uint32_t n, bool coherent, BinView *views, int *launches = nullptr) {
 	hipStream_t s = c->stream;
 	const bool testRetry = tuningOr(c, "test_retry", 0) != 0;      // exercises the retry (tests)
+	const bool leanHere = leanClosest(c, n, coherent);
 	for (int attempt = 0; attempt < 2; ++attempt) {
 		if (attempt) HIPCHK(c, hipMemsetAsync(c->q.counters, 0, kCounterSetBytes, s));
 		c->q.force_static = attempt ? 1u : 0u;
+		const bool lean = leanHere && attempt == 0;
+		if (launches) *launches += 1;
 		int rc = timedLaunch(c, s, coherent ? kClosestFirst : kClosest, [&] {
-			launch_trace(s, 0, c->countTraversal && attempt == 0, true, c->dsc, c->paths, c->q, queue, n, coherent); });
+			launch_trace(s, 0, c->countTraversal && attempt == 0, true, c->dsc, c->paths, c->q, queue, n, coherent, nullptr, lean); });
 		if (!rc) rc = readCounters(c);
+		const uint32_t nRedo = lean ? c->hostCounters[kRedoWord] : 0u;
+		if (!rc && nRedo > n) rc = fail(c, MTSGPU_EHIP, "internal: redo list longer than the queue");
+		if (!rc && nRedo) {
+			// the list is not in queue order: its rays come from the path records.  Timed with the class of the launch it completes
+			DPaths viaRecords = c->paths; viaRecords.rq_o = viaRecords.rq_d = nullptr;
+			c->q.force_static = 1;
+			if (launches) *launches += 1;
+			rc = timedLaunch(c, s, coherent ? kClosestFirst : kClosest, [&] {
+				launch_trace(s, 0, false, true, c->dsc, viaRecords, c->q, c->q.redo, nRedo, false); });
+			if (!rc) rc = readCounters(c);
+			c->raysRedone += nRedo;
+		}
 		c->q.force_static = 0;
 		if (rc) return rc;
 		bool overflow = attempt == 0 && testRetry;
@@ -463,13 +497,18 @@ int collectDeviceStats(mtsgpu_ctx *c) {
 	return 0;
 }
 
-// MTSGPU_DEBUG: what the launches of a host-driven bounce took, once they are done (tools/bounce_times.py)
-int printBounce(mtsgpu_ctx *c, uint32_t nClosest, uint32_t nShadow) {
+// MTSGPU_DEBUG: what the launches of a host-driven bounce took, once they are done (tools/bounce_times.py); nClosestLaunches:
+// the closest-hit launches of the bounce (the redo launch and a retry are part of its closest-hit time)
+int printBounce(mtsgpu_ctx *c, uint32_t nClosest, uint32_t nShadow, int nClosestLaunches) {
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	float a = 0, b = 0, c2 = 0;
 	if (c->timeKernels) {
 		const size_t ti = c->traceEvUsed - (nShadow ? 2 : 1);
-		(void) hipEventElapsedTime(&a, c->traceEvents[ti].first, c->traceEvents[ti].second);
+		for (int k = 0; k < nClosestLaunches && (size_t) k <= ti; ++k) {
+			float ms = 0;
+			(void) hipEventElapsedTime(&ms, c->traceEvents[ti - k].first, c->traceEvents[ti - k].second);
+			a += ms;
+		}
 		(void) hipEventElapsedTime(&b, c->shadeEvents[c->shadeEvUsed - 1].first, c->shadeEvents[c->shadeEvUsed - 1].second);
 		if (nShadow) (void) hipEventElapsedTime(&c2, c->traceEvents[ti + 1].first, c->traceEvents[ti + 1].second);
 	}
@@ -508,7 +547,8 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 		rayQueues(c, cur, nxt);
 		// closest hit + material sort
 		BinView views[kNumBins];
-		int rc = traceAndBin(c, cur, nQ, first, views); if (rc) return rc;
+		int closestLaunches = 0;
+		int rc = traceAndBin(c, cur, nQ, first, views, &closestLaunches); if (rc) return rc;
 		c->stats.rays_closest += nQ;
 		// shade, one launch per BSDF type
 		rc = timedLaunch(c, s, kShading, [&] { shade.bins(views); }); if (rc) return rc;
@@ -521,7 +561,7 @@ int runBounces(mtsgpu_ctx *c, const DConfig &cfg, uint32_t nPaths, volatile cons
 			rc = traceShadows(c, s, nShadow, first); if (rc) return rc;
 			c->stats.rays_shadow += nShadow;
 		}
-		if (c->debug) { rc = printBounce(c, nQ, nShadow); if (rc) return rc; }
+		if (c->debug) { rc = printBounce(c, nQ, nShadow, closestLaunches); if (rc) return rc; }
 		std::swap(cur, nxt);
 		nQ = nNext;
 		first = false;
@@ -631,6 +671,7 @@ int readCameraRows(mtsgpu_ctx *c, size_t first, uint32_t n, float *out) {
 void beginFrame(mtsgpu_ctx *c, bool bins = true) {
 	std::memset(&c->stats, 0, sizeof(c->stats));
 	if (bins) std::memset(c->binEntries, 0, sizeof(c->binEntries));
+	c->raysRedone = 0;
 	c->traceEvUsed = c->shadeEvUsed = 0;
 	c->debug = getenv("MTSGPU_DEBUG") != nullptr;
 }
@@ -853,9 +894,26 @@ int mtsgpu_trace_rays(mtsgpu_ctx *c, const float *rays, uint32_t n, int shadow, 
 	launch_iota(c->stream, c->queueA, n);
 	if (c->countTraversal) HIPCHK(c, hipMemsetAsync(c->q.trace_counts, 0, kNumTraceCounts * sizeof(unsigned long long), c->stream));
 	HIPCHK(c, hipMemsetAsync(c->q.counters, 0, kCounterSetBytes, c->stream));     // dynamic batch head
-	rc = timedLaunch(c, c->stream, shadow ? kAnyHit : kClosest, [&] {
-		launch_trace(c->stream, shadow ? 2 : 0, c->countTraversal, false, c->dsc, c->paths, c->q, c->queueA, n, false); });
-	if (rc) return rc;
+	if (!shadow && leanClosest(c, n, false)) {
+		// As the bounces trace an incoherent queue of this size: through the material sort (the kernel without the mailbox, the
+		// redo, the retry), every ray binned -- a miss in the terminal bin -- and the hits moved from the bins to the records
+		const uint32_t settled = c->q.miss_settled;
+		uint64_t bins[kNumBins];
+		std::memcpy(bins, c->binEntries, sizeof(bins));
+		c->q.miss_settled = 0;
+		rayQueues(c, nullptr, nullptr);
+		BinView views[kNumBins];
+		rc = traceAndBin(c, c->queueA, n, false, views);
+		c->q.miss_settled = settled;
+		std::memcpy(c->binEntries, bins, sizeof(bins));      // a frame's statistic
+		if (rc) return rc;
+		launch_unbin_hits(c->stream, c->paths, c->q, n);
+		HIPCHK(c, hipGetLastError());
+	} else {
+		rc = timedLaunch(c, c->stream, shadow ? kAnyHit : kClosest, [&] {
+			launch_trace(c->stream, shadow ? 2 : 0, c->countTraversal, false, c->dsc, c->paths, c->q, c->queueA, n, false); });
+		if (rc) return rc;
+	}
 	HIPCHK(c, hipMemcpy2DAsync(hits, 16, c->paths.base + 2, kPathSlots * sizeof(float4), 16, n, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	if (shadow) c->stats.rays_shadow = n; else c->stats.rays_closest = n;
@@ -944,6 +1002,12 @@ int mtsgpu_camera_rays(mtsgpu_ctx *c, const int32_t *pix_samples, uint32_t first
 	rc = generatePaths(c, cfg, 0, n, c->explicitSamples, n); if (rc) return rc;
 	// `samples` and `keys` live on this stack; the read-back below waits for the stream
 	return readCameraRows(c, 0, n, out);
+}
+
+int mtsgpu_hook_rays_redone(mtsgpu_ctx *c, uint64_t *out) {
+	if (!c || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	*out = c->raysRedone;
+	return 0;
 }
 
 int mtsgpu_bin_entries(mtsgpu_ctx *c, uint64_t *out) {

@@ -15,7 +15,8 @@ namespace mg {
 // per level: parent index * 2 + "far child is the right one".  The top exit
 // point lives in registers; deeper levels sit in LDS ([level][lane], conflict
 // free), levels beyond kStackLDS spill to HBM.  The 8-entry hashed mailbox
-// (sahkdtree3.h:130-144) is kept (LDS) because it decides equal-t ties.
+// (sahkdtree3.h:130-144) is kept (LDS) because it decides equal-t ties; the LEAN
+// closest-hit kernel runs without it and hands the tied rays back (see trace_body).
 // ===========================================================================
 
 // How many lanes below this one have their bit set in a wave mask (ranks of the material sort, of the refill).  The hardware counts
@@ -45,7 +46,27 @@ __device__ __forceinline__ const uint4 *leaf_tail(const DTraceScene &sc, uint32_
 
 // PARKED (any-hit only): the launches of frames that park their direct-light terms in the path records (DQueues::nee_parked):
 // the kernel without the code that carries a term along and adds it to Li, which frames that do not park run
-template <int MODE, bool COUNT, bool BIN, bool PARKED>
+//
+// LEAN (closest-hit only, with the material sort, no counting): the closest-hit kernel at the any-hit kernel's footprint -- no
+// mailbox, and ONE register of hit state across the loops, best_e = the leaf entry of the accepted record (kNoPrim = none; maxt
+// is its t).  u, v, the primitive and the shape are rebuilt at retirement from that record with the loop's own expressions on
+// the same operands (the stored t, the lane's o and d, the record), so they have the same bits.
+// Why leaving the mailbox out is exact, and when it is not.  The mailbox only ever SKIPS the test of a primitive P that this ray
+// tested before (sahkdtree3.h:130-144, :278-283), so the two kernels differ by tests that run here and not there.  Such a
+// repeated test (a) of a P that was rejected is rejected again: t, u and v are functions of (ray, record) and the interval
+// [mint, maxt] has only shrunk; (b) of a P that was accepted, with t_P, is rejected when maxt < t_P by now and, when
+// maxt == t_P, accepted again -- which changes nothing if P is still the hit that is held (its record in the later leaf is a
+// copy), and replaces the held hit Q if another primitive Q with t_Q == t_P was accepted in between.  Only that last case can
+// change what is reported, and Q's acceptance is then an accepted candidate with t == maxt on a primitive other than the held
+// one while a hit is held.  That event is what marks a ray TIED (kTiedBit of best_e).  Both kernels keep the same maxt throughout
+// (tied hits have equal t), hence the same traversal; an accepted candidate with t < maxt was tested by both (a skipped one would
+// have been accepted before, with maxt <= t since), leaves both with the same hit, and clears the mark.  A primitive met again in
+// a later leaf with t == maxt is therefore compared with the primitive of record best_e (one load, on that rare path only): the
+// same primitive is no tie.  A ray that retires tied goes to no bin: its path id is appended to q.redo and the host runs the list
+// through the kernel with the mailbox.  A sphere (k == 3, A.y != 0) takes part like a triangle: accepted with t = ts, u = v = 0
+// at retirement, its shape in dword 10 like a triangle's.
+constexpr uint32_t kTiedBit = 0x80000000u;     // leaf entries are < 2^31 (bit 31 of a leaf node's first word is its leaf flag)
+template <int MODE, bool COUNT, bool BIN, bool PARKED, bool LEAN>
 __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &ps, const DQueues &q, const TracePlan &plan,
                                            const uint32_t *queue, uint32_t n, const uint32_t first, const uint32_t stride,
                                            uint32_t (*s_stack)[kTraceBlock], uint32_t (*s_mbox)[kTraceBlock], const uint4 *s_top) {
@@ -73,7 +94,8 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 	// closest-hit rays keep it.  For any-hit rays it only saves repeated tests of a primitive that spans several leaves --
 	// the answer is a disjunction over the same primitives either way -- and its 8 dwords per lane are better spent on
 	// the LDS copy of the tree: the shadow kernels run without it (counting builds keep it: the oracle counts with it).
-	constexpr bool kMbox = MODE == 0 || COUNT;
+	static_assert(!LEAN || (MODE == 0 && BIN && !COUNT), "the lean form exists for binned closest-hit launches");
+	constexpr bool kMbox = (MODE == 0 && !LEAN) || COUNT;
 	const uint32_t tid = threadIdx.x;
 	const uint32_t gtid = blockIdx.x * kTraceBlock + tid;     // spill slot of this lane
 	const uint32_t lane = lane_id();
@@ -111,7 +133,17 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 	float best_t = MG_INF, best_u = 0, best_v = 0;
 	uint32_t best_prim = kNoPrim, best_shape = 0;
 	// best_shape: shape index of the accepted hit (dword 10 of its record), read while the record is at hand
-	uint32_t e_cont = kNoPrim;              // position inside an interrupted leaf
+	// LEAN: the five above are written at retirement only; across the loops the hit is best_e (| kTiedBit), with its t in maxt
+	uint32_t best_e = kNoPrim;
+	auto accept_lean = [&](float t, uint32_t e, uint32_t prim) {
+		uint32_t tied = 0u;
+		if (best_e != kNoPrim && t == maxt) {
+			tied = best_e & kTiedBit;
+			if (!tied && (leaf_head(sc, best_e)->x & 0x0FFFFFFFu) != prim) tied = kTiedBit;
+		}
+		best_e = e | tied;
+	};
+	uint32_t e_cont = kNoPrim;             // position inside an interrupted leaf
 	uint2 nd = make_uint2(0u, 0u);          // sc.nodes[cur], fetched as soon as cur is known
 	bool found = false;
 	bool has = false;                       // this lane is traversing a ray
@@ -140,7 +172,35 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 			if (MODE == 0) {
 				int bin = -1;
 				constexpr bool hitsToBins = BIN;      // a binned path's hit travels with its id (DQueues::bin_hits)
-				if (done) {
+				bool tied = false;
+				if (LEAN) {
+					// the hit, rebuilt from record best_e: three independent loads, then the expressions of the primitive loop
+					best_t = MG_INF; best_u = 0; best_v = 0; best_prim = kNoPrim; best_shape = 0;
+					tied = done && found && (best_e & kTiedBit) != 0u;
+					if (done && found && !tied) {
+						const uint4 A = ld_stream<2>(leaf_head(sc, best_e));
+						const uint4 B = ld_stream<2>(leaf_tail(sc, best_e, 0));
+						const uint4 C = ld_stream<2>(leaf_tail(sc, best_e, 1));
+						const uint32_t k = A.x >> 30;
+						const float t = maxt;
+						best_t = t; best_prim = A.x & 0x0FFFFFFFu; best_shape = C.z;
+						if (k != 3u) {      // k == 3 was accepted as a sphere: u = v = 0
+							const bool k0 = k == 0u, k1 = k == 1u;
+							const float o_u = k0 ? oy : (k1 ? oz : ox), o_v = k0 ? oz : (k1 ? ox : oy);
+							const float d_u = k0 ? dy : (k1 ? dz : dx), d_v = k0 ? dz : (k1 ? dx : dy);
+							const float a_u = __uint_as_float(B.x), a_v = __uint_as_float(B.y);
+							const float b_nu = __uint_as_float(B.z), b_nv = __uint_as_float(B.w);
+							const float c_nu = __uint_as_float(C.x), c_nv = __uint_as_float(C.y);
+							const float hu = o_u + t * d_u - a_u;
+							const float hv = o_v + t * d_v - a_v;
+							best_u = hv * b_nu + hu * b_nv;
+							best_v = hu * c_nu + hv * c_nv;
+						}
+					}
+					// two primitives tied on this ray: the mailbox decides (coincident geometry, hits on shared edges)
+					if (tied) q.redo[atomicAdd(&q.counters[kCntRedo * kCounterStride], 1u)] = id;
+				}
+				if (done && !tied) {
 					if (!hitsToBins) st_stream<1>(&ps.hit(id), make_uint4(__float_as_uint(best_t), __float_as_uint(best_u), __float_as_uint(best_v), best_prim));
 					if (BIN) {
 						bin = kNumBins - 1;
@@ -250,7 +310,8 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 				if (rayMinT > mint) mint = rayMinT;
 				if (rmaxt < maxt) maxt = rmaxt;
 				if (!(maxt > mint)) go = false;
-				best_t = MG_INF; best_u = 0; best_v = 0; best_prim = kNoPrim; best_shape = 0;
+				if (LEAN) best_e = kNoPrim;
+				else { best_t = MG_INF; best_u = 0; best_v = 0; best_prim = kNoPrim; best_shape = 0; }
 				found = false;
 				done = !go;       // a ray that misses the scene's box is finished at once
 				has = go;
@@ -370,9 +431,12 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 							} else {
 								float ts;
 								if (sphere_intersect(ctr, rad, V3(ox, oy, oz), V3(dx, dy, dz), mint, maxt, ts)) {
+									if (LEAN) accept_lean(ts, e, prim);
 									maxt = ts;
-									best_t = ts; best_u = 0.0f; best_v = 0.0f; best_prim = prim;
-									best_shape = leaf_tail(sc, e, 1)->z;
+									if (!LEAN) {
+										best_t = ts; best_u = 0.0f; best_v = 0.0f; best_prim = prim;
+										best_shape = leaf_tail(sc, e, 1)->z;
+									}
 								}
 							}
 						}
@@ -396,8 +460,9 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 							const float v = hu * c_nu + hv * c_nv;
 							if (u >= 0 && v >= 0 && u + v <= 1.0f) {
 								if (MODE != 0) hitShadow = true;
+								if (LEAN) accept_lean(t, e, prim);
 								maxt = t;      // a later hit with equal t replaces this one (t > maxt rejects)
-								best_t = t; best_u = u; best_v = v; best_prim = prim; best_shape = C.z;
+								if (!LEAN) { best_t = t; best_u = u; best_v = v; best_prim = prim; best_shape = C.z; }
 							}
 						}
 						if (kMbox) *mslot = prim;         // (re)writing an entry that is already there changes nothing
@@ -441,7 +506,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 					}
 				}
 				if (finished) {
-					has = false; done = true; found = (MODE == 0) ? (best_prim != kNoPrim) : hitShadow;
+					has = false; done = true; found = (MODE == 0) ? ((LEAN ? best_e : best_prim) != kNoPrim) : hitShadow;
 					if (COUNT && q.rec) { if (MODE != 1 && !(MODE == 0 && BIN)) rec_add(kReqHit, id * kPathSlots + 2); q.rec_len[rec_slot] = rec_n; }      // binned hits are streamed
 				}
 				}
@@ -463,15 +528,15 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 	}
 }
 
-template <int MODE, bool COUNT, bool BIN, bool PARKED = false>
-__global__ __launch_bounds__(kTraceBlock, trace_waves_per_simd(MODE)) void k_trace(DTraceScene sc, DPaths ps, DQueues q,
+template <int MODE, bool COUNT, bool BIN, bool PARKED = false, bool LEAN = false>
+__global__ __launch_bounds__(kTraceBlock, trace_waves_per_simd(MODE, LEAN)) void k_trace(DTraceScene sc, DPaths ps, DQueues q,
                                                           const uint32_t *queue, uint32_t n_host, const uint32_t *n_dev) {
 	__shared__ uint32_t s_stack[kStackLDS][kTraceBlock];
-	__shared__ uint32_t s_mbox[(MODE == 0 || COUNT) ? 8 : 1][kTraceBlock];
+	__shared__ uint32_t s_mbox[((MODE == 0 && !LEAN) || COUNT) ? 8 : 1][kTraceBlock];
 	__shared__ uint4 s_top[kTopPairs ? kTopPairs : 1];
 	// the number of rays: known to the host, or left in device memory by the kernel that filled the queue
 	const uint32_t n = n_dev ? (uint32_t) __builtin_amdgcn_readfirstlane((int) *n_dev) : n_host;
-	const TracePlan plan = trace_plan(n, MODE, q);
+	const TracePlan plan = trace_plan(n, MODE, q);      // q.lean == LEAN (launch_trace)
 	if (blockIdx.x >= plan.blocks)
 		return;                            // a grid sized for the worst case: nothing left for this workgroup
 	if (q.dev_stats && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -485,7 +550,7 @@ __global__ __launch_bounds__(kTraceBlock, trace_waves_per_simd(MODE)) void k_tra
 		for (uint32_t t = threadIdx.x; t < kTopPairs; t += kTraceBlock) s_top[t] = reinterpret_cast<const uint4 *>(sc.nodes)[t];
 		__syncthreads();
 	}
-	trace_body<MODE, COUNT, BIN, PARKED>(sc, ps, q, plan, queue, n, first, stride, s_stack, s_mbox, s_top);
+	trace_body<MODE, COUNT, BIN, PARKED, LEAN>(sc, ps, q, plan, queue, n, first, stride, s_stack, s_mbox, s_top);
 }
 
 // Device-driven bounces: the per-bin views k_shade needs, from the shard counters the closest-hit launch left in `cur`
@@ -513,7 +578,7 @@ __global__ __launch_bounds__(256) void k_prep(const uint32_t *cur, uint32_t *nex
 	}
 }
 
-template <int MODE, bool COUNT, bool BIN, bool PARKED = false>
+template <int MODE, bool COUNT, bool BIN, bool PARKED = false, bool LEAN = false>
 static void launch_trace_t(hipStream_t s, const DScene &sc, const DPaths &ps, const DQueues &q, const uint32_t *queue, uint32_t n,
                            const uint32_t *n_dev) {
 	// persistent grid: enough workgroups to fill every CU, never more than there are rays (trace_plan); when only the
@@ -522,23 +587,30 @@ static void launch_trace_t(hipStream_t s, const DScene &sc, const DPaths &ps, co
 	if (n_dev) {
 		// any count up to n: the narrowest batches need the most workgroups
 		const unsigned minBatch = (q.tune_batch >= 1 && q.tune_batch <= 64) ? q.tune_batch : (q.coherent ? 64u : 8u);
-		unsigned perCu = trace_blocks_per_cu(MODE);
+		unsigned perCu = trace_blocks_per_cu(MODE, LEAN);
 		if (q.tune_blocks_per_cu && q.tune_blocks_per_cu < perCu) perCu = q.tune_blocks_per_cu;
 		blocks = std::min<unsigned>(blocks_for(n, minBatch * (kTraceBlock / 64)), q.n_cus * perCu);
 	}
 	if (!blocks) return;
-	hipLaunchKernelGGL((k_trace<MODE, COUNT, BIN, PARKED>), dim3(blocks), dim3(kTraceBlock), 0, s, trace_scene(sc), ps, q, queue, n, n_dev);
+	hipLaunchKernelGGL((k_trace<MODE, COUNT, BIN, PARKED, LEAN>), dim3(blocks), dim3(kTraceBlock), 0, s, trace_scene(sc), ps, q, queue, n, n_dev);
 }
 
 void launch_trace(hipStream_t s, int mode, bool count, bool bin, const DScene &sc, const DPaths &ps,
-                  const DQueues &q, const uint32_t *queue, uint32_t n, bool coherent, const uint32_t *n_dev) {
+                  const DQueues &q, const uint32_t *queue, uint32_t n, bool coherent, const uint32_t *n_dev, bool lean) {
 	if (!n) return;
 	DQueues qq = q;
 	qq.coherent = coherent ? 1u : 0u;
+	// the lean kernel needs the host behind it (the redo launch): counting builds keep the mailbox, which the oracle counts with
+	lean = lean && mode == 0 && bin && !count && !n_dev && qq.redo;
+	qq.lean = lean ? 1u : 0u;
 	if (n_dev)
 		qq.force_static = 1u;        // no dynamically claimed batches: the material-queue segments cannot overflow then
 	if (mode == 0) {
-		if (bin) { if (count) launch_trace_t<0, true, true>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<0, false, true>(s, sc, ps, qq, queue, n, n_dev); }
+		if (bin) {
+			if (count) launch_trace_t<0, true, true>(s, sc, ps, qq, queue, n, n_dev);
+			else if (lean) launch_trace_t<0, false, true, false, true>(s, sc, ps, qq, queue, n, n_dev);
+			else launch_trace_t<0, false, true>(s, sc, ps, qq, queue, n, n_dev);
+		}
 		else     { if (count) launch_trace_t<0, true, false>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<0, false, false>(s, sc, ps, qq, queue, n, n_dev); }
 	} else if (mode == 1) {
 		if (qq.nee_parked) { if (count) launch_trace_t<1, true, false, true>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<1, false, false, true>(s, sc, ps, qq, queue, n, n_dev); }
@@ -546,6 +618,20 @@ void launch_trace(hipStream_t s, int mode, bool count, bool bin, const DScene &s
 	} else {
 		if (count) launch_trace_t<2, true, false>(s, sc, ps, qq, queue, n, n_dev); else launch_trace_t<2, false, false>(s, sc, ps, qq, queue, n, n_dev);
 	}
+}
+
+// segment blockIdx.y (= bin * kBinShards + shard) of the material queues: ps.hit(id) = the hit that travelled with the id
+__global__ __launch_bounds__(256) void k_unbin_hits(DPaths ps, DQueues q) {
+	const uint32_t seg = blockIdx.y;
+	uint32_t cnt = q.counters[seg * kCounterStride];
+	if (cnt > q.bin_seg_cap) cnt = q.bin_seg_cap;
+	const size_t base = (size_t) (seg / kBinShards) * q.bin_stride + (size_t) (seg % kBinShards) * q.bin_seg_cap;
+	for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < cnt; i += gridDim.x * 256u)
+		ps.hit(q.bins_base[base + i]) = q.bin_hits[base + i];
+}
+void launch_unbin_hits(hipStream_t s, const DPaths &ps, const DQueues &q, uint32_t n) {
+	const unsigned bx = std::max(1u, std::min(64u, blocks_for(n, 256)));
+	hipLaunchKernelGGL(k_unbin_hits, dim3(bx, kNumBins * kBinShards), dim3(256), 0, s, ps, q);
 }
 
 void launch_prep(hipStream_t s, const uint32_t *cur, uint32_t *next_set, BinView *views_dev, uint32_t bin_seg_cap,

@@ -40,6 +40,7 @@
 #include <mitsuba/core/plugin.h>
 #include <mitsuba/core/sched.h>
 #include <mtsgpu.h>
+#include <mtsgpu_mask.h>
 #include "streamparse.h"
 #include <sstream>
 #include <cstdlib>
@@ -137,6 +138,9 @@ struct FlatScene {
 	std::vector<mtsgpu_stream::LdrTexture> ldrTextures;
 	std::vector<std::vector<float> > ldrTexels;
 	std::vector<uint32_t> ldrWidth, ldrHeight;
+	/* per BSDF table entry the opacity of the `mask` adapter around it (none, a constant, one of uvTextures): what
+	 * mtsgpu_group_set_uv_masked_textures takes on top */
+	std::vector<mtsgpu_bsdf_mask> bsdfMasks;
 	/* vertex tangents (TriMesh::getVertexTangents, trimesh.h:136-140: TriMesh::configure computes them for a mesh whose BSDF is
 	 * anisotropic, trimesh.cpp:288-290): dpdu in the order of vtxPos, one flag per shape -- what
 	 * mtsgpu_group_upload_scene_tangents takes */
@@ -154,8 +158,10 @@ struct FlatScene {
 	/* after upload() and setVertexColors: hands the textures over when a BSDF slot holds one (a mesh
 	 * without texcoords is then shaded with uv = (0, 0), as in the reference) */
 	int setUvTextures(mtsgpu_group *group) const {
-		if (uvTextures.empty()) return MTSGPU_OK;
-		if (ldrTextures.empty())      /* no bitmap: the call such a scene has always taken */
+		bool anyMask = false;
+		for (size_t b = 0; b < bsdfMasks.size(); ++b) if (bsdfMasks[b].kind != MTSGPU_MASK_NONE) anyMask = true;
+		if (uvTextures.empty() && !anyMask) return MTSGPU_OK;
+		if (ldrTextures.empty() && !anyMask)      /* no bitmap: the call such a scene has always taken */
 			return mtsgpu_group_set_uv_textures(group, anyUv ? ptr(vtxUv) : NULL, anyUv ? ptr(shapeHasUv) : NULL, (uint32_t) uvTextures.size(),
 				&uvTextures[0], ptr(bsdfSlotTexture));
 		std::vector<mtsgpu_bitmap> bitmaps(ldrTextures.size());
@@ -166,6 +172,9 @@ struct FlatScene {
 			bitmaps[k].texels = &ldrTexels[k][0];
 			textureBitmap[ldrTextures[k].texture] = (int32_t) k;
 		}
+		if (anyMask)      /* a masked BSDF: the call that keeps textures and texcoords for the masks too */
+			return mtsgpu_group_set_uv_masked_textures(group, anyUv ? ptr(vtxUv) : NULL, anyUv ? ptr(shapeHasUv) : NULL, (uint32_t) uvTextures.size(),
+				ptr(uvTextures), ptr(bsdfSlotTexture), (uint32_t) bitmaps.size(), ptr(bitmaps), ptr(textureBitmap), ptr(bsdfMasks));
 		return mtsgpu_group_set_uv_bitmap_textures(group, anyUv ? ptr(vtxUv) : NULL, anyUv ? ptr(shapeHasUv) : NULL, (uint32_t) uvTextures.size(),
 			&uvTextures[0], ptr(bsdfSlotTexture), (uint32_t) bitmaps.size(), &bitmaps[0], &textureBitmap[0]);
 	}
@@ -464,6 +473,9 @@ private:
 				if (bsdfSlotTexture[2 * b + slot] == t.texture && o >= 0)
 					memcpy(&bsdfParams[MTSGPU_BSDF_NPARAMS * b + o], average, sizeof(average));
 			}
+		for (size_t b = firstEntry; b < bsdfMasks.size(); ++b)
+			if (bsdfMasks[b].kind == MTSGPU_MASK_TEXTURE && bsdfMasks[b].texture == t.texture)
+				memcpy(bsdfMasks[b].opacity, average, sizeof(average));
 		ldrTexels.push_back(texels); ldrWidth.push_back(w); ldrHeight.push_back(h);
 	}
 
@@ -477,7 +489,7 @@ private:
 		std::string err;
 		const size_t firstEntry = bsdfType.size(), firstLdr = ldrTextures.size();
 		const int index = mtsgpu_stream::parseBSDFTable<Float>(st->getData(), st->getSize(), bsdfType, bsdfParams, &err, &bsdfColorSlots, &uvTextures, &bsdfSlotTexture,
-			&ldrTextures);
+			&ldrTextures, &bsdfMasks);
 		if (index < 0)
 			SLog(EError, "gpupath: %s", err.c_str());
 		for (size_t k = firstLdr; k < ldrTextures.size(); ++k)

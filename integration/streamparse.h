@@ -16,6 +16,7 @@
 #define MTSGPU_STREAMPARSE_H
 
 #include <mtsgpu.h>
+#include <mtsgpu_mask.h>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -225,6 +226,20 @@ public:
 	/* per slot of the block read since the last resetColorSlots(): the index of its texture in that list, or -1 */
 	const int32_t *slotTextures() const { return m_slotTextures; }
 	bool hasSlotTexture() const { return m_slotTextures[0] >= 0 || m_slotTextures[1] >= 0; }
+	/* The opacity of the Mask the reader stands on (mask.cpp:47-52: BSDF::serialize, then the opacity texture instance, then the
+	 * nested BSDF instance) -> one mtsgpu_bsdf_mask.  A ConstantSpectrumTexture becomes MTSGPU_MASK_CONSTANT; a Checkerboard, a
+	 * GridTexture or an unfiltered LDRTexture becomes MTSGPU_MASK_TEXTURE through the lists of takeUvTextures / takeBitmaps, with
+	 * the texture's getAverage() in `opacity` (an LDRTexture: left 0 for the caller, who has the decoder).  VertexColors is
+	 * refused: there is no mask kind for it. */
+	void readMaskOpacity(mtsgpu_bsdf_mask &m) {
+		resetColorSlots();
+		memset(&m, 0, sizeof(m));
+		readSpectrumTexture("opacity", m.opacity, 0);
+		if (r.ok() && m_colorSlots) r.fail("opacity of Mask is a VertexColors texture: vertex colours as opacity are not supported");
+		m.kind = m_slotTextures[0] >= 0 ? MTSGPU_MASK_TEXTURE : MTSGPU_MASK_CONSTANT;
+		m.texture = m_slotTextures[0];
+		resetColorSlots();
+	}
 	/* a ConstantFloatTexture child (roughglass' alpha): [id][class name][Texture::serialize][the value] (texture.cpp:95-103) */
 	FloatT readConstantFloatTexture(const char *what) {
 		const uint32_t id = r.readUInt();
@@ -361,23 +376,46 @@ template <typename FloatT> inline bool parseBSDF(const uint8_t *data, size_t siz
 /* bitmaps (optional, with uvTextures and slotTextures): one LdrTexture per LDRTexture with filterType none, whose descriptor
  * (kind MTSGPU_TEX_BITMAP) goes to uvTextures; offset counts from `data`.  The slot's floats in the block are left 0: the
  * caller decodes the file and writes getAverage() there.  Without the list an LDRTexture is refused like any other texture. */
+/* masks (optional): one mtsgpu_bsdf_mask per appended entry, next to `types` (what mtsgpu_set_uv_masked_textures takes as
+ * bsdf_mask).  With the list an outermost Mask (mask.cpp) is opened: its opacity is read (readMaskOpacity), its nested BSDF is
+ * entered like a twosided child, and the instance's own entry receives the mask; every other entry receives MTSGPU_MASK_NONE.
+ * Refused with the reason: a Mask inside a Mask, under TwoSidedBRDF (twosided.cpp:71-73 refuses that child too), around a
+ * Composite or as a composite's child, and a VertexColors opacity.  Without the list a Mask is refused like every class that is
+ * not on this path. */
 template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t size, std::vector<uint32_t> &types, std::vector<float> &params,
                                                      std::string *err, std::vector<uint32_t> *colorSlots = NULL,
                                                      std::vector<mtsgpu_uv_texture> *uvTextures = NULL, std::vector<int32_t> *slotTextures = NULL,
-                                                     std::vector<LdrTexture> *bitmaps = NULL) {
+                                                     std::vector<LdrTexture> *bitmaps = NULL, std::vector<mtsgpu_bsdf_mask> *masks = NULL) {
 	BSDFStream<FloatT> rd(data, size);
 	const size_t first = types.size(), firstTex = uvTextures ? uvTextures->size() : 0, firstBmp = bitmaps ? bitmaps->size() : 0;
 	if (uvTextures && slotTextures) rd.takeUvTextures(uvTextures);
 	if (uvTextures && slotTextures && bitmaps) rd.takeBitmaps(bitmaps);
+	mtsgpu_bsdf_mask none, mask;
+	memset(&none, 0, sizeof(none)); none.kind = MTSGPU_MASK_NONE; none.texture = -1;
+	mask = none;
+	if (masks && rd.className() == "Mask") {
+		rd.readMaskOpacity(mask);
+		rd.enterNestedBSDF();
+		if (rd.r.ok() && rd.className() == "Mask") rd.r.fail("a Mask inside a Mask: nested masks are not supported");
+	}
 	uint32_t flags = 0;
-	if (rd.className() == "TwoSidedBRDF") { flags |= MTSGPU_BSDF_TWOSIDED; rd.enterNestedBSDF(); }
+	if (rd.r.ok() && rd.className() == "TwoSidedBRDF") {
+		flags |= MTSGPU_BSDF_TWOSIDED; rd.enterNestedBSDF();
+		if (masks && rd.r.ok() && rd.className() == "Mask")
+			rd.r.fail("a Mask under TwoSidedBRDF: the mask transmits, and the adapter takes no child with a transmission component (twosided.cpp:71-73)");
+	}
 	int own = -1;
-	if (rd.className() != "Composite") {
+	if (!rd.r.ok()) {
+		/* the mask or an adapter could not be opened */
+	} else if (rd.className() == "Composite" && mask.kind != MTSGPU_MASK_NONE) {
+		rd.r.fail("a Mask around a Composite is not supported");
+	} else if (rd.className() != "Composite") {
 		types.push_back(0); params.insert(params.end(), MTSGPU_BSDF_NPARAMS, 0.0f);
 		uint32_t slots = 0;
 		parseBSDFFields(rd, flags, &types.back(), &params[params.size() - MTSGPU_BSDF_NPARAMS], colorSlots ? &slots : NULL);
 		if (colorSlots) colorSlots->push_back(slots);
 		if (slotTextures) slotTextures->insert(slotTextures->end(), rd.slotTextures(), rd.slotTextures() + 2);
+		if (masks) masks->push_back(mask);
 		own = (int) types.size() - 1;
 	} else {
 		const uint64_t n = rd.r.readSize();
@@ -394,6 +432,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 			if (rd.r.ok() && rd.className() == "TwoSidedBRDF") { childFlags |= MTSGPU_BSDF_TWOSIDED; rd.enterNestedBSDF(); }
 			if (!rd.r.ok()) break;
 			if (rd.className() == "Composite") { rd.r.fail("Composite: nested composites are not supported"); break; }
+			if (masks && rd.className() == "Mask") { rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " is a Mask: a mask is the outermost adapter, not supported as a composite's child"); break; }
 			if (rd.className() == "Dielectric" || rd.className() == "Mirror") {
 				rd.r.fail("Composite: child " + rd.className() + " is a delta BSDF (a composite would need fDelta / pdfDelta): not supported"); break;
 			}
@@ -402,6 +441,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 			parseBSDFFields(rd, childFlags, &types.back(), &params[params.size() - MTSGPU_BSDF_NPARAMS], &slots);
 			if (colorSlots) colorSlots->push_back(0u);
 			if (slotTextures) slotTextures->insert(slotTextures->end(), 2, (int32_t) -1);
+			if (masks) masks->push_back(none);
 			if (rd.r.ok() && rd.hasSlotTexture()) { rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " (" + rd.className() + ") has a uv texture: a composite's children keep constant parameters, not supported"); break; }
 			if (rd.r.ok() && slots) { rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " (" + rd.className() + ") takes vertex colours: a composite's children keep constant parameters, not supported"); break; }
 			block[1 + n + i] = (float) (types.size() - 1);
@@ -410,6 +450,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 			types.push_back(MTSGPU_BSDF_COMPOSITE | flags);
 			if (colorSlots) colorSlots->push_back(0u);
 			if (slotTextures) slotTextures->insert(slotTextures->end(), 2, (int32_t) -1);
+			if (masks) masks->push_back(none);
 			params.insert(params.end(), block, block + MTSGPU_BSDF_NPARAMS);
 			own = (int) types.size() - 1;
 		}
@@ -418,6 +459,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 		types.resize(first); params.resize(first * MTSGPU_BSDF_NPARAMS);
 		if (colorSlots) colorSlots->resize(first);
 		if (slotTextures) slotTextures->resize(2 * first);
+		if (masks) masks->resize(first);
 		if (uvTextures) uvTextures->resize(firstTex);
 		if (bitmaps) bitmaps->resize(firstBmp);
 		if (err) *err = rd.r.error() + " (while reading a " + rd.className() + ")";

@@ -45,6 +45,8 @@ EXPORTS = [
     "mtsgpu_set_uv_bitmap_textures", "mtsgpu_group_set_uv_bitmap_textures", "mtsgpu_bitmap_texture_eval", "mtsgpu_ldr_texels",
     "mtsgpu_camera_rays",
 ]
+# the mask BSDF's entry points: an extension declared in include/mtsgpu_mask.h, next to the list of mtsgpu.h that ABI version 8 fixes
+MASK_EXPORTS = ["mtsgpu_set_uv_masked_textures", "mtsgpu_group_set_uv_masked_textures", "mtsgpu_bsdf_eval_masked"]
 
 
 class MtsGpuError(RuntimeError):
@@ -242,6 +244,10 @@ def lib():
     L.mtsgpu_set_uv_bitmap_textures.argtypes = [vp, f32p, u32p, C.c_uint32, texp, abi.i32p, C.c_uint32, bmpp, abi.i32p]
     L.mtsgpu_group_set_uv_bitmap_textures.argtypes = [vp, f32p, u32p, C.c_uint32, texp, abi.i32p, C.c_uint32, bmpp, abi.i32p]
     L.mtsgpu_bitmap_texture_eval.argtypes = [vp, texp, bmpp, C.c_uint32, u32p, f32p, f32p]
+    mskp = C.POINTER(abi.BsdfMask)
+    L.mtsgpu_set_uv_masked_textures.argtypes = [vp, f32p, u32p, C.c_uint32, texp, abi.i32p, C.c_uint32, bmpp, abi.i32p, mskp]
+    L.mtsgpu_group_set_uv_masked_textures.argtypes = [vp, f32p, u32p, C.c_uint32, texp, abi.i32p, C.c_uint32, bmpp, abi.i32p, mskp]
+    L.mtsgpu_bsdf_eval_masked.argtypes = [vp, C.c_uint32, f32p, f32p, C.c_int, C.c_uint32, f32p, f32p]
     L.mtsgpu_ldr_texels.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_float, f32p]
     _lib = L
     return L
@@ -249,6 +255,18 @@ def lib():
 
 def _f(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def bsdf_mask_array(masks):
+    """rows (kind, texture, opacity rgb) or abi.BsdfMask objects -> the ctypes array mtsgpu_set_uv_masked_textures takes"""
+    arr = (abi.BsdfMask * max(len(masks), 1))()
+    for i, m in enumerate(masks):
+        if isinstance(m, abi.BsdfMask):
+            arr[i] = m
+        else:
+            kind, tex, op = m
+            arr[i] = abi.BsdfMask(int(kind), int(tex), (C.c_float * 3)(*[float(x) for x in op]), 0)
+    return arr
 
 
 def uv_texture_array(textures):
@@ -346,6 +364,8 @@ class Scene:
         self.bitmaps = bitmap_array(self._bitmap_objects)
         table = np.asarray(getattr(description, "bsdf_slot_texture", []), dtype=np.int32).reshape(-1, 2)
         self.bsdf_slot_texture = np.ascontiguousarray(table) if (table >= 0).any() else None
+        # the masks around the BSDFs (none: the scene takes the texture calls as ever)
+        self.bsdf_mask = bsdf_mask_array(description.mask_table()) if getattr(description, "bsdf_masks", None) else None
 
     @property
     def sc(self):
@@ -376,6 +396,19 @@ class Scene:
         if ut is None or not self._bitmap_objects:
             return None
         return ut + (len(self._bitmap_objects), self.bitmaps, abi.ptr(self.texture_bitmap, abi.i32p))
+
+    def uv_masked_texture_args(self):
+        """what mtsgpu_set_uv_masked_textures takes for this scene: the nine arguments of mtsgpu_set_uv_bitmap_textures (slot
+        table, bitmaps and bitmap indices None where the scene has none) and bsdf_mask, or None when no BSDF of the scene has a
+        mask -- such a scene takes the two older calls"""
+        if self.bsdf_mask is None:
+            return None
+        uv = lib().mtsgpu_flat_scene_vertex_texcoords(self._h)
+        has = lib().mtsgpu_flat_scene_shape_has_texcoords(self._h)
+        nb, nt = len(self._bitmap_objects), len(getattr(self.description, "textures", []))
+        return (uv if uv else None, has if has else None, nt, self.textures if nt else None,
+                abi.ptr(self.bsdf_slot_texture, abi.i32p), nb, self.bitmaps if nb else None,
+                abi.ptr(self.texture_bitmap, abi.i32p) if nb else None, self.bsdf_mask)
 
     def vertex_tangents(self):
         """(pool [n_verts][6] float32 = dpdu, dpdv; flags [n_shapes] uint32) of the flat scene, or (None, None) when no mesh has
@@ -523,7 +556,10 @@ class MIPathTracer:
             self._chk(lib().mtsgpu_set_vertex_colors(self._ctx, *vc), "set_vertex_colors")
         ut = scene.uv_texture_args() if isinstance(scene, Scene) else None
         ub = scene.uv_bitmap_texture_args() if isinstance(scene, Scene) else None
-        if ub is not None:
+        um = scene.uv_masked_texture_args() if isinstance(scene, Scene) else None
+        if um is not None:
+            self._chk(lib().mtsgpu_set_uv_masked_textures(self._ctx, *um), "set_uv_masked_textures")
+        elif ub is not None:
             self._chk(lib().mtsgpu_set_uv_bitmap_textures(self._ctx, *ub), "set_uv_bitmap_textures")
         elif ut is not None:
             self._chk(lib().mtsgpu_set_uv_textures(self._ctx, *ut), "set_uv_textures")
@@ -733,6 +769,37 @@ class MIPathTracer:
                                                       abi.ptr(s, abi.i32p), 0 if bm is None else len(bitmaps), bm, abi.ptr(tb, abi.i32p)),
                   "set_uv_bitmap_textures")
 
+    def set_uv_masked_textures(self, vtx_uv=None, shape_has_uv=None, textures=None, bsdf_slot_texture=None, bitmaps=None, texture_bitmap=None,
+                               bsdf_mask=None):
+        """mtsgpu_set_uv_masked_textures on the uploaded scene: set_uv_bitmap_textures() with one mask per BSDF, rows (kind,
+        texture, opacity rgb) or abi.BsdfMask; all None switches masks and textures off"""
+        a = None if vtx_uv is None else np.ascontiguousarray(vtx_uv, dtype=np.float32)
+        b = None if shape_has_uv is None else np.ascontiguousarray(shape_has_uv, dtype=np.uint32)
+        if bitmaps is None and texture_bitmap is None and textures is not None:
+            bitmaps, texture_bitmap = bitmap_table(textures)
+        t = None if textures is None else uv_texture_array(textures)
+        s = None if bsdf_slot_texture is None else np.ascontiguousarray(bsdf_slot_texture, dtype=np.int32)
+        bm = None if not bitmaps else bitmap_array(bitmaps)
+        tb = None if texture_bitmap is None else np.ascontiguousarray(texture_bitmap, dtype=np.int32)
+        m = None if bsdf_mask is None else bsdf_mask_array(bsdf_mask)
+        self._chk(lib().mtsgpu_set_uv_masked_textures(self._ctx, abi.ptr(a, abi.f32p), abi.ptr(b, abi.u32p), 0 if t is None else len(t), t,
+                                                      abi.ptr(s, abi.i32p), 0 if bm is None else len(bitmaps), bm, abi.ptr(tb, abi.i32p), m),
+                  "set_uv_masked_textures")
+
+    def bsdf_eval_masked(self, bsdf_type, params, opacity, op, wi, aux):
+        """bsdf_eval() through the mask adapter whose opacity is the spectrum `opacity` (mtsgpu_bsdf_eval_masked) -> [n][8]"""
+        aux = np.atleast_2d(np.asarray(aux, dtype=np.float32))
+        n = aux.shape[0]
+        q = np.zeros((n, 6), dtype=np.float32)
+        q[:, :3] = np.asarray(wi, dtype=np.float32).reshape(-1, 3)
+        q[:, 3:3 + aux.shape[1]] = aux
+        P = np.zeros(abi.BSDF_NPARAMS, dtype=np.float32); P[:len(params)] = params
+        o = np.ascontiguousarray(np.broadcast_to(np.asarray(opacity, dtype=np.float32), (3,)))
+        out = np.zeros((n, 8), dtype=np.float32)
+        self._chk(lib().mtsgpu_bsdf_eval_masked(self._ctx, int(bsdf_type), abi.ptr(P, abi.f32p), abi.ptr(o, abi.f32p), int(op), n,
+                                                abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)), "bsdf_eval_masked")
+        return out
+
     def bitmap_texture_eval(self, texture, prim, rec, bitmap=None):
         """uv_texture_eval() for a scenes.BitmapTexture (or an abi.UvTexture of kind TEX_BITMAP with an abi.Bitmap)
         (mtsgpu_bitmap_texture_eval) -> [n][5] = uv, rgb"""
@@ -914,7 +981,10 @@ class DeviceGroup:
             self._chk(lib().mtsgpu_group_set_vertex_colors(self._g, *vc), "set_vertex_colors")
         ut = scene.uv_texture_args() if isinstance(scene, Scene) else None
         ub = scene.uv_bitmap_texture_args() if isinstance(scene, Scene) else None
-        if ub is not None:
+        um = scene.uv_masked_texture_args() if isinstance(scene, Scene) else None
+        if um is not None:
+            self._chk(lib().mtsgpu_group_set_uv_masked_textures(self._g, *um), "set_uv_masked_textures")
+        elif ub is not None:
             self._chk(lib().mtsgpu_group_set_uv_bitmap_textures(self._g, *ub), "set_uv_bitmap_textures")
         elif ut is not None:
             self._chk(lib().mtsgpu_group_set_uv_textures(self._g, *ut), "set_uv_textures")

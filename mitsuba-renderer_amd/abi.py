@@ -17,6 +17,7 @@ TEX_CHECKERBOARD, TEX_GRID = 0, 1
 TEX_BITMAP = 2
 WRAP_REPEAT, WRAP_CLAMP, WRAP_BLACK, WRAP_WHITE = 0, 1, 2, 3      # MTSGPU_WRAP_* (not the numbering of MIPMap::EWrapMode)
 BITMAP_MAX_TEXELS = 2147483647
+MASK_NONE, MASK_CONSTANT, MASK_TEXTURE = 0, 1, 2                    # MTSGPU_MASK_*
 LUM_AREA, LUM_CONSTANT, LUM_POINT, LUM_DIRECTIONAL, LUM_SPOT, LUM_ENVMAP, LUM_COLLIMATED, LUM_SKY = 0, 1, 2, 3, 4, 5, 6, 7
 LUM_NPARAMS = 32
 SKY_NDERIVED = 24
@@ -41,6 +42,11 @@ class UvTexture(C.Structure):
 class Bitmap(C.Structure):
     """mtsgpu_bitmap"""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("wrap_mode", C.c_uint32), ("reserved", C.c_uint32), ("texels", f32p)]
+
+
+class BsdfMask(C.Structure):
+    """mtsgpu_bsdf_mask"""
+    _fields_ = [("kind", C.c_uint32), ("texture", C.c_int32), ("opacity", C.c_float * 3), ("reserved", C.c_uint32)]
 
 
 class Scene(C.Structure):

@@ -96,6 +96,8 @@ struct mtsgpu_ctx {
 	// (empty = none), so that each of the two calls can refuse a slot the other one has taken
 	std::vector<void *> texAllocs;
 	mg::DTextures dtex{ nullptr, nullptr, nullptr, nullptr };
+	// mtsgpu_set_uv_masked_textures: DMasks' table, owned with the textures (texAllocs); NULL while no BSDF has a mask
+	mg::DMasks dmsk{ nullptr };
 	// mtsgpu_upload_scene_tangents: DTangents' arrays, owned with the scene (sceneAllocs); NULL, NULL without a tangent mesh
 	mg::DTangents dtan{ nullptr, nullptr };
 	std::vector<uint32_t> hostColorSlots;

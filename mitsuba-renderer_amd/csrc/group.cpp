@@ -438,7 +438,7 @@ int mtsgpu_group_set_vertex_colors(mtsgpu_group *g, const float *vtx_col, const 
 	               [](mtsgpu_ctx *c) { return mtsgpu_set_vertex_colors(c, nullptr, nullptr, nullptr); });
 }
 
-// both texture setters are undone by the first one without textures
+// the three texture setters are undone by the first one without textures
 static int clearUvTextures(mtsgpu_ctx *c) { return mtsgpu_set_uv_textures(c, nullptr, nullptr, 0, nullptr, nullptr); }
 
 int mtsgpu_group_set_uv_textures(mtsgpu_group *g, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
@@ -454,6 +454,15 @@ int mtsgpu_group_set_uv_bitmap_textures(mtsgpu_group *g, const float *vtx_uv, co
 	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
 	return forEach(g, "set_uv_bitmap_textures", [&](mtsgpu_ctx *c) {
 		return mtsgpu_set_uv_bitmap_textures(c, vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture, n_bitmaps, bitmaps, texture_bitmap); },
+	               clearUvTextures);
+}
+
+int mtsgpu_group_set_uv_masked_textures(mtsgpu_group *g, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
+                                        const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture, uint32_t n_bitmaps,
+                                        const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap, const mtsgpu_bsdf_mask *bsdf_mask) {
+	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
+	return forEach(g, "set_uv_masked_textures", [&](mtsgpu_ctx *c) {
+		return mtsgpu_set_uv_masked_textures(c, vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture, n_bitmaps, bitmaps, texture_bitmap, bsdf_mask); },
 	               clearUvTextures);
 }
 

@@ -1,6 +1,7 @@
 // host.h -- host-side pieces of libmtsgpu shared between translation units.
 #pragma once
 #include "../../include/mtsgpu.h"
+#include "../../include/mtsgpu_mask.h"
 #include "devmath.h"
 #include "kdtree.h"
 #include <cmath>
@@ -89,6 +90,33 @@ inline std::string checkBsdfSlotTextures(uint32_t n_bsdfs, const uint32_t *type,
 			if (slotTex[2 * (size_t) ch] >= 0 || slotTex[2 * (size_t) ch + 1] >= 0)
 				return msg(b, "composite child " + std::to_string(i) + " has a uv texture: a composite's children keep constant parameters, not supported");
 		}
+	}
+	return std::string();
+}
+
+// What mtsgpu_set_uv_masked_textures requires of the mask table [n_bsdfs] against a checked BSDF table: known kinds, zero
+// reserved words, finite opacities, texture indices inside the texture list, none on a composite or on a composite's child.
+// Returns the reason, or an empty string.
+inline std::string checkBsdfMasks(uint32_t n_bsdfs, const uint32_t *type, const float *params, const mtsgpu_bsdf_mask *mask, uint32_t n_textures) {
+	auto msg = [](uint32_t b, const std::string &what) { return "BSDF " + std::to_string(b) + ": " + what; };
+	for (uint32_t b = 0; b < n_bsdfs; ++b) {
+		const mtsgpu_bsdf_mask &m = mask[b];
+		if (m.kind > (uint32_t) MTSGPU_MASK_TEXTURE) return msg(b, "unknown mask kind " + std::to_string(m.kind));
+		if (m.reserved != 0) return msg(b, "the reserved word of its mask is not zero");
+		for (int k = 0; k < 3; ++k)
+			if (!(std::fabs(m.opacity[k]) <= 3.4028235e38f)) return msg(b, "the opacity of its mask is not finite");
+		if (m.kind == (uint32_t) MTSGPU_MASK_TEXTURE && (m.texture < 0 || m.texture >= (int64_t) n_textures))
+			return msg(b, "its mask names texture " + std::to_string(m.texture) + " of " + std::to_string(n_textures));
+		if (m.kind != (uint32_t) MTSGPU_MASK_NONE && (type[b] & 0xFFu) == MTSGPU_BSDF_COMPOSITE)
+			return msg(b, "a mask around a composite is not supported");
+	}
+	for (uint32_t b = 0; b < n_bsdfs; ++b) {
+		if ((type[b] & 0xFFu) != MTSGPU_BSDF_COMPOSITE) continue;
+		const float *P = params + (size_t) MTSGPU_BSDF_NPARAMS * b;
+		const int n = (int) P[0];
+		for (int i = 0; i < n; ++i)
+			if (mask[(uint32_t) P[1 + n + i]].kind != (uint32_t) MTSGPU_MASK_NONE)
+				return msg(b, "composite child " + std::to_string(i) + " has a mask: a mask is the outermost adapter (mask.cpp), not supported inside a composite");
 	}
 	return std::string();
 }

@@ -181,6 +181,20 @@ struct DTangents {
 	const uint32_t *shape_has_tan;
 };
 constexpr int kTriDpduStride = 3;     // float4 per primitive of DTangents::tri_dpdu
+// The mask adapters (mtsgpu_set_uv_masked_textures), NULL without one.  Like DTangents an argument of kernels of its own
+// (k_shade_msk, k_shade_all_msk) only, which read the uv arrays of DTextures for a textured opacity.  bsdf_mask[n_bsdfs]: the
+// opacity of the Mask around the BSDF (mask.cpp): none, a constant spectrum, or entry `texture` of DTextures::textures; non-NULL
+// only while some BSDF has one, and the shading launches pick the mask kernels by it
+struct DMask {
+	uint32_t kind;                          // kMaskNone, kMaskConstant, kMaskTexture = MTSGPU_MASK_*
+	int32_t  texture;                       // kMaskTexture: index into DTextures::textures
+	float    opacity[3];                    // kMaskConstant: the spectrum
+	uint32_t reserved;
+};
+struct DMasks {
+	const DMask *bsdf_mask;
+};
+constexpr uint32_t kMaskNone = 0, kMaskConstant = 1, kMaskTexture = 2;
 // what a texture slot of a BSDF takes at a hit (bsdf_block_with_slots)
 enum : int { kSlotBlock = 0, kSlotColor = 1, kSlotTexture = 2 };
 
@@ -424,6 +438,10 @@ void launch_vertex_color_eval(hipStream_t s, const float4 *tri_col, uint32_t n, 
 // color[3] (kSlotColor) or values[s][3] (kSlotTexture)
 void launch_bsdf_eval_slots(hipStream_t s, uint32_t type, const float *params, const int *source, const float *color, const float *values,
                             int op, uint32_t n, const float *queries, float *out);
+// mtsgpu_bsdf_eval_masked: the same read-out through BsdfMasked, the Mask adapter of the mask kernels, with the luminance of
+// opacity[3] formed on the device
+void launch_bsdf_eval_masked(hipStream_t s, uint32_t type, const float *params, const float *opacity, int op, uint32_t n,
+                             const float *queries, float *out);
 // mtsgpu_uv_texture_eval: its.uv (its_uv) and tex_eval of `tex` there for n records of the uploaded scene; rec [n][3] =
 // (u, v, -) on a triangle, the world-space hit point on a sphere; out [n][5] = uv, rgb
 void launch_uv_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, uint32_t n, const uint32_t *prim,
@@ -462,12 +480,14 @@ struct BinView { uint32_t prefix[kBinShards + 1]; };
 void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                   const DQueues &q, const BinView &view, const BinView *views_dev = nullptr, uint32_t n_bound = 0,
                   const uint32_t *bin_ids = nullptr, const DColors &col = DColors{ nullptr, nullptr },
-                  const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr });
+                  const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr },
+                  const DMasks &msk = DMasks{ nullptr });
 // device-driven bounces, path integrator / one-sample direct integrator: all bins of bin_mask in one launch; views_dev as
 // above, n_bound bounds the sum of the bin sizes
 void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,
                       const BinView *views_dev, uint32_t bin_mask, uint32_t n_bound, const DColors &col = DColors{ nullptr, nullptr },
-                      const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr });
+                      const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr },
+                      const DMasks &msk = DMasks{ nullptr });
 // device-driven bounces: per-bin views from the shard counters of the closest-hit launch that just ran (`cur`), and
 // the counter set of the next bounce zeroed
 void launch_prep(hipStream_t s, const uint32_t *cur, uint32_t *next_set, BinView *views_dev, uint32_t bin_seg_cap,

@@ -333,6 +333,20 @@ int mtsgpu_bsdf_eval_slots(mtsgpu_ctx *c, uint32_t bsdf_type, const float *param
 	return s.finish("BSDF read-out");
 }
 
+int mtsgpu_bsdf_eval_masked(mtsgpu_ctx *c, uint32_t bsdf_type, const float *params, const float opacity[3], int op, uint32_t n,
+                            const float *queries, float *out) {
+	if (!c || !params || !opacity || !queries || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (int rc = checkBsdfRequest(c, bsdf_type, op, "a mask around a composite is not supported")) return rc;
+	if (n == 0) return 0;
+	if (int rc = checkRecordCount(c, n)) return rc;
+	Scratch s(c);
+	const float *dQ = s.put(queries, (size_t) n * 6);
+	float *dOut = s.alloc<float>((size_t) n * 8);
+	if (s.ok()) launch_bsdf_eval_masked(c->stream, bsdf_type, params, opacity, op, n, dQ, dOut);
+	s.get(out, dOut, (size_t) n * 8);
+	return s.finish("BSDF read-out");
+}
+
 int mtsgpu_uv_texture_eval(mtsgpu_ctx *c, const mtsgpu_uv_texture *tex, uint32_t n, const uint32_t *prim, const float *rec, float *out) {
 	if (!c || !tex || !prim || !rec || !out) return fail(c, MTSGPU_EINVAL, "null argument");
 	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_uv_texture_eval before mtsgpu_upload_scene");

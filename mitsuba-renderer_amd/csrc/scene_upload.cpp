@@ -208,6 +208,7 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 	c->hostColorSlots.clear();
 	freeAll(c->texAllocs);        // ... and without uv textures (mtsgpu_set_uv_textures, mtsgpu_set_uv_bitmap_textures)
 	c->dtex = DTextures{ nullptr, nullptr, nullptr, nullptr };
+	c->dmsk = DMasks{ nullptr };
 	c->hostSlotTex.clear();
 	c->dtan = DTangents{ nullptr, nullptr };      // ... and its tangents go with the scene's arrays
 	c->haveScene = false;
@@ -462,6 +463,10 @@ static_assert(sizeof(mtsgpu_uv_texture) == sizeof(DTexture) && offsetof(mtsgpu_u
 static_assert(MTSGPU_TEX_CHECKERBOARD == (int) kTexCheckerboard && MTSGPU_TEX_GRID == (int) kTexGrid, "texture kinds differ");
 static_assert(MTSGPU_TEX_BITMAP == (int) kTexBitmap && offsetof(DTexture, width) == offsetof(mtsgpu_uv_texture, bright)
               && offsetof(DTexture, reserved) + sizeof(DTexture::reserved) == sizeof(DTexture), "the bitmap words are the seven behind vscale");
+static_assert(sizeof(mtsgpu_bsdf_mask) == sizeof(DMask) && offsetof(mtsgpu_bsdf_mask, opacity) == offsetof(DMask, opacity)
+              && offsetof(mtsgpu_bsdf_mask, texture) == offsetof(DMask, texture), "mtsgpu_bsdf_mask and DMask are one layout");
+static_assert(MTSGPU_MASK_NONE == (int) kMaskNone && MTSGPU_MASK_CONSTANT == (int) kMaskConstant && MTSGPU_MASK_TEXTURE == (int) kMaskTexture,
+              "mask kinds differ");
 static_assert(MTSGPU_WRAP_REPEAT == (int) kWrapRepeat && MTSGPU_WRAP_CLAMP == (int) kWrapClamp && MTSGPU_WRAP_BLACK == (int) kWrapBlack
               && MTSGPU_WRAP_WHITE == (int) kWrapWhite, "wrap modes differ");
 
@@ -473,11 +478,12 @@ static bool uvCastInRange(const mtsgpu_uv_texture &t, float u, float v, double s
 	return std::fabs(x) < lim && std::fabs(y) < lim;
 }
 
-// mtsgpu_set_uv_textures (withBitmaps = false: no bitmaps, and kind MTSGPU_TEX_BITMAP is unknown) and mtsgpu_set_uv_bitmap_textures
+// mtsgpu_set_uv_textures (withBitmaps = false: no bitmaps, and kind MTSGPU_TEX_BITMAP is unknown), mtsgpu_set_uv_bitmap_textures
+// and mtsgpu_set_uv_masked_textures (me: the caller's name; bsdf_mask: only the last one has a table)
 static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
                          const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture, uint32_t n_bitmaps,
-                         const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap, bool withBitmaps) {
-	const char *me = withBitmaps ? "mtsgpu_set_uv_bitmap_textures" : "mtsgpu_set_uv_textures";
+                         const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap, bool withBitmaps, const char *me,
+                         const mtsgpu_bsdf_mask *bsdf_mask = nullptr) {
 	if (!c) return fail(c, MTSGPU_EINVAL, "null argument");
 	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "%s before mtsgpu_upload_scene", me);
 	c->lastPass.valid = false;
@@ -487,8 +493,9 @@ static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *sha
 	if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
 	freeAll(c->texAllocs);
 	c->dtex = DTextures{ nullptr, nullptr, nullptr, nullptr };
+	c->dmsk = DMasks{ nullptr };
 	c->hostSlotTex.clear();
-	if (!vtx_uv && !shape_has_uv && !textures && !bsdf_slot_texture && !bitmaps && !texture_bitmap) return 0;
+	if (!vtx_uv && !shape_has_uv && !textures && !bsdf_slot_texture && !bitmaps && !texture_bitmap && !bsdf_mask) return 0;
 	if ((vtx_uv == nullptr) != (shape_has_uv == nullptr))
 		return fail(c, MTSGPU_EINVAL, "vtx_uv and shape_has_uv must both be given or both be NULL");
 	if (n_textures && !textures) return fail(c, MTSGPU_EINVAL, "n_textures without textures");
@@ -527,6 +534,32 @@ static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *sha
 		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
 		for (size_t i = 0; i < 2 * (size_t) nBsdfs; ++i) anySlot |= bsdf_slot_texture[i] >= 0;
 	}
+	bool anyMask = false, anyMaskTex = false;
+	if (bsdf_mask) {
+		const std::string why = checkBsdfMasks(nBsdfs, h.bsdfType.data(), h.bsdfParams.data(), bsdf_mask, n_textures);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+		for (uint32_t b = 0; b < nBsdfs; ++b) {
+			anyMask |= bsdf_mask[b].kind != (uint32_t) MTSGPU_MASK_NONE;
+			anyMaskTex |= bsdf_mask[b].kind == (uint32_t) MTSGPU_MASK_TEXTURE;
+		}
+	}
+	// the casts of texture k on shape s (s == nShapes: on no shape, at uv = 0); the reason, or an empty string
+	auto castRange = [&](uint32_t s, int32_t k, const std::vector<float> &triUv) -> std::string {
+		const size_t US = 4 * (size_t) kTriUvStride;
+		bool ok = true;
+		const bool bitmap = textures[k].kind == (uint32_t) MTSGPU_TEX_BITMAP;
+		const double sx = bitmap ? (double) desc[k].width : 2.0, sy = bitmap ? (double) desc[k].height : 2.0;
+		const bool mesh = s < nShapes && h.shapeType[s] == MTSGPU_SHAPE_TRIMESH, hasUv = s < nShapes && shape_has_uv && shape_has_uv[s];
+		if (s < nShapes && !mesh) ok = uvCastInRange(textures[k], 0.0f, 0.0f, sx, sy) && uvCastInRange(textures[k], 1.0f, 1.0f, sx, sy);
+		else if (!hasUv) ok = uvCastInRange(textures[k], 0.0f, 0.0f, sx, sy);
+		else
+			for (uint32_t t = h.shapeTriOffset[s]; ok && t < h.shapeTriOffset[s + 1]; ++t)
+				for (int v = 0; v < 3; ++v)
+					ok = ok && uvCastInRange(textures[k], triUv[US * (size_t) t + 2 * v], triUv[US * (size_t) t + 2 * v + 1], sx, sy);
+		if (ok) return std::string();
+		return "texture " + std::to_string(k) + " maps a texcoord outside the range of the (int) cast ("
+		       + (bitmap ? "|uv' * size|" : "|2 uv'|") + " >= 2^31 - 2^16)";
+	};
 	// the gather array: the texcoords of the three vertices of every primitive of a mesh that has them, zero elsewhere
 	const size_t US = 4 * (size_t) kTriUvStride;
 	std::vector<float> triUv(US * ((size_t) c->nTris + 1), 0.0f);
@@ -539,31 +572,39 @@ static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *sha
 			return fail(c, MTSGPU_EINVAL, "shape %u: non-finite texcoord at vertex %u", s, bad);
 		// the casts of the textures this shape is shaded with
 		const int32_t b = h.shapeBsdf[s];
-		if (b < 0 || !bsdf_slot_texture) continue;
-		for (int slot = 0; slot < 2; ++slot) {
+		if (b < 0) continue;
+		for (int slot = 0; bsdf_slot_texture && slot < 2; ++slot) {
 			const int32_t k = bsdf_slot_texture[2 * (size_t) b + slot];
 			if (k < 0) continue;
-			bool ok = true;
-			const bool bitmap = textures[k].kind == (uint32_t) MTSGPU_TEX_BITMAP;
-			const double sx = bitmap ? (double) desc[k].width : 2.0, sy = bitmap ? (double) desc[k].height : 2.0;
-			if (!mesh) ok = uvCastInRange(textures[k], 0.0f, 0.0f, sx, sy) && uvCastInRange(textures[k], 1.0f, 1.0f, sx, sy);
-			else if (!hasUv) ok = uvCastInRange(textures[k], 0.0f, 0.0f, sx, sy);
-			else
-				for (uint32_t t = h.shapeTriOffset[s]; ok && t < h.shapeTriOffset[s + 1]; ++t)
-					for (int v = 0; v < 3; ++v)
-						ok = ok && uvCastInRange(textures[k], triUv[US * (size_t) t + 2 * v], triUv[US * (size_t) t + 2 * v + 1], sx, sy);
-			if (!ok && bitmap)
-				return fail(c, MTSGPU_EINVAL, "shape %u: texture %d maps a texcoord outside the range of the (int) cast (|uv' * size| >= 2^31 - 2^16)", s, k);
-			if (!ok)
-				return fail(c, MTSGPU_EINVAL, "shape %u: texture %d maps a texcoord outside the range of the (int) cast (|2 uv'| >= 2^31 - 2^16)", s, k);
+			const std::string why = castRange(s, k, triUv);
+			if (!why.empty()) return fail(c, MTSGPU_EINVAL, "shape %u: %s", s, why.c_str());
+		}
+		// ... and of the texture its mask reads
+		if (bsdf_mask && bsdf_mask[b].kind == (uint32_t) MTSGPU_MASK_TEXTURE) {
+			const std::string why = castRange(s, bsdf_mask[b].texture, triUv);
+			if (!why.empty()) return fail(c, MTSGPU_EINVAL, "shape %u: BSDF %d: the opacity of its mask: %s", s, b, why.c_str());
 		}
 	}
-	if (!anySlot && !vtx_uv) return 0;       // nothing to keep
+	// a textured mask on a BSDF that no shape uses: the texture's offsets alone
+	if (anyMaskTex) {
+		std::vector<bool> used(nBsdfs, false);
+		for (uint32_t s = 0; s < nShapes; ++s)
+			if (h.shapeBsdf[s] >= 0) used[h.shapeBsdf[s]] = true;
+		for (uint32_t b = 0; b < nBsdfs; ++b) {
+			if (used[b] || bsdf_mask[b].kind != (uint32_t) MTSGPU_MASK_TEXTURE) continue;
+			const std::string why = castRange(nShapes, bsdf_mask[b].texture, triUv);
+			if (!why.empty()) return fail(c, MTSGPU_EINVAL, "BSDF %u: the opacity of its mask: %s", b, why.c_str());
+		}
+	}
+	if (!anySlot && !vtx_uv && !anyMask) return 0;       // nothing to keep
 	const float *dUv = nullptr, *dTexels = nullptr; const DTexture *dTex = nullptr; const int32_t *dSlots = nullptr;
 	int rc = upload(c, &dUv, triUv.data(), triUv.size(), &c->texAllocs);
-	if (!rc && anySlot) rc = upload(c, &dTex, desc.data(), n_textures, &c->texAllocs);
+	// (a mask keeps the textures and the bitmaps when no slot uses them)
+	if (!rc && (anySlot || anyMaskTex)) rc = upload(c, &dTex, desc.data(), n_textures, &c->texAllocs);
 	if (!rc && anySlot) rc = upload(c, &dSlots, bsdf_slot_texture, 2 * (size_t) nBsdfs, &c->texAllocs);
-	if (!rc && anySlot && anyBitmap) {
+	const DMask *dMask = nullptr;
+	if (!rc && anyMask) rc = upload(c, &dMask, reinterpret_cast<const DMask *>(bsdf_mask), nBsdfs, &c->texAllocs);
+	if (!rc && (anySlot || anyMaskTex) && anyBitmap) {
 		// the pool: the bitmaps one behind the other, 16 bytes per texel
 		std::vector<float> pool(4 * (size_t) nTexels);
 		for (uint32_t b = 0; b < n_bitmaps; ++b) packBitmapTexels(bitmaps[b], &pool[4 * (size_t) first[b]]);
@@ -571,19 +612,28 @@ static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *sha
 	}
 	if (rc) { freeAll(c->texAllocs); return rc; }
 	c->dtex = DTextures{ reinterpret_cast<const float4 *>(dUv), dTex, dSlots, reinterpret_cast<const float4 *>(dTexels) };
+	c->dmsk = DMasks{ dMask };
 	if (anySlot) c->hostSlotTex.assign(bsdf_slot_texture, bsdf_slot_texture + 2 * (size_t) nBsdfs);
 	return 0;
 }
 
 int mtsgpu_set_uv_textures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
                            const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture) {
-	return setUvTextures(c, vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture, 0, nullptr, nullptr, false);
+	return setUvTextures(c, vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture, 0, nullptr, nullptr, false, "mtsgpu_set_uv_textures");
 }
 
 int mtsgpu_set_uv_bitmap_textures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
                                   const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture, uint32_t n_bitmaps,
                                   const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap) {
-	return setUvTextures(c, vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture, n_bitmaps, bitmaps, texture_bitmap, true);
+	return setUvTextures(c, vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture, n_bitmaps, bitmaps, texture_bitmap, true,
+	                     "mtsgpu_set_uv_bitmap_textures");
+}
+
+int mtsgpu_set_uv_masked_textures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *shape_has_uv, uint32_t n_textures,
+                                  const mtsgpu_uv_texture *textures, const int32_t *bsdf_slot_texture, uint32_t n_bitmaps,
+                                  const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap, const mtsgpu_bsdf_mask *bsdf_mask) {
+	return setUvTextures(c, vtx_uv, shape_has_uv, n_textures, textures, bsdf_slot_texture, n_bitmaps, bitmaps, texture_bitmap, true,
+	                     "mtsgpu_set_uv_masked_textures", bsdf_mask);
 }
 
 // LDRTexture::initializeFrom (ldrtexture.cpp:116-202) and MIPMap::fromBitmap (mipmap.cpp:156-177)

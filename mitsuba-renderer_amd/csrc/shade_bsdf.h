@@ -1197,6 +1197,35 @@ template <int BT> struct Bsdf2 {
 	}
 };
 
+// Spectrum::getLuminance of an RGB build (spectrum.h:387-389)
+__device__ __forceinline__ float luminance(V3 c) {
+	return (c.x * 0.212671f + c.y * 0.715160f) + c.z * 0.072169f;
+}
+// Mask adapter (src/bsdfs/mask.cpp:73-161) around Bsdf2<BT>, typeMask = EAll and component = -1: with probability p =
+// opacity.getLuminance() the nested BSDF, otherwise the ray passes straight through as a delta transmission.  Nothing clamps p;
+// p == 0 with sx == 0 divides 0 by 0 as the reference does.  The mask kernels (k_shade_msk, k_shade_all_msk) and the read-out
+// hook (k_bsdf_eval_masked) both call this.
+template <int BT> struct BsdfMasked {
+	static __device__ __forceinline__ V3 f(const BsdfTable &tab, bool two, const float *P, float p, V3 wi, V3 wo) {
+		return Bsdf2<BT>::f(tab, two, P, wi, wo) * p;
+	}
+	static __device__ __forceinline__ float pdf(const BsdfTable &tab, bool two, const float *P, float p, V3 wi, V3 wo) {
+		return Bsdf2<BT>::pdf(tab, two, P, wi, wo) * p;
+	}
+	static __device__ __forceinline__ V3 sample(const BsdfTable &tab, bool two, const float *P, float p, V3 wi, float sx, float sy, V3 &wo, float &pdf,
+	                                            uint32_t &st) {
+		if (sx <= p) {
+			const V3 result = Bsdf2<BT>::sample(tab, two, P, wi, sx / p, sy, wo, pdf, st) * p;
+			pdf *= p;
+			return result;
+		}
+		wo = V3(-wi.x, -wi.y, -wi.z);
+		st = T_DELTA_TRANS;
+		pdf = (1 - p) * fabsf(wo.z);
+		return V3(1 - p, 1 - p, 1 - p);
+	}
+};
+
 __device__ __forceinline__ float mi_weight(float pdfA, float pdfB) {     // path.cpp:218-222
 	pdfA *= pdfA;
 	pdfB *= pdfB;

@@ -133,6 +133,44 @@ __global__ void k_bsdf_eval_slots(uint32_t type, BsdfParams params, SlotValues s
 	#pragma unroll
 	for (int k = 0; k < 8; ++k) out[8 * (size_t) i + k] = o[k];
 }
+// mtsgpu_bsdf_eval_masked: k_bsdf_eval through BsdfMasked, p = the luminance of the opacity (luminance)
+template <int BT>
+__device__ __forceinline__ void bsdf_eval_masked_one(bool two, const float *P, float p, int op, const float *q, float *o) {
+	const BsdfTable tab{ nullptr, nullptr };
+	const V3 wi(q[0], q[1], q[2]);
+	if (op == 0) {
+		const V3 f = BsdfMasked<BT>::f(tab, two, P, p, wi, V3(q[3], q[4], q[5]));
+		o[0] = f.x; o[1] = f.y; o[2] = f.z;
+	} else if (op == 1) {
+		o[0] = BsdfMasked<BT>::pdf(tab, two, P, p, wi, V3(q[3], q[4], q[5]));
+	} else {
+		V3 wo; float pdf; uint32_t st;
+		const V3 f = BsdfMasked<BT>::sample(tab, two, P, p, wi, q[3], q[4], wo, pdf, st);
+		o[0] = wo.x; o[1] = wo.y; o[2] = wo.z; o[3] = pdf; o[4] = f.x; o[5] = f.y; o[6] = f.z; o[7] = __uint_as_float(st);
+	}
+}
+__global__ void k_bsdf_eval_masked(uint32_t type, BsdfParams params, float cr, float cg, float cb, int op, uint32_t n, const float *queries,
+                                   float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const bool two = (type & 0x100u) != 0;
+	const float *P = params.v, *q = queries + 6 * (size_t) i;
+	const float p = luminance(V3(cr, cg, cb));
+	float o[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+	switch (type & 0xFFu) {
+		case 0: bsdf_eval_masked_one<0>(two, P, p, op, q, o); break;
+		case 1: bsdf_eval_masked_one<1>(two, P, p, op, q, o); break;
+		case 2: bsdf_eval_masked_one<2>(two, P, p, op, q, o); break;
+		case 3: bsdf_eval_masked_one<3>(two, P, p, op, q, o); break;
+		case 4: bsdf_eval_masked_one<4>(two, P, p, op, q, o); break;
+		case 5: bsdf_eval_masked_one<5>(two, P, p, op, q, o); break;
+		case 6: bsdf_eval_masked_one<6>(two, P, p, op, q, o); break;
+		case 7: bsdf_eval_masked_one<7>(two, P, p, op, q, o); break;
+		default: bsdf_eval_masked_one<8>(two, P, p, op, q, o); break;
+	}
+	#pragma unroll
+	for (int k = 0; k < 8; ++k) out[8 * (size_t) i + k] = o[k];
+}
 // mtsgpu_uv_texture_eval: its_uv and tex_eval for n records; the host has checked prim < n_tris
 __global__ void k_uv_texture_eval(DScene sc, const float4 *tri_uv, DTexture tex, uint32_t n, const uint32_t *prim, const float *rec, float *out) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -268,6 +306,13 @@ void launch_bsdf_eval_slots(hipStream_t s, uint32_t type, const float *params, c
 	for (int k = 0; k < 3; ++k) sv.color[k] = color[k];
 	for (int k = 0; k < 6; ++k) sv.val[k / 3][k % 3] = values[k];
 	if (n) hipLaunchKernelGGL(k_bsdf_eval_slots, dim3(blocks_for(n, 256)), dim3(256), 0, s, type, p, sv, op, n, queries, out);
+}
+
+void launch_bsdf_eval_masked(hipStream_t s, uint32_t type, const float *params, const float *opacity, int op, uint32_t n,
+                             const float *queries, float *out) {
+	BsdfParams p;
+	for (int k = 0; k < kBsdfNParams; ++k) p.v[k] = params[k];
+	if (n) hipLaunchKernelGGL(k_bsdf_eval_masked, dim3(blocks_for(n, 256)), dim3(256), 0, s, type, p, opacity[0], opacity[1], opacity[2], op, n, queries, out);
 }
 
 void launch_uv_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, uint32_t n, const uint32_t *prim,

@@ -1,5 +1,5 @@
-// shade_path.h -- K3+K5: one iteration of MIPathTracer::Li per material queue, and the kernel templates of the four families
-// (k_shade*, k_shade_all*).  Each family is instantiated by the unit that launches it: shade_plain / _vcol / _tex / _tan.hip.
+// shade_path.h -- K3+K5: one iteration of MIPathTracer::Li per material queue, and the kernel templates of the five families
+// (k_shade*, k_shade_all*).  Each family is instantiated by the unit that launches it: shade_plain / _vcol / _tex / _tan / _mask.hip.
 #pragma once
 #include "shade_bsdf.h"
 
@@ -36,11 +36,14 @@ __device__ __forceinline__ uint32_t shade_row_index(uint32_t lane, uint32_t k) {
 // (DTextures::bsdf_slot_texture != NULL), which serves coloured slots as well: bsdf_block_with_slots.  Every other scene
 // (kSlotBlock) runs the instantiation without that code.  TAN: the instantiation for scenes with a tangent mesh
 // (DTangents::tri_dpdu != NULL), on top of kSlotTexture: the record comes from fill_its_tan, and the texture table may be NULL.
-template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false>
+// MSK: the instantiation for scenes with a mask adapter (DMasks::bsdf_mask != NULL), on top of TAN: the BSDF is evaluated through
+// BsdfMasked with the opacity's luminance at the hit, and the tangent table may be NULL as well.
+template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false>
 __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, const DConfig &cfg, const uint32_t id,
                                            const float4 ro, const float4 rd, const uint4 h, const float4 T4, const float4 L4,
                                            const ShadeRow row, bool &continues, bool &wantShadow, V3 &neeV, V3 &shO, V3 &shD, const DColors &col,
-                                           const DTextures &tex, const DTangents &tan = DTangents{ nullptr, nullptr }) {
+                                           const DTextures &tex, const DTangents &tan = DTangents{ nullptr, nullptr },
+                                           const DMasks &msk = DMasks{ nullptr }) {
 	{
 		// rounds of MIDirectIntegrator (DConfig::dr_mode): later BSDF samples start again from the camera hit
 		const int mode = ROUNDS ? cfg.dr_mode : 0;
@@ -67,7 +70,8 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 		const bool settled = !ROUNDS && cfg.miss_settled && !direct;
 		Its its;
 		if (valid) {
-			if (TAN) fill_its_tan(sc, tan, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
+			// (a scene that is here for its masks alone has no tangent table)
+			if (TAN && !(MSK && tan.shape_has_tan == nullptr)) fill_its_tan(sc, tan, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
 			else fill_its(sc, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
 		}
 		const int shapeLum = valid ? sc.shape_lum[its.shape] : -1;
@@ -150,6 +154,8 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			const int bsdfIdx = sc.shape_bsdf[its.shape];
 			const float *BP = sc.bsdf_params + 16 * (size_t) bsdfIdx;
 			float colouredBlock[kBsdfNParams];
+			// mask kernels: the Mask around this BSDF, p = opacity.getLuminance() at the hit, 1 without one (what BsdfMasked takes)
+			float maskP = 1.0f;
 			if (VCOL == kSlotTexture && BT < 9) {
 				// a checkerboard, a grid texture or a bitmap in a slot of this BSDF: that slot holds the texture's value at its.uv; a
 				// `vertexcolors` texture in the other one its.color
@@ -158,8 +164,13 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				const int k0 = noTex ? -1 : tex.bsdf_slot_texture[2 * (size_t) bsdfIdx], k1 = noTex ? -1 : tex.bsdf_slot_texture[2 * (size_t) bsdfIdx + 1];
 				const uint32_t slots = col.bsdf_color_slots ? col.bsdf_color_slots[bsdfIdx] : 0u;
 				float uvx = 0, uvy = 0;
-				if (k0 >= 0 || k1 >= 0)
+				// (mask kernels: the opacity first, with its.uv computed once for the mask and the slots)
+				DMask m{ kMaskNone, -1, { 0, 0, 0 }, 0u };
+				if (MSK) m = msk.bsdf_mask[bsdfIdx];
+				if (k0 >= 0 || k1 >= 0 || (MSK && m.kind == kMaskTexture))
 					its_uv(sc, tex.tri_uv, h.w, its.shape, __uint_as_float(h.y), __uint_as_float(h.z), its.p, uvx, uvy);
+				if (MSK && m.kind == kMaskConstant) maskP = luminance(V3(m.opacity[0], m.opacity[1], m.opacity[2]));
+				else if (MSK && m.kind == kMaskTexture) maskP = luminance(tex_eval(tex.textures[m.texture], tex.texels, uvx, uvy));
 				// one slot after the other, so that only one value is alive next to the block
 				const V3 zero(0, 0, 0);
 				bsdf_block_with_slots<BT>(BP, kSlotBlock, kSlotBlock, zero, zero, zero, colouredBlock);
@@ -209,12 +220,12 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				if ((!direct || cfg.n_lum > 0) && sample_luminaire<SKY>(sc, its.p, s0, s1, lRec)) {
 					const V3 wo = -lRec.d;
 					const V3 woL(dot(wo, its.shS), dot(wo, its.shT), dot(wo, its.shN));
-					V3 bsdfVal = Bsdf2<BT>::f(tab, twoSided, BP, its.wi, woL) * fabsf(woL.z);
+					V3 bsdfVal = (MSK ? BsdfMasked<BT>::f(tab, twoSided, BP, maskP, its.wi, woL) : Bsdf2<BT>::f(tab, twoSided, BP, its.wi, woL)) * fabsf(woL.z);
 					const float woDotGeoN = dot(its.geoN, wo);
 					if (!isZero(bsdfVal) && (!strict || woDotGeoN * woL.z > 0)) {
 						// isIntersectable() || isBackgroundLuminaire() (path.cpp:118-120): 0 for delta luminaires
 						const uint32_t lt = sc.lum_type[lRec.lum];      // area, constant, envmap and sky luminaires can be hit by BSDF samples
-						const float bsdfPdf = (lt <= 1u || lt == 5u || (SKY && lt == 7u)) ? Bsdf2<BT>::pdf(tab, twoSided, BP, its.wi, woL) : 0.0f;
+						const float bsdfPdf = (lt <= 1u || lt == 5u || (SKY && lt == 7u)) ? (MSK ? BsdfMasked<BT>::pdf(tab, twoSided, BP, maskP, its.wi, woL) : Bsdf2<BT>::pdf(tab, twoSided, BP, its.wi, woL)) : 0.0f;
 						const float weight = direct ? mi_weight(lRec.pdf * cfg.frac_lum, bsdfPdf * cfg.frac_bsdf) * cfg.weight_lum
 						                            : mi_weight(lRec.pdf, bsdfPdf);          // direct.cpp:143-145
 						// added to Li iff the segment is unoccluded: parked in the record by shade_block and cancelled by
@@ -239,7 +250,8 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			if (direct && cfg.n_bsdf <= 0)
 				break;                                      // the sample is drawn even when it is not used (direct.cpp:156-161)
 			V3 woL; float bsdfPdf; uint32_t sampledType;
-			V3 bsdfVal = Bsdf2<BT>::sample(tab, twoSided, BP, its.wi, s0, s1, woL, bsdfPdf, sampledType);
+			V3 bsdfVal = MSK ? BsdfMasked<BT>::sample(tab, twoSided, BP, maskP, its.wi, s0, s1, woL, bsdfPdf, sampledType)
+			                 : Bsdf2<BT>::sample(tab, twoSided, BP, its.wi, s0, s1, woL, bsdfPdf, sampledType);
 			if (!isZero(bsdfVal))
 				bsdfVal = bsdfVal * fabsf(woL.z);          // sampleCos (bsdf.h:273-279)
 			if (isZero(bsdfVal))
@@ -284,10 +296,11 @@ struct ShadeShared {
 };
 // One workgroup of k_shade: the paths block * kShadeBlock .. of the material queue whose segment sizes are `prefix`
 // (prefix[kBinShards] entries in kBinShards segments of bin_ids)
-template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false>
+template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false>
 __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const uint32_t *prefix,
                                             const uint32_t *bin_ids, const uint32_t block, ShadeShared &sh, const DColors &col,
-                                            const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr }) {
+                                            const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr },
+                                            const DMasks &msk = DMasks{ nullptr }) {
 	uint32_t (&s_cnt)[2][kShadeBlock / 64] = sh.cnt;
 	uint32_t (&s_base)[2] = sh.base;
 	float4 (&s_rows)[kShadeBlock / 64][64 * kRowStride] = sh.rows;
@@ -373,7 +386,7 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	}
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	if (active)
-		shade_path<BT, ROUNDS, SKY, VCOL, TAN>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col, tex, tan);
+		shade_path<BT, ROUNDS, SKY, VCOL, TAN, MSK>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col, tex, tan, msk);
 	// the pending direct-light term is parked in the record with the write-back below (the line is written whole anyway):
 	// the any-hit kernel clears the slot if the shadow ray is occluded, the record's next reader adds what is still there
 	if (q.nee_parked && wantShadow) row[2] = make_float4(neeV.x, neeV.y, neeV.z, __uint_as_float(kNeeTag));
@@ -454,6 +467,15 @@ __global__ MG_SHADE_BOUNDS void k_shade_tan(DScene sc, DPaths ps, DConfig cfg, D
 	__shared__ ShadeShared sh;
 	shade_block<BT, ROUNDS, SKY, kSlotTexture, true>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col, tex, tan);
 }
+// and for scenes with a mask adapter (DMasks), built on the tangent kernels: the only ones that take the masks.  Bins 0..8: a
+// composite takes no mask.  Any of the colour, texture-slot and tangent tables may be NULL here
+template <int BT, bool ROUNDS, bool SKY>
+__global__ MG_SHADE_BOUNDS void k_shade_msk(DScene sc, DPaths ps, DConfig cfg, DQueues q, BinView view_host,
+                                                           const BinView *views_dev, const uint32_t *bin_ids, DColors col, DTextures tex, DTangents tan,
+                                                           DMasks msk) {
+	__shared__ ShadeShared sh;
+	shade_block<BT, ROUNDS, SKY, kSlotTexture, true, true>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col, tex, tan, msk);
+}
 
 // All material queues of a bounce in ONE launch (device-driven bounces): the workgroups are dealt to the bins in bin order,
 // ceil(size / kShadeBlock) each, the sizes read from what k_prep left in device memory.  A frame of few paths is a chain of
@@ -462,10 +484,10 @@ __global__ MG_SHADE_BOUNDS void k_shade_tan(DScene sc, DPaths ps, DConfig cfg, D
 // SKY: the launch for scenes whose background is a sky (launch_shade_all picks it): every other scene runs the instantiation
 // without that code, whose registers are what they were before the sky existed.  VCOL: likewise for scenes with a coloured
 // BSDF slot; the bins that cannot have one (composite, terminal) run the same code either way
-template <bool SKY, int VCOL, bool TAN = false>
+template <bool SKY, int VCOL, bool TAN = false, bool MSK = false>
 __device__ __forceinline__ void shade_all(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const BinView *views_dev, uint32_t bin_mask,
                                           ShadeShared &sh, const DColors &col, const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr },
-                                          const DTangents &tan = DTangents{ nullptr, nullptr }) {
+                                          const DTangents &tan = DTangents{ nullptr, nullptr }, const DMasks &msk = DMasks{ nullptr }) {
 	uint32_t block = blockIdx.x;
 	int bin = -1;
 	for (int b = 0; b < kNumBins; ++b) {
@@ -477,15 +499,15 @@ __device__ __forceinline__ void shade_all(const DScene &sc, const DPaths &ps, co
 	if (bin < 0) return;
 	const uint32_t *prefix = views_dev[bin].prefix, *ids = q.bin(bin);
 	switch (bin) {
-		case 0: shade_block<0, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
-		case 1: shade_block<1, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
-		case 2: shade_block<2, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
-		case 3: shade_block<3, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
-		case 4: shade_block<4, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
-		case 5: shade_block<5, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
-		case 6: shade_block<6, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
-		case 7: shade_block<7, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
-		case 8: shade_block<8, false, SKY, VCOL, TAN>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan); break;
+		case 0: shade_block<0, false, SKY, VCOL, TAN, MSK>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan, msk); break;
+		case 1: shade_block<1, false, SKY, VCOL, TAN, MSK>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan, msk); break;
+		case 2: shade_block<2, false, SKY, VCOL, TAN, MSK>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan, msk); break;
+		case 3: shade_block<3, false, SKY, VCOL, TAN, MSK>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan, msk); break;
+		case 4: shade_block<4, false, SKY, VCOL, TAN, MSK>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan, msk); break;
+		case 5: shade_block<5, false, SKY, VCOL, TAN, MSK>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan, msk); break;
+		case 6: shade_block<6, false, SKY, VCOL, TAN, MSK>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan, msk); break;
+		case 7: shade_block<7, false, SKY, VCOL, TAN, MSK>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan, msk); break;
+		case 8: shade_block<8, false, SKY, VCOL, TAN, MSK>(sc, ps, cfg, q, prefix, ids, block, sh, col, tex, tan, msk); break;
 		case 9: return;      // the composite's loop over its children is launched on its own (kShadeAllBins)
 		default: shade_block<kNumBsdfTypes, false, SKY, kSlotBlock>(sc, ps, cfg, q, prefix, ids, block, sh, col); break;
 	}
@@ -511,6 +533,12 @@ __global__ MG_SHADE_BOUNDS void k_shade_all_tan(DScene sc, DPaths ps, DConfig cf
                                                 DTextures tex, DTangents tan) {
 	__shared__ ShadeShared sh;
 	shade_all<SKY, kSlotTexture, true>(sc, ps, cfg, q, views_dev, bin_mask, sh, col, tex, tan);
+}
+template <bool SKY>
+__global__ MG_SHADE_BOUNDS void k_shade_all_msk(DScene sc, DPaths ps, DConfig cfg, DQueues q, const BinView *views_dev, uint32_t bin_mask, DColors col,
+                                                DTextures tex, DTangents tan, DMasks msk) {
+	__shared__ ShadeShared sh;
+	shade_all<SKY, kSlotTexture, true, true>(sc, ps, cfg, q, views_dev, bin_mask, sh, col, tex, tan, msk);
 }
 
 } // namespace mg

@@ -168,6 +168,7 @@ class SceneDescription:
         self.textures = []          # the Checkerboard / GridTexture / BitmapTexture objects in use (what mtsgpu_set_uv_textures takes)
         self.bsdf_slot_texture = [] # per BSDF: [index into textures or -1] for its two texture slots
         self._slot_textures = ()
+        self.bsdf_masks = {}        # BSDF index -> the opacity of the mask around it: an RGB triple or an entry of textures
         self.lum_type = []
         self.lum_params = []
         self.camera = dict(origin=(0.0, 1.0, 3.4), target=(0.0, 1.0, 0.0), up=(0.0, 1.0, 0.0), fov=39.3)
@@ -298,6 +299,43 @@ class SceneDescription:
         """wrap an existing BSDF block in the `twosided` adapter (src/bsdfs/twosided.cpp)"""
         self.bsdf_type[bsdf] |= abi.BSDF_TWOSIDED
         return bsdf
+
+    def mask(self, bsdf, opacity=0.5):
+        """wrap an existing BSDF block in the `mask` adapter (src/bsdfs/mask.cpp): opacity is a grey level, an RGB triple or a
+        Checkerboard / GridTexture / BitmapTexture.  The mask is the outermost adapter: call it last, after twosided()"""
+        if opacity is VERTEX_COLORS:
+            raise ValueError("mask: vertex colours as opacity are not supported")
+        if bsdf in self.bsdf_masks:
+            raise ValueError("mask: BSDF %d has a mask already, nested masks are not supported" % bsdf)
+        if self.bsdf_type[bsdf] & 0xFF == abi.BSDF_COMPOSITE:
+            raise ValueError("mask: a mask around a composite is not supported")
+        for b, t in enumerate(self.bsdf_type):
+            n = int(self.bsdf_params[b][0])
+            if t & 0xFF == abi.BSDF_COMPOSITE and bsdf in [int(c) for c in self.bsdf_params[b][1 + n:1 + 2 * n]]:
+                raise ValueError("mask: BSDF %d is a child of composite %d, a mask inside a composite is not supported" % (bsdf, b))
+        if isinstance(opacity, _UvTexture):
+            if not any(opacity is u for u in self.textures):
+                self.textures.append(opacity)
+        else:
+            opacity = np.array(_rgb(opacity), dtype=np.float32)
+            if not np.isfinite(opacity).all():
+                raise ValueError("mask: the opacity is not finite")
+        self.bsdf_masks[int(bsdf)] = opacity
+        return bsdf
+
+    def mask_table(self):
+        """one (kind, texture index, opacity rgb) per BSDF: what mtsgpu_bsdf_mask holds; a textured mask's three floats are the
+        texture's getAverage()"""
+        rows = []
+        for b in range(len(self.bsdf_type)):
+            o = self.bsdf_masks.get(b)
+            if o is None:
+                rows.append((abi.MASK_NONE, -1, [F(0), F(0), F(0)]))
+            elif isinstance(o, _UvTexture):
+                rows.append((abi.MASK_TEXTURE, [i for i, u in enumerate(self.textures) if u is o][0], _rgb(o.average())))
+            else:
+                rows.append((abi.MASK_CONSTANT, -1, _rgb(o)))
+        return rows
 
     def point_light(self, position, intensity):
         l = self.add_lum(abi.LUM_POINT, [intensity] * 3 if np.isscalar(intensity) else intensity)

@@ -41,6 +41,7 @@
 #include <mitsuba/core/sched.h>
 #include <mtsgpu.h>
 #include <mtsgpu_mask.h>
+#include <mtsgpu_snow.h>
 #include "streamparse.h"
 #include <sstream>
 #include <cstdlib>
@@ -141,6 +142,15 @@ struct FlatScene {
 	/* per BSDF table entry the opacity of the `mask` adapter around it (none, a constant, one of uvTextures): what
 	 * mtsgpu_group_set_uv_masked_textures takes on top */
 	std::vector<mtsgpu_bsdf_mask> bsdfMasks;
+	/* per BSDF table entry the snow record of a `wiscombe` in place of it (none: MTSGPU_SNOW_NONE): what
+	 * mtsgpu_group_set_snow_bsdfs takes */
+	std::vector<mtsgpu_bsdf_snow> bsdfSnow;
+	/* after upload() and the colour and texture calls: hands the snow table over when a BSDF has a record */
+	int setSnowBsdfs(mtsgpu_group *group) const {
+		for (size_t b = 0; b < bsdfSnow.size(); ++b)
+			if (bsdfSnow[b].kind != MTSGPU_SNOW_NONE) return mtsgpu_group_set_snow_bsdfs(group, ptr(bsdfSnow));
+		return MTSGPU_OK;
+	}
 	/* vertex tangents (TriMesh::getVertexTangents, trimesh.h:136-140: TriMesh::configure computes them for a mesh whose BSDF is
 	 * anisotropic, trimesh.cpp:288-290): dpdu in the order of vtxPos, one flag per shape -- what
 	 * mtsgpu_group_upload_scene_tangents takes */
@@ -489,7 +499,7 @@ private:
 		std::string err;
 		const size_t firstEntry = bsdfType.size(), firstLdr = ldrTextures.size();
 		const int index = mtsgpu_stream::parseBSDFTable<Float>(st->getData(), st->getSize(), bsdfType, bsdfParams, &err, &bsdfColorSlots, &uvTextures, &bsdfSlotTexture,
-			&ldrTextures, &bsdfMasks);
+			&ldrTextures, &bsdfMasks, &bsdfSnow, &mtsgpu_wiscombe_configure);
 		if (index < 0)
 			SLog(EError, "gpupath: %s", err.c_str());
 		for (size_t k = firstLdr; k < ldrTextures.size(); ++k)
@@ -550,6 +560,7 @@ struct GPURenderDriver {
 			check(flat.upload(group));
 			check(flat.setVertexColors(group));
 			check(flat.setUvTextures(group));
+			check(flat.setSnowBsdfs(group));
 		}
 
 		/* --- camera: raster space of the FULL film, crop window as offset + size (perspective.cpp:43-71, film.cpp:33-41) --- */

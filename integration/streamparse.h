@@ -17,6 +17,7 @@
 
 #include <mtsgpu.h>
 #include <mtsgpu_mask.h>
+#include <mtsgpu_snow.h>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -382,11 +383,27 @@ template <typename FloatT> inline bool parseBSDF(const uint8_t *data, size_t siz
  * Refused with the reason: a Mask inside a Mask, under TwoSidedBRDF (twosided.cpp:71-73 refuses that child too), around a
  * Composite or as a composite's child, and a VertexColors opacity.  Without the list a Mask is refused like every class that is
  * not on this path. */
+/* snow (optional) + wiscombeConfigure: one mtsgpu_bsdf_snow per appended entry, next to `types` (what mtsgpu_set_snow_bsdfs
+ * takes).  With the list a Wiscombe (wiscombe.cpp:172-179: g, depth, w0, sigmaT after BSDF::serialize's own fields) becomes a
+ * Lambertian entry whose block is zero, with the record wiscombeConfigure -- the library's mtsgpu_wiscombe_configure -- makes
+ * of the four fields; twosided(Wiscombe) sets the bit; every other entry receives MTSGPU_SNOW_NONE.  Refused with the reason: a
+ * Wiscombe whose derived values are not finite, under a Mask or as a composite's child, and every HanrahanKrueger: its stream
+ * holds the size multiplier and the two sigmas alone (hanrahan-krueger.cpp:225-230), not g, the two indices, the two factors
+ * and the flag.  Without the list both are refused like every class that is not on this path. */
+typedef int (*WiscombeConfigure)(const float raw[8], mtsgpu_bsdf_snow *out);
+inline std::string hkRefusal() {
+	return "HanrahanKrueger: its stream holds only sizeMultiplier, sigmaA and sigmaS (hanrahan-krueger.cpp:225-230) and its unserialising "
+	       "constructor reads nothing, so g, etaInt, etaExt, ssFactor, drFactor and diffuseReflectance are out of reach: the BRDF is served "
+	       "through the C ABI (mtsgpu_hk_configure, mtsgpu_set_snow_bsdfs) only";
+}
 template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t size, std::vector<uint32_t> &types, std::vector<float> &params,
                                                      std::string *err, std::vector<uint32_t> *colorSlots = NULL,
                                                      std::vector<mtsgpu_uv_texture> *uvTextures = NULL, std::vector<int32_t> *slotTextures = NULL,
-                                                     std::vector<LdrTexture> *bitmaps = NULL, std::vector<mtsgpu_bsdf_mask> *masks = NULL) {
+                                                     std::vector<LdrTexture> *bitmaps = NULL, std::vector<mtsgpu_bsdf_mask> *masks = NULL,
+                                                     std::vector<mtsgpu_bsdf_snow> *snow = NULL, WiscombeConfigure wiscombeConfigure = NULL) {
 	BSDFStream<FloatT> rd(data, size);
+	mtsgpu_bsdf_snow noSnow;
+	memset(&noSnow, 0, sizeof(noSnow)); noSnow.kind = MTSGPU_SNOW_NONE;
 	const size_t first = types.size(), firstTex = uvTextures ? uvTextures->size() : 0, firstBmp = bitmaps ? bitmaps->size() : 0;
 	if (uvTextures && slotTextures) rd.takeUvTextures(uvTextures);
 	if (uvTextures && slotTextures && bitmaps) rd.takeBitmaps(bitmaps);
@@ -409,6 +426,29 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 		/* the mask or an adapter could not be opened */
 	} else if (rd.className() == "Composite" && mask.kind != MTSGPU_MASK_NONE) {
 		rd.r.fail("a Mask around a Composite is not supported");
+	} else if (snow && rd.className() == "HanrahanKrueger") {
+		rd.r.fail(hkRefusal());
+	} else if (snow && rd.className() == "Wiscombe") {
+		float raw[8];
+		raw[0] = (float) rd.r.readFloat(); raw[1] = (float) rd.r.readFloat();            /* m_g, m_depth */
+		rd.r.readSpectrum(raw + 2); rd.r.readSpectrum(raw + 5);                          /* m_w0, m_sigmaT */
+		mtsgpu_bsdf_snow record = noSnow;
+		if (!rd.r.ok()) {
+			/* truncated */
+		} else if (mask.kind != MTSGPU_MASK_NONE) {
+			rd.r.fail("a Mask around a Wiscombe is not supported");
+		} else if (!wiscombeConfigure) {
+			rd.r.fail("Wiscombe: the caller gave a snow list without mtsgpu_wiscombe_configure");
+		} else if (wiscombeConfigure(raw, &record) != MTSGPU_OK) {
+			rd.r.fail("Wiscombe: configure() leaves a derived value that is not finite (g = " + std::to_string(raw[0]) + ", w0 = " + std::to_string(raw[2])
+			          + " " + std::to_string(raw[3]) + " " + std::to_string(raw[4]) + ")");
+		}
+		types.push_back(MTSGPU_BSDF_LAMBERTIAN | flags); params.insert(params.end(), MTSGPU_BSDF_NPARAMS, 0.0f);
+		if (colorSlots) colorSlots->push_back(0u);
+		if (slotTextures) slotTextures->insert(slotTextures->end(), 2, (int32_t) -1);
+		if (masks) masks->push_back(none);
+		snow->push_back(record);
+		own = (int) types.size() - 1;
 	} else if (rd.className() != "Composite") {
 		types.push_back(0); params.insert(params.end(), MTSGPU_BSDF_NPARAMS, 0.0f);
 		uint32_t slots = 0;
@@ -416,6 +456,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 		if (colorSlots) colorSlots->push_back(slots);
 		if (slotTextures) slotTextures->insert(slotTextures->end(), rd.slotTextures(), rd.slotTextures() + 2);
 		if (masks) masks->push_back(mask);
+		if (snow) snow->push_back(noSnow);
 		own = (int) types.size() - 1;
 	} else {
 		const uint64_t n = rd.r.readSize();
@@ -433,6 +474,9 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 			if (!rd.r.ok()) break;
 			if (rd.className() == "Composite") { rd.r.fail("Composite: nested composites are not supported"); break; }
 			if (masks && rd.className() == "Mask") { rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " is a Mask: a mask is the outermost adapter, not supported as a composite's child"); break; }
+			if (snow && (rd.className() == "Wiscombe" || rd.className() == "HanrahanKrueger")) {
+				rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " is a " + rd.className() + ": the composite's loop would run its entry as a Lambertian, not supported"); break;
+			}
 			if (rd.className() == "Dielectric" || rd.className() == "Mirror") {
 				rd.r.fail("Composite: child " + rd.className() + " is a delta BSDF (a composite would need fDelta / pdfDelta): not supported"); break;
 			}
@@ -442,6 +486,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 			if (colorSlots) colorSlots->push_back(0u);
 			if (slotTextures) slotTextures->insert(slotTextures->end(), 2, (int32_t) -1);
 			if (masks) masks->push_back(none);
+			if (snow) snow->push_back(noSnow);
 			if (rd.r.ok() && rd.hasSlotTexture()) { rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " (" + rd.className() + ") has a uv texture: a composite's children keep constant parameters, not supported"); break; }
 			if (rd.r.ok() && slots) { rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " (" + rd.className() + ") takes vertex colours: a composite's children keep constant parameters, not supported"); break; }
 			block[1 + n + i] = (float) (types.size() - 1);
@@ -451,6 +496,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 			if (colorSlots) colorSlots->push_back(0u);
 			if (slotTextures) slotTextures->insert(slotTextures->end(), 2, (int32_t) -1);
 			if (masks) masks->push_back(none);
+			if (snow) snow->push_back(noSnow);
 			params.insert(params.end(), block, block + MTSGPU_BSDF_NPARAMS);
 			own = (int) types.size() - 1;
 		}
@@ -460,6 +506,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 		if (colorSlots) colorSlots->resize(first);
 		if (slotTextures) slotTextures->resize(2 * first);
 		if (masks) masks->resize(first);
+		if (snow) snow->resize(first);
 		if (uvTextures) uvTextures->resize(firstTex);
 		if (bitmaps) bitmaps->resize(firstBmp);
 		if (err) *err = rd.r.error() + " (while reading a " + rd.className() + ")";

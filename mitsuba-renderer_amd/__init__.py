@@ -47,6 +47,9 @@ EXPORTS = [
 ]
 # the mask BSDF's entry points: an extension declared in include/mtsgpu_mask.h, next to the list of mtsgpu.h that ABI version 8 fixes
 MASK_EXPORTS = ["mtsgpu_set_uv_masked_textures", "mtsgpu_group_set_uv_masked_textures", "mtsgpu_bsdf_eval_masked"]
+# the snow BRDFs' entry points (wiscombe, hanrahankrueger): the extension declared in include/mtsgpu_snow.h
+SNOW_EXPORTS = ["mtsgpu_wiscombe_configure", "mtsgpu_hk_configure", "mtsgpu_set_snow_bsdfs", "mtsgpu_group_set_snow_bsdfs",
+                "mtsgpu_bsdf_eval_snow"]
 
 
 class MtsGpuError(RuntimeError):
@@ -248,6 +251,12 @@ def lib():
     L.mtsgpu_set_uv_masked_textures.argtypes = [vp, f32p, u32p, C.c_uint32, texp, abi.i32p, C.c_uint32, bmpp, abi.i32p, mskp]
     L.mtsgpu_group_set_uv_masked_textures.argtypes = [vp, f32p, u32p, C.c_uint32, texp, abi.i32p, C.c_uint32, bmpp, abi.i32p, mskp]
     L.mtsgpu_bsdf_eval_masked.argtypes = [vp, C.c_uint32, f32p, f32p, C.c_int, C.c_uint32, f32p, f32p]
+    snwp = C.POINTER(abi.BsdfSnow)
+    L.mtsgpu_wiscombe_configure.argtypes = [f32p, snwp]
+    L.mtsgpu_hk_configure.argtypes = [f32p, snwp]
+    L.mtsgpu_set_snow_bsdfs.argtypes = [vp, snwp]
+    L.mtsgpu_group_set_snow_bsdfs.argtypes = [vp, snwp]
+    L.mtsgpu_bsdf_eval_snow.argtypes = [vp, C.c_uint32, snwp, C.c_int, C.c_uint32, f32p, f32p]
     L.mtsgpu_ldr_texels.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_float, f32p]
     _lib = L
     return L
@@ -266,6 +275,33 @@ def bsdf_mask_array(masks):
         else:
             kind, tex, op = m
             arr[i] = abi.BsdfMask(int(kind), int(tex), (C.c_float * 3)(*[float(x) for x in op]), 0)
+    return arr
+
+
+def snow_configure(kind, raw):
+    """the reference's configure() of a snow BRDF on the host: kind abi.SNOW_WISCOMBE with raw = g, depth, w0 rgb, sigmaT rgb
+    (mtsgpu_wiscombe_configure), or abi.SNOW_HK with raw = sigmaA rgb, sigmaS rgb, g, etaInt, etaExt, ssFactor rgb, drFactor rgb,
+    useDiffuseReflectance (mtsgpu_hk_configure) -> abi.BsdfSnow"""
+    n, call = {abi.SNOW_WISCOMBE: (8, lib().mtsgpu_wiscombe_configure), abi.SNOW_HK: (16, lib().mtsgpu_hk_configure)}[int(kind)]
+    r = np.ascontiguousarray(raw, dtype=np.float32)
+    if r.shape != (n,):
+        raise ValueError("snow_configure: %d raw values, not %d" % (r.size, n))
+    out = abi.BsdfSnow()
+    if call(abi.ptr(r, abi.f32p), C.byref(out)) != 0:
+        raise MtsGpuError("snow_configure: %s" % lib().mtsgpu_last_error(None).decode())
+    return out
+
+
+def bsdf_snow_array(rows):
+    """abi.BsdfSnow objects, rows (kind, derived) or None (no snow record) -> the ctypes array mtsgpu_set_snow_bsdfs takes"""
+    arr = (abi.BsdfSnow * max(len(rows), 1))()
+    for i, m in enumerate(rows):
+        if isinstance(m, abi.BsdfSnow):
+            arr[i] = m
+        elif m is not None:
+            kind, derived = m
+            d = np.zeros(abi.SNOW_NDERIVED, dtype=np.float32); d[:len(derived)] = derived
+            arr[i] = abi.BsdfSnow(int(kind), 0, (C.c_float * abi.SNOW_NDERIVED)(*[float(x) for x in d]))
     return arr
 
 
@@ -366,6 +402,8 @@ class Scene:
         self.bsdf_slot_texture = np.ascontiguousarray(table) if (table >= 0).any() else None
         # the masks around the BSDFs (none: the scene takes the texture calls as ever)
         self.bsdf_mask = bsdf_mask_array(description.mask_table()) if getattr(description, "bsdf_masks", None) else None
+        # the snow records of the BSDFs (none: the scene never calls mtsgpu_set_snow_bsdfs)
+        self.bsdf_snow = bsdf_snow_array(description.snow_table(snow_configure)) if getattr(description, "bsdf_snow", None) else None
 
     @property
     def sc(self):
@@ -563,6 +601,8 @@ class MIPathTracer:
             self._chk(lib().mtsgpu_set_uv_bitmap_textures(self._ctx, *ub), "set_uv_bitmap_textures")
         elif ut is not None:
             self._chk(lib().mtsgpu_set_uv_textures(self._ctx, *ut), "set_uv_textures")
+        if isinstance(scene, Scene) and scene.bsdf_snow is not None:
+            self._chk(lib().mtsgpu_set_snow_bsdfs(self._ctx, scene.bsdf_snow), "set_snow_bsdfs")
         self.camera = camera
         self._chk(lib().mtsgpu_set_camera(self._ctx, C.byref(camera.c if hasattr(camera, "c") else camera)), "set_camera")
         kind = {"independent": abi.SAMPLER_INDEPENDENT_KEYED, "ldsampler": abi.SAMPLER_LD_KEYED, "halton": abi.SAMPLER_HALTON,
@@ -786,6 +826,24 @@ class MIPathTracer:
                                                       abi.ptr(s, abi.i32p), 0 if bm is None else len(bitmaps), bm, abi.ptr(tb, abi.i32p), m),
                   "set_uv_masked_textures")
 
+    def set_snow_bsdfs(self, table=None):
+        """mtsgpu_set_snow_bsdfs on the uploaded scene: one abi.BsdfSnow, row (kind, derived) or None per BSDF; None switches the
+        table off"""
+        self._chk(lib().mtsgpu_set_snow_bsdfs(self._ctx, None if table is None else bsdf_snow_array(table)), "set_snow_bsdfs")
+
+    def bsdf_eval_snow(self, bsdf_type, entry, op, wi, aux):
+        """bsdf_eval() of the snow record `entry`, an abi.BsdfSnow or a row (kind, derived) (mtsgpu_bsdf_eval_snow) -> [n][8]"""
+        aux = np.atleast_2d(np.asarray(aux, dtype=np.float32))
+        n = aux.shape[0]
+        q = np.zeros((n, 6), dtype=np.float32)
+        q[:, :3] = np.asarray(wi, dtype=np.float32).reshape(-1, 3)
+        q[:, 3:3 + aux.shape[1]] = aux
+        e = bsdf_snow_array([entry])
+        out = np.zeros((n, 8), dtype=np.float32)
+        self._chk(lib().mtsgpu_bsdf_eval_snow(self._ctx, int(bsdf_type), e, int(op), n, abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)),
+                  "bsdf_eval_snow")
+        return out
+
     def bsdf_eval_masked(self, bsdf_type, params, opacity, op, wi, aux):
         """bsdf_eval() through the mask adapter whose opacity is the spectrum `opacity` (mtsgpu_bsdf_eval_masked) -> [n][8]"""
         aux = np.atleast_2d(np.asarray(aux, dtype=np.float32))
@@ -988,6 +1046,8 @@ class DeviceGroup:
             self._chk(lib().mtsgpu_group_set_uv_bitmap_textures(self._g, *ub), "set_uv_bitmap_textures")
         elif ut is not None:
             self._chk(lib().mtsgpu_group_set_uv_textures(self._g, *ut), "set_uv_textures")
+        if isinstance(scene, Scene) and scene.bsdf_snow is not None:
+            self._chk(lib().mtsgpu_group_set_snow_bsdfs(self._g, scene.bsdf_snow), "set_snow_bsdfs")
         self.camera = camera
         self._chk(lib().mtsgpu_group_set_camera(self._g, C.byref(camera.c)), "set_camera")
         kind = {"independent": abi.SAMPLER_INDEPENDENT_KEYED, "ldsampler": abi.SAMPLER_LD_KEYED, "halton": abi.SAMPLER_HALTON,

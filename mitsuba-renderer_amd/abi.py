@@ -18,6 +18,8 @@ TEX_BITMAP = 2
 WRAP_REPEAT, WRAP_CLAMP, WRAP_BLACK, WRAP_WHITE = 0, 1, 2, 3      # MTSGPU_WRAP_* (not the numbering of MIPMap::EWrapMode)
 BITMAP_MAX_TEXELS = 2147483647
 MASK_NONE, MASK_CONSTANT, MASK_TEXTURE = 0, 1, 2                    # MTSGPU_MASK_*
+SNOW_NONE, SNOW_WISCOMBE, SNOW_HK = 0, 1, 2                          # MTSGPU_SNOW_*
+SNOW_NDERIVED = 14
 LUM_AREA, LUM_CONSTANT, LUM_POINT, LUM_DIRECTIONAL, LUM_SPOT, LUM_ENVMAP, LUM_COLLIMATED, LUM_SKY = 0, 1, 2, 3, 4, 5, 6, 7
 LUM_NPARAMS = 32
 SKY_NDERIVED = 24
@@ -47,6 +49,11 @@ class Bitmap(C.Structure):
 class BsdfMask(C.Structure):
     """mtsgpu_bsdf_mask"""
     _fields_ = [("kind", C.c_uint32), ("texture", C.c_int32), ("opacity", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class BsdfSnow(C.Structure):
+    """mtsgpu_bsdf_snow"""
+    _fields_ = [("kind", C.c_uint32), ("reserved", C.c_uint32), ("derived", C.c_float * SNOW_NDERIVED)]
 
 
 class Scene(C.Structure):

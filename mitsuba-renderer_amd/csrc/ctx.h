@@ -56,7 +56,7 @@ inline void freeAll(std::vector<void *> &v) { for (void *p : v) (void) hipFree(p
 struct mtsgpu_ctx {
 	// with `device` current and idle (mtsgpu_destroy): everything no DevBuf member owns.  A caller's stream or film is not ours.
 	~mtsgpu_ctx() {
-		for (auto *list : { &sceneAllocs, &colorAllocs, &texAllocs, &pathAllocs }) mg::freeAll(*list);
+		for (auto *list : { &sceneAllocs, &colorAllocs, &texAllocs, &snowAllocs, &pathAllocs }) mg::freeAll(*list);
 		if (hostCounters) (void) hipHostFree(hostCounters);
 		for (auto *pool : { &traceEvents, &shadeEvents })
 			for (auto &e : *pool) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
@@ -100,6 +100,12 @@ struct mtsgpu_ctx {
 	mg::DMasks dmsk{ nullptr };
 	// mtsgpu_upload_scene_tangents: DTangents' arrays, owned with the scene (sceneAllocs); NULL, NULL without a tangent mesh
 	mg::DTangents dtan{ nullptr, nullptr };
+	// mtsgpu_set_snow_bsdfs: DSnows' table, owned like the colours' (snowAllocs), and a host copy of its kinds (empty = no
+	// table), so that the colour, texture and mask calls can refuse a slot or a mask on a snow entry; and the mask kinds in force
+	// (empty = none), so that this call can refuse a snow record on a masked entry
+	std::vector<void *> snowAllocs;
+	mg::DSnows dsnw{ nullptr };
+	std::vector<uint32_t> hostSnowKind, hostMaskKind;
 	std::vector<uint32_t> hostColorSlots;
 	std::vector<int32_t> hostSlotTex;
 

@@ -466,6 +466,12 @@ int mtsgpu_group_set_uv_masked_textures(mtsgpu_group *g, const float *vtx_uv, co
 	               clearUvTextures);
 }
 
+int mtsgpu_group_set_snow_bsdfs(mtsgpu_group *g, const mtsgpu_bsdf_snow *table) {
+	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
+	return forEach(g, "set_snow_bsdfs", [&](mtsgpu_ctx *c) { return mtsgpu_set_snow_bsdfs(c, table); },
+	               [](mtsgpu_ctx *c) { return mtsgpu_set_snow_bsdfs(c, nullptr); });
+}
+
 int mtsgpu_hbm_triad(int device, size_t bytes, int iters, double *gbs) {
 	if (!gbs || bytes < 4096 || iters <= 0) return gfail(nullptr, MTSGPU_EINVAL, "bad triad arguments");
 	*gbs = 0;

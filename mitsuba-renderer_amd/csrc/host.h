@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/mtsgpu.h"
 #include "../../include/mtsgpu_mask.h"
+#include "../../include/mtsgpu_snow.h"
 #include "devmath.h"
 #include "kdtree.h"
 #include <cmath>
@@ -117,6 +118,105 @@ inline std::string checkBsdfMasks(uint32_t n_bsdfs, const uint32_t *type, const 
 		for (int i = 0; i < n; ++i)
 			if (mask[(uint32_t) P[1 + n + i]].kind != (uint32_t) MTSGPU_MASK_NONE)
 				return msg(b, "composite child " + std::to_string(i) + " has a mask: a mask is the outermost adapter (mask.cpp), not supported inside a composite");
+	}
+	return std::string();
+}
+
+// Wiscombe::configure (wiscombe.cpp:70-101) in binary32, in the reference's operation order and with its operators as compiled
+// (spectrum.h): Float * Spectrum and Float / Spectrum are the friends that return spd * f and spd / f, and Spectrum / Float
+// multiplies by 1.0f / f.  raw = g, depth, w0 rgb, sigmaT rgb.  m_tau, m_tauStar, m_gamma1 and m_gamma2 are computed there and
+// never read.  derived: wStar, bStar, xi, P.
+inline void snowWiscombeConfigure(const float *raw, float *derived) {
+	const float g = raw[0];
+	const float gSq = g * g;
+	const float gStar = g / (1.0f + g);
+	const float recipGStar = 1.0f / gStar;
+	for (int k = 0; k < 3; ++k) {
+		const float w0 = raw[2 + k];
+		const float wStar = (w0 * (1.0f - gSq)) / (1.0f - w0 * gSq);
+		const float bTmp = 1.0f - wStar * gStar;
+		const float bStar = bTmp * recipGStar;                        // m_gStar / bTmp: operator/(Float, Spectrum &) = bTmp / gStar
+		const float xiSq = ((1.0f - wStar * gStar) * (1.0f - wStar)) * 3.0f;
+		const float xi = sqrtf(xiSq);
+		const float P = (xi * 2.0f) / ((1.0f - wStar * gStar) * 3.0f);
+		derived[k] = wStar; derived[3 + k] = bStar; derived[6 + k] = xi; derived[9 + k] = P;
+	}
+	derived[12] = derived[13] = 0.0f;
+}
+
+// HanrahanKrueger::configure (hanrahan-krueger.cpp:89-132) likewise; exp is dexp.  raw = sigmaA rgb, sigmaS
+// rgb, g, etaInt, etaExt, ssFactor rgb, drFactor rgb, useDiffuseReflectance.  (4.0 / 3.0) * A is a binary64 product, rounded
+// once when the friend operator*(Float, Spectrum &) takes it; reducedAlbedo / 2.0 is Spectrum / Float = * (1.0f / 2.0f).
+// derived: sigmaS / sigmaT, ssFactor, the diffuse reflectance times drFactor, g, eta, the flag as 0 / 1.
+inline void snowHkConfigure(const float *raw, float *derived) {
+	const float g = raw[6], eta = raw[7] / raw[8];
+	float Fdr;
+	if (eta > 1)
+		Fdr = -1.440f / (eta * eta) + 0.710f / eta + 0.668f + 0.0636f * eta;                       // [Groenhuis et al. 1983]
+	else
+		Fdr = -0.4399f + 0.7099f / eta - 0.3319f / (eta * eta) + 0.0636f / (eta * eta * eta);      // [Egan et al. 1973]
+	float Fdt = 1.0f - Fdr;
+	if (eta == 1.0f) { Fdr = 0.0f; Fdt = 1.0f; }
+	const float A = (1 + Fdr) / Fdt;
+	const float fourThirdsA = (float) ((4.0 / 3.0) * (double) A);
+	for (int k = 0; k < 3; ++k) {
+		const float sigmaA = raw[k], sigmaS = raw[3 + k];
+		const float sigmaT = sigmaA + sigmaS;
+		const float sigmaSPrime = sigmaS * (1 - g);
+		const float sigmaTPrime = sigmaA + sigmaSPrime;
+		const float reducedAlbedo = sigmaSPrime / sigmaTPrime;
+		const float var1 = -sqrtf((1.0f - reducedAlbedo) * 3.0f);
+		const float dr = ((reducedAlbedo * (1.0f / 2.0f)) * (1.0f + mg::dexp(var1 * fourThirdsA))) * mg::dexp(var1);
+		derived[k] = sigmaS / sigmaT;
+		derived[3 + k] = raw[9 + k];
+		derived[6 + k] = dr * raw[12 + k];
+	}
+	derived[9] = g; derived[10] = eta; derived[11] = raw[15] != 0.0f ? 1.0f : 0.0f;
+	derived[12] = derived[13] = 0.0f;
+}
+
+// the first word of `derived` that is not finite, or -1
+inline int snowFirstNonFinite(const mtsgpu_bsdf_snow &e) {
+	for (int k = 0; k < 14; ++k)
+		if (!(std::fabs(e.derived[k]) <= 3.4028235e38f)) return k;
+	return -1;
+}
+
+// What mtsgpu_set_snow_bsdfs and mtsgpu_bsdf_eval_snow require of one snow record on an entry of type word `type`: a known kind,
+// a zero reserved word, finite derived words, and for a snow kind a Lambertian under at most the twosided adapter.  Returns the
+// reason, or an empty string.
+inline std::string checkSnowEntry(const mtsgpu_bsdf_snow &e, uint32_t type) {
+	if (e.kind > (uint32_t) MTSGPU_SNOW_HK) return "unknown snow kind " + std::to_string(e.kind);
+	if (e.reserved != 0) return "the reserved word of its snow record is not zero";
+	const int bad = snowFirstNonFinite(e);
+	if (bad >= 0) return "derived word " + std::to_string(bad) + " of its snow record is not finite";
+	if (e.kind != (uint32_t) MTSGPU_SNOW_NONE && (type & ~(uint32_t) MTSGPU_BSDF_TWOSIDED) != (uint32_t) MTSGPU_BSDF_LAMBERTIAN)
+		return "a snow record sits on a Lambertian entry (twosided allowed), not on type word " + std::to_string(type);
+	return std::string();
+}
+
+// ... and of the table [n_bsdfs] against a checked BSDF table: every record as above, none on a composite's child.  colorSlots
+// [n_bsdfs], slotTex [2 n_bsdfs] and maskKind [n_bsdfs] are the tables in force or NULL: a snow entry has no coloured slot, no
+// textured slot and no mask.
+inline std::string checkBsdfSnow(uint32_t n_bsdfs, const uint32_t *type, const float *params, const mtsgpu_bsdf_snow *snow,
+                                 const uint32_t *colorSlots, const int32_t *slotTex, const uint32_t *maskKind) {
+	auto msg = [](uint32_t b, const std::string &what) { return "BSDF " + std::to_string(b) + ": " + what; };
+	for (uint32_t b = 0; b < n_bsdfs; ++b) {
+		const std::string why = checkSnowEntry(snow[b], type[b]);
+		if (!why.empty()) return msg(b, why);
+		if (snow[b].kind == (uint32_t) MTSGPU_SNOW_NONE) continue;
+		if (colorSlots && colorSlots[b]) return msg(b, "a snow BRDF has no texture slot, and the entry takes vertex colours");
+		if (slotTex && (slotTex[2 * (size_t) b] >= 0 || slotTex[2 * (size_t) b + 1] >= 0))
+			return msg(b, "a snow BRDF has no texture slot, and the entry has a uv texture");
+		if (maskKind && maskKind[b] != (uint32_t) MTSGPU_MASK_NONE) return msg(b, "a mask around a snow BRDF is not supported");
+	}
+	for (uint32_t b = 0; b < n_bsdfs; ++b) {
+		if ((type[b] & 0xFFu) != MTSGPU_BSDF_COMPOSITE) continue;
+		const float *P = params + (size_t) MTSGPU_BSDF_NPARAMS * b;
+		const int n = (int) P[0];
+		for (int i = 0; i < n; ++i)
+			if (snow[(uint32_t) P[1 + n + i]].kind != (uint32_t) MTSGPU_SNOW_NONE)
+				return msg(b, "composite child " + std::to_string(i) + " has a snow record: the composite's loop would run it as a Lambertian, not supported");
 	}
 	return std::string();
 }

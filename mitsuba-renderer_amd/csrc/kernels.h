@@ -195,6 +195,18 @@ struct DMasks {
 	const DMask *bsdf_mask;
 };
 constexpr uint32_t kMaskNone = 0, kMaskConstant = 1, kMaskTexture = 2;
+// The snow BRDFs (mtsgpu_set_snow_bsdfs), NULL without one.  An argument of kernels of their own (k_shade_snw, bin 0) only.
+// bsdf_snow[n_bsdfs]: what configure() of the Wiscombe or HanrahanKrueger in place of this Lambertian entry left behind
+// (mtsgpu_bsdf_snow: the layout of `derived` is in mtsgpu_snow.h); non-NULL only while some BSDF has one
+struct DSnow {
+	uint32_t kind;                          // kSnowNone, kSnowWiscombe, kSnowHK = MTSGPU_SNOW_*
+	uint32_t reserved;
+	float    derived[14];
+};
+struct DSnows {
+	const DSnow *bsdf_snow;
+};
+constexpr uint32_t kSnowNone = 0, kSnowWiscombe = 1, kSnowHK = 2;
 // what a texture slot of a BSDF takes at a hit (bsdf_block_with_slots)
 enum : int { kSlotBlock = 0, kSlotColor = 1, kSlotTexture = 2 };
 
@@ -442,6 +454,8 @@ void launch_bsdf_eval_slots(hipStream_t s, uint32_t type, const float *params, c
 // opacity[3] formed on the device
 void launch_bsdf_eval_masked(hipStream_t s, uint32_t type, const float *params, const float *opacity, int op, uint32_t n,
                              const float *queries, float *out);
+// mtsgpu_bsdf_eval_snow: the same read-out through BsdfSnow2, the evaluator of the snow kernels
+void launch_bsdf_eval_snow(hipStream_t s, uint32_t type, const DSnow &entry, int op, uint32_t n, const float *queries, float *out);
 // mtsgpu_uv_texture_eval: its.uv (its_uv) and tex_eval of `tex` there for n records of the uploaded scene; rec [n][3] =
 // (u, v, -) on a triangle, the world-space hit point on a sphere; out [n][5] = uv, rgb
 void launch_uv_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, uint32_t n, const uint32_t *prim,
@@ -481,7 +495,7 @@ void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, co
                   const DQueues &q, const BinView &view, const BinView *views_dev = nullptr, uint32_t n_bound = 0,
                   const uint32_t *bin_ids = nullptr, const DColors &col = DColors{ nullptr, nullptr },
                   const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr },
-                  const DMasks &msk = DMasks{ nullptr });
+                  const DMasks &msk = DMasks{ nullptr }, const DSnows &snw = DSnows{ nullptr });
 // device-driven bounces, path integrator / one-sample direct integrator: all bins of bin_mask in one launch; views_dev as
 // above, n_bound bounds the sum of the bin sizes
 void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,

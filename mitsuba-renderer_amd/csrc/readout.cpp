@@ -347,6 +347,26 @@ int mtsgpu_bsdf_eval_masked(mtsgpu_ctx *c, uint32_t bsdf_type, const float *para
 	return s.finish("BSDF read-out");
 }
 
+int mtsgpu_bsdf_eval_snow(mtsgpu_ctx *c, uint32_t bsdf_type, const mtsgpu_bsdf_snow *entry, int op, uint32_t n, const float *queries, float *out) {
+	if (!c || !entry || !queries || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	if ((bsdf_type & ~(uint32_t) MTSGPU_BSDF_TWOSIDED) != (uint32_t) MTSGPU_BSDF_LAMBERTIAN || op < 0 || op > 2)
+		return fail(c, MTSGPU_EINVAL, "bad BSDF type or operation: a snow record sits on a Lambertian entry (twosided allowed)");
+	{
+		const std::string why = checkSnowEntry(*entry, bsdf_type);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+	}
+	if (n == 0) return 0;
+	if (int rc = checkRecordCount(c, n)) return rc;
+	Scratch s(c);
+	const float *dQ = s.put(queries, (size_t) n * 6);
+	float *dOut = s.alloc<float>((size_t) n * 8);
+	DSnow e;
+	std::memcpy(&e, entry, sizeof(e));
+	if (s.ok()) launch_bsdf_eval_snow(c->stream, bsdf_type, e, op, n, dQ, dOut);
+	s.get(out, dOut, (size_t) n * 8);
+	return s.finish("BSDF read-out");
+}
+
 int mtsgpu_uv_texture_eval(mtsgpu_ctx *c, const mtsgpu_uv_texture *tex, uint32_t n, const uint32_t *prim, const float *rec, float *out) {
 	if (!c || !tex || !prim || !rec || !out) return fail(c, MTSGPU_EINVAL, "null argument");
 	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_uv_texture_eval before mtsgpu_upload_scene");
@@ -424,6 +444,30 @@ int mtsgpu_shading_frame_eval(mtsgpu_ctx *c, uint32_t n, const uint32_t *prim, c
 int mtsgpu_sky_configure(const float *block, float *derived) {
 	if (!block || !derived) return fail(nullptr, MTSGPU_EINVAL, "null argument");
 	skyConfigure(block, derived);
+	return 0;
+}
+
+int mtsgpu_wiscombe_configure(const float *raw, mtsgpu_bsdf_snow *out) {
+	if (!raw || !out) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	std::memset(out, 0, sizeof(*out));
+	out->kind = MTSGPU_SNOW_WISCOMBE;
+	snowWiscombeConfigure(raw, out->derived);
+	static const char *const names[4] = { "wStar", "bStar", "xi", "P" };
+	const int bad = snowFirstNonFinite(*out);
+	if (bad >= 0) return fail(nullptr, MTSGPU_EINVAL, "Wiscombe: %s[%d] is not finite (g = %g, w0 = %g %g %g)", names[bad / 3], bad % 3, raw[0], raw[2], raw[3], raw[4]);
+	return 0;
+}
+
+int mtsgpu_hk_configure(const float *raw, mtsgpu_bsdf_snow *out) {
+	if (!raw || !out) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	std::memset(out, 0, sizeof(*out));
+	out->kind = MTSGPU_SNOW_HK;
+	snowHkConfigure(raw, out->derived);
+	static const char *const names[12] = { "albedo[0]", "albedo[1]", "albedo[2]", "ssFactor[0]", "ssFactor[1]", "ssFactor[2]",
+	                                       "diffuseReflectance[0]", "diffuseReflectance[1]", "diffuseReflectance[2]", "g", "eta", "the flag" };
+	const int bad = snowFirstNonFinite(*out);
+	if (bad >= 0) return fail(nullptr, MTSGPU_EINVAL, "HanrahanKrueger: %s is not finite (sigmaA + sigmaS = %g %g %g, etaInt / etaExt = %g / %g)", names[bad],
+	                          raw[0] + raw[3], raw[1] + raw[4], raw[2] + raw[5], raw[7], raw[8]);
 	return 0;
 }
 

@@ -210,6 +210,10 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 	c->dtex = DTextures{ nullptr, nullptr, nullptr, nullptr };
 	c->dmsk = DMasks{ nullptr };
 	c->hostSlotTex.clear();
+	c->hostMaskKind.clear();
+	freeAll(c->snowAllocs);       // ... and without snow BRDFs (mtsgpu_set_snow_bsdfs)
+	c->dsnw = DSnows{ nullptr };
+	c->hostSnowKind.clear();
 	c->dtan = DTangents{ nullptr, nullptr };      // ... and its tangents go with the scene's arrays
 	c->haveScene = false;
 	DScene d{};
@@ -426,6 +430,9 @@ int mtsgpu_set_vertex_colors(mtsgpu_ctx *c, const float *vtx_col, const uint32_t
 				for (int s = 0; s < 2; ++s)
 					if (((bsdf_color_slots[b] >> s) & 1u) && c->hostSlotTex[2 * (size_t) b + s] >= 0)
 						return fail(c, MTSGPU_EINVAL, "BSDF %u: slot %d takes vertex colours and has a uv texture as well", b, s);
+		for (uint32_t b = 0; b < nBsdfs && !c->hostSnowKind.empty(); ++b)      // an entry mtsgpu_set_snow_bsdfs has given a snow record
+			if (bsdf_color_slots[b] && c->hostSnowKind[b] != (uint32_t) MTSGPU_SNOW_NONE)
+				return fail(c, MTSGPU_EINVAL, "BSDF %u: the entry takes vertex colours and has a snow record, whose BRDF has no texture slot", b);
 		for (uint32_t s = 0; s < nShapes; ++s) {
 			const int32_t b = h.shapeBsdf[s];
 			if (b < 0 || !bsdf_color_slots[b]) continue;
@@ -495,6 +502,7 @@ static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *sha
 	c->dtex = DTextures{ nullptr, nullptr, nullptr, nullptr };
 	c->dmsk = DMasks{ nullptr };
 	c->hostSlotTex.clear();
+	c->hostMaskKind.clear();
 	if (!vtx_uv && !shape_has_uv && !textures && !bsdf_slot_texture && !bitmaps && !texture_bitmap && !bsdf_mask) return 0;
 	if ((vtx_uv == nullptr) != (shape_has_uv == nullptr))
 		return fail(c, MTSGPU_EINVAL, "vtx_uv and shape_has_uv must both be given or both be NULL");
@@ -542,6 +550,14 @@ static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *sha
 			anyMask |= bsdf_mask[b].kind != (uint32_t) MTSGPU_MASK_NONE;
 			anyMaskTex |= bsdf_mask[b].kind == (uint32_t) MTSGPU_MASK_TEXTURE;
 		}
+	}
+	// an entry mtsgpu_set_snow_bsdfs has given a snow record takes neither a textured slot nor a mask
+	for (uint32_t b = 0; b < nBsdfs && !c->hostSnowKind.empty(); ++b) {
+		if (c->hostSnowKind[b] == (uint32_t) MTSGPU_SNOW_NONE) continue;
+		if (bsdf_slot_texture && (bsdf_slot_texture[2 * (size_t) b] >= 0 || bsdf_slot_texture[2 * (size_t) b + 1] >= 0))
+			return fail(c, MTSGPU_EINVAL, "BSDF %u: the entry has a uv texture and a snow record, whose BRDF has no texture slot", b);
+		if (bsdf_mask && bsdf_mask[b].kind != (uint32_t) MTSGPU_MASK_NONE)
+			return fail(c, MTSGPU_EINVAL, "BSDF %u: the entry has a mask and a snow record: a mask around a snow BRDF is not supported", b);
 	}
 	// the casts of texture k on shape s (s == nShapes: on no shape, at uv = 0); the reason, or an empty string
 	auto castRange = [&](uint32_t s, int32_t k, const std::vector<float> &triUv) -> std::string {
@@ -614,6 +630,41 @@ static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *sha
 	c->dtex = DTextures{ reinterpret_cast<const float4 *>(dUv), dTex, dSlots, reinterpret_cast<const float4 *>(dTexels) };
 	c->dmsk = DMasks{ dMask };
 	if (anySlot) c->hostSlotTex.assign(bsdf_slot_texture, bsdf_slot_texture + 2 * (size_t) nBsdfs);
+	if (anyMask)
+		for (uint32_t b = 0; b < nBsdfs; ++b) c->hostMaskKind.push_back(bsdf_mask[b].kind);
+	return 0;
+}
+
+static_assert(sizeof(mtsgpu_bsdf_snow) == 64 && sizeof(mtsgpu_bsdf_snow) == sizeof(DSnow) && offsetof(mtsgpu_bsdf_snow, derived) == offsetof(DSnow, derived)
+              && offsetof(mtsgpu_bsdf_snow, derived) == 8, "mtsgpu_bsdf_snow and DSnow are one layout");
+static_assert(MTSGPU_SNOW_NONE == (int) kSnowNone && MTSGPU_SNOW_WISCOMBE == (int) kSnowWiscombe && MTSGPU_SNOW_HK == (int) kSnowHK, "snow kinds differ");
+
+int mtsgpu_set_snow_bsdfs(mtsgpu_ctx *c, const mtsgpu_bsdf_snow *table) {
+	if (!c) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_set_snow_bsdfs before mtsgpu_upload_scene");
+	c->lastPass.valid = false;
+	HIPCHK(c, hipSetDevice(c->device));
+	// nothing may still read the table that goes (the shading launches of a render that was not synchronised)
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
+	freeAll(c->snowAllocs);
+	c->dsnw = DSnows{ nullptr };
+	c->hostSnowKind.clear();
+	if (!table) return 0;
+	const mtsgpu_ctx::HostScene &h = c->host;
+	const uint32_t nBsdfs = (uint32_t) h.bsdfType.size();
+	const std::string why = checkBsdfSnow(nBsdfs, h.bsdfType.data(), h.bsdfParams.data(), table,
+	                                      c->hostColorSlots.empty() ? nullptr : c->hostColorSlots.data(),
+	                                      c->hostSlotTex.empty() ? nullptr : c->hostSlotTex.data(),
+	                                      c->hostMaskKind.empty() ? nullptr : c->hostMaskKind.data());
+	if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+	bool any = false;
+	for (uint32_t b = 0; b < nBsdfs; ++b) any |= table[b].kind != (uint32_t) MTSGPU_SNOW_NONE;
+	if (!any) return 0;           // nothing to keep: the context launches what it launches without a table
+	const DSnow *dSnow = nullptr;
+	if (int rc = upload(c, &dSnow, reinterpret_cast<const DSnow *>(table), nBsdfs, &c->snowAllocs)) { freeAll(c->snowAllocs); return rc; }
+	c->dsnw = DSnows{ dSnow };
+	for (uint32_t b = 0; b < nBsdfs; ++b) c->hostSnowKind.push_back(table[b].kind);
 	return 0;
 }
 

@@ -1226,6 +1226,101 @@ template <int BT> struct BsdfMasked {
 	}
 };
 
+// The snow BRDFs of the reference, Wiscombe (src/bsdfs/wiscombe.cpp:108-166) and HanrahanKrueger
+// (src/bsdfs/hanrahan-krueger.cpp:134-214), as written, quirks included.  Both sample like the Lambertian; D is the record's
+// `derived` (mtsgpu_snow.h has the layout).  kSnowNone is Bsdf<0> on the block P, so a queue may mix Lambertian and snow hits.
+// f, pdf and the sample-with-pdf form are what the integrators call (path.cpp:109,120,135).  The snow kernels (k_shade_snw) and
+// the read-out hook (k_bsdf_eval_snow) both call this.
+struct BsdfSnow {
+	// Wiscombe::reflectance (:122-127) = albedo(mu0) * fBar * INV_PI; albedo (:133-135) is two component-wise divisions.
+	// b = 1.07 * mu0 - 0.84 is binary64 (the literals), rounded once
+	static __device__ __forceinline__ V3 wiscombe_reflectance(const float *D, float mu0, float muPrime) {
+		const float b = (float) (1.07 * (double) mu0 - 0.84);
+		const float fBar = (3.0f / (3.0f - b)) * (1.0f + b * (muPrime - 1.0f));
+		float R[3];
+		#pragma unroll
+		for (int k = 0; k < 3; ++k) {
+			const float wStar = D[k], bStar = D[3 + k], xi = D[6 + k], Pk = D[9 + k];
+			const float albedo = (wStar / (1.0f + Pk)) * ((1.0f - xi * mu0 * bStar) / (1.0f + xi * mu0));
+			R[k] = albedo * fBar * kInvPi;
+		}
+		return V3(R[0], R[1], R[2]);
+	}
+	// HanrahanKrueger::radiance (:171-193) with hgPhaseFunction (:140-147).  std::pow(base, 1.5) is base * sqrt(base) in
+	// binary64 with the correctly rounded sqrt, rounded once to binary32
+	static __device__ __forceinline__ V3 hk_radiance(const float *D, V3 wi, V3 wo) {
+		const float cos_wi = wi.z, cos_wo = wo.z;
+		const float g = D[9], eta = D[10];
+		const float Ft1 = 1.0f - fresnel(cos_wo, 1.0f, eta);
+		const float Ft2 = 1.0f - fresnel(cos_wi, 1.0f, eta);
+		const float F = Ft1 * Ft2;
+		const float costheta = dot(-wi, wo);
+		const float gSq = g * g;
+		const float num = (float) (1.0 - (double) gSq);
+		const double base = 1.0 + (double) gSq - 2.0 * (double) g * (double) costheta;
+		const float den = (float) (base * sqrt(base));
+		const float p = (float) (0.5 * (double) (num / den));
+		const float recip = 1.0f / (fabsf(cos_wi) + fabsf(cos_wo));      // Spectrum / Float (spectrum.h:229-243)
+		float Lo[3];
+		#pragma unroll
+		for (int k = 0; k < 3; ++k) {
+			const float f1 = D[k] * F * p * recip;
+			Lo[k] = D[3 + k] * f1;
+			if (D[11] != 0.0f) Lo[k] += D[6 + k] * F * kInvPi;
+		}
+		return V3(Lo[0], Lo[1], Lo[2]);
+	}
+	static __device__ __forceinline__ V3 f(uint32_t kind, const float *D, const float *P, V3 wi, V3 wo) {
+		if (kind == kSnowNone) return Bsdf<0>::f(P, wi, wo);
+		if (wi.z <= 0 || wo.z <= 0) return V3(0, 0, 0);
+		// Wiscombe: mu0 = cosTheta(wo), muPrime = cosTheta(wi), and a second 1 / pi (:113-115)
+		if (kind == kSnowWiscombe) return wiscombe_reflectance(D, wo.z, wi.z) * kInvPi;
+		return hk_radiance(D, wi, wo) * kInvPi;
+	}
+	static __device__ __forceinline__ float pdf(uint32_t kind, const float *D, const float *P, V3 wi, V3 wo) {
+		return Bsdf<0>::pdf(P, wi, wo);      // wiscombe.cpp:137-141, hanrahan-krueger.cpp:162-166: the Lambertian's
+	}
+	static __device__ __forceinline__ V3 sample(uint32_t kind, const float *D, const float *P, V3 wi, float sx, float sy, V3 &wo, float &pdf,
+	                                            uint32_t &st) {
+		if (kind == kSnowNone) return Bsdf<0>::sample(P, wi, sx, sy, wo, pdf, st);
+		pdf = 0; st = 0; wo = V3(0, 0, 0);
+		if (wi.z <= 0) return V3(0, 0, 0);
+		wo = squareToHemispherePSA(sx, sy);
+		st = T_DIFFUSE_REFL;
+		pdf = wo.z * kInvPi;
+		// Wiscombe: muPrime = |cosTheta(wi)|, one 1 / pi (:163-165); HanrahanKrueger: radiance * INV_PI (:213)
+		if (kind == kSnowWiscombe) return wiscombe_reflectance(D, wo.z, fabsf(wi.z));
+		return hk_radiance(D, wi, wo) * kInvPi;
+	}
+};
+// BsdfSnow behind the TwoSidedBRDF adapter of Bsdf2 and the Mask adapter of BsdfMasked (p = 1 without a mask: a snow entry
+// has none, a Lambertian of the same queue may)
+struct BsdfSnow2 {
+	static __device__ __forceinline__ V3 f(bool two, uint32_t kind, const float *D, const float *P, float p, V3 wi, V3 wo) {
+		if (two && wi.z < 0) { wi.z *= -1; wo.z *= -1; }
+		return BsdfSnow::f(kind, D, P, wi, wo) * p;
+	}
+	static __device__ __forceinline__ float pdf(bool two, uint32_t kind, const float *D, const float *P, float p, V3 wi, V3 wo) {
+		if (two && wi.z < 0) { wi.z *= -1; wo.z *= -1; }
+		return BsdfSnow::pdf(kind, D, P, wi, wo) * p;
+	}
+	static __device__ __forceinline__ V3 sample(bool two, uint32_t kind, const float *D, const float *P, float p, V3 wi, float sx, float sy, V3 &wo,
+	                                            float &pdf, uint32_t &st) {
+		if (sx <= p) {
+			bool flipped = false;
+			if (two && wi.z < 0) { wi.z *= -1; flipped = true; }
+			const V3 result = BsdfSnow::sample(kind, D, P, wi, sx / p, sy, wo, pdf, st);
+			if (flipped && !isZero(result) && pdf != 0) wo.z *= -1;
+			pdf *= p;
+			return result * p;
+		}
+		wo = V3(-wi.x, -wi.y, -wi.z);
+		st = T_DELTA_TRANS;
+		pdf = (1 - p) * fabsf(wo.z);
+		return V3(1 - p, 1 - p, 1 - p);
+	}
+};
+
 __device__ __forceinline__ float mi_weight(float pdfA, float pdfB) {     // path.cpp:218-222
 	pdfA *= pdfA;
 	pdfB *= pdfB;

@@ -171,6 +171,27 @@ __global__ void k_bsdf_eval_masked(uint32_t type, BsdfParams params, float cr, f
 	#pragma unroll
 	for (int k = 0; k < 8; ++k) out[8 * (size_t) i + k] = o[k];
 }
+// mtsgpu_bsdf_eval_snow: k_bsdf_eval through BsdfSnow2 without a mask (p = 1); kSnowNone: the Lambertian whose block is derived[0..2]
+__global__ void k_bsdf_eval_snow(uint32_t type, DSnow e, int op, uint32_t n, const float *queries, float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const bool two = (type & 0x100u) != 0;
+	const float *q = queries + 6 * (size_t) i, *D = e.derived;
+	const V3 wi(q[0], q[1], q[2]);
+	float o[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+	if (op == 0) {
+		const V3 f = BsdfSnow2::f(two, e.kind, D, D, 1.0f, wi, V3(q[3], q[4], q[5]));
+		o[0] = f.x; o[1] = f.y; o[2] = f.z;
+	} else if (op == 1) {
+		o[0] = BsdfSnow2::pdf(two, e.kind, D, D, 1.0f, wi, V3(q[3], q[4], q[5]));
+	} else {
+		V3 wo; float pdf; uint32_t st;
+		const V3 f = BsdfSnow2::sample(two, e.kind, D, D, 1.0f, wi, q[3], q[4], wo, pdf, st);
+		o[0] = wo.x; o[1] = wo.y; o[2] = wo.z; o[3] = pdf; o[4] = f.x; o[5] = f.y; o[6] = f.z; o[7] = __uint_as_float(st);
+	}
+	#pragma unroll
+	for (int k = 0; k < 8; ++k) out[8 * (size_t) i + k] = o[k];
+}
 // mtsgpu_uv_texture_eval: its_uv and tex_eval for n records; the host has checked prim < n_tris
 __global__ void k_uv_texture_eval(DScene sc, const float4 *tri_uv, DTexture tex, uint32_t n, const uint32_t *prim, const float *rec, float *out) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -313,6 +334,10 @@ void launch_bsdf_eval_masked(hipStream_t s, uint32_t type, const float *params, 
 	BsdfParams p;
 	for (int k = 0; k < kBsdfNParams; ++k) p.v[k] = params[k];
 	if (n) hipLaunchKernelGGL(k_bsdf_eval_masked, dim3(blocks_for(n, 256)), dim3(256), 0, s, type, p, opacity[0], opacity[1], opacity[2], op, n, queries, out);
+}
+
+void launch_bsdf_eval_snow(hipStream_t s, uint32_t type, const DSnow &entry, int op, uint32_t n, const float *queries, float *out) {
+	if (n) hipLaunchKernelGGL(k_bsdf_eval_snow, dim3(blocks_for(n, 256)), dim3(256), 0, s, type, entry, op, n, queries, out);
 }
 
 void launch_uv_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, uint32_t n, const uint32_t *prim,

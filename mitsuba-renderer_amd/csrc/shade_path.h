@@ -1,5 +1,5 @@
-// shade_path.h -- K3+K5: one iteration of MIPathTracer::Li per material queue, and the kernel templates of the five families
-// (k_shade*, k_shade_all*).  Each family is instantiated by the unit that launches it: shade_plain / _vcol / _tex / _tan / _mask.hip.
+// shade_path.h -- K3+K5: one iteration of MIPathTracer::Li per material queue, and the kernel templates of the six families
+// (k_shade*, k_shade_all*).  Each family is instantiated by the unit that launches it: shade_plain / _vcol / _tex / _tan / _mask / _snow.hip.
 #pragma once
 #include "shade_bsdf.h"
 
@@ -38,12 +38,14 @@ __device__ __forceinline__ uint32_t shade_row_index(uint32_t lane, uint32_t k) {
 // (DTangents::tri_dpdu != NULL), on top of kSlotTexture: the record comes from fill_its_tan, and the texture table may be NULL.
 // MSK: the instantiation for scenes with a mask adapter (DMasks::bsdf_mask != NULL), on top of TAN: the BSDF is evaluated through
 // BsdfMasked with the opacity's luminance at the hit, and the tangent table may be NULL as well.
-template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false>
+// SNW: the instantiation of bin 0 for scenes with a snow BRDF (DSnows::bsdf_snow != NULL), on top of MSK: a hit whose BSDF has a
+// snow record is evaluated through BsdfSnow2, every other one as in the mask kernel, and the mask table may be NULL as well.
+template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false, bool SNW = false>
 __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, const DConfig &cfg, const uint32_t id,
                                            const float4 ro, const float4 rd, const uint4 h, const float4 T4, const float4 L4,
                                            const ShadeRow row, bool &continues, bool &wantShadow, V3 &neeV, V3 &shO, V3 &shD, const DColors &col,
                                            const DTextures &tex, const DTangents &tan = DTangents{ nullptr, nullptr },
-                                           const DMasks &msk = DMasks{ nullptr }) {
+                                           const DMasks &msk = DMasks{ nullptr }, const DSnows &snw = DSnows{ nullptr }) {
 	{
 		// rounds of MIDirectIntegrator (DConfig::dr_mode): later BSDF samples start again from the camera hit
 		const int mode = ROUNDS ? cfg.dr_mode : 0;
@@ -156,6 +158,10 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			float colouredBlock[kBsdfNParams];
 			// mask kernels: the Mask around this BSDF, p = opacity.getLuminance() at the hit, 1 without one (what BsdfMasked takes)
 			float maskP = 1.0f;
+			// snow kernels: the record of this BSDF (BsdfSnow2), kSnowNone without one
+			uint32_t snowKind = kSnowNone;
+			const float *snowD = nullptr;
+			if (SNW && snw.bsdf_snow != nullptr) { snowKind = snw.bsdf_snow[bsdfIdx].kind; snowD = snw.bsdf_snow[bsdfIdx].derived; }
 			if (VCOL == kSlotTexture && BT < 9) {
 				// a checkerboard, a grid texture or a bitmap in a slot of this BSDF: that slot holds the texture's value at its.uv; a
 				// `vertexcolors` texture in the other one its.color
@@ -166,7 +172,8 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				float uvx = 0, uvy = 0;
 				// (mask kernels: the opacity first, with its.uv computed once for the mask and the slots)
 				DMask m{ kMaskNone, -1, { 0, 0, 0 }, 0u };
-				if (MSK) m = msk.bsdf_mask[bsdfIdx];
+				// (a scene that is here for its snow alone has no mask table)
+				if (MSK && !(SNW && msk.bsdf_mask == nullptr)) m = msk.bsdf_mask[bsdfIdx];
 				if (k0 >= 0 || k1 >= 0 || (MSK && m.kind == kMaskTexture))
 					its_uv(sc, tex.tri_uv, h.w, its.shape, __uint_as_float(h.y), __uint_as_float(h.z), its.p, uvx, uvy);
 				if (MSK && m.kind == kMaskConstant) maskP = luminance(V3(m.opacity[0], m.opacity[1], m.opacity[2]));
@@ -220,12 +227,14 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				if ((!direct || cfg.n_lum > 0) && sample_luminaire<SKY>(sc, its.p, s0, s1, lRec)) {
 					const V3 wo = -lRec.d;
 					const V3 woL(dot(wo, its.shS), dot(wo, its.shT), dot(wo, its.shN));
-					V3 bsdfVal = (MSK ? BsdfMasked<BT>::f(tab, twoSided, BP, maskP, its.wi, woL) : Bsdf2<BT>::f(tab, twoSided, BP, its.wi, woL)) * fabsf(woL.z);
+					V3 bsdfVal = (SNW ? BsdfSnow2::f(twoSided, snowKind, snowD, BP, maskP, its.wi, woL)
+					                  : MSK ? BsdfMasked<BT>::f(tab, twoSided, BP, maskP, its.wi, woL) : Bsdf2<BT>::f(tab, twoSided, BP, its.wi, woL)) * fabsf(woL.z);
 					const float woDotGeoN = dot(its.geoN, wo);
 					if (!isZero(bsdfVal) && (!strict || woDotGeoN * woL.z > 0)) {
 						// isIntersectable() || isBackgroundLuminaire() (path.cpp:118-120): 0 for delta luminaires
 						const uint32_t lt = sc.lum_type[lRec.lum];      // area, constant, envmap and sky luminaires can be hit by BSDF samples
-						const float bsdfPdf = (lt <= 1u || lt == 5u || (SKY && lt == 7u)) ? (MSK ? BsdfMasked<BT>::pdf(tab, twoSided, BP, maskP, its.wi, woL) : Bsdf2<BT>::pdf(tab, twoSided, BP, its.wi, woL)) : 0.0f;
+						const float bsdfPdf = (lt <= 1u || lt == 5u || (SKY && lt == 7u)) ? (SNW ? BsdfSnow2::pdf(twoSided, snowKind, snowD, BP, maskP, its.wi, woL)
+						                                                                             : MSK ? BsdfMasked<BT>::pdf(tab, twoSided, BP, maskP, its.wi, woL) : Bsdf2<BT>::pdf(tab, twoSided, BP, its.wi, woL)) : 0.0f;
 						const float weight = direct ? mi_weight(lRec.pdf * cfg.frac_lum, bsdfPdf * cfg.frac_bsdf) * cfg.weight_lum
 						                            : mi_weight(lRec.pdf, bsdfPdf);          // direct.cpp:143-145
 						// added to Li iff the segment is unoccluded: parked in the record by shade_block and cancelled by
@@ -250,7 +259,8 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			if (direct && cfg.n_bsdf <= 0)
 				break;                                      // the sample is drawn even when it is not used (direct.cpp:156-161)
 			V3 woL; float bsdfPdf; uint32_t sampledType;
-			V3 bsdfVal = MSK ? BsdfMasked<BT>::sample(tab, twoSided, BP, maskP, its.wi, s0, s1, woL, bsdfPdf, sampledType)
+			V3 bsdfVal = SNW ? BsdfSnow2::sample(twoSided, snowKind, snowD, BP, maskP, its.wi, s0, s1, woL, bsdfPdf, sampledType)
+			           : MSK ? BsdfMasked<BT>::sample(tab, twoSided, BP, maskP, its.wi, s0, s1, woL, bsdfPdf, sampledType)
 			                 : Bsdf2<BT>::sample(tab, twoSided, BP, its.wi, s0, s1, woL, bsdfPdf, sampledType);
 			if (!isZero(bsdfVal))
 				bsdfVal = bsdfVal * fabsf(woL.z);          // sampleCos (bsdf.h:273-279)
@@ -296,11 +306,11 @@ struct ShadeShared {
 };
 // One workgroup of k_shade: the paths block * kShadeBlock .. of the material queue whose segment sizes are `prefix`
 // (prefix[kBinShards] entries in kBinShards segments of bin_ids)
-template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false>
+template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false, bool SNW = false>
 __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const uint32_t *prefix,
                                             const uint32_t *bin_ids, const uint32_t block, ShadeShared &sh, const DColors &col,
                                             const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr },
-                                            const DMasks &msk = DMasks{ nullptr }) {
+                                            const DMasks &msk = DMasks{ nullptr }, const DSnows &snw = DSnows{ nullptr }) {
 	uint32_t (&s_cnt)[2][kShadeBlock / 64] = sh.cnt;
 	uint32_t (&s_base)[2] = sh.base;
 	float4 (&s_rows)[kShadeBlock / 64][64 * kRowStride] = sh.rows;
@@ -386,7 +396,7 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	}
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	if (active)
-		shade_path<BT, ROUNDS, SKY, VCOL, TAN, MSK>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col, tex, tan, msk);
+		shade_path<BT, ROUNDS, SKY, VCOL, TAN, MSK, SNW>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col, tex, tan, msk, snw);
 	// the pending direct-light term is parked in the record with the write-back below (the line is written whole anyway):
 	// the any-hit kernel clears the slot if the shadow ray is occluded, the record's next reader adds what is still there
 	if (q.nee_parked && wantShadow) row[2] = make_float4(neeV.x, neeV.y, neeV.z, __uint_as_float(kNeeTag));
@@ -475,6 +485,17 @@ __global__ MG_SHADE_BOUNDS void k_shade_msk(DScene sc, DPaths ps, DConfig cfg, D
                                                            DMasks msk) {
 	__shared__ ShadeShared sh;
 	shade_block<BT, ROUNDS, SKY, kSlotTexture, true, true>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col, tex, tan, msk);
+}
+// and for scenes with a snow BRDF (DSnows), built on the mask kernels: the only ones that take the snow table, its last
+// argument.  Bin 0 only: a snow record sits on a Lambertian entry.  Any of the other tables may be NULL here.  Device-driven
+// bounces launch this kernel next to the fused one, which then leaves bin 0 out (the composite's bin 9 is launched likewise)
+template <int BT, bool ROUNDS, bool SKY>
+__global__ MG_SHADE_BOUNDS void k_shade_snw(DScene sc, DPaths ps, DConfig cfg, DQueues q, BinView view_host,
+                                                           const BinView *views_dev, const uint32_t *bin_ids, DColors col, DTextures tex, DTangents tan,
+                                                           DMasks msk, DSnows snw) {
+	static_assert(BT == 0, "a snow record sits on a Lambertian entry");
+	__shared__ ShadeShared sh;
+	shade_block<BT, ROUNDS, SKY, kSlotTexture, true, true, true>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col, tex, tan, msk, snw);
 }
 
 // All material queues of a bounce in ONE launch (device-driven bounces): the workgroups are dealt to the bins in bin order,

@@ -169,6 +169,7 @@ class SceneDescription:
         self.bsdf_slot_texture = [] # per BSDF: [index into textures or -1] for its two texture slots
         self._slot_textures = ()
         self.bsdf_masks = {}        # BSDF index -> the opacity of the mask around it: an RGB triple or an entry of textures
+        self.bsdf_snow = {}         # BSDF index -> (abi.SNOW_*, the raw parameters its configure call takes)
         self.lum_type = []
         self.lum_params = []
         self.camera = dict(origin=(0.0, 1.0, 3.4), target=(0.0, 1.0, 0.0), up=(0.0, 1.0, 0.0), fov=39.3)
@@ -336,6 +337,31 @@ class SceneDescription:
             else:
                 rows.append((abi.MASK_CONSTANT, -1, _rgb(o)))
         return rows
+
+    def wiscombe(self, g=0.874, depth=1.0, w0=0.99, sigma_t=(16.4967, 6.0957, 4.6547)):
+        """<bsdf type="wiscombe"> with the reference's defaults (wiscombe.cpp:44-55): a Lambertian entry whose block is zero and
+        is not read, with a snow record; raw = g, depth, w0 rgb, sigmaT rgb (what Wiscombe::serialize writes)"""
+        b = self.add_bsdf(abi.BSDF_LAMBERTIAN, [0.0, 0.0, 0.0])
+        self.bsdf_snow[b] = (abi.SNOW_WISCOMBE, np.array([F(g), F(depth)] + _rgb(w0) + _rgb(sigma_t), dtype=np.float32))
+        return b
+
+    def hanrahan_krueger(self, sigma_a=(0.0014, 0.0025, 0.0142), sigma_s=(0.7, 1.22, 1.9), size_multiplier=1.0, g=0.0, eta_int=1.32,
+                         eta_ext=1.0, ss_factor=1.0, dr_factor=1.0, diffuse_reflectance=True):
+        """<bsdf type="hanrahankrueger"> with the reference's defaults (hanrahan-krueger.cpp:46-74): as wiscombe(); raw = sigmaA
+        rgb, sigmaS rgb (both times the size multiplier, in binary32), g, etaInt, etaExt, ssFactor rgb, drFactor rgb, the flag"""
+        m = F(size_multiplier)
+        raw = [F(x) * m for x in _rgb(sigma_a)] + [F(x) * m for x in _rgb(sigma_s)] + [F(g), F(eta_int), F(eta_ext)] \
+            + _rgb(ss_factor) + _rgb(dr_factor) + [F(1.0 if diffuse_reflectance else 0.0)]
+        b = self.add_bsdf(abi.BSDF_LAMBERTIAN, [0.0, 0.0, 0.0])
+        self.bsdf_snow[b] = (abi.SNOW_HK, np.array(raw, dtype=np.float32))
+        return b
+
+    def snow_table(self, configure=None):
+        """one entry per BSDF: what mtsgpu_bsdf_snow holds, None for a BSDF without a snow record.  configure(kind, raw) is the
+        reference's configure() -- by default the library's own (snow_configure: mtsgpu_wiscombe_configure, mtsgpu_hk_configure)"""
+        if configure is None:
+            from . import snow_configure as configure
+        return [configure(*self.bsdf_snow[b]) if b in self.bsdf_snow else None for b in range(len(self.bsdf_type))]
 
     def point_light(self, position, intensity):
         l = self.add_lum(abi.LUM_POINT, [intensity] * 3 if np.isscalar(intensity) else intensity)

@@ -429,7 +429,8 @@ int  mtsgpu_set_uv_bitmap_textures(mtsgpu_ctx *ctx, const float *vtx_uv, const u
                                    const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap);
 /* The mask BSDF (src/bsdfs/mask.cpp) -- its side table and the call that hands it over, a superset of the call above -- is an
  * extension of this ABI with a header of its own, mtsgpu_mask.h: the list of entry points declared here is part of ABI version 8.
- * Likewise the snow BRDFs (src/bsdfs/wiscombe.cpp, hanrahan-krueger.cpp), a side table on Lambertian entries: mtsgpu_snow.h. */
+ * Likewise the snow BRDFs (src/bsdfs/wiscombe.cpp, hanrahan-krueger.cpp), a side table on Lambertian entries: mtsgpu_snow.h;
+ * and the woven-cloth BRDF (src/bsdfs/irawan.cpp), a weave pool and a side table on Lambertian entries: mtsgpu_cloth.h. */
 /* LDRTexture::initializeFrom (ldrtexture.cpp:116-202) and MIPMap::fromBitmap (mipmap.cpp:156-177) on the host: the decoded
  * file's bytes -> the texels an mtsgpu_bitmap takes.  data: height rows of width pixels of bpp bits -- 32 (r g b a), 24 (r g b),
  * 16 (luminance a), 8 (luminance), 1 (bit pos % 8 of byte pos / 8, pos counting pixels without row padding; set = 255).  The

@@ -42,6 +42,7 @@
 #include <mtsgpu.h>
 #include <mtsgpu_mask.h>
 #include <mtsgpu_snow.h>
+#include <mtsgpu_cloth.h>
 #include "streamparse.h"
 #include <sstream>
 #include <cstdlib>
@@ -150,6 +151,24 @@ struct FlatScene {
 		for (size_t b = 0; b < bsdfSnow.size(); ++b)
 			if (bsdfSnow[b].kind != MTSGPU_SNOW_NONE) return mtsgpu_group_set_snow_bsdfs(group, ptr(bsdfSnow));
 		return MTSGPU_OK;
+	}
+	/* the weaves of the `irawan` BSDFs and per BSDF table entry its weave (none: -1): what mtsgpu_group_set_cloth_bsdfs takes.  A
+	 * cloth mesh has its tangents from Mitsuba itself: IrawanClothBRDF is EAnisotropic, so TriMesh::configure computed them */
+	mtsgpu_stream::ClothTable cloth;
+	/* after upload(), the colour and texture calls and setSnowBsdfs(): hands the cloth table over when a BSDF has a weave.  The
+	 * cloth kernels read its.uv, so a scene whose texture call had nothing to hand over (no uv texture, no mask) first hands the
+	 * texcoords of its meshes over alone; a sphere's its.uv comes from the hit point and needs none */
+	int setClothBsdfs(mtsgpu_group *group) {
+		if (!cloth.any()) return MTSGPU_OK;
+		bool anyMask = false;
+		for (size_t b = 0; b < bsdfMasks.size(); ++b) if (bsdfMasks[b].kind != MTSGPU_MASK_NONE) anyMask = true;
+		if (uvTextures.empty() && !anyMask && anyUv) {
+			const int rc = mtsgpu_group_set_uv_textures(group, ptr(vtxUv), ptr(shapeHasUv), 0, NULL, NULL);
+			if (rc != MTSGPU_OK) return rc;
+		}
+		std::vector<mtsgpu_weave> weaves;
+		cloth.fill(weaves);
+		return mtsgpu_group_set_cloth_bsdfs(group, (uint32_t) weaves.size(), ptr(weaves), ptr(cloth.bsdfWeave));
 	}
 	/* vertex tangents (TriMesh::getVertexTangents, trimesh.h:136-140: TriMesh::configure computes them for a mesh whose BSDF is
 	 * anisotropic, trimesh.cpp:288-290): dpdu in the order of vtxPos, one flag per shape -- what
@@ -499,7 +518,7 @@ private:
 		std::string err;
 		const size_t firstEntry = bsdfType.size(), firstLdr = ldrTextures.size();
 		const int index = mtsgpu_stream::parseBSDFTable<Float>(st->getData(), st->getSize(), bsdfType, bsdfParams, &err, &bsdfColorSlots, &uvTextures, &bsdfSlotTexture,
-			&ldrTextures, &bsdfMasks, &bsdfSnow, &mtsgpu_wiscombe_configure);
+			&ldrTextures, &bsdfMasks, &bsdfSnow, &mtsgpu_wiscombe_configure, &cloth);
 		if (index < 0)
 			SLog(EError, "gpupath: %s", err.c_str());
 		for (size_t k = firstLdr; k < ldrTextures.size(); ++k)
@@ -561,6 +580,7 @@ struct GPURenderDriver {
 			check(flat.setVertexColors(group));
 			check(flat.setUvTextures(group));
 			check(flat.setSnowBsdfs(group));
+			check(flat.setClothBsdfs(group));
 		}
 
 		/* --- camera: raster space of the FULL film, crop window as offset + size (perspective.cpp:43-71, film.cpp:33-41) --- */

@@ -18,6 +18,7 @@
 #include <mtsgpu.h>
 #include <mtsgpu_mask.h>
 #include <mtsgpu_snow.h>
+#include <mtsgpu_cloth.h>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -396,12 +397,44 @@ inline std::string hkRefusal() {
 	       "constructor reads nothing, so g, etaInt, etaExt, ssFactor, drFactor and diffuseReflectance are out of reach: the BRDF is served "
 	       "through the C ABI (mtsgpu_hk_configure, mtsgpu_set_snow_bsdfs) only";
 }
+/* cloth (optional): the weaves of the IrawanClothBRDFs and one weave index per appended entry, -1 without one (what
+ * mtsgpu_set_cloth_bsdfs takes once ClothTable::fill has set the pointers).  With it an IrawanClothBRDF -- after BSDF::serialize's own
+ * fields WeavePattern::serialize (irawan.h:191-211: the name, alpha, beta, ss, hWidth, warpArea, weftArea, tileWidth, tileHeight,
+ * the four d*UmaxOverD*, fineness, period, the pattern array of tileWidth * tileHeight words, writeSize of the yarn count, per yarn
+ * type, psi, umax, kappa, width, length, centerU, centerV and the two Spectrums), then repeatU, repeatV, kdMultiplier,
+ * ksMultiplier (irawan.cpp:265-273) -- becomes a Lambertian entry whose block is zero, with its weave; twosided(Irawan) sets the
+ * bit.  Refused with the reason: under a Mask, as a composite's child, a tile dimension of zero or above 32768 (the library's
+ * limit).  What the library checks of a weave (mtsgpu_cloth.h) it checks when the table is handed over.  Without the list the
+ * class is refused like every class that is not on this path. */
+struct ClothWeave {
+	mtsgpu_weave w;                      /* pattern and yarns are NULL until ClothTable::fill */
+	std::string name;
+	std::vector<uint32_t> pattern;
+	std::vector<mtsgpu_yarn> yarns;
+};
+struct ClothTable {
+	std::vector<ClothWeave> weaves;
+	std::vector<int32_t> bsdfWeave;
+	bool any() const { return !weaves.empty(); }
+	/* the array mtsgpu_set_cloth_bsdfs takes: valid while this table is neither changed nor destroyed */
+	void fill(std::vector<mtsgpu_weave> &out) {
+		out.resize(weaves.size());
+		for (size_t k = 0; k < weaves.size(); ++k) {
+			weaves[k].w.n_pattern = (uint32_t) weaves[k].pattern.size(); weaves[k].w.n_yarns = (uint32_t) weaves[k].yarns.size();
+			weaves[k].w.pattern = weaves[k].pattern.empty() ? NULL : &weaves[k].pattern[0];
+			weaves[k].w.yarns = weaves[k].yarns.empty() ? NULL : &weaves[k].yarns[0];
+			out[k] = weaves[k].w;
+		}
+	}
+};
 template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t size, std::vector<uint32_t> &types, std::vector<float> &params,
                                                      std::string *err, std::vector<uint32_t> *colorSlots = NULL,
                                                      std::vector<mtsgpu_uv_texture> *uvTextures = NULL, std::vector<int32_t> *slotTextures = NULL,
                                                      std::vector<LdrTexture> *bitmaps = NULL, std::vector<mtsgpu_bsdf_mask> *masks = NULL,
-                                                     std::vector<mtsgpu_bsdf_snow> *snow = NULL, WiscombeConfigure wiscombeConfigure = NULL) {
+                                                     std::vector<mtsgpu_bsdf_snow> *snow = NULL, WiscombeConfigure wiscombeConfigure = NULL,
+                                                     ClothTable *cloth = NULL) {
 	BSDFStream<FloatT> rd(data, size);
+	const size_t firstWeave = cloth ? cloth->weaves.size() : 0;
 	mtsgpu_bsdf_snow noSnow;
 	memset(&noSnow, 0, sizeof(noSnow)); noSnow.kind = MTSGPU_SNOW_NONE;
 	const size_t first = types.size(), firstTex = uvTextures ? uvTextures->size() : 0, firstBmp = bitmaps ? bitmaps->size() : 0;
@@ -448,6 +481,42 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 		if (slotTextures) slotTextures->insert(slotTextures->end(), 2, (int32_t) -1);
 		if (masks) masks->push_back(none);
 		snow->push_back(record);
+		if (cloth) cloth->bsdfWeave.push_back(-1);
+		own = (int) types.size() - 1;
+	} else if (cloth && rd.className() == "IrawanClothBRDF") {
+		ClothWeave cw;
+		memset(&cw.w, 0, sizeof(cw.w));
+		mtsgpu_weave &w = cw.w;
+		cw.name = rd.r.readString();
+		w.alpha = (float) rd.r.readFloat(); w.beta = (float) rd.r.readFloat(); w.ss = (float) rd.r.readFloat(); w.hWidth = (float) rd.r.readFloat();
+		w.warpArea = (float) rd.r.readFloat(); w.weftArea = (float) rd.r.readFloat();
+		w.tileWidth = rd.r.readUInt(); w.tileHeight = rd.r.readUInt();
+		w.dWarpUmaxOverDWarp = (float) rd.r.readFloat(); w.dWarpUmaxOverDWeft = (float) rd.r.readFloat();
+		w.dWeftUmaxOverDWarp = (float) rd.r.readFloat(); w.dWeftUmaxOverDWeft = (float) rd.r.readFloat();
+		w.fineness = (float) rd.r.readFloat(); w.period = (float) rd.r.readFloat();
+		if (rd.r.ok() && (w.tileWidth == 0 || w.tileHeight == 0 || w.tileWidth > 32768u || w.tileHeight > 32768u))
+			rd.r.fail("IrawanClothBRDF: tile of " + std::to_string(w.tileWidth) + " x " + std::to_string(w.tileHeight) + ": a dimension is zero or above 32768");
+		for (uint64_t i = 0, n = (uint64_t) w.tileWidth * w.tileHeight; i < n && rd.r.ok(); ++i) cw.pattern.push_back(rd.r.readUInt());
+		const uint64_t nYarns = rd.r.ok() ? rd.r.readSize() : 0;
+		for (uint64_t i = 0; i < nYarns && rd.r.ok(); ++i) {
+			mtsgpu_yarn y;
+			y.type = (uint32_t) rd.r.readInt();
+			y.psi = (float) rd.r.readFloat(); y.umax = (float) rd.r.readFloat(); y.kappa = (float) rd.r.readFloat();
+			y.width = (float) rd.r.readFloat(); y.length = (float) rd.r.readFloat();
+			y.centerU = (float) rd.r.readFloat(); y.centerV = (float) rd.r.readFloat();
+			rd.r.readSpectrum(y.kd); rd.r.readSpectrum(y.ks);
+			cw.yarns.push_back(y);
+		}
+		w.repeatU = (float) rd.r.readFloat(); w.repeatV = (float) rd.r.readFloat();
+		w.kdMultiplier = (float) rd.r.readFloat(); w.ksMultiplier = (float) rd.r.readFloat();
+		if (rd.r.ok() && mask.kind != MTSGPU_MASK_NONE) rd.r.fail("a Mask around an IrawanClothBRDF is not supported");
+		types.push_back(MTSGPU_BSDF_LAMBERTIAN | flags); params.insert(params.end(), MTSGPU_BSDF_NPARAMS, 0.0f);
+		if (colorSlots) colorSlots->push_back(0u);
+		if (slotTextures) slotTextures->insert(slotTextures->end(), 2, (int32_t) -1);
+		if (masks) masks->push_back(none);
+		if (snow) snow->push_back(noSnow);
+		cloth->bsdfWeave.push_back((int32_t) cloth->weaves.size());
+		cloth->weaves.push_back(cw);
 		own = (int) types.size() - 1;
 	} else if (rd.className() != "Composite") {
 		types.push_back(0); params.insert(params.end(), MTSGPU_BSDF_NPARAMS, 0.0f);
@@ -457,6 +526,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 		if (slotTextures) slotTextures->insert(slotTextures->end(), rd.slotTextures(), rd.slotTextures() + 2);
 		if (masks) masks->push_back(mask);
 		if (snow) snow->push_back(noSnow);
+		if (cloth) cloth->bsdfWeave.push_back(-1);
 		own = (int) types.size() - 1;
 	} else {
 		const uint64_t n = rd.r.readSize();
@@ -474,6 +544,9 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 			if (!rd.r.ok()) break;
 			if (rd.className() == "Composite") { rd.r.fail("Composite: nested composites are not supported"); break; }
 			if (masks && rd.className() == "Mask") { rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " is a Mask: a mask is the outermost adapter, not supported as a composite's child"); break; }
+			if (cloth && rd.className() == "IrawanClothBRDF") {
+				rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " is an IrawanClothBRDF: the composite's loop would run its entry as a Lambertian, not supported"); break;
+			}
 			if (snow && (rd.className() == "Wiscombe" || rd.className() == "HanrahanKrueger")) {
 				rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " is a " + rd.className() + ": the composite's loop would run its entry as a Lambertian, not supported"); break;
 			}
@@ -487,6 +560,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 			if (slotTextures) slotTextures->insert(slotTextures->end(), 2, (int32_t) -1);
 			if (masks) masks->push_back(none);
 			if (snow) snow->push_back(noSnow);
+			if (cloth) cloth->bsdfWeave.push_back(-1);
 			if (rd.r.ok() && rd.hasSlotTexture()) { rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " (" + rd.className() + ") has a uv texture: a composite's children keep constant parameters, not supported"); break; }
 			if (rd.r.ok() && slots) { rd.r.fail("Composite: child " + std::to_string((unsigned long long) i) + " (" + rd.className() + ") takes vertex colours: a composite's children keep constant parameters, not supported"); break; }
 			block[1 + n + i] = (float) (types.size() - 1);
@@ -497,6 +571,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 			if (slotTextures) slotTextures->insert(slotTextures->end(), 2, (int32_t) -1);
 			if (masks) masks->push_back(none);
 			if (snow) snow->push_back(noSnow);
+			if (cloth) cloth->bsdfWeave.push_back(-1);
 			params.insert(params.end(), block, block + MTSGPU_BSDF_NPARAMS);
 			own = (int) types.size() - 1;
 		}
@@ -507,6 +582,7 @@ template <typename FloatT> inline int parseBSDFTable(const uint8_t *data, size_t
 		if (slotTextures) slotTextures->resize(2 * first);
 		if (masks) masks->resize(first);
 		if (snow) snow->resize(first);
+		if (cloth) { cloth->bsdfWeave.resize(first); cloth->weaves.resize(firstWeave); }
 		if (uvTextures) uvTextures->resize(firstTex);
 		if (bitmaps) bitmaps->resize(firstBmp);
 		if (err) *err = rd.r.error() + " (while reading a " + rd.className() + ")";

@@ -18,6 +18,7 @@ import numpy as np
 
 from . import abi, scenes, filmreduce, testmode  # noqa: F401
 from .testmode import write_mfile, analyze  # noqa: F401
+from .scenes import load_weave, Weave, Yarn  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MTSGPU_LIB selects an experiment build (tools/build_variant.sh); the product is libmtsgpu.so next to this file
@@ -50,6 +51,9 @@ MASK_EXPORTS = ["mtsgpu_set_uv_masked_textures", "mtsgpu_group_set_uv_masked_tex
 # the snow BRDFs' entry points (wiscombe, hanrahankrueger): the extension declared in include/mtsgpu_snow.h
 SNOW_EXPORTS = ["mtsgpu_wiscombe_configure", "mtsgpu_hk_configure", "mtsgpu_set_snow_bsdfs", "mtsgpu_group_set_snow_bsdfs",
                 "mtsgpu_bsdf_eval_snow"]
+# the woven-cloth BRDF's entry points (irawan): the extension declared in include/mtsgpu_cloth.h
+CLOTH_EXPORTS = ["mtsgpu_set_cloth_bsdfs", "mtsgpu_group_set_cloth_bsdfs", "mtsgpu_flatten_tangents_flagged", "mtsgpu_bsdf_eval_cloth",
+                 "mtsgpu_cloth_check", "mtsgpu_devmath"]
 
 
 class MtsGpuError(RuntimeError):
@@ -257,6 +261,13 @@ def lib():
     L.mtsgpu_set_snow_bsdfs.argtypes = [vp, snwp]
     L.mtsgpu_group_set_snow_bsdfs.argtypes = [vp, snwp]
     L.mtsgpu_bsdf_eval_snow.argtypes = [vp, C.c_uint32, snwp, C.c_int, C.c_uint32, f32p, f32p]
+    wvp = C.POINTER(abi.Weave)
+    L.mtsgpu_set_cloth_bsdfs.argtypes = [vp, C.c_uint32, wvp, abi.i32p]
+    L.mtsgpu_group_set_cloth_bsdfs.argtypes = [vp, C.c_uint32, wvp, abi.i32p]
+    L.mtsgpu_bsdf_eval_cloth.argtypes = [vp, C.c_uint32, wvp, C.c_int, C.c_uint32, f32p, f32p]
+    L.mtsgpu_cloth_check.argtypes = [wvp, f32p]
+    L.mtsgpu_devmath.argtypes = [C.c_int, C.c_uint32, f32p, f32p, f32p]
+    L.mtsgpu_flatten_tangents_flagged.argtypes = L.mtsgpu_flatten_tangents.argtypes[:3] + [u32p] + L.mtsgpu_flatten_tangents.argtypes[3:]
     L.mtsgpu_ldr_texels.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_float, f32p]
     _lib = L
     return L
@@ -303,6 +314,46 @@ def bsdf_snow_array(rows):
             d = np.zeros(abi.SNOW_NDERIVED, dtype=np.float32); d[:len(derived)] = derived
             arr[i] = abi.BsdfSnow(int(kind), 0, (C.c_float * abi.SNOW_NDERIVED)(*[float(x) for x in d]))
     return arr
+
+
+def weave_array(weaves):
+    """scenes.Weave objects -> (the ctypes array of mtsgpu_weave that mtsgpu_set_cloth_bsdfs takes, the arrays it points into)"""
+    arr = (abi.Weave * max(len(weaves), 1))()
+    keep = []
+    for i, w in enumerate(weaves):
+        for n in abi.WEAVE_SCALARS:
+            setattr(arr[i], n, getattr(w, n))
+        pat = (C.c_uint32 * max(len(w.pattern), 1))(*[int(p) & 0xFFFFFFFF for p in w.pattern])
+        yarns = (abi.Yarn * max(len(w.yarns), 1))()
+        for j, y in enumerate(w.yarns):
+            yarns[j] = abi.Yarn(int(y.type), float(y.psi), float(y.umax), float(y.kappa), float(y.width), float(y.length), float(y.centerU),
+                                float(y.centerV), (C.c_float * 3)(*[float(x) for x in y.kd]), (C.c_float * 3)(*[float(x) for x in y.ks]))
+        arr[i].n_pattern, arr[i].n_yarns = len(w.pattern), len(w.yarns)
+        arr[i].pattern, arr[i].yarns = C.cast(pat, C.POINTER(C.c_uint32)), C.cast(yarns, C.POINTER(abi.Yarn))
+        keep += [pat, yarns]
+    return arr, keep
+
+
+def cloth_check(weave, uv_range=None):
+    """mtsgpu_cloth_check: what the cloth setter requires of one scenes.Weave, and with uv_range = (uMin, uMax, vMin, vMax) the casts
+    of f on such texcoords; raises MtsGpuError with the reason"""
+    arr, keep = weave_array([weave])
+    r = None if uv_range is None else np.ascontiguousarray(uv_range, dtype=np.float32)
+    if lib().mtsgpu_cloth_check(arr, abi.ptr(r, abi.f32p)) != 0:
+        raise MtsGpuError("cloth_check: %s" % lib().mtsgpu_last_error(None).decode())
+
+
+DEVMATH = dict(sin=0, cos=1, tan=2, exp=3, log=4, atan=5, acos=6, atan2=7, sinh=8, cosh=9, pow15=10)
+
+
+def devmath(fn, x, y=None):
+    """mtsgpu_devmath: the library's elementary function `fn` (a key of DEVMATH) of float32 arguments, on the host"""
+    x = np.ascontiguousarray(x, dtype=np.float32).ravel()
+    y = None if y is None else np.ascontiguousarray(y, dtype=np.float32).ravel()
+    out = np.zeros_like(x)
+    if lib().mtsgpu_devmath(DEVMATH[fn], len(x), abi.ptr(x, abi.f32p), abi.ptr(y, abi.f32p), abi.ptr(out, abi.f32p)) != 0:
+        raise MtsGpuError("devmath: %s" % lib().mtsgpu_last_error(None).decode())
+    return out
 
 
 def uv_texture_array(textures):
@@ -368,13 +419,23 @@ class Scene:
         # the _tangents calls only when a mesh with texcoords has an anisotropic BSDF (TriMesh::configure asks for tangents
         # then, trimesh.cpp:288-290); every other scene goes through the calls it always went through
         self.wants_tangents = any(m.shape_type == abi.SHAPE_TRIMESH and getattr(m, "texcoords", None) is not None and m.bsdf >= 0
-                                  and description.bsdf_is_anisotropic(m.bsdf) for m in description.meshes)
+                                  and (description.bsdf_is_anisotropic(m.bsdf) or m.bsdf in getattr(description, "bsdf_weave", {}))
+                                  for m in description.meshes)
+        # the cloth BSDFs of the scene (none: the scene never calls mtsgpu_set_cloth_bsdfs): IrawanClothBRDF is EAnisotropic and its
+        # Lambertian entry is not, so its entries are flagged for the flattener
+        self.cloth = None
+        if getattr(description, "bsdf_weave", None):
+            self.cloth = weave_array(description.weaves) + (description.weave_table(),)
         if self.wants_tangents:
             tcs = (abi.f32p * max(len(description.meshes), 1))()
             for i, m in enumerate(description.meshes):
                 if m.shape_type == abi.SHAPE_TRIMESH and getattr(m, "texcoords", None) is not None:
                     tcs[i] = abi.ptr(m.texcoords, abi.f32p)
-            rc = lib().mtsgpu_flatten_tangents(C.byref(self._desc), C.byref(kp), tcs, C.byref(self._h))
+            if self.cloth is not None:
+                flags = np.ascontiguousarray(self.cloth[2] >= 0, dtype=np.uint32)
+                rc = lib().mtsgpu_flatten_tangents_flagged(C.byref(self._desc), C.byref(kp), tcs, abi.ptr(flags, abi.u32p), C.byref(self._h))
+            else:
+                rc = lib().mtsgpu_flatten_tangents(C.byref(self._desc), C.byref(kp), tcs, C.byref(self._h))
         else:
             rc = lib().mtsgpu_flatten(C.byref(self._desc), C.byref(kp), C.byref(self._h))
         if rc != 0:
@@ -426,6 +487,16 @@ class Scene:
         uv = lib().mtsgpu_flat_scene_vertex_texcoords(self._h)
         has = lib().mtsgpu_flat_scene_shape_has_texcoords(self._h)
         return (uv if uv else None, has if has else None, len(self.textures), self.textures, abi.ptr(self.bsdf_slot_texture, abi.i32p))
+
+    def uv_only_args(self):
+        """what mtsgpu_set_uv_textures takes to hand over the texcoords alone (a cloth scene without a uv texture)"""
+        uv = lib().mtsgpu_flat_scene_vertex_texcoords(self._h)
+        has = lib().mtsgpu_flat_scene_shape_has_texcoords(self._h)
+        if not uv:       # no mesh has texcoords (spheres only): a zero pool, so that the call keeps a uv array
+            n = max(int(self.sc.n_verts), 1)
+            self._uv_zero = (np.zeros((n, 2), dtype=np.float32), np.zeros(max(int(self.sc.n_shapes), 1), dtype=np.uint32))
+            return (abi.ptr(self._uv_zero[0], abi.f32p), abi.ptr(self._uv_zero[1], abi.u32p), 0, None, None)
+        return (uv, has, 0, None, None)
 
     def uv_bitmap_texture_args(self):
         """what mtsgpu_set_uv_bitmap_textures takes for this scene: uv_texture_args() and (n_bitmaps, bitmaps, texture_bitmap), or
@@ -603,6 +674,11 @@ class MIPathTracer:
             self._chk(lib().mtsgpu_set_uv_textures(self._ctx, *ut), "set_uv_textures")
         if isinstance(scene, Scene) and scene.bsdf_snow is not None:
             self._chk(lib().mtsgpu_set_snow_bsdfs(self._ctx, scene.bsdf_snow), "set_snow_bsdfs")
+        if isinstance(scene, Scene) and scene.cloth is not None:
+            if um is None and ub is None and ut is None:       # no texture call has handed the texcoords over: one without textures
+                self._chk(lib().mtsgpu_set_uv_textures(self._ctx, *scene.uv_only_args()), "set_uv_textures")
+            self._chk(lib().mtsgpu_set_cloth_bsdfs(self._ctx, len(scene.description.weaves), scene.cloth[0], abi.ptr(scene.cloth[2], abi.i32p)),
+                      "set_cloth_bsdfs")
         self.camera = camera
         self._chk(lib().mtsgpu_set_camera(self._ctx, C.byref(camera.c if hasattr(camera, "c") else camera)), "set_camera")
         kind = {"independent": abi.SAMPLER_INDEPENDENT_KEYED, "ldsampler": abi.SAMPLER_LD_KEYED, "halton": abi.SAMPLER_HALTON,
@@ -844,6 +920,31 @@ class MIPathTracer:
                   "bsdf_eval_snow")
         return out
 
+    def set_cloth_bsdfs(self, weaves=None, bsdf_weave=None):
+        """mtsgpu_set_cloth_bsdfs on the uploaded scene: scenes.Weave objects and one weave index (or -1) per BSDF; None switches
+        the table off"""
+        if bsdf_weave is None:
+            self._chk(lib().mtsgpu_set_cloth_bsdfs(self._ctx, 0, None, None), "set_cloth_bsdfs")
+            return
+        arr, keep = weave_array(list(weaves or []))
+        table = np.ascontiguousarray(bsdf_weave, dtype=np.int32)
+        self._chk(lib().mtsgpu_set_cloth_bsdfs(self._ctx, len(weaves or []), arr, abi.ptr(table, abi.i32p)), "set_cloth_bsdfs")
+
+    def bsdf_eval_cloth(self, bsdf_type, weave, op, wi, aux, uv):
+        """bsdf_eval() of the cloth BRDF with the scenes.Weave `weave` at its.uv = uv (mtsgpu_bsdf_eval_cloth); op 3: the
+        internals of f (yarn id, centre x, y, random1, random2, intensityVariation, u, v) -> [n][8]"""
+        aux = np.atleast_2d(np.asarray(aux, dtype=np.float32))
+        n = aux.shape[0]
+        q = np.zeros((n, 8), dtype=np.float32)
+        q[:, :3] = np.asarray(wi, dtype=np.float32).reshape(-1, 3)
+        q[:, 3:3 + aux.shape[1]] = aux
+        q[:, 6:8] = np.asarray(uv, dtype=np.float32).reshape(-1, 2)
+        arr, keep = weave_array([weave])
+        out = np.zeros((n, 8), dtype=np.float32)
+        self._chk(lib().mtsgpu_bsdf_eval_cloth(self._ctx, int(bsdf_type), arr, int(op), n, abi.ptr(q, abi.f32p), abi.ptr(out, abi.f32p)),
+                  "bsdf_eval_cloth")
+        return out
+
     def bsdf_eval_masked(self, bsdf_type, params, opacity, op, wi, aux):
         """bsdf_eval() through the mask adapter whose opacity is the spectrum `opacity` (mtsgpu_bsdf_eval_masked) -> [n][8]"""
         aux = np.atleast_2d(np.asarray(aux, dtype=np.float32))
@@ -1048,6 +1149,11 @@ class DeviceGroup:
             self._chk(lib().mtsgpu_group_set_uv_textures(self._g, *ut), "set_uv_textures")
         if isinstance(scene, Scene) and scene.bsdf_snow is not None:
             self._chk(lib().mtsgpu_group_set_snow_bsdfs(self._g, scene.bsdf_snow), "set_snow_bsdfs")
+        if isinstance(scene, Scene) and scene.cloth is not None:
+            if um is None and ub is None and ut is None:
+                self._chk(lib().mtsgpu_group_set_uv_textures(self._g, *scene.uv_only_args()), "set_uv_textures")
+            self._chk(lib().mtsgpu_group_set_cloth_bsdfs(self._g, len(scene.description.weaves), scene.cloth[0], abi.ptr(scene.cloth[2], abi.i32p)),
+                      "set_cloth_bsdfs")
         self.camera = camera
         self._chk(lib().mtsgpu_group_set_camera(self._g, C.byref(camera.c)), "set_camera")
         kind = {"independent": abi.SAMPLER_INDEPENDENT_KEYED, "ldsampler": abi.SAMPLER_LD_KEYED, "halton": abi.SAMPLER_HALTON,

@@ -20,6 +20,7 @@ BITMAP_MAX_TEXELS = 2147483647
 MASK_NONE, MASK_CONSTANT, MASK_TEXTURE = 0, 1, 2                    # MTSGPU_MASK_*
 SNOW_NONE, SNOW_WISCOMBE, SNOW_HK = 0, 1, 2                          # MTSGPU_SNOW_*
 SNOW_NDERIVED = 14
+YARN_WARP, YARN_WEFT = 0, 1                                         # MTSGPU_YARN_*
 LUM_AREA, LUM_CONSTANT, LUM_POINT, LUM_DIRECTIONAL, LUM_SPOT, LUM_ENVMAP, LUM_COLLIMATED, LUM_SKY = 0, 1, 2, 3, 4, 5, 6, 7
 LUM_NPARAMS = 32
 SKY_NDERIVED = 24
@@ -54,6 +55,23 @@ class BsdfMask(C.Structure):
 class BsdfSnow(C.Structure):
     """mtsgpu_bsdf_snow"""
     _fields_ = [("kind", C.c_uint32), ("reserved", C.c_uint32), ("derived", C.c_float * SNOW_NDERIVED)]
+
+
+class Yarn(C.Structure):
+    """mtsgpu_yarn"""
+    _fields_ = [("type", C.c_uint32), ("psi", C.c_float), ("umax", C.c_float), ("kappa", C.c_float), ("width", C.c_float),
+                ("length", C.c_float), ("centerU", C.c_float), ("centerV", C.c_float), ("kd", C.c_float * 3), ("ks", C.c_float * 3)]
+
+
+WEAVE_SCALARS = ("alpha", "beta", "ss", "hWidth", "warpArea", "weftArea", "tileWidth", "tileHeight", "dWarpUmaxOverDWarp",
+                 "dWarpUmaxOverDWeft", "dWeftUmaxOverDWarp", "dWeftUmaxOverDWeft", "fineness", "period", "repeatU", "repeatV",
+                 "kdMultiplier", "ksMultiplier")
+
+
+class Weave(C.Structure):
+    """mtsgpu_weave"""
+    _fields_ = [(n, C.c_uint32 if n in ("tileWidth", "tileHeight") else C.c_float) for n in WEAVE_SCALARS] \
+        + [("n_pattern", C.c_uint32), ("n_yarns", C.c_uint32), ("pattern", C.POINTER(C.c_uint32)), ("yarns", C.POINTER(Yarn))]
 
 
 class Scene(C.Structure):

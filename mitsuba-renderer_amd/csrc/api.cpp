@@ -375,11 +375,16 @@ int mtsgpu_flatten(const mtsgpu_scene_desc *desc, const mtsgpu_kd_params *kd, mt
 }
 
 int mtsgpu_flatten_tangents(const mtsgpu_scene_desc *desc, const mtsgpu_kd_params *kd, const float *const *mesh_texcoords, mtsgpu_flat_scene **out) {
+	return mtsgpu_flatten_tangents_flagged(desc, kd, mesh_texcoords, nullptr, out);
+}
+
+int mtsgpu_flatten_tangents_flagged(const mtsgpu_scene_desc *desc, const mtsgpu_kd_params *kd, const float *const *mesh_texcoords,
+                                    const uint32_t *bsdf_anisotropic, mtsgpu_flat_scene **out) {
 	if (!desc || !out || !mesh_texcoords) return fail(nullptr, MTSGPU_EINVAL, "null argument");
 	*out = nullptr;
 	try {
 		std::unique_ptr<mtsgpu_flat_scene> p(new mtsgpu_flat_scene());
-		flattenScene(*desc, kd, p->fs, mesh_texcoords);
+		flattenScene(*desc, kd, p->fs, mesh_texcoords, bsdf_anisotropic);
 		for (uint32_t s = 0; s < desc->n_meshes; ++s)
 			if (mesh_texcoords[s] && desc->meshes[s].shape_type == MTSGPU_SHAPE_TRIMESH) {
 				const std::string why = setMeshTexcoords(p->fs, s, mesh_texcoords[s]);

@@ -56,7 +56,7 @@ inline void freeAll(std::vector<void *> &v) { for (void *p : v) (void) hipFree(p
 struct mtsgpu_ctx {
 	// with `device` current and idle (mtsgpu_destroy): everything no DevBuf member owns.  A caller's stream or film is not ours.
 	~mtsgpu_ctx() {
-		for (auto *list : { &sceneAllocs, &colorAllocs, &texAllocs, &snowAllocs, &pathAllocs }) mg::freeAll(*list);
+		for (auto *list : { &sceneAllocs, &colorAllocs, &texAllocs, &snowAllocs, &clothAllocs, &pathAllocs }) mg::freeAll(*list);
 		if (hostCounters) (void) hipHostFree(hostCounters);
 		for (auto *pool : { &traceEvents, &shadeEvents })
 			for (auto &e : *pool) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
@@ -89,6 +89,7 @@ struct mtsgpu_ctx {
 		std::vector<uint32_t> triIdx, shapeTriOffset, shapeType, bsdfType, lumType;
 		std::vector<int32_t> shapeBsdf;
 		std::vector<float> bsdfParams;
+		std::vector<uint32_t> shapeNormals, shapeTangents;      // per shape: has vertex normals / uploaded tangents (0 / 1)
 	} host;
 	std::vector<void *> colorAllocs;
 	mg::DColors dcol{ nullptr, nullptr };   // what the vertex-colour kernels take (NULL, NULL without colours)
@@ -106,6 +107,15 @@ struct mtsgpu_ctx {
 	std::vector<void *> snowAllocs;
 	mg::DSnows dsnw{ nullptr };
 	std::vector<uint32_t> hostSnowKind, hostMaskKind;
+	// mtsgpu_set_cloth_bsdfs: DCloths' pool, owned like the snow table (clothAllocs), and a host copy of bsdf_weave (empty = no
+	// table), so that the colour, texture, mask and snow calls can refuse what a cloth entry does not take; and, from the texture
+	// call, the shapes that have texcoords with the extremes of their texcoords (uMin, uMax, vMin, vMax per shape; empty = no
+	// texture call supplied any), which the cloth call checks its casts on
+	std::vector<void *> clothAllocs;
+	mg::DCloths dclo{ nullptr, nullptr, nullptr, nullptr };
+	std::vector<int32_t> hostClothWeave;
+	std::vector<double> hostUvRange;
+	std::vector<uint32_t> hostShapeHasUv;
 	std::vector<uint32_t> hostColorSlots;
 	std::vector<int32_t> hostSlotTex;
 

@@ -213,6 +213,8 @@ HD float datan2(float y, float x) {
 	return (float) r;
 }
 
+// std::pow(x, 1.5f) (irawan.cpp:467-480): x * sqrt(x) in binary64 with the correctly rounded sqrt, rounded once
+HD float dpow15(float x) { const double b = (double) x; return (float) (b * sqrt(b)); }
 HD float dpow4(float x) { double d = (double) x * (double) x; return (float) (d * d); }
 HD float dpow3(float x) { double d = (double) x; return (float) ((d * d) * d); }      // std::pow(x, 3) (ward.cpp:193)
 
@@ -274,6 +276,20 @@ HD float dpow(float x, float y) {
 	if (x == 1.0f) return 1.0f;
 	if (x == MG_INF) return y > 0.0f ? MG_INF : 0.0f;
 	return (float) exp_d((double) y * log_d((double) x));
+}
+
+// std::sinh / std::cosh (irawan.cpp:471-475): (exp_d(x) -+ exp_d(-x)) / 2 in binary64, one rounding.  Below 2^-13 the
+// difference cancels, and sinh is its series x + x^3 / 6 (the next term is under 2^-54 relative)
+HD float dsinh(float x) {
+	if (x != x) return x;
+	const double xd = (double) x;
+	if (xd < 0.0001220703125 && xd > -0.0001220703125) return (float) (xd + ((xd * xd) * xd) * (1.0 / 6.0));
+	return (float) ((exp_d(xd) - exp_d(-xd)) * 0.5);
+}
+HD float dcosh(float x) {
+	if (x != x) return x;
+	const double xd = (double) x;
+	return (float) ((exp_d(xd) + exp_d(-xd)) * 0.5);
 }
 
 // ---------------------------------------------------------------------------

@@ -164,7 +164,7 @@ std::string setMeshTexcoords(FlatScene &f, uint32_t mesh, const float *texcoords
 	return std::string();
 }
 
-void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs, const float *const *meshTexcoords) {
+void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs, const float *const *meshTexcoords, const uint32_t *bsdfAnisotropic) {
 	const uint32_t nShapes = d.n_meshes, nLums = d.n_lums;
 	size_t nVerts = 0, nTris = 0;
 	// m_shapeMap (skdtree.cpp:43-60): a TriMesh contributes its triangles, any other shape ONE primitive
@@ -218,7 +218,9 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 		fs.shapeBsdf[s] = m.bsdf;
 		// TriMesh::configure (trimesh.cpp:288-290) asks for tangents when the BSDF is anisotropic; they need texcoords, which
 		// only mtsgpu_flatten_tangents knows at this point
-		const bool anisoMesh = m.bsdf >= 0 && !shapeHasTangentFrame((uint32_t) m.shape_type) && bsdfIsAnisotropic(d.bsdf_type, d.bsdf_params, (uint32_t) m.bsdf);
+		// (bsdfAnisotropic: entries the caller flags as anisotropic whatever their block says -- a cloth BRDF sits on a Lambertian)
+		const bool anisoMesh = m.bsdf >= 0 && !shapeHasTangentFrame((uint32_t) m.shape_type)
+		                       && (bsdfIsAnisotropic(d.bsdf_type, d.bsdf_params, (uint32_t) m.bsdf) || (bsdfAnisotropic && bsdfAnisotropic[m.bsdf]));
 		const float *texcoords = (meshTexcoords && m.shape_type == MTSGPU_SHAPE_TRIMESH) ? meshTexcoords[s] : nullptr;
 		if (anisoMesh && !texcoords)
 			throw std::runtime_error("flatten: " + anisotropicOnMeshMessage(s));

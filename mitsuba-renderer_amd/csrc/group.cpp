@@ -472,6 +472,12 @@ int mtsgpu_group_set_snow_bsdfs(mtsgpu_group *g, const mtsgpu_bsdf_snow *table) 
 	               [](mtsgpu_ctx *c) { return mtsgpu_set_snow_bsdfs(c, nullptr); });
 }
 
+int mtsgpu_group_set_cloth_bsdfs(mtsgpu_group *g, uint32_t n_weaves, const mtsgpu_weave *weaves, const int32_t *bsdf_weave) {
+	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
+	return forEach(g, "set_cloth_bsdfs", [&](mtsgpu_ctx *c) { return mtsgpu_set_cloth_bsdfs(c, n_weaves, weaves, bsdf_weave); },
+	               [](mtsgpu_ctx *c) { return mtsgpu_set_cloth_bsdfs(c, 0, nullptr, nullptr); });
+}
+
 int mtsgpu_hbm_triad(int device, size_t bytes, int iters, double *gbs) {
 	if (!gbs || bytes < 4096 || iters <= 0) return gfail(nullptr, MTSGPU_EINVAL, "bad triad arguments");
 	*gbs = 0;

@@ -3,6 +3,7 @@
 #include "../../include/mtsgpu.h"
 #include "../../include/mtsgpu_mask.h"
 #include "../../include/mtsgpu_snow.h"
+#include "../../include/mtsgpu_cloth.h"
 #include "devmath.h"
 #include "kdtree.h"
 #include <cmath>
@@ -221,6 +222,76 @@ inline std::string checkBsdfSnow(uint32_t n_bsdfs, const uint32_t *type, const f
 	return std::string();
 }
 
+// What mtsgpu_set_cloth_bsdfs and mtsgpu_bsdf_eval_cloth require of one weave: the reference's SAsserts (irawan.cpp:73-77), known
+// yarn types, finite parameters, and positive width, length, umax and areas, non-negative fineness and period (narrower than the
+// reference, which divides by them).  Returns the reason, or an empty string.
+inline std::string checkWeave(const mtsgpu_weave &w) {
+	auto finite = [](float x) { return std::fabs(x) <= 3.4028235e38f; };
+	if (w.tileWidth == 0 || w.tileHeight == 0) return "zero tile dimension (" + std::to_string(w.tileWidth) + " x " + std::to_string(w.tileHeight) + ")";
+	if (w.tileWidth > 32768u || w.tileHeight > 32768u) return "a tile dimension above 32768";
+	if ((uint64_t) w.n_pattern != (uint64_t) w.tileWidth * w.tileHeight)
+		return "pattern size " + std::to_string(w.n_pattern) + " is not tileWidth * tileHeight = " + std::to_string((uint64_t) w.tileWidth * w.tileHeight);
+	if (!w.pattern || !w.yarns || w.n_yarns == 0) return "no pattern or no yarns";
+	for (uint32_t i = 0; i < w.n_pattern; ++i)
+		if (w.pattern[i] == 0 || w.pattern[i] > w.n_yarns)
+			return "pattern entry " + std::to_string(i) + " = " + std::to_string(w.pattern[i]) + " is outside 1.." + std::to_string(w.n_yarns);
+	const float scalars[16] = { w.alpha, w.beta, w.ss, w.hWidth, w.warpArea, w.weftArea, w.dWarpUmaxOverDWarp, w.dWarpUmaxOverDWeft,
+	                            w.dWeftUmaxOverDWarp, w.dWeftUmaxOverDWeft, w.fineness, w.period, w.repeatU, w.repeatV, w.kdMultiplier, w.ksMultiplier };
+	static const char *const names[16] = { "alpha", "beta", "ss", "hWidth", "warpArea", "weftArea", "dWarpUmaxOverDWarp", "dWarpUmaxOverDWeft",
+	                                       "dWeftUmaxOverDWarp", "dWeftUmaxOverDWeft", "fineness", "period", "repeatU", "repeatV", "kdMultiplier", "ksMultiplier" };
+	for (int i = 0; i < 16; ++i)
+		if (!finite(scalars[i])) return std::string(names[i]) + " is not finite";
+	if (!(w.warpArea > 0) || !(w.weftArea > 0)) return "warpArea and weftArea must be positive";
+	if (w.fineness < 0 || w.period < 0) return "fineness and period must not be negative";
+	for (uint32_t y = 0; y < w.n_yarns; ++y) {
+		const mtsgpu_yarn &Y = w.yarns[y];
+		const std::string me = "yarn " + std::to_string(y) + ": ";
+		if (Y.type > (uint32_t) MTSGPU_YARN_WEFT) return me + "unknown type " + std::to_string(Y.type);
+		const float p[13] = { Y.psi, Y.umax, Y.kappa, Y.width, Y.length, Y.centerU, Y.centerV, Y.kd[0], Y.kd[1], Y.kd[2], Y.ks[0], Y.ks[1], Y.ks[2] };
+		for (int i = 0; i < 13; ++i)
+			if (!finite(p[i])) return me + "a parameter is not finite";
+		if (!(Y.width > 0) || !(Y.length > 0) || !(Y.umax > 0)) return me + "width, length and umax must be positive";
+	}
+	return std::string();
+}
+
+// The casts of IrawanClothBRDF::f (irawan.cpp:114-125, 170-181, 206-208; noise.cpp:66) on a surface whose texcoords reach
+// (u, v) in [uMin, uMax] x [vMin, vMax]: every one must stay inside its type's range with the margin of the texture calls,
+// L = 2^31 - 2^16.  In binary64, from the extremes:
+//   X = max |u repeatU tileWidth|, Y = max |(1 - v) repeatV tileHeight|          the two (int) casts: X, Y < L
+//   Cx = max |center.x|: (int) xy.x / tileWidth is unsigned, so Cx <= 2^32 + |centerU| tileWidth where xy.x can be negative,
+//        and X + |centerU| tileWidth otherwise (any negative extreme counts: an interpolated texcoord may round past -1); Cy likewise with |1 - centerV| tileHeight
+//   period > 0: the seed factors (uint64_t) center.x, (uint64_t) (tileHeight repeatV), (uint64_t) center.y need Cx, Cy,
+//        |tileHeight repeatV| < 2^63 -- held to L for the last one, 2^33 bounds the others; the two floorToInt arguments are at most
+//        (Cx (|tileHeight repeatV| + 1) + Cy) / period and (Cy (|tileWidth repeatU| + 1) + Cx) / period (nextFloat() < 1): < L
+//   fineness > 0: the local xy after the translation (and the weft's rotation, which swaps the axes) is at most
+//        S = max(X + Cx, Y + Cy), so |center + xy| <= max(Cx, Cy) + S; times fineness < L, and |tileHeight repeatV fineness| < L
+// Returns the reason, or an empty string.
+inline std::string clothCastRange(const mtsgpu_weave &w, double uMin, double uMax, double vMin, double vMax) {
+	const double L = 2147483648.0 - 65536.0;
+	const double tw = w.tileWidth, th = w.tileHeight, ru = w.repeatU, rv = w.repeatV;
+	const double x0 = uMin * ru * tw, x1 = uMax * ru * tw, y0 = (1.0 - vMin) * rv * th, y1 = (1.0 - vMax) * rv * th;
+	const double X = std::max(std::fabs(x0), std::fabs(x1)), Y = std::max(std::fabs(y0), std::fabs(y1));
+	if (!(X < L) || !(Y < L)) return "a texcoord maps outside the range of the (int) cast (|xy| >= 2^31 - 2^16)";
+	double cu = 0, cv = 0;
+	for (uint32_t y = 0; y < w.n_yarns; ++y) {
+		cu = std::max(cu, std::fabs((double) w.yarns[y].centerU) * tw);
+		cv = std::max(cv, std::fabs(1.0 - (double) w.yarns[y].centerV) * th);
+	}
+	const double Cx = (std::min(x0, x1) < 0.0 ? 4294967296.0 : X) + cu, Cy = (std::min(y0, y1) < 0.0 ? 4294967296.0 : Y) + cv;
+	if (w.period > 0) {
+		if (!(std::fabs(th * rv) < L)) return "tileHeight * repeatV leaves the range of the seed's cast";
+		const double a = (Cx * (std::fabs(th * rv) + 1.0) + Cy) / w.period, b = (Cy * (std::fabs(tw * ru) + 1.0) + Cx) / w.period;
+		if (!(a < L) || !(b < L)) return "a noise argument can leave the range of floorToInt (>= 2^31 - 2^16)";
+	}
+	if (w.fineness > 0) {
+		const double S = std::max(X + Cx, Y + Cy);
+		if (!((std::max(Cx, Cy) + S) * w.fineness < L) || !(std::fabs(th * rv * w.fineness) < L))
+			return "a fineness seed factor can leave the range of its cast (>= 2^31 - 2^16)";
+	}
+	return std::string();
+}
+
 // What the kernels require of a BSDF table (mtsgpu_upload_scene, mtsgpu_bsdf_eval_table and the flattener all ask here):
 // known types, and for a composite (block: [0] n, [1..n] weights, [1+n..2n] child indices as floats) 1 <= n <=
 // MTSGPU_COMPOSITE_MAX, no negative weight (composite.cpp:45-46), children that exist and are neither composites nor delta
@@ -346,7 +417,9 @@ inline std::string checkSkyLuminaire(uint32_t l, const float *LP, int32_t backgr
 
 // meshTexcoords [n_meshes] (mtsgpu_flatten_tangents): the texcoords [that mesh's n_verts][2] of each mesh or NULL; with them a
 // mesh whose BSDF is anisotropic is accepted and receives tangents (fs.vtxTan, fs.shapeHasTan).  NULL: no mesh has any.
-void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs, const float *const *meshTexcoords = nullptr);
+// bsdfAnisotropic [n_bsdfs] (mtsgpu_flatten_tangents_flagged): non-zero = treat the entry as anisotropic as well; NULL: none.
+void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs, const float *const *meshTexcoords = nullptr,
+                  const uint32_t *bsdfAnisotropic = nullptr);
 // The per-vertex colours of shape `mesh` of a flattened scene (mtsgpu_flat_scene_set_mesh_colors): colors [that mesh's
 // n_verts][3] copied into fs.vtxCol at the mesh's rows, NULL takes them away again.  Returns the reason it refuses, or an
 // empty string.

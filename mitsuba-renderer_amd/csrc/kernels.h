@@ -207,6 +207,32 @@ struct DSnows {
 	const DSnow *bsdf_snow;
 };
 constexpr uint32_t kSnowNone = 0, kSnowWiscombe = 1, kSnowHK = 2;
+// The woven-cloth BRDFs (mtsgpu_set_cloth_bsdfs), all NULL without one.  An argument of kernels of their own (k_shade_clo, bin 0)
+// only, which read the uv array of DTextures and the tangents of DTangents.  One pool: weaves[n_weaves] (96 bytes each), the
+// pattern words of all weaves one behind the other (DWeave::first_pattern), the yarns likewise (56 bytes each,
+// DWeave::first_yarn).  bsdf_weave[n_bsdfs]: the weave of the IrawanClothBRDF in place of this Lambertian entry, -1 = none;
+// non-NULL only while some BSDF has one, and the shading launches pick the cloth kernels by it
+struct DYarn {                              // mtsgpu_yarn
+	uint32_t type;                          // 0 warp, 1 weft
+	float    psi, umax, kappa, width, length, centerU, centerV;
+	float    kd[3], ks[3];
+};
+struct DWeave {                             // the scalars of mtsgpu_weave in its order, then the place of its arrays in the pool
+	float    alpha, beta, ss, hWidth, warpArea, weftArea;
+	uint32_t tileWidth, tileHeight;
+	float    dWarpUmaxOverDWarp, dWarpUmaxOverDWeft, dWeftUmaxOverDWarp, dWeftUmaxOverDWeft;
+	float    fineness, period;
+	float    repeatU, repeatV, kdMultiplier, ksMultiplier;
+	uint32_t n_pattern, n_yarns;
+	uint32_t first_pattern, first_yarn;
+	uint32_t reserved[2];
+};
+struct DCloths {
+	const DWeave   *weaves;
+	const uint32_t *pattern;
+	const DYarn    *yarns;
+	const int32_t  *bsdf_weave;
+};
 // what a texture slot of a BSDF takes at a hit (bsdf_block_with_slots)
 enum : int { kSlotBlock = 0, kSlotColor = 1, kSlotTexture = 2 };
 
@@ -456,6 +482,9 @@ void launch_bsdf_eval_masked(hipStream_t s, uint32_t type, const float *params, 
                              const float *queries, float *out);
 // mtsgpu_bsdf_eval_snow: the same read-out through BsdfSnow2, the evaluator of the snow kernels
 void launch_bsdf_eval_snow(hipStream_t s, uint32_t type, const DSnow &entry, int op, uint32_t n, const float *queries, float *out);
+// mtsgpu_bsdf_eval_cloth: the read-out through BsdfCloth2, the evaluator of the cloth kernels; queries [n][8], op 3 = the internals
+void launch_bsdf_eval_cloth(hipStream_t s, uint32_t type, const DWeave &weave, const uint32_t *pattern, const DYarn *yarns, int op, uint32_t n,
+                            const float *queries, float *out);
 // mtsgpu_uv_texture_eval: its.uv (its_uv) and tex_eval of `tex` there for n records of the uploaded scene; rec [n][3] =
 // (u, v, -) on a triangle, the world-space hit point on a sphere; out [n][5] = uv, rgb
 void launch_uv_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, uint32_t n, const uint32_t *prim,
@@ -495,7 +524,8 @@ void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, co
                   const DQueues &q, const BinView &view, const BinView *views_dev = nullptr, uint32_t n_bound = 0,
                   const uint32_t *bin_ids = nullptr, const DColors &col = DColors{ nullptr, nullptr },
                   const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr },
-                  const DMasks &msk = DMasks{ nullptr }, const DSnows &snw = DSnows{ nullptr });
+                  const DMasks &msk = DMasks{ nullptr }, const DSnows &snw = DSnows{ nullptr },
+                  const DCloths &clo = DCloths{ nullptr, nullptr, nullptr, nullptr });
 // device-driven bounces, path integrator / one-sample direct integrator: all bins of bin_mask in one launch; views_dev as
 // above, n_bound bounds the sum of the bin sizes
 void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,

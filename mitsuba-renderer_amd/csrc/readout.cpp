@@ -367,6 +367,60 @@ int mtsgpu_bsdf_eval_snow(mtsgpu_ctx *c, uint32_t bsdf_type, const mtsgpu_bsdf_s
 	return s.finish("BSDF read-out");
 }
 
+int mtsgpu_bsdf_eval_cloth(mtsgpu_ctx *c, uint32_t bsdf_type, const mtsgpu_weave *weave, int op, uint32_t n, const float *queries, float *out) {
+	if (!c || !weave || !queries || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	if ((bsdf_type & ~(uint32_t) MTSGPU_BSDF_TWOSIDED) != (uint32_t) MTSGPU_BSDF_LAMBERTIAN || op < 0 || op > 3)
+		return fail(c, MTSGPU_EINVAL, "bad BSDF type or operation: a weave sits on a Lambertian entry (twosided allowed)");
+	{
+		const std::string why = checkWeave(*weave);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "weave: %s", why.c_str());
+	}
+	if (n == 0) return 0;
+	if (int rc = checkRecordCount(c, n)) return rc;
+	// the casts of f at the extremes of the queries' texcoords, as the setter checks them on a shape
+	{
+		double uMin = 0, uMax = 0, vMin = 0, vMax = 0;
+		for (uint32_t i = 0; i < n; ++i) {
+			const float u = queries[8 * (size_t) i + 6], v = queries[8 * (size_t) i + 7];
+			if (!(std::fabs(u) <= 3.4028235e38f) || !(std::fabs(v) <= 3.4028235e38f)) return fail(c, MTSGPU_EINVAL, "query %u: non-finite texcoord", i);
+			if (i == 0) { uMin = uMax = u; vMin = vMax = v; }
+			uMin = std::min(uMin, (double) u); uMax = std::max(uMax, (double) u); vMin = std::min(vMin, (double) v); vMax = std::max(vMax, (double) v);
+		}
+		const std::string why = clothCastRange(*weave, uMin, uMax, vMin, vMax);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "weave: %s", why.c_str());
+	}
+	Scratch s(c);
+	const float *dQ = s.put(queries, (size_t) n * 8);
+	const uint32_t *dP = s.put(weave->pattern, (size_t) weave->n_pattern);
+	const DYarn *dY = s.put(reinterpret_cast<const DYarn *>(weave->yarns), (size_t) weave->n_yarns);
+	float *dOut = s.alloc<float>((size_t) n * 8);
+	DWeave w;
+	std::memset(&w, 0, sizeof(w));
+	std::memcpy(&w, weave, offsetof(mtsgpu_weave, pattern));
+	if (s.ok()) launch_bsdf_eval_cloth(c->stream, bsdf_type, w, dP, dY, op, n, dQ, dOut);
+	s.get(out, dOut, (size_t) n * 8);
+	return s.finish("BSDF read-out");
+}
+
+int mtsgpu_cloth_check(const mtsgpu_weave *weave, const float *uv_range) {
+	if (!weave) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	std::string why = checkWeave(*weave);
+	if (why.empty() && uv_range) why = clothCastRange(*weave, uv_range[0], uv_range[1], uv_range[2], uv_range[3]);
+	if (!why.empty()) return fail(nullptr, MTSGPU_EINVAL, "weave: %s", why.c_str());
+	return 0;
+}
+
+int mtsgpu_devmath(int fn, uint32_t n, const float *x, const float *y, float *out) {
+	if (!x || !out || (fn == 7 && !y)) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	if (fn < 0 || fn > 10) return fail(nullptr, MTSGPU_EINVAL, "unknown function %d", fn);
+	for (uint32_t i = 0; i < n; ++i) {
+		const float a = x[i];
+		out[i] = fn == 0 ? dsin(a) : fn == 1 ? dcos(a) : fn == 2 ? dtan(a) : fn == 3 ? dexp(a) : fn == 4 ? dlog(a) : fn == 5 ? datan(a)
+		       : fn == 6 ? dacos(a) : fn == 7 ? datan2(a, y[i]) : fn == 8 ? dsinh(a) : fn == 9 ? dcosh(a) : dpow15(a);
+	}
+	return 0;
+}
+
 int mtsgpu_uv_texture_eval(mtsgpu_ctx *c, const mtsgpu_uv_texture *tex, uint32_t n, const uint32_t *prim, const float *rec, float *out) {
 	if (!c || !tex || !prim || !rec || !out) return fail(c, MTSGPU_EINVAL, "null argument");
 	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_uv_texture_eval before mtsgpu_upload_scene");

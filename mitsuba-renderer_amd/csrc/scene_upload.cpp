@@ -214,6 +214,11 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 	freeAll(c->snowAllocs);       // ... and without snow BRDFs (mtsgpu_set_snow_bsdfs)
 	c->dsnw = DSnows{ nullptr };
 	c->hostSnowKind.clear();
+	freeAll(c->clothAllocs);      // ... and without cloth BRDFs (mtsgpu_set_cloth_bsdfs)
+	c->dclo = DCloths{ nullptr, nullptr, nullptr, nullptr };
+	c->hostClothWeave.clear();
+	c->hostUvRange.clear();
+	c->hostShapeHasUv.clear();
 	c->dtan = DTangents{ nullptr, nullptr };      // ... and its tangents go with the scene's arrays
 	c->haveScene = false;
 	DScene d{};
@@ -379,6 +384,12 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 		h.bsdfParams.assign(sc->bsdf_params, sc->bsdf_params + (size_t) MTSGPU_BSDF_NPARAMS * sc->n_bsdfs);
 		h.shapeBsdf.assign(sc->shape_bsdf, sc->shape_bsdf + sc->n_shapes);
 		h.lumType.assign(sc->lum_type, sc->lum_type + sc->n_lums);
+		h.shapeNormals.assign(sc->n_shapes, 0u);
+		h.shapeTangents.assign(sc->n_shapes, 0u);
+		for (uint32_t s = 0; s < sc->n_shapes; ++s) {
+			h.shapeNormals[s] = (sc->shape_flags[s] & MTSGPU_SHAPE_HAS_NORMALS) ? 1u : 0u;
+			h.shapeTangents[s] = (shape_has_tangents && shape_has_tangents[s]) ? 1u : 0u;
+		}
 	}
 	// material queues that can ever be non-empty: the BSDF types of shapes that have one, and the "terminal" bin
 	c->binMask = 1u << kNumBsdfTypes;
@@ -433,6 +444,9 @@ int mtsgpu_set_vertex_colors(mtsgpu_ctx *c, const float *vtx_col, const uint32_t
 		for (uint32_t b = 0; b < nBsdfs && !c->hostSnowKind.empty(); ++b)      // an entry mtsgpu_set_snow_bsdfs has given a snow record
 			if (bsdf_color_slots[b] && c->hostSnowKind[b] != (uint32_t) MTSGPU_SNOW_NONE)
 				return fail(c, MTSGPU_EINVAL, "BSDF %u: the entry takes vertex colours and has a snow record, whose BRDF has no texture slot", b);
+		for (uint32_t b = 0; b < nBsdfs && !c->hostClothWeave.empty(); ++b)      // an entry mtsgpu_set_cloth_bsdfs has given a weave
+			if (bsdf_color_slots[b] && c->hostClothWeave[b] >= 0)
+				return fail(c, MTSGPU_EINVAL, "BSDF %u: the entry takes vertex colours and has a weave, whose BRDF has no texture slot", b);
 		for (uint32_t s = 0; s < nShapes; ++s) {
 			const int32_t b = h.shapeBsdf[s];
 			if (b < 0 || !bsdf_color_slots[b]) continue;
@@ -493,6 +507,18 @@ static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *sha
                          const mtsgpu_bsdf_mask *bsdf_mask = nullptr) {
 	if (!c) return fail(c, MTSGPU_EINVAL, "null argument");
 	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "%s before mtsgpu_upload_scene", me);
+	// an entry mtsgpu_set_cloth_bsdfs has given a weave takes neither a textured slot nor a mask; and the cloth table was
+	// checked against the texcoords that go with this call, so a texture call while one is in force is refused before anything
+	// is freed (the cloth kernels read the uv array): the order is the texture call first (mtsgpu_cloth.h)
+	for (uint32_t b = 0; b < (uint32_t) c->host.bsdfType.size() && !c->hostClothWeave.empty(); ++b) {
+		if (c->hostClothWeave[b] < 0) continue;
+		if (bsdf_slot_texture && (bsdf_slot_texture[2 * (size_t) b] >= 0 || bsdf_slot_texture[2 * (size_t) b + 1] >= 0))
+			return fail(c, MTSGPU_EINVAL, "BSDF %u: the entry has a uv texture and a weave, whose BRDF has no texture slot", b);
+		if (bsdf_mask && bsdf_mask[b].kind != (uint32_t) MTSGPU_MASK_NONE)
+			return fail(c, MTSGPU_EINVAL, "BSDF %u: the entry has a mask and a weave: a mask around a cloth BRDF is not supported", b);
+	}
+	if (!c->hostClothWeave.empty())
+		return fail(c, MTSGPU_EINVAL, "%s while a cloth table is in force: the texture call comes first (switch the table off with mtsgpu_set_cloth_bsdfs(ctx, 0, NULL, NULL))", me);
 	c->lastPass.valid = false;
 	HIPCHK(c, hipSetDevice(c->device));
 	// nothing may still read the arrays that go (the shading launches of a render that was not synchronised)
@@ -503,6 +529,8 @@ static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *sha
 	c->dmsk = DMasks{ nullptr };
 	c->hostSlotTex.clear();
 	c->hostMaskKind.clear();
+	c->hostUvRange.clear();
+	c->hostShapeHasUv.clear();
 	if (!vtx_uv && !shape_has_uv && !textures && !bsdf_slot_texture && !bitmaps && !texture_bitmap && !bsdf_mask) return 0;
 	if ((vtx_uv == nullptr) != (shape_has_uv == nullptr))
 		return fail(c, MTSGPU_EINVAL, "vtx_uv and shape_has_uv must both be given or both be NULL");
@@ -630,6 +658,22 @@ static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *sha
 	c->dtex = DTextures{ reinterpret_cast<const float4 *>(dUv), dTex, dSlots, reinterpret_cast<const float4 *>(dTexels) };
 	c->dmsk = DMasks{ dMask };
 	if (anySlot) c->hostSlotTex.assign(bsdf_slot_texture, bsdf_slot_texture + 2 * (size_t) nBsdfs);
+	if (vtx_uv) {
+		// what mtsgpu_set_cloth_bsdfs checks its casts on: the extremes of every shape's texcoords
+		c->hostShapeHasUv.assign(shape_has_uv, shape_has_uv + nShapes);
+		c->hostUvRange.assign(4 * (size_t) nShapes, 0.0);
+		for (uint32_t s = 0; s < nShapes; ++s) {
+			if (!shape_has_uv[s]) continue;
+			double *r = &c->hostUvRange[4 * (size_t) s];
+			bool first = true;
+			for (uint32_t t = h.shapeTriOffset[s]; t < h.shapeTriOffset[s + 1]; ++t)
+				for (int v = 0; v < 3; ++v) {
+					const double u = triUv[US * (size_t) t + 2 * v], w = triUv[US * (size_t) t + 2 * v + 1];
+					if (first) { r[0] = r[1] = u; r[2] = r[3] = w; first = false; }
+					r[0] = std::min(r[0], u); r[1] = std::max(r[1], u); r[2] = std::min(r[2], w); r[3] = std::max(r[3], w);
+				}
+		}
+	}
 	if (anyMask)
 		for (uint32_t b = 0; b < nBsdfs; ++b) c->hostMaskKind.push_back(bsdf_mask[b].kind);
 	return 0;
@@ -658,6 +702,9 @@ int mtsgpu_set_snow_bsdfs(mtsgpu_ctx *c, const mtsgpu_bsdf_snow *table) {
 	                                      c->hostSlotTex.empty() ? nullptr : c->hostSlotTex.data(),
 	                                      c->hostMaskKind.empty() ? nullptr : c->hostMaskKind.data());
 	if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+	for (uint32_t b = 0; b < nBsdfs && !c->hostClothWeave.empty(); ++b)      // an entry mtsgpu_set_cloth_bsdfs has given a weave
+		if (table[b].kind != (uint32_t) MTSGPU_SNOW_NONE && c->hostClothWeave[b] >= 0)
+			return fail(c, MTSGPU_EINVAL, "BSDF %u: the entry has a weave and a snow record", b);
 	bool any = false;
 	for (uint32_t b = 0; b < nBsdfs; ++b) any |= table[b].kind != (uint32_t) MTSGPU_SNOW_NONE;
 	if (!any) return 0;           // nothing to keep: the context launches what it launches without a table
@@ -665,6 +712,95 @@ int mtsgpu_set_snow_bsdfs(mtsgpu_ctx *c, const mtsgpu_bsdf_snow *table) {
 	if (int rc = upload(c, &dSnow, reinterpret_cast<const DSnow *>(table), nBsdfs, &c->snowAllocs)) { freeAll(c->snowAllocs); return rc; }
 	c->dsnw = DSnows{ dSnow };
 	for (uint32_t b = 0; b < nBsdfs; ++b) c->hostSnowKind.push_back(table[b].kind);
+	return 0;
+}
+
+static_assert(sizeof(mtsgpu_yarn) == 56 && sizeof(mtsgpu_yarn) == sizeof(DYarn) && offsetof(mtsgpu_yarn, kd) == offsetof(DYarn, kd), "mtsgpu_yarn and DYarn are one layout");
+static_assert(sizeof(DWeave) == 96 && offsetof(mtsgpu_weave, n_yarns) + 4 == offsetof(DWeave, first_pattern) && offsetof(mtsgpu_weave, pattern) == 80,
+              "DWeave is the scalars of mtsgpu_weave, then the place of its arrays");
+
+int mtsgpu_set_cloth_bsdfs(mtsgpu_ctx *c, uint32_t n_weaves, const mtsgpu_weave *weaves, const int32_t *bsdf_weave) {
+	if (!c) return fail(c, MTSGPU_EINVAL, "null argument");
+	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_set_cloth_bsdfs before mtsgpu_upload_scene");
+	c->lastPass.valid = false;
+	HIPCHK(c, hipSetDevice(c->device));
+	// nothing may still read the pool that goes (the shading launches of a render that was not synchronised)
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
+	freeAll(c->clothAllocs);
+	c->dclo = DCloths{ nullptr, nullptr, nullptr, nullptr };
+	c->hostClothWeave.clear();
+	if (!bsdf_weave) return 0;
+	if (n_weaves && !weaves) return fail(c, MTSGPU_EINVAL, "n_weaves without weaves");
+	if (n_weaves > (1u << 20)) return fail(c, MTSGPU_EINVAL, "at most 2^20 weaves");
+	const mtsgpu_ctx::HostScene &h = c->host;
+	const uint32_t nBsdfs = (uint32_t) h.bsdfType.size(), nShapes = (uint32_t) h.shapeBsdf.size();
+	for (uint32_t k = 0; k < n_weaves; ++k) {
+		const std::string why = checkWeave(weaves[k]);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "weave %u: %s", k, why.c_str());
+	}
+	bool any = false;
+	for (uint32_t b = 0; b < nBsdfs; ++b) {
+		const int32_t k = bsdf_weave[b];
+		if (k < -1 || k >= (int32_t) n_weaves) return fail(c, MTSGPU_EINVAL, "BSDF %u: weave index %d out of range (%u weaves)", b, k, n_weaves);
+		if (k < 0) continue;
+		any = true;
+		if ((h.bsdfType[b] & ~(uint32_t) MTSGPU_BSDF_TWOSIDED) != (uint32_t) MTSGPU_BSDF_LAMBERTIAN)
+			return fail(c, MTSGPU_EINVAL, "BSDF %u: a weave sits on a Lambertian entry (twosided allowed), not on type word %u", b, h.bsdfType[b]);
+		if (!c->hostColorSlots.empty() && c->hostColorSlots[b])
+			return fail(c, MTSGPU_EINVAL, "BSDF %u: a cloth BRDF has no texture slot, and the entry takes vertex colours", b);
+		if (!c->hostSlotTex.empty() && (c->hostSlotTex[2 * (size_t) b] >= 0 || c->hostSlotTex[2 * (size_t) b + 1] >= 0))
+			return fail(c, MTSGPU_EINVAL, "BSDF %u: a cloth BRDF has no texture slot, and the entry has a uv texture", b);
+		if (!c->hostMaskKind.empty() && c->hostMaskKind[b] != (uint32_t) MTSGPU_MASK_NONE)
+			return fail(c, MTSGPU_EINVAL, "BSDF %u: a mask around a cloth BRDF is not supported", b);
+		if (!c->hostSnowKind.empty() && c->hostSnowKind[b] != (uint32_t) MTSGPU_SNOW_NONE)
+			return fail(c, MTSGPU_EINVAL, "BSDF %u: the entry has a snow record and a weave", b);
+	}
+	for (uint32_t b = 0; b < nBsdfs; ++b) {
+		if ((h.bsdfType[b] & 0xFFu) != MTSGPU_BSDF_COMPOSITE) continue;
+		const float *P = h.bsdfParams.data() + (size_t) MTSGPU_BSDF_NPARAMS * b;
+		const int n = (int) P[0];
+		for (int i = 0; i < n; ++i)
+			if (bsdf_weave[(uint32_t) P[1 + n + i]] >= 0)
+				return fail(c, MTSGPU_EINVAL, "BSDF %u: composite child %d has a weave: the composite's loop would run it as a Lambertian, not supported", b, i);
+	}
+	if (!any) return 0;           // nothing to keep: the context launches what it launches without a table
+	// the shapes a weave is shaded on: texcoords, a tangent frame, and the casts of f at the extremes of their texcoords
+	for (uint32_t s = 0; s < nShapes; ++s) {
+		const int32_t b = h.shapeBsdf[s];
+		if (b < 0 || bsdf_weave[b] < 0) continue;
+		double uMin = 0, uMax = 1, vMin = 0, vMax = 1;      // a sphere: uv in [0, 1]^2
+		if (h.shapeType[s] == MTSGPU_SHAPE_TRIMESH) {
+			if (c->hostShapeHasUv.empty() || !c->hostShapeHasUv[s])
+				return fail(c, MTSGPU_EINVAL, "shape %u: the cloth BSDF (BSDF %d) needs texture coordinates: a mesh without them must be given some (trimesh.cpp:551-555)", s, b);
+			if (h.shapeNormals[s] && !h.shapeTangents[s])
+				return fail(c, MTSGPU_EINVAL, "shape %u: the cloth BSDF (BSDF %d) is anisotropic: a mesh with vertex normals needs its tangents (mtsgpu_upload_scene_tangents)", s, b);
+			const double *r = &c->hostUvRange[4 * (size_t) s];
+			uMin = r[0]; uMax = r[1]; vMin = r[2]; vMax = r[3];
+		}       // (a sphere's its.uv comes from the hit point: it needs no texture call)
+		const std::string why = clothCastRange(weaves[bsdf_weave[b]], uMin, uMax, vMin, vMax);
+		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "shape %u: weave %d: %s", s, bsdf_weave[b], why.c_str());
+	}
+	// one pool: the records, the pattern words and the yarns
+	std::vector<DWeave> rec(n_weaves);
+	std::vector<uint32_t> pat;
+	std::vector<DYarn> yarns;
+	for (uint32_t k = 0; k < n_weaves; ++k) {
+		std::memset(&rec[k], 0, sizeof(DWeave));
+		std::memcpy(&rec[k], &weaves[k], offsetof(mtsgpu_weave, pattern));
+		rec[k].first_pattern = (uint32_t) pat.size(); rec[k].first_yarn = (uint32_t) yarns.size();
+		pat.insert(pat.end(), weaves[k].pattern, weaves[k].pattern + weaves[k].n_pattern);
+		const DYarn *y = reinterpret_cast<const DYarn *>(weaves[k].yarns);
+		yarns.insert(yarns.end(), y, y + weaves[k].n_yarns);
+	}
+	const DWeave *dW = nullptr; const uint32_t *dP = nullptr; const DYarn *dY = nullptr; const int32_t *dB = nullptr;
+	int rc = upload(c, &dW, rec.data(), rec.size(), &c->clothAllocs);
+	if (!rc) rc = upload(c, &dP, pat.data(), pat.size(), &c->clothAllocs);
+	if (!rc) rc = upload(c, &dY, yarns.data(), yarns.size(), &c->clothAllocs);
+	if (!rc) rc = upload(c, &dB, bsdf_weave, nBsdfs, &c->clothAllocs);
+	if (rc) { freeAll(c->clothAllocs); return rc; }
+	c->dclo = DCloths{ dW, dP, dY, dB };
+	c->hostClothWeave.assign(bsdf_weave, bsdf_weave + nBsdfs);
 	return 0;
 }
 

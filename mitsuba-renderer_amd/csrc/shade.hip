@@ -1,23 +1,25 @@
 // shade.hip -- K3+K5: launch_shade / launch_shade_all pick the kernel family of the scene.  The device code is shade_bsdf.h and
-// shade_path.h; each family's kernels are instantiated in a unit of their own (shade_plain / _vcol / _tex / _tan / _mask / _snow.hip).
+// shade_path.h; each family's kernels are instantiated in a unit of their own (shade_plain / _vcol / _tex / _tan / _mask / _snow / _cloth.hip).
 #include "kdevice.h"
 #include "shade_launch.h"
 
 namespace mg {
 
-// one material queue with the kernels its scene needs: a snow BRDF (DSnows::bsdf_snow; bin 0 alone, first: the snow kernels serve
+// one material queue with the kernels its scene needs: a woven-cloth BRDF (DCloths::bsdf_weave; bin 0 alone, first: the cloth kernels
+// serve snow and everything below it as well), a snow BRDF (DSnows::bsdf_snow; bin 0 alone, first: the snow kernels serve
 // masks, tangents, textures and colours as well), a mask adapter (DMasks::bsdf_mask; bins 0..8, first: the mask kernels serve
 // tangents, textures and colours as well), a tangent mesh (DTangents::tri_dpdu; bins 0..9 -- the composite too, for
 // the frame of its children), a uv-textured or a coloured BSDF slot (DTextures::bsdf_slot_texture, DColors::bsdf_color_slots;
 // bins 0..8 only -- a composite's children and the terminal bin take no colours)
 void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                   const DQueues &q, const BinView &view, const BinView *views_dev, uint32_t n_bound, const uint32_t *bin_ids, const DColors &col,
-                  const DTextures &tex, const DTangents &tan, const DMasks &msk, const DSnows &snw) {
+                  const DTextures &tex, const DTangents &tan, const DMasks &msk, const DSnows &snw, const DCloths &clo) {
 	const uint32_t n = views_dev ? n_bound : view.prefix[kBinShards];
 	if (!n) return;
 	if (!bin_ids) bin_ids = q.bin(bin);
 	const ShadeBinLaunch a{ s, dim3(blocks_for(n, kShadeBlock)), dim3(kShadeBlock), sc, ps, cfg, q, view, views_dev, bin_ids };
-	if (bin == 0 && snw.bsdf_snow != nullptr) launch_shade_snw(a, col, tex, tan, msk, snw);
+	if (bin == 0 && clo.bsdf_weave != nullptr) launch_shade_clo(a, col, tex, tan, msk, snw, clo);
+	else if (bin == 0 && snw.bsdf_snow != nullptr) launch_shade_snw(a, col, tex, tan, msk, snw);
 	else if (bin >= 0 && bin < 9 && msk.bsdf_mask != nullptr) launch_shade_msk(a, bin, col, tex, tan, msk);
 	else if (bin >= 0 && bin <= 9 && tan.tri_dpdu != nullptr) launch_shade_tan(a, bin, col, tex, tan);
 	else if (bin >= 0 && bin < 9 && tex.bsdf_slot_texture != nullptr) launch_shade_tex(a, bin, col, tex);

@@ -1,5 +1,6 @@
 // shade_hooks.hip -- the code of shade_bsdf.h read out for tests: the mtsgpu_*_eval hooks, one record per thread.
 #include "shade_bsdf.h"
+#include "shade_cloth.h"
 
 namespace mg {
 
@@ -192,6 +193,31 @@ __global__ void k_bsdf_eval_snow(uint32_t type, DSnow e, int op, uint32_t n, con
 	#pragma unroll
 	for (int k = 0; k < 8; ++k) out[8 * (size_t) i + k] = o[k];
 }
+// mtsgpu_bsdf_eval_cloth: k_bsdf_eval through BsdfCloth2; a query is wi, wo or the sample, its.uv; op 3: the internals of f
+__global__ void k_bsdf_eval_cloth(uint32_t type, DWeave W, const uint32_t *pattern, const DYarn *yarns, int op, uint32_t n, const float *queries,
+                                  float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const bool two = (type & 0x100u) != 0;
+	const float *q = queries + 8 * (size_t) i;
+	const V3 wi(q[0], q[1], q[2]);
+	float o[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+	if (op == 0) {
+		const V3 f = BsdfCloth2::f(two, W, pattern, yarns, wi, V3(q[3], q[4], q[5]), q[6], q[7]);
+		o[0] = f.x; o[1] = f.y; o[2] = f.z;
+	} else if (op == 1) {
+		o[0] = BsdfCloth2::pdf(two, wi, V3(q[3], q[4], q[5]));
+	} else if (op == 2) {
+		V3 wo; float pdf; uint32_t st;
+		const BsdfCloth::Hit H = BsdfCloth::prepare(W, pattern, yarns, q[6], q[7]);
+		const V3 f = BsdfCloth2::sample(two, W, yarns, H, wi, q[3], q[4], wo, pdf, st);
+		o[0] = wo.x; o[1] = wo.y; o[2] = wo.z; o[3] = pdf; o[4] = f.x; o[5] = f.y; o[6] = f.z; o[7] = __uint_as_float(st);
+	} else {
+		(void) BsdfCloth2::f(two, W, pattern, yarns, wi, V3(q[3], q[4], q[5]), q[6], q[7], o);
+	}
+	#pragma unroll
+	for (int k = 0; k < 8; ++k) out[8 * (size_t) i + k] = o[k];
+}
 // mtsgpu_uv_texture_eval: its_uv and tex_eval for n records; the host has checked prim < n_tris
 __global__ void k_uv_texture_eval(DScene sc, const float4 *tri_uv, DTexture tex, uint32_t n, const uint32_t *prim, const float *rec, float *out) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -338,6 +364,11 @@ void launch_bsdf_eval_masked(hipStream_t s, uint32_t type, const float *params, 
 
 void launch_bsdf_eval_snow(hipStream_t s, uint32_t type, const DSnow &entry, int op, uint32_t n, const float *queries, float *out) {
 	if (n) hipLaunchKernelGGL(k_bsdf_eval_snow, dim3(blocks_for(n, 256)), dim3(256), 0, s, type, entry, op, n, queries, out);
+}
+
+void launch_bsdf_eval_cloth(hipStream_t s, uint32_t type, const DWeave &weave, const uint32_t *pattern, const DYarn *yarns, int op, uint32_t n,
+                            const float *queries, float *out) {
+	if (n) hipLaunchKernelGGL(k_bsdf_eval_cloth, dim3(blocks_for(n, 256)), dim3(256), 0, s, type, weave, pattern, yarns, op, n, queries, out);
 }
 
 void launch_uv_texture_eval(hipStream_t s, const DScene &sc, const float4 *tri_uv, const DTexture &tex, uint32_t n, const uint32_t *prim,

@@ -1,12 +1,12 @@
 // shade_launch.h -- private to the shading units: what launch_shade / launch_shade_all (shade.hip) call in the unit of each
-// kernel family (shade_plain / _vcol / _tex / _tan / _mask / _snow.hip), and the one ROUNDS x SKY ladder those units launch through.
+// kernel family (shade_plain / _vcol / _tex / _tan / _mask / _snow / _cloth.hip), and the one ROUNDS x SKY ladder those units launch through.
 #pragma once
 #include <type_traits>
 #include "kernels.h"
 
 namespace mg {
 
-// the arguments every k_shade* takes, with the launch they go to: a family appends its own (DColors, DTextures, DTangents, DMasks, DSnows)
+// the arguments every k_shade* takes, with the launch they go to: a family appends its own (DColors, DTextures, DTangents, DMasks, DSnows, DCloths)
 struct ShadeBinLaunch {
 	hipStream_t s; dim3 g, b;
 	const DScene &sc; const DPaths &ps; const DConfig &cfg; const DQueues &q;
@@ -20,7 +20,7 @@ struct ShadeAllLaunch {
 };
 
 // One material queue, per family.  plain: every bin.  vcol, tex: bins 0..8 (a composite's children and the terminal bin take no
-// colours).  tan: bins 0..9 (the composite too, for the frame of its children).  msk: bins 0..8 (a composite takes no mask).  snw: bin 0 (a snow record sits on a Lambertian entry).
+// colours).  tan: bins 0..9 (the composite too, for the frame of its children).  msk: bins 0..8 (a composite takes no mask).  snw, clo: bin 0 (a snow record or a weave sits on a Lambertian entry).
 // launch_shade asks for no other bin.
 void launch_shade_plain(const ShadeBinLaunch &a, int bin);
 void launch_shade_vcol(const ShadeBinLaunch &a, int bin, const DColors &col);
@@ -28,6 +28,8 @@ void launch_shade_tex(const ShadeBinLaunch &a, int bin, const DColors &col, cons
 void launch_shade_tan(const ShadeBinLaunch &a, int bin, const DColors &col, const DTextures &tex, const DTangents &tan);
 void launch_shade_msk(const ShadeBinLaunch &a, int bin, const DColors &col, const DTextures &tex, const DTangents &tan, const DMasks &msk);
 void launch_shade_snw(const ShadeBinLaunch &a, const DColors &col, const DTextures &tex, const DTangents &tan, const DMasks &msk, const DSnows &snw);
+void launch_shade_clo(const ShadeBinLaunch &a, const DColors &col, const DTextures &tex, const DTangents &tan, const DMasks &msk, const DSnows &snw,
+                      const DCloths &clo);
 // All material queues of a bounce in one launch, per family
 void launch_shade_all_plain(const ShadeAllLaunch &a);
 void launch_shade_all_vcol(const ShadeAllLaunch &a, const DColors &col);

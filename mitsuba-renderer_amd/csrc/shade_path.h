@@ -1,9 +1,26 @@
-// shade_path.h -- K3+K5: one iteration of MIPathTracer::Li per material queue, and the kernel templates of the six families
-// (k_shade*, k_shade_all*).  Each family is instantiated by the unit that launches it: shade_plain / _vcol / _tex / _tan / _mask / _snow.hip.
+// shade_path.h -- K3+K5: one iteration of MIPathTracer::Li per material queue, and the kernel templates of the seven families
+// (k_shade*, k_shade_all*).  Each family is instantiated by the unit that launches it: shade_plain / _vcol / _tex / _tan / _mask / _snow /
+// _cloth.hip.
 #pragma once
 #include "shade_bsdf.h"
+#include "shade_cloth.h"
 
 namespace mg {
+
+// BsdfCloth2 on weave k of the cloth tables: the stage of f that depends on its.uv alone, once per hit, and the two evaluations
+__device__ __forceinline__ BsdfCloth::Hit cloth_prepare(const DCloths &clo, int k, float uvx, float uvy) {
+	const DWeave W = clo.weaves[k];
+	return BsdfCloth::prepare(W, clo.pattern + W.first_pattern, clo.yarns + W.first_yarn, uvx, uvy);
+}
+__device__ __forceinline__ V3 cloth_f(const DCloths &clo, int k, const BsdfCloth::Hit &H, bool two, V3 wi, V3 wo) {
+	const DWeave W = clo.weaves[k];
+	return BsdfCloth2::eval(two, W, clo.yarns + W.first_yarn, H, wi, wo);
+}
+__device__ __forceinline__ V3 cloth_sample(const DCloths &clo, int k, const BsdfCloth::Hit &H, bool two, V3 wi, float sx, float sy, V3 &wo,
+                                           float &pdf, uint32_t &st) {
+	const DWeave W = clo.weaves[k];
+	return BsdfCloth2::sample(two, W, clo.yarns + W.first_yarn, H, wi, sx, sy, wo, pdf, st);
+}
 
 // ===========================================================================
 // K3+K5: one iteration of the loop of MIPathTracer::Li (path.cpp:61-209) for
@@ -40,12 +57,15 @@ __device__ __forceinline__ uint32_t shade_row_index(uint32_t lane, uint32_t k) {
 // BsdfMasked with the opacity's luminance at the hit, and the tangent table may be NULL as well.
 // SNW: the instantiation of bin 0 for scenes with a snow BRDF (DSnows::bsdf_snow != NULL), on top of MSK: a hit whose BSDF has a
 // snow record is evaluated through BsdfSnow2, every other one as in the mask kernel, and the mask table may be NULL as well.
-template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false, bool SNW = false>
+// CLO: the instantiation of bin 0 for scenes with a woven-cloth BRDF (DCloths::bsdf_weave != NULL), on top of SNW: a hit whose
+// BSDF has a weave is evaluated through BsdfCloth2 at its.uv, every other one as in the snow kernel, and the snow table may be NULL.
+template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false, bool SNW = false, bool CLO = false>
 __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, const DConfig &cfg, const uint32_t id,
                                            const float4 ro, const float4 rd, const uint4 h, const float4 T4, const float4 L4,
                                            const ShadeRow row, bool &continues, bool &wantShadow, V3 &neeV, V3 &shO, V3 &shD, const DColors &col,
                                            const DTextures &tex, const DTangents &tan = DTangents{ nullptr, nullptr },
-                                           const DMasks &msk = DMasks{ nullptr }, const DSnows &snw = DSnows{ nullptr }) {
+                                           const DMasks &msk = DMasks{ nullptr }, const DSnows &snw = DSnows{ nullptr },
+                                           const DCloths &clo = DCloths{ nullptr, nullptr, nullptr, nullptr }) {
 	{
 		// rounds of MIDirectIntegrator (DConfig::dr_mode): later BSDF samples start again from the camera hit
 		const int mode = ROUNDS ? cfg.dr_mode : 0;
@@ -162,6 +182,17 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			uint32_t snowKind = kSnowNone;
 			const float *snowD = nullptr;
 			if (SNW && snw.bsdf_snow != nullptr) { snowKind = snw.bsdf_snow[bsdfIdx].kind; snowD = snw.bsdf_snow[bsdfIdx].derived; }
+			// cloth kernels: the weave of this BSDF (BsdfCloth2) and its.uv, -1 without one
+			int weaveIdx = -1;
+			BsdfCloth::Hit clothHit{};
+			if (CLO) {
+				weaveIdx = clo.bsdf_weave[bsdfIdx];
+				if (weaveIdx >= 0) {
+					float clothU = 0, clothV = 0;
+					its_uv(sc, tex.tri_uv, h.w, its.shape, __uint_as_float(h.y), __uint_as_float(h.z), its.p, clothU, clothV);
+					clothHit = cloth_prepare(clo, weaveIdx, clothU, clothV);
+				}
+			}
 			if (VCOL == kSlotTexture && BT < 9) {
 				// a checkerboard, a grid texture or a bitmap in a slot of this BSDF: that slot holds the texture's value at its.uv; a
 				// `vertexcolors` texture in the other one its.color
@@ -227,13 +258,15 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				if ((!direct || cfg.n_lum > 0) && sample_luminaire<SKY>(sc, its.p, s0, s1, lRec)) {
 					const V3 wo = -lRec.d;
 					const V3 woL(dot(wo, its.shS), dot(wo, its.shT), dot(wo, its.shN));
-					V3 bsdfVal = (SNW ? BsdfSnow2::f(twoSided, snowKind, snowD, BP, maskP, its.wi, woL)
+					V3 bsdfVal = ((CLO && weaveIdx >= 0) ? cloth_f(clo, weaveIdx, clothHit, twoSided, its.wi, woL)
+					                  : SNW ? BsdfSnow2::f(twoSided, snowKind, snowD, BP, maskP, its.wi, woL)
 					                  : MSK ? BsdfMasked<BT>::f(tab, twoSided, BP, maskP, its.wi, woL) : Bsdf2<BT>::f(tab, twoSided, BP, its.wi, woL)) * fabsf(woL.z);
 					const float woDotGeoN = dot(its.geoN, wo);
 					if (!isZero(bsdfVal) && (!strict || woDotGeoN * woL.z > 0)) {
 						// isIntersectable() || isBackgroundLuminaire() (path.cpp:118-120): 0 for delta luminaires
 						const uint32_t lt = sc.lum_type[lRec.lum];      // area, constant, envmap and sky luminaires can be hit by BSDF samples
-						const float bsdfPdf = (lt <= 1u || lt == 5u || (SKY && lt == 7u)) ? (SNW ? BsdfSnow2::pdf(twoSided, snowKind, snowD, BP, maskP, its.wi, woL)
+						const float bsdfPdf = (lt <= 1u || lt == 5u || (SKY && lt == 7u)) ? ((CLO && weaveIdx >= 0) ? BsdfCloth2::pdf(twoSided, its.wi, woL)
+						                                                                             : SNW ? BsdfSnow2::pdf(twoSided, snowKind, snowD, BP, maskP, its.wi, woL)
 						                                                                             : MSK ? BsdfMasked<BT>::pdf(tab, twoSided, BP, maskP, its.wi, woL) : Bsdf2<BT>::pdf(tab, twoSided, BP, its.wi, woL)) : 0.0f;
 						const float weight = direct ? mi_weight(lRec.pdf * cfg.frac_lum, bsdfPdf * cfg.frac_bsdf) * cfg.weight_lum
 						                            : mi_weight(lRec.pdf, bsdfPdf);          // direct.cpp:143-145
@@ -259,7 +292,8 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 			if (direct && cfg.n_bsdf <= 0)
 				break;                                      // the sample is drawn even when it is not used (direct.cpp:156-161)
 			V3 woL; float bsdfPdf; uint32_t sampledType;
-			V3 bsdfVal = SNW ? BsdfSnow2::sample(twoSided, snowKind, snowD, BP, maskP, its.wi, s0, s1, woL, bsdfPdf, sampledType)
+			V3 bsdfVal = (CLO && weaveIdx >= 0) ? cloth_sample(clo, weaveIdx, clothHit, twoSided, its.wi, s0, s1, woL, bsdfPdf, sampledType)
+			           : SNW ? BsdfSnow2::sample(twoSided, snowKind, snowD, BP, maskP, its.wi, s0, s1, woL, bsdfPdf, sampledType)
 			           : MSK ? BsdfMasked<BT>::sample(tab, twoSided, BP, maskP, its.wi, s0, s1, woL, bsdfPdf, sampledType)
 			                 : Bsdf2<BT>::sample(tab, twoSided, BP, its.wi, s0, s1, woL, bsdfPdf, sampledType);
 			if (!isZero(bsdfVal))
@@ -306,11 +340,12 @@ struct ShadeShared {
 };
 // One workgroup of k_shade: the paths block * kShadeBlock .. of the material queue whose segment sizes are `prefix`
 // (prefix[kBinShards] entries in kBinShards segments of bin_ids)
-template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false, bool SNW = false>
+template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false, bool SNW = false, bool CLO = false>
 __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const uint32_t *prefix,
                                             const uint32_t *bin_ids, const uint32_t block, ShadeShared &sh, const DColors &col,
                                             const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr },
-                                            const DMasks &msk = DMasks{ nullptr }, const DSnows &snw = DSnows{ nullptr }) {
+                                            const DMasks &msk = DMasks{ nullptr }, const DSnows &snw = DSnows{ nullptr },
+                                            const DCloths &clo = DCloths{ nullptr, nullptr, nullptr, nullptr }) {
 	uint32_t (&s_cnt)[2][kShadeBlock / 64] = sh.cnt;
 	uint32_t (&s_base)[2] = sh.base;
 	float4 (&s_rows)[kShadeBlock / 64][64 * kRowStride] = sh.rows;
@@ -396,7 +431,7 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	}
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	if (active)
-		shade_path<BT, ROUNDS, SKY, VCOL, TAN, MSK, SNW>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col, tex, tan, msk, snw);
+		shade_path<BT, ROUNDS, SKY, VCOL, TAN, MSK, SNW, CLO>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col, tex, tan, msk, snw, clo);
 	// the pending direct-light term is parked in the record with the write-back below (the line is written whole anyway):
 	// the any-hit kernel clears the slot if the shadow ray is occluded, the record's next reader adds what is still there
 	if (q.nee_parked && wantShadow) row[2] = make_float4(neeV.x, neeV.y, neeV.z, __uint_as_float(kNeeTag));
@@ -496,6 +531,17 @@ __global__ MG_SHADE_BOUNDS void k_shade_snw(DScene sc, DPaths ps, DConfig cfg, D
 	static_assert(BT == 0, "a snow record sits on a Lambertian entry");
 	__shared__ ShadeShared sh;
 	shade_block<BT, ROUNDS, SKY, kSlotTexture, true, true, true>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col, tex, tan, msk, snw);
+}
+// and for scenes with a woven-cloth BRDF (DCloths), built on the snow kernels: the only ones that take the cloth tables, their
+// last argument.  Bin 0 only: a weave sits on a Lambertian entry.  The uv array of DTextures is never NULL here (the host
+// refuses a cloth mesh without texcoords, and a table before the texture call); any other table may be.  Launched like k_shade_snw
+template <int BT, bool ROUNDS, bool SKY>
+__global__ MG_SHADE_BOUNDS void k_shade_clo(DScene sc, DPaths ps, DConfig cfg, DQueues q, BinView view_host,
+                                                           const BinView *views_dev, const uint32_t *bin_ids, DColors col, DTextures tex, DTangents tan,
+                                                           DMasks msk, DSnows snw, DCloths clo) {
+	static_assert(BT == 0, "a weave sits on a Lambertian entry");
+	__shared__ ShadeShared sh;
+	shade_block<BT, ROUNDS, SKY, kSlotTexture, true, true, true, true>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col, tex, tan, msk, snw, clo);
 }
 
 // All material queues of a bounce in ONE launch (device-driven bounces): the workgroups are dealt to the bins in bin order,

@@ -130,6 +130,162 @@ def _rgb(v):
     return [F(x) for x in np.broadcast_to(np.asarray(v, dtype=np.float32), (3,))]
 
 
+class Yarn:
+    """one `Yarn` of a weave pattern (irawan.h:41-73): type "warp" / "weft" (or abi.YARN_*), angles in radians"""
+
+    def __init__(self, type="warp", psi=0.0, umax=0.0, kappa=0.0, width=0.0, length=0.0, centerU=0.0, centerV=0.0, kd=0.0, ks=0.0):
+        self.type = {"warp": abi.YARN_WARP, "weft": abi.YARN_WEFT}.get(type, type)
+        self.psi, self.umax, self.kappa, self.width, self.length = F(psi), F(umax), F(kappa), F(width), F(length)
+        self.centerU, self.centerV = F(centerU), F(centerV)
+        self.kd, self.ks = np.float32(_rgb(kd)), np.float32(_rgb(ks))
+
+    def __eq__(self, o):
+        return isinstance(o, Yarn) and all(np.array_equal(np.float32(getattr(self, n)), np.float32(getattr(o, n))) for n in
+                                           ("type", "psi", "umax", "kappa", "width", "length", "centerU", "centerV", "kd", "ks"))
+
+
+class Weave:
+    """a `WeavePattern` (irawan.h:130-165) with the four properties IrawanClothBRDF keeps next to it: the scalars of
+    abi.WEAVE_SCALARS, pattern (1-based yarn ids, row by row) and yarns (Yarn objects)"""
+
+    def __init__(self, name="", pattern=(), yarns=(), **scalars):
+        self.name = name
+        self.pattern = [int(p) for p in pattern]
+        self.yarns = list(yarns)
+        for n in abi.WEAVE_SCALARS:
+            v = scalars.pop(n, 1.0 if n in ("repeatU", "repeatV", "kdMultiplier", "ksMultiplier") else 0)
+            setattr(self, n, int(v) if n in ("tileWidth", "tileHeight") else F(v))
+        if scalars:
+            raise ValueError("Weave: unknown parameter(s) %s" % ", ".join(sorted(scalars)))
+
+    def replace(self, **scalars):
+        """a copy with some scalars replaced"""
+        w = Weave(self.name, self.pattern, self.yarns, **{n: getattr(self, n) for n in abi.WEAVE_SCALARS})
+        for n, v in scalars.items():
+            if n not in abi.WEAVE_SCALARS:
+                raise ValueError("Weave: unknown parameter %s" % n)
+            setattr(w, n, int(v) if n in ("tileWidth", "tileHeight") else F(v))
+        return w
+
+    def __eq__(self, o):
+        return isinstance(o, Weave) and self.name == o.name and self.pattern == o.pattern and self.yarns == o.yarns \
+            and all(getattr(self, n) == getattr(o, n) for n in abi.WEAVE_SCALARS)
+
+
+def load_weave(text, params=None):
+    """The weave-file grammar of the reference (irawan.h:268-377): `weave { name = "...", key = value, ..., pattern { 1, 2, ... },
+    yarn { type = warp | weft, key = value, ..., kd = {r, g, b} | $name, ks = ... }, ... }` with /* */ comments; a value is a
+    number or $name, substituted from `params` (a spectrum parameter: a grey level or an RGB triple).  psi, umax and the four d*UmaxOverD* are given in degrees and kept in radians
+    (value * M_PI / 180 in binary64, rounded to binary32, as the grammar's actions compute it).  -> Weave.  ValueError with the reason otherwise."""
+    import re
+    params = params or {}
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    tokens = re.findall(r'"[^"]*"|\$[A-Za-z_][A-Za-z_0-9]*|[A-Za-z_][A-Za-z_0-9]*|[-+]?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?|[{}=,]|\S', text)
+    pos = [0]
+
+    def peek():
+        return tokens[pos[0]] if pos[0] < len(tokens) else None
+
+    def take(expect=None):
+        t = peek()
+        if t is None or (expect is not None and t != expect):
+            raise ValueError("load_weave: expected %s, found %s (token %d)" % (expect or "a token", "the end" if t is None else repr(t), pos[0]))
+        pos[0] += 1
+        return t
+
+    def number():
+        t = take()
+        if t.startswith("$"):
+            if t[1:] not in params:
+                raise ValueError("load_weave: parameter %s is not given" % t)
+            return F(params[t[1:]])
+        try:
+            return F(float(t))
+        except ValueError:
+            raise ValueError("load_weave: expected a number, found %r (token %d)" % (t, pos[0] - 1))
+
+    def spectrum():
+        if peek() == "{":
+            take("{"); r = number(); take(","); g = number(); take(","); b = number(); take("}")
+            return [r, g, b]
+        t = take()
+        if not t.startswith("$"):
+            raise ValueError("load_weave: a spectrum is {r, g, b} or a $parameter, found %r" % t)
+        if t[1:] not in params:
+            raise ValueError("load_weave: parameter %s is not given" % t)
+        return _rgb(params[t[1:]])
+
+    deg = lambda v: F(float(v) * np.pi / 180)           # _1 * M_PI / 180: binary64, stored in a Float
+    weave_floats = ("alpha", "beta", "ss", "hWidth", "warpArea", "weftArea", "fineness", "period")
+    weave_degrees = ("dWarpUmaxOverDWarp", "dWarpUmaxOverDWeft", "dWeftUmaxOverDWarp", "dWeftUmaxOverDWeft")
+    yarn_floats = ("kappa", "width", "length", "centerU", "centerV")
+
+    def yarn():
+        take("{")
+        kw = {}
+        while peek() != "}":
+            key = take()
+            take("=")
+            if key == "type":
+                t = take()
+                if t not in ("warp", "weft"):
+                    raise ValueError("load_weave: yarn type %r is neither warp nor weft" % t)
+                kw["type"] = t
+            elif key in ("psi", "umax"):
+                kw[key] = deg(number())
+            elif key in yarn_floats:
+                kw[key] = number()
+            elif key in ("kd", "ks"):
+                kw[key] = spectrum()
+            else:
+                raise ValueError("load_weave: unknown yarn parameter %r" % key)
+            if peek() == ",":
+                take(",")
+        take("}")
+        return Yarn(**kw)
+
+    take("weave"); take("{")
+    name, scalars, pattern, yarns = "", {}, [], []
+    while peek() != "}":
+        key = take()
+        if key == "pattern":
+            take("{")
+            while peek() != "}":
+                t = take()
+                if not t.isdigit():
+                    raise ValueError("load_weave: pattern entry %r is not an unsigned integer" % t)
+                pattern.append(int(t))
+                if peek() == ",":
+                    take(",")
+            take("}")
+        elif key == "yarn":
+            yarns.append(yarn())
+        else:
+            take("=")
+            if key == "name":
+                t = take()
+                if not t.startswith('"'):
+                    raise ValueError("load_weave: the name is a quoted string, found %r" % t)
+                name = t[1:-1]
+            elif key in ("tileWidth", "tileHeight"):
+                t = take()
+                if not t.isdigit():
+                    raise ValueError("load_weave: %s = %r is not an unsigned integer" % (key, t))
+                scalars[key] = int(t)
+            elif key in weave_floats:
+                scalars[key] = number()
+            elif key in weave_degrees:
+                scalars[key] = deg(number())
+            else:
+                raise ValueError("load_weave: unknown weave parameter %r" % key)
+        if peek() == ",":
+            take(",")
+    take("}")
+    if peek() is not None:
+        raise ValueError("load_weave: text after the weave: %r" % peek())
+    return Weave(name, pattern, yarns, **scalars)
+
+
 class MeshDesc:
     def __init__(self, positions, triangles, bsdf=-1, lum=-1, face_normals=True, normals=None, name="", colors=None, texcoords=None):
         self.positions = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
@@ -170,6 +326,8 @@ class SceneDescription:
         self._slot_textures = ()
         self.bsdf_masks = {}        # BSDF index -> the opacity of the mask around it: an RGB triple or an entry of textures
         self.bsdf_snow = {}         # BSDF index -> (abi.SNOW_*, the raw parameters its configure call takes)
+        self.weaves = []            # the Weave objects of the cloth BSDFs
+        self.bsdf_weave = {}        # BSDF index -> index into weaves
         self.lum_type = []
         self.lum_params = []
         self.camera = dict(origin=(0.0, 1.0, 3.4), target=(0.0, 1.0, 0.0), up=(0.0, 1.0, 0.0), fov=39.3)
@@ -362,6 +520,22 @@ class SceneDescription:
         if configure is None:
             from . import snow_configure as configure
         return [configure(*self.bsdf_snow[b]) if b in self.bsdf_snow else None for b in range(len(self.bsdf_type))]
+
+    def irawan(self, weave, repeat_u=None, repeat_v=None, kd_multiplier=None, ks_multiplier=None):
+        """<bsdf type="irawan">: a Lambertian entry whose block is zero and is not read, with the Weave `weave` (load_weave); the
+        four properties of the plugin (irawan.cpp:80-85) override the weave's own when given"""
+        over = dict(repeatU=repeat_u, repeatV=repeat_v, kdMultiplier=kd_multiplier, ksMultiplier=ks_multiplier)
+        if any(v is not None for v in over.values()):
+            weave = weave.replace(**{k: v for k, v in over.items() if v is not None})
+        b = self.add_bsdf(abi.BSDF_LAMBERTIAN, [0.0, 0.0, 0.0])
+        if not any(weave is w for w in self.weaves):
+            self.weaves.append(weave)
+        self.bsdf_weave[b] = [i for i, w in enumerate(self.weaves) if w is weave][0]
+        return b
+
+    def weave_table(self):
+        """one weave index per BSDF, -1 for a BSDF without one (what mtsgpu_set_cloth_bsdfs takes as bsdf_weave)"""
+        return np.asarray([self.bsdf_weave.get(b, -1) for b in range(len(self.bsdf_type))], dtype=np.int32)
 
     def point_light(self, position, intensity):
         l = self.add_lum(abi.LUM_POINT, [intensity] * 3 if np.isscalar(intensity) else intensity)

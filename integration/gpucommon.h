@@ -13,7 +13,7 @@
  * into Mitsuba is annotated with the file:line of the declaration it relies on.
  *
  * What of a Mitsuba scene reaches the GPU (everything else stops with an error message that names the class):
- *   shapes      every TriMesh (obj, ply, serialized, ...: TriMesh accessors), `sphere`
+ *   shapes      every TriMesh (obj, ply, serialized, ...: TriMesh accessors), `sphere`, `cylinder` (a plain Lambertian on it, no luminaire)
  *   BSDFs       lambertian, dielectric, roughmetal, microfacet, mirror, phong, roughglass, difftrans, ward (anisotropic on
  *               spheres and on meshes with texture coordinates, whose vertex tangents travel along), twosided(any of them), composite(up to 7 of the non-delta ones, each with or without twosided);
  *               constant reflectances only (textures need uv partials and a MIPMap lookup per hit: out of scope)
@@ -22,7 +22,7 @@
  *   samplers    independent, ldsampler, stratified (keyed forms), halton, hammersley
  *   films       any (the result goes back as ImageBlocks); reconstruction filter = the film's own TabulatedFilter
  * Private members that block more: Texture2D bitmaps (BitmapTexture::m_mipmap has no accessor); every shape
- * other than TriMesh / Sphere (not implemented by the library, not blocked by access), media and
+ * other than TriMesh / Sphere / Cylinder (not implemented by the library, not blocked by access), media and
  * subsurface integrators (path.cpp ignores media, :31-34).
  */
 #ifndef MTSGPU_GPUCOMMON_H
@@ -43,6 +43,7 @@
 #include <mtsgpu_mask.h>
 #include <mtsgpu_snow.h>
 #include <mtsgpu_cloth.h>
+#include <mtsgpu_cylinder.h>
 #include "streamparse.h"
 #include <sstream>
 #include <cstdlib>
@@ -176,10 +177,17 @@ struct FlatScene {
 	std::vector<float> vtxDpdu;
 	std::vector<uint32_t> shapeHasTangents;
 	bool anyTangents;
+	/* the derived blocks of the cylinders, [n_shapes][MTSGPU_CYLINDER_NDERIVED] with zero rows for the other shapes: what
+	 * mtsgpu_group_upload_scene_cylinders takes */
+	std::vector<float> cylinders;
+	bool anyCylinders;
 
 	/* the scene, with the tangents when a mesh has some; an anisotropic BSDF on a mesh that has vertex normals but no
 	 * tangents (no texture coordinates: Mitsuba has stopped with an error long before) is refused by the library */
 	int upload(mtsgpu_group *group) const {
+		/* a scene with a cylinder takes the upload that carries the derived blocks (include/mtsgpu_cylinder.h) */
+		if (anyCylinders)
+			return mtsgpu_group_upload_scene_cylinders(group, &sc, anyTangents ? ptr(vtxDpdu) : NULL, anyTangents ? ptr(shapeHasTangents) : NULL, ptr(cylinders));
 		if (!anyTangents) return mtsgpu_group_upload_scene(group, &sc);
 		return mtsgpu_group_upload_scene_tangents(group, &sc, ptr(vtxDpdu), ptr(shapeHasTangents));
 	}
@@ -215,7 +223,7 @@ struct FlatScene {
 		return mtsgpu_group_set_vertex_colors(group, anyColors ? ptr(vtxCol) : NULL, anyColors ? ptr(shapeHasColors) : NULL, ptr(bsdfColorSlots));
 	}
 
-	FlatScene(const Scene *scene) : anyColors(false), anyColorSlots(false), anyUv(false), anyTangents(false) {
+	FlatScene(const Scene *scene) : anyColors(false), anyColorSlots(false), anyUv(false), anyTangents(false), anyCylinders(false) {
 		memset(&sc, 0, sizeof(sc));
 		sc.abi_version = MTSGPU_ABI_VERSION;
 		const ShapeKDTree *kd = scene->getKDTree();                                   /* scene.h:498 */
@@ -300,6 +308,7 @@ struct FlatScene {
 			shapeBsdf.push_back(bsdfOf(shape->getBSDF()));                            /* shape.h:385; NULL = not an occluder */
 			shapeLum.push_back(shape->isLuminaire() ? lumIndex[shape->getLuminaire()] : -1);   /* shape.h:329-340 */
 			shapeParams.insert(shapeParams.end(), MTSGPU_SHAPE_NPARAMS, 0.0f);
+			cylinders.insert(cylinders.end(), MTSGPU_CYLINDER_NDERIVED, 0.0f);
 			if (isMesh) {
 				const TriMesh *mesh = static_cast<const TriMesh *>(shape);
 				const uint32_t base = (uint32_t) (vtxPos.size() / 3);
@@ -368,8 +377,28 @@ struct FlatScene {
 					lumShape[l] = (int32_t) s;
 					lumInvArea[l] = SP[23];
 				}
+			} else if (shape->getClass()->getName() == "Cylinder") {
+				/* one kd-tree primitive like the sphere; src/shapes/cylinder.cpp keeps its transform, radius and length private:
+				 * read back from serialize() (:75-80), the constructor's derivation restated (:66-73).  The tree is Mitsuba's
+				 * own, built with Cylinder::getClippedAABB */
+				ref<MemoryStream> st = serializedDetached(const_cast<Shape *>(shape));
+				std::string err;
+				if (!mtsgpu_stream::parseCylinder<Float>(st->getData(), st->getSize(), shape->isLuminaire(),
+				                                          &cylinders[(size_t) MTSGPU_CYLINDER_NDERIVED * s], &err)) SLog(EError, "gpupath: %s", err.c_str());
+				anyCylinders = true;
+				TriAccel ta; memset(&ta, 0, sizeof(ta));
+				ta.k = KNoTriangleFlag; ta.shapeIndex = (uint32_t) s; ta.primIndex = 0;       /* triaccel.h:34-48,28 */
+				const uint32_t *w = reinterpret_cast<const uint32_t *>(&ta);
+				triaccel.insert(triaccel.end(), w, w + 12);
+				for (int k = 0; k < 3; ++k) triIdx.push_back(0xFFFFFFFFu);
+				shapeTriOffset.push_back(shapeTriOffset.back() + 1);
+				shapeFlags.push_back(0u);
+				shapeType.push_back(MTSGPU_SHAPE_CYLINDER);
+				shapeHasColors.push_back(0u);
+				shapeHasUv.push_back(0u);
+				shapeHasTangents.push_back(0u);
 			} else {
-				SLog(EError, "gpupath: shape class %s is not on this path (triangle meshes of any loader and spheres are)",
+				SLog(EError, "gpupath: shape class %s is not on this path (triangle meshes of any loader, spheres and cylinders are)",
 					shape->getClass()->getName().c_str());
 			}
 		}

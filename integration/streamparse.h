@@ -19,6 +19,7 @@
 #include <mtsgpu_mask.h>
 #include <mtsgpu_snow.h>
 #include <mtsgpu_cloth.h>
+#include <mtsgpu_cylinder.h>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -720,6 +721,40 @@ template <typename FloatT> inline bool parseSphere(const uint8_t *data, size_t s
 	const FloatT pi = (FloatT) 3.14159265358979323846;                       /* Mitsuba's M_PI has Float's precision (constants.h:38-53) */
 	SP[23] = (float) (1 / (4 * pi * radius * radius));                       /* m_invSurfaceArea (sphere.cpp:59, :69) */
 	if (!r.ok()) { if (err) *err = r.error(); return false; }
+	return true;
+}
+
+/* Cylinder (cylinder.cpp:75-80) behind Shape::serialize (shape.cpp:130-138), whose nested BSDF / luminaire are skipped by seeking
+ * from the END like parseSphere: the tail is a Transform (matrix and inverse), radius and length.  Then the unserialising
+ * constructor's own derivation (cylinder.cpp:66-73): worldToObject = objectToWorld.inverse(), which swaps the two matrices
+ * (transform.h:61-63), and m_invSurfaceArea.  D = the derived block of include/mtsgpu_cylinder.h (MTSGPU_CYLINDER_NDERIVED floats).
+ * isLuminaire: what shape->isLuminaire() says; a cylinder with an area luminaire is refused here with the library's reason
+ * (the nested luminaire cannot be seen from the end of the stream) */
+template <typename FloatT> inline bool parseCylinder(const uint8_t *data, size_t size, bool isLuminaire, float *D, std::string *err) {
+	if (isLuminaire) {
+		if (err) *err = "a cylinder cannot carry an area luminaire: Cylinder has no pdfArea, and Shape::pdfArea raises an error on the first "
+		                "BSDF-sampled hit (shape.cpp:174-178), so the reference cannot render it either";
+		return false;
+	}
+	ByteReader<FloatT> r(data, size);
+	openDetached(r, "Cylinder");
+	const size_t tail = 2 * 16 * sizeof(FloatT) + 2 * sizeof(FloatT);
+	if (r.ok() && size < tail + r.pos()) r.fail("the serialized cylinder is too short");
+	if (r.ok()) r.setPos(size - tail);
+	const Xform<FloatT> o2w = r.readTransform();
+	const FloatT radius = r.readFloat();
+	const FloatT length = r.readFloat();
+	copy3x4(D, o2w.fwd); copy3x4(D + 12, o2w.inv);
+	D[24] = (float) radius; D[25] = (float) length;
+	const FloatT pi = (FloatT) 3.14159265358979323846;                       /* Mitsuba's M_PI has Float's precision (constants.h:38-53) */
+	D[26] = (float) (1 / (2 * pi * radius * length));                        /* m_invSurfaceArea (cylinder.cpp:72) */
+	D[27] = 0.0f;
+	if (!r.ok()) { if (err) *err = r.error(); return false; }
+	for (int j = 0; j < 4; ++j)
+		if (o2w.fwd.m[3][j] != (FloatT) (j == 3 ? 1 : 0) || o2w.inv.m[3][j] != (FloatT) (j == 3 ? 1 : 0)) {
+			if (err) *err = "the serialized cylinder's transform is not affine";
+			return false;
+		}
 	return true;
 }
 

@@ -56,6 +56,11 @@ CLOTH_EXPORTS = ["mtsgpu_set_cloth_bsdfs", "mtsgpu_group_set_cloth_bsdfs", "mtsg
                  "mtsgpu_cloth_check", "mtsgpu_devmath"]
 
 
+# the cylinder shape's entry points: the extension declared in include/mtsgpu_cylinder.h
+CYLINDER_EXPORTS = ["mtsgpu_cylinder_configure", "mtsgpu_flatten_cylinders", "mtsgpu_flat_scene_cylinders", "mtsgpu_upload_scene_cylinders",
+                    "mtsgpu_group_upload_scene_cylinders", "mtsgpu_cylinder_aabb", "mtsgpu_cylinder_clip"]
+
+
 class MtsGpuError(RuntimeError):
     pass
 
@@ -247,6 +252,14 @@ def lib():
     L.mtsgpu_upload_scene_tangents.argtypes = [vp, C.POINTER(abi.Scene), f32p, u32p]
     L.mtsgpu_group_upload_scene_tangents.argtypes = [vp, C.POINTER(abi.Scene), f32p, u32p]
     L.mtsgpu_shading_frame_eval.argtypes = [vp, C.c_uint32, u32p, f32p, f32p]
+    cylp = C.POINTER(abi.Cylinder)
+    L.mtsgpu_cylinder_configure.argtypes = [cylp, f32p]
+    L.mtsgpu_flatten_cylinders.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.KdParams), C.POINTER(f32p), u32p, cylp, C.POINTER(vp)]
+    L.mtsgpu_flat_scene_cylinders.argtypes = [vp]; L.mtsgpu_flat_scene_cylinders.restype = f32p
+    L.mtsgpu_upload_scene_cylinders.argtypes = [vp, C.POINTER(abi.Scene), f32p, u32p, f32p]
+    L.mtsgpu_group_upload_scene_cylinders.argtypes = [vp, C.POINTER(abi.Scene), f32p, u32p, f32p]
+    L.mtsgpu_cylinder_aabb.argtypes = [f32p, f32p]
+    L.mtsgpu_cylinder_clip.argtypes = [f32p, C.c_uint32, f32p, C.c_int, f32p, u32p]
     bmpp = C.POINTER(abi.Bitmap)
     L.mtsgpu_set_uv_bitmap_textures.argtypes = [vp, f32p, u32p, C.c_uint32, texp, abi.i32p, C.c_uint32, bmpp, abi.i32p]
     L.mtsgpu_group_set_uv_bitmap_textures.argtypes = [vp, f32p, u32p, C.c_uint32, texp, abi.i32p, C.c_uint32, bmpp, abi.i32p]
@@ -403,6 +416,34 @@ def ldr_texels(pixels, gamma=-1.0, bpp=None, width=None, height=None):
     return out
 
 
+def cylinder_configure(cyl):
+    """mtsgpu_cylinder_configure of a scenes.CylinderDesc or an abi.Cylinder -> the derived block [28]"""
+    c = cyl.to_struct() if hasattr(cyl, "to_struct") else cyl
+    out = np.zeros(abi.CYLINDER_NDERIVED, dtype=np.float32)
+    if lib().mtsgpu_cylinder_configure(C.byref(c), abi.ptr(out, abi.f32p)) != 0:
+        raise MtsGpuError(lib().mtsgpu_last_error(None).decode())
+    return out
+
+
+def cylinder_aabb(derived):
+    """mtsgpu_cylinder_aabb -> [6] = min, max"""
+    d = np.ascontiguousarray(derived, dtype=np.float32).reshape(abi.CYLINDER_NDERIVED)
+    out = np.zeros(6, dtype=np.float32)
+    if lib().mtsgpu_cylinder_aabb(abi.ptr(d, abi.f32p), abi.ptr(out, abi.f32p)) != 0:
+        raise MtsGpuError(lib().mtsgpu_last_error(None).decode())
+    return out
+
+
+def cylinder_clip(derived, boxes, on_device=False):
+    """mtsgpu_cylinder_clip: boxes [n][6] -> (clipped [n][6], valid [n])"""
+    d = np.ascontiguousarray(derived, dtype=np.float32).reshape(abi.CYLINDER_NDERIVED)
+    b = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 6)
+    out = np.zeros_like(b); valid = np.zeros(b.shape[0], dtype=np.uint32)
+    if lib().mtsgpu_cylinder_clip(abi.ptr(d, abi.f32p), b.shape[0], abi.ptr(b, abi.f32p), int(on_device), abi.ptr(out, abi.f32p), abi.ptr(valid, abi.u32p)) != 0:
+        raise MtsGpuError(lib().mtsgpu_last_error(None).decode())
+    return out, valid.astype(bool)
+
+
 class Scene:
     """A flattened, render-ready scene: what Scene::initialize() leaves behind
     (kd-tree, TriAccel table, vertex normals, luminaire CDFs), built by mtsgpu_flatten()."""
@@ -426,7 +467,20 @@ class Scene:
         self.cloth = None
         if getattr(description, "bsdf_weave", None):
             self.cloth = weave_array(description.weaves) + (description.weave_table(),)
-        if self.wants_tangents:
+        # a description with a cylinder goes through the cylinder calls (include/mtsgpu_cylinder.h), every other one through
+        # the calls it always went through
+        self.has_cylinders = any(m.shape_type == abi.SHAPE_CYLINDER for m in description.meshes)
+        if self.has_cylinders:
+            tcs = (abi.f32p * max(len(description.meshes), 1))()
+            cyl = (abi.Cylinder * max(len(description.meshes), 1))()
+            for i, m in enumerate(description.meshes):
+                if m.shape_type == abi.SHAPE_TRIMESH and getattr(m, "texcoords", None) is not None:
+                    tcs[i] = abi.ptr(m.texcoords, abi.f32p)
+                if m.shape_type == abi.SHAPE_CYLINDER:
+                    cyl[i] = m.to_struct()
+            flags = None if self.cloth is None else np.ascontiguousarray(self.cloth[2] >= 0, dtype=np.uint32)
+            rc = lib().mtsgpu_flatten_cylinders(C.byref(self._desc), C.byref(kp), tcs, abi.ptr(flags, abi.u32p), cyl, C.byref(self._h))
+        elif self.wants_tangents:
             tcs = (abi.f32p * max(len(description.meshes), 1))()
             for i, m in enumerate(description.meshes):
                 if m.shape_type == abi.SHAPE_TRIMESH and getattr(m, "texcoords", None) is not None:
@@ -469,6 +523,11 @@ class Scene:
     @property
     def sc(self):
         return self.ptr.contents
+
+    def cylinder_blocks(self):
+        """the derived blocks mtsgpu_upload_scene_cylinders takes behind the scene, [n_shapes][28], or None without a cylinder"""
+        p = lib().mtsgpu_flat_scene_cylinders(self._h)
+        return abi.np_from(p, (self.sc.n_shapes, abi.CYLINDER_NDERIVED), np.float32) if p else None
 
     def vertex_color_args(self):
         """what mtsgpu_set_vertex_colors takes for this scene: (vtx_col, shape_has_colors, bsdf_color_slots) pointers, or
@@ -656,7 +715,11 @@ class MIPathTracer:
         self.configure()
         sp = scene.ptr if isinstance(scene, Scene) else scene
         ta = scene.tangent_args() if isinstance(scene, Scene) else None
-        if ta is not None:
+        cb = scene.cylinder_blocks() if isinstance(scene, Scene) else None
+        if cb is not None:
+            ta = ta if ta is not None else (None, None)
+            self._chk(lib().mtsgpu_upload_scene_cylinders(self._ctx, sp, abi.ptr(ta[0], abi.f32p), abi.ptr(ta[1], abi.u32p), abi.ptr(cb, abi.f32p)), "upload_scene_cylinders")
+        elif ta is not None:
             self._chk(lib().mtsgpu_upload_scene_tangents(self._ctx, sp, abi.ptr(ta[0], abi.f32p), abi.ptr(ta[1], abi.u32p)), "upload_scene_tangents")
         else:
             self._chk(lib().mtsgpu_upload_scene(self._ctx, sp), "upload_scene")
@@ -1131,7 +1194,11 @@ class DeviceGroup:
         sp = scene.ptr if isinstance(scene, Scene) else scene
         self._chk(lib().mtsgpu_group_set_integrator(self._g, self.maxDepth, self.rrDepth, int(self.strictNormals)), "set_integrator")
         ta = scene.tangent_args() if isinstance(scene, Scene) else None
-        if ta is not None:
+        cb = scene.cylinder_blocks() if isinstance(scene, Scene) else None
+        if cb is not None:
+            ta = ta if ta is not None else (None, None)
+            self._chk(lib().mtsgpu_group_upload_scene_cylinders(self._g, sp, abi.ptr(ta[0], abi.f32p), abi.ptr(ta[1], abi.u32p), abi.ptr(cb, abi.f32p)), "upload_scene_cylinders")
+        elif ta is not None:
             self._chk(lib().mtsgpu_group_upload_scene_tangents(self._g, sp, abi.ptr(ta[0], abi.f32p), abi.ptr(ta[1], abi.u32p)), "upload_scene_tangents")
         else:
             self._chk(lib().mtsgpu_group_upload_scene(self._g, sp), "upload_scene")

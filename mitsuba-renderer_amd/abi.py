@@ -27,6 +27,9 @@ SKY_NDERIVED = 24
 SAMPLER_INDEPENDENT_KEYED, SAMPLER_LD_KEYED, SAMPLER_HALTON, SAMPLER_HAMMERSLEY, SAMPLER_STRATIFIED_KEYED = 0, 1, 2, 3, 4
 SHAPE_HAS_NORMALS = 1
 SHAPE_TRIMESH, SHAPE_SPHERE = 0, 1
+SHAPE_CYLINDER = 2            # include/mtsgpu_cylinder.h
+CYLINDER_POINTS, CYLINDER_TOWORLD = 0, 1
+CYLINDER_NDERIVED = 28
 SHAPE_NPARAMS = 24
 KNOTRIANGLE = 0xFFFFFFFF
 CAMERA_RAY_FLOATS = 14          # a row of mtsgpu_camera_rays: o, mint, d, maxt, raster x, y | u32: d1, d2, pixel key, sample index
@@ -208,3 +211,8 @@ def scene_arrays(sc):
     out["env_pdf"] = np_from(sc.env_pdf, (npdf,), np.float32)
     out["env_cdf"] = np_from(sc.env_cdf, (npdf + 1 if npdf else 0,), np.float32)
     return out
+
+
+class Cylinder(C.Structure):
+    """mtsgpu_cylinder (include/mtsgpu_cylinder.h)"""
+    _fields_ = [("form", C.c_uint32), ("p1", C.c_float * 3), ("p2", C.c_float * 3), ("radius", C.c_float), ("to_world", C.c_float * 16)]

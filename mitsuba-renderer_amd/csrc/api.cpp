@@ -396,6 +396,57 @@ int mtsgpu_flatten_tangents_flagged(const mtsgpu_scene_desc *desc, const mtsgpu_
 	}
 	return 0;
 }
+int mtsgpu_flatten_cylinders(const mtsgpu_scene_desc *desc, const mtsgpu_kd_params *kd, const float *const *mesh_texcoords,
+                             const uint32_t *bsdf_anisotropic, const mtsgpu_cylinder *cylinders, mtsgpu_flat_scene **out) {
+	if (!desc || !out) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	*out = nullptr;
+	try {
+		std::unique_ptr<mtsgpu_flat_scene> p(new mtsgpu_flat_scene());
+		flattenScene(*desc, kd, p->fs, mesh_texcoords, bsdf_anisotropic, cylinders);
+		for (uint32_t s = 0; mesh_texcoords && s < desc->n_meshes; ++s)
+			if (mesh_texcoords[s] && desc->meshes[s].shape_type == MTSGPU_SHAPE_TRIMESH) {
+				const std::string why = setMeshTexcoords(p->fs, s, mesh_texcoords[s]);
+				if (!why.empty()) throw std::runtime_error(why);
+			}
+		*out = p.release();
+	} catch (const std::exception &e) {
+		return fail(nullptr, MTSGPU_EINVAL, "%s", e.what());
+	}
+	return 0;
+}
+const float *mtsgpu_flat_scene_cylinders(const mtsgpu_flat_scene *fs) { return (fs && !fs->fs.cylinders.empty()) ? fs->fs.cylinders.data() : nullptr; }
+
+int mtsgpu_cylinder_configure(const mtsgpu_cylinder *in, float *derived) {
+	if (!in || !derived) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	float D[MTSGPU_CYLINDER_NDERIVED];
+	const std::string why = cylinderConfigure(*in, D);
+	if (!why.empty()) return fail(nullptr, MTSGPU_EINVAL, "mtsgpu_cylinder_configure: %s", why.c_str());
+	std::memcpy(derived, D, sizeof(D));
+	return 0;
+}
+int mtsgpu_cylinder_aabb(const float *derived, float *out6) {
+	if (!derived || !out6) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	const std::string why = checkCylinderBlock(derived);
+	if (!why.empty()) return fail(nullptr, MTSGPU_EINVAL, "mtsgpu_cylinder_aabb: %s", why.c_str());
+	cylinderAabb(derived, out6);
+	return 0;
+}
+int mtsgpu_cylinder_clip(const float *derived, uint32_t n, const float *boxes, int on_device, float *out, uint32_t *valid) {
+	if (!derived || !boxes || !out || !valid) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	const std::string why = checkCylinderBlock(derived);
+	if (!why.empty()) return fail(nullptr, MTSGPU_EINVAL, "mtsgpu_cylinder_clip: %s", why.c_str());
+	float own[6], row[8];
+	cylinderAabb(derived, own);
+	cylinderBuilderRow(derived, row);
+	try {
+		if (on_device) cylinderClipDevice(row, own, n, boxes, out, valid);
+		else cylinderClipHost(row, own, n, boxes, out, valid);
+	} catch (const std::exception &e) {
+		return fail(nullptr, MTSGPU_EINVAL, "mtsgpu_cylinder_clip: %s", e.what());
+	}
+	return 0;
+}
+
 static bool flatSceneHasTangents(const mtsgpu_flat_scene *fs) {
 	if (!fs) return false;
 	for (uint32_t h : fs->fs.shapeHasTan) if (h) return true;

@@ -164,17 +164,29 @@ std::string setMeshTexcoords(FlatScene &f, uint32_t mesh, const float *texcoords
 	return std::string();
 }
 
-void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs, const float *const *meshTexcoords, const uint32_t *bsdfAnisotropic) {
+void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs, const float *const *meshTexcoords, const uint32_t *bsdfAnisotropic,
+                  const mtsgpu_cylinder *cylinders) {
 	const uint32_t nShapes = d.n_meshes, nLums = d.n_lums;
 	size_t nVerts = 0, nTris = 0;
+	bool anyCylinder = false;
 	// m_shapeMap (skdtree.cpp:43-60): a TriMesh contributes its triangles, any other shape ONE primitive
 	for (uint32_t s = 0; s < nShapes; ++s) {
-		const bool sphere = d.meshes[s].shape_type == MTSGPU_SHAPE_SPHERE;
+		const bool cylinder = d.meshes[s].shape_type == MTSGPU_SHAPE_CYLINDER;
+		if (cylinder && !cylinders)
+			throw std::runtime_error("flatten: shape " + std::to_string(s) + " is a cylinder: its geometry travels beside the description (mtsgpu_flatten_cylinders)");
+		const bool sphere = d.meshes[s].shape_type == MTSGPU_SHAPE_SPHERE || cylinder;      // one primitive, no vertices
 		if (!sphere && d.meshes[s].shape_type != MTSGPU_SHAPE_TRIMESH)
 			throw std::runtime_error("flatten: unknown shape type");
 		nVerts += sphere ? 0 : d.meshes[s].n_verts; nTris += sphere ? 1 : d.meshes[s].n_tris;
+		anyCylinder |= cylinder;
 	}
 	std::vector<float> genBox(6 * nTris + 6, 0.0f);
+	std::vector<float> cylTable;
+	fs.cylinders.clear();
+	if (anyCylinder) {
+		cylTable.assign(8 * nTris + 8, 0.0f);
+		fs.cylinders.assign((size_t) MTSGPU_CYLINDER_NDERIVED * (nShapes + 1), 0.0f);
+	}
 	fs.shapeType.assign(nShapes + 1, (uint32_t) MTSGPU_SHAPE_TRIMESH);
 	fs.shapeParams.assign((size_t) MTSGPU_SHAPE_NPARAMS * (nShapes + 1), 0.0f);
 	if (nTris >= 0x7FFFFFFFull || nVerts >= 0xFFFFFFFFull)
@@ -247,6 +259,22 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 			tbase += 1;
 			continue;
 		}
+		if (m.shape_type == MTSGPU_SHAPE_CYLINDER) {
+			// Cylinder::Cylinder (src/shapes/cylinder.cpp:34-64); the block lives beside the scene (fs.cylinders), the 24 shape
+			// parameters stay zero
+			if (m.lum >= 0)
+				throw std::runtime_error("flatten: shape " + std::to_string(s) + ": a cylinder cannot carry an area luminaire: Cylinder has no pdfArea, and "
+				                         "Shape::pdfArea raises an error on the first BSDF-sampled hit (shape.cpp:174-178), so the reference cannot render it either");
+			float *D = &fs.cylinders[(size_t) MTSGPU_CYLINDER_NDERIVED * s];
+			const std::string why = cylinderConfigure(cylinders[s], D);
+			if (!why.empty()) throw std::runtime_error("flatten: shape " + std::to_string(s) + ": " + why);
+			fs.shapeType[s] = MTSGPU_SHAPE_CYLINDER;
+			cylinderAabb(D, &genBox[6 * (size_t) tbase]);
+			cylinderBuilderRow(D, &cylTable[8 * (size_t) tbase]);
+			for (int k = 0; k < 3; ++k) fs.triIdx[3 * (size_t) tbase + k] = MTSGPU_KNOTRIANGLE;
+			tbase += 1;
+			continue;
+		}
 		std::memcpy(&fs.vtxPos[3 * (size_t) vbase], m.positions, sizeof(float) * 3 * (size_t) m.n_verts);
 		if (!m.face_normals) {
 			fs.shapeFlags[s] |= MTSGPU_SHAPE_HAS_NORMALS;
@@ -277,7 +305,7 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
 	fs.shapeVtxOffset[nShapes] = vbase;
 
 	// kd-tree + TriAccel table (ShapeKDTree::build, skdtree.cpp:62-101)
-	buildKdTree(fs.vtxPos.data(), fs.triIdx.data(), tbase, genBox.data(), kp, fs.kd);
+	buildKdTree(fs.vtxPos.data(), fs.triIdx.data(), tbase, genBox.data(), kp, fs.kd, anyCylinder ? cylTable.data() : nullptr);
 	for (uint32_t s = 0; s < nShapes; ++s)
 		for (uint32_t t = fs.shapeTriOffset[s]; t < fs.shapeTriOffset[s + 1]; ++t) {
 			const uint32_t *tri = &fs.triIdx[3 * (size_t) t];
@@ -563,6 +591,92 @@ Xf scale(float x, float y, float z) {                                           
 }
 
 } // namespace
+
+// ---------------------------------------------------------------------------
+// Cylinder (src/shapes/cylinder.cpp): the constructors, getAABB
+// ---------------------------------------------------------------------------
+std::string checkCylinderBlock(const float *D) {
+	for (int i = 0; i < MTSGPU_CYLINDER_NDERIVED; ++i)
+		if (!std::isfinite(D[i])) return "non-finite cylinder parameter";
+	if (!(D[24] > 0.0f) || !(D[25] > 0.0f)) return "a cylinder needs radius > 0 and length > 0 (Assert, cylinder.cpp:63)";
+	return std::string();
+}
+
+std::string cylinderConfigure(const mtsgpu_cylinder &in, float *D) {
+	Xf o2w;
+	float radius, len;
+	if (in.form == MTSGPU_CYLINDER_POINTS) {
+		for (int i = 0; i < 3; ++i)
+			if (!std::isfinite(in.p1[i]) || !std::isfinite(in.p2[i])) return "non-finite cylinder end point";
+		if (!std::isfinite(in.radius)) return "non-finite cylinder radius";
+		const V3 rel = ld3(in.p2) - ld3(in.p1);
+		radius = in.radius;
+		len = length(rel);
+		if (!(len > 0.0f) || !(radius > 0.0f) || !std::isfinite(len)) return "a cylinder needs radius > 0 and length > 0 (Assert, cylinder.cpp:63)";
+		// Frame(rel / length) (frame.h: coordinateSystem(n, s, t)), Transform::fromFrame (transform.cpp:192-203)
+		const V3 n = divs(rel, len);
+		V3 s, t;
+		coordinateSystem(n, s, t);
+		const Xf frame{ M4{ { { s.x, t.x, n.x, 0 }, { s.y, t.y, n.y, 0 }, { s.z, t.z, n.z, 0 }, { 0, 0, 0, 1 } } },
+		                M4{ { { s.x, s.y, s.z, 0 }, { t.x, t.y, t.z, 0 }, { n.x, n.y, n.z, 0 }, { 0, 0, 0, 1 } } } };
+		o2w = translate(in.p1[0], in.p1[1], in.p1[2]) * frame;
+	} else if (in.form == MTSGPU_CYLINDER_TOWORLD) {
+		Xf tw;
+		for (int i = 0; i < 4; ++i)
+			for (int j = 0; j < 4; ++j) {
+				if (!std::isfinite(in.to_world[4 * i + j])) return "non-finite cylinder transform";
+				tw.fwd.m[i][j] = in.to_world[4 * i + j];
+			}
+		if (tw.fwd.m[3][0] != 0 || tw.fwd.m[3][1] != 0 || tw.fwd.m[3][2] != 0 || tw.fwd.m[3][3] != 1) return "the last row of a cylinder's toWorld must be 0 0 0 1";
+		if (!invert(tw.fwd, tw.inv)) return "a cylinder's toWorld is singular";      // Transform(const Matrix4x4 &)
+		// objectToWorld(Vector(1,0,0)).length(), objectToWorld(Vector(0,0,1)).length() (transform.h:152-160)
+		const M4 &m = tw.fwd;
+		const V3 ex(m.m[0][0] * 1 + m.m[0][1] * 0 + m.m[0][2] * 0, m.m[1][0] * 1 + m.m[1][1] * 0 + m.m[1][2] * 0, m.m[2][0] * 1 + m.m[2][1] * 0 + m.m[2][2] * 0);
+		const V3 ez(m.m[0][0] * 0 + m.m[0][1] * 0 + m.m[0][2] * 1, m.m[1][0] * 0 + m.m[1][1] * 0 + m.m[1][2] * 1, m.m[2][0] * 0 + m.m[2][1] * 0 + m.m[2][2] * 1);
+		radius = length(ex);
+		len = length(ez);
+		if (!(len > 0.0f) || !(radius > 0.0f) || !std::isfinite(len) || !std::isfinite(radius)) return "a cylinder needs radius > 0 and length > 0 (Assert, cylinder.cpp:63)";
+		o2w = tw * scale(1 / radius, 1 / radius, 1 / len);      // the scale removed (cylinder.cpp:57-59)
+	} else {
+		return "unknown cylinder form " + std::to_string(in.form);
+	}
+	const Xf w2o = inverse(o2w);      // Transform::inverse swaps the two matrices (transform.h:61-63)
+	for (int i = 0; i < 3; ++i)
+		for (int j = 0; j < 4; ++j) { D[4 * i + j] = o2w.fwd.m[i][j]; D[12 + 4 * i + j] = w2o.fwd.m[i][j]; }
+	D[24] = radius; D[25] = len;
+	D[26] = 1 / (2 * kPi * radius * len);      // m_invSurfaceArea (cylinder.cpp:62)
+	D[27] = 0.0f;
+	// the last rows of both matrices must be 0 0 0 1 for the 3x4 blocks to be the transforms (w == 1, transform.h:102-119)
+	for (int j = 0; j < 4; ++j)
+		if (o2w.fwd.m[3][j] != (j == 3 ? 1.0f : 0.0f) || w2o.fwd.m[3][j] != (j == 3 ? 1.0f : 0.0f)) return "a cylinder's transform is not affine";
+	return checkCylinderBlock(D);
+}
+
+// Transform::operator()(Point) / (Vector) of objectToWorld (transform.h:102-119, :152-160) with w == 1
+static V3 cylPoint(const float *M, V3 p) {
+	return V3(M[0] * p.x + M[1] * p.y + M[2] * p.z + M[3], M[4] * p.x + M[5] * p.y + M[6] * p.z + M[7], M[8] * p.x + M[9] * p.y + M[10] * p.z + M[11]);
+}
+static V3 cylVector(const float *M, V3 v) {
+	return V3(M[0] * v.x + M[1] * v.y + M[2] * v.z, M[4] * v.x + M[5] * v.y + M[6] * v.z, M[8] * v.x + M[9] * v.y + M[10] * v.z);
+}
+
+void cylinderAabb(const float *D, float *out6) {
+	const float radius = D[24], len = D[25];
+	const V3 x1 = cylVector(D, V3(radius, 0, 0)), x2 = cylVector(D, V3(0, radius, 0));
+	const V3 p0 = cylPoint(D, V3(0, 0, 0)), p1 = cylPoint(D, V3(0, 0, len));
+	for (int i = 0; i < 3; ++i) {
+		const float range = std::sqrt(x1[i] * x1[i] + x2[i] * x2[i]);
+		out6[i] = std::min(std::min(std::numeric_limits<float>::infinity(), p0[i] - range), p1[i] - range);
+		out6[3 + i] = std::max(std::max(-std::numeric_limits<float>::infinity(), p0[i] + range), p1[i] + range);
+	}
+}
+
+void cylinderBuilderRow(const float *D, float *row8) {
+	const V3 cylPt = cylPoint(D, V3(0, 0, 0)), cylD = cylVector(D, V3(0, 0, 1));
+	row8[0] = cylPt.x; row8[1] = cylPt.y; row8[2] = cylPt.z;
+	row8[3] = cylD.x; row8[4] = cylD.y; row8[5] = cylD.z;
+	row8[6] = D[24]; row8[7] = 1.0f;
+}
 
 // ---------------------------------------------------------------------------
 // Environment map: MIPMap::fromBitmap (src/librender/mipmap.cpp:161-181) -> MIPMap::MIPMap with the

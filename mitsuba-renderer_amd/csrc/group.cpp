@@ -253,6 +253,11 @@ int mtsgpu_group_upload_scene(mtsgpu_group *g, const mtsgpu_scene *scene) {
 	return forAll(g, "upload_scene", [&](mtsgpu_ctx *c, int) { return mtsgpu_upload_scene(c, scene); });
 }
 
+int mtsgpu_group_upload_scene_cylinders(mtsgpu_group *g, const mtsgpu_scene *scene, const float *vtx_dpdu, const uint32_t *shape_has_tangents, const float *cylinders) {
+	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
+	return forAll(g, "upload_scene_cylinders", [&](mtsgpu_ctx *c, int) { return mtsgpu_upload_scene_cylinders(c, scene, vtx_dpdu, shape_has_tangents, cylinders); });
+}
+
 int mtsgpu_group_upload_scene_tangents(mtsgpu_group *g, const mtsgpu_scene *scene, const float *vtx_dpdu, const uint32_t *shape_has_tangents) {
 	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
 	return forAll(g, "upload_scene_tangents", [&](mtsgpu_ctx *c, int) { return mtsgpu_upload_scene_tangents(c, scene, vtx_dpdu, shape_has_tangents); });

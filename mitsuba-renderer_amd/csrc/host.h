@@ -4,6 +4,7 @@
 #include "../../include/mtsgpu_mask.h"
 #include "../../include/mtsgpu_snow.h"
 #include "../../include/mtsgpu_cloth.h"
+#include "../../include/mtsgpu_cylinder.h"
 #include "devmath.h"
 #include "kdtree.h"
 #include <cmath>
@@ -33,6 +34,9 @@ struct FlatScene {
 	// with texcoords has an anisotropic BSDF (TriMesh::computeTangentSpaceBasis)
 	std::vector<float> vtxTan;
 	std::vector<uint32_t> shapeHasTan;
+	// the derived blocks of the cylinders (mtsgpu_flatten_cylinders): [n_shapes + 1][MTSGPU_CYLINDER_NDERIVED], zero rows for the
+	// other shapes; empty without a cylinder
+	std::vector<float> cylinders;
 };
 
 // Texture-typed spectrum slots per BSDF type, in slot order (include/mtsgpu.h): the first float of each slot's three in the
@@ -339,7 +343,8 @@ inline bool bsdfIsAnisotropic(const uint32_t *type, const float *params, uint32_
 // Shapes that give the shading frame a tangent an anisotropic BSDF can use on their own: spheres (dpdu / dpdv).  A triangle
 // mesh has one when tangents were computed from its texture coordinates (mtsgpu_flatten_tangents,
 // mtsgpu_upload_scene_tangents); any shape type added later has none until it says so here.
-inline bool shapeHasTangentFrame(uint32_t shape_type) { return shape_type == MTSGPU_SHAPE_SPHERE; }
+// cylinders have one too (cylinder.cpp:165-171)
+inline bool shapeHasTangentFrame(uint32_t shape_type) { return shape_type == MTSGPU_SHAPE_SPHERE || shape_type == MTSGPU_SHAPE_CYLINDER; }
 // the reference's refusal of an anisotropic BSDF on a mesh without texture coordinates (trimesh.cpp:288-290, :547-556)
 inline std::string anisotropicOnMeshMessage(uint32_t shape) {
 	return "shape " + std::to_string(shape) + ": computeTangentSpace(): texture coordinates are required to generate tangent vectors. "
@@ -419,7 +424,15 @@ inline std::string checkSkyLuminaire(uint32_t l, const float *LP, int32_t backgr
 // mesh whose BSDF is anisotropic is accepted and receives tangents (fs.vtxTan, fs.shapeHasTan).  NULL: no mesh has any.
 // bsdfAnisotropic [n_bsdfs] (mtsgpu_flatten_tangents_flagged): non-zero = treat the entry as anisotropic as well; NULL: none.
 void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatScene &fs, const float *const *meshTexcoords = nullptr,
-                  const uint32_t *bsdfAnisotropic = nullptr);
+                  const uint32_t *bsdfAnisotropic = nullptr, const mtsgpu_cylinder *cylinders = nullptr);
+// mtsgpu_cylinder_configure: both constructors of cylinder.cpp:34-64; the reason it refuses, or an empty string
+std::string cylinderConfigure(const mtsgpu_cylinder &in, float *derived);
+// What the upload requires of a derived block; the reason, or an empty string
+std::string checkCylinderBlock(const float *derived);
+// Cylinder::getAABB (cylinder.cpp:187-208) of a derived block: out6 = min, max
+void cylinderAabb(const float *derived, float *out6);
+// the row of the kd-tree builder's cylinder table (kdtree.h) of a derived block
+void cylinderBuilderRow(const float *derived, float *row8);
 // The per-vertex colours of shape `mesh` of a flattened scene (mtsgpu_flat_scene_set_mesh_colors): colors [that mesh's
 // n_verts][3] copied into fs.vtxCol at the mesh's rows, NULL takes them away again.  Returns the reason it refuses, or an
 // empty string.

@@ -563,13 +563,26 @@ static void layOut(const Context &root, uint32_t prelimRoot, const std::vector<s
 
 } // namespace kd
 
-void buildKdTree(const float *vtx, const uint32_t *tri, uint32_t nTris, const float *genBox, const mtsgpu_kd_params *kp, KdTree &out) {
+void cylinderClipHost(const float *cyl8, const float *own6, uint32_t n, const float *boxes, float *out, uint32_t *valid) {
+	using namespace kd;
+	Box own;
+	for (int a = 0; a < 3; ++a) { own.mn[a] = own6[a]; own.mx[a] = own6[3 + a]; }
+	for (uint32_t i = 0; i < n; ++i) {
+		Box to, b;
+		for (int a = 0; a < 3; ++a) { to.mn[a] = boxes[6 * (size_t) i + a]; to.mx[a] = boxes[6 * (size_t) i + 3 + a]; }
+		valid[i] = cylinderClippedBox(cyl8, own, to, b) ? 1u : 0u;
+		for (int a = 0; a < 3; ++a) { out[6 * (size_t) i + a] = b.mn[a]; out[6 * (size_t) i + 3 + a] = b.mx[a]; }
+	}
+}
+
+void buildKdTree(const float *vtx, const uint32_t *tri, uint32_t nTris, const float *genBox, const mtsgpu_kd_params *kp, KdTree &out,
+                 const float *cylTable) {
 	using namespace kd;
 	const Params p = Params::from(kp, nTris);
 	const int nThreads = (kp && kp->n_threads > 0) ? kp->n_threads : (int) std::thread::hardware_concurrency();
 	out = KdTree();
 	if (nTris == 0) { out.nodes = { 0x80000000u, 0u }; return; }
-	const Geometry g{ { vtx, tri }, genBox };
+	const Geometry g{ { vtx, tri }, genBox, cylTable };
 	Builder b(g, p, nTris);
 	// gpu_binning is a bit set: 1 = min-max binning phase on the device, 2 = exact phase on the device
 	const bool exactOnDev = kp && (kp->gpu_binning & 2) != 0;

@@ -101,6 +101,143 @@ KD_HD static inline bool clippedTriangleBoxHD(const float *p0, const float *p1, 
 	return true;
 }
 
+// ---------------------------------------------------------------------------
+// Cylinder::getClippedAABB (src/shapes/cylinder.cpp:216-375), operation for operation in binary32 (the units are compiled
+// without FMA contraction).  One text for the host builder and the device exact phase.  cyl = one row of the builder's
+// cylinder table (kCylRow floats): cylPt = objectToWorld(Point(0,0,0)), cylD = objectToWorld(Vector(0,0,1)), radius, 1.
+// ---------------------------------------------------------------------------
+constexpr int kCylRow = 8;
+struct F3 { float x, y, z; };
+KD_HD inline float f3at(const F3 &a, int i) { return i == 0 ? a.x : (i == 1 ? a.y : a.z); }
+KD_HD inline void f3set(F3 &a, int i, float v) { if (i == 0) a.x = v; else if (i == 1) a.y = v; else a.z = v; }
+KD_HD inline F3 f3add(F3 a, F3 b) { return F3{ a.x + b.x, a.y + b.y, a.z + b.z }; }
+KD_HD inline F3 f3sub(F3 a, F3 b) { return F3{ a.x - b.x, a.y - b.y, a.z - b.z }; }
+KD_HD inline F3 f3mul(F3 a, float s) { return F3{ a.x * s, a.y * s, a.z * s }; }
+KD_HD inline float f3dot(F3 a, F3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+KD_HD inline F3 f3cross(F3 a, F3 b) { return F3{ a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x }; }
+// solveQuadratic (src/libcore/util.cpp:450-488)
+KD_HD inline bool kdSolveQuadratic(float a, float b, float c, float &x0, float &x1) {
+	if (a == 0) {
+		if (b != 0) { x0 = x1 = -c / b; return true; }
+		return false;
+	}
+	const float discrim = b * b - 4.0f * a * c;
+	if (discrim < 0)
+		return false;
+	const float sqrtDiscrim = sqrtf(discrim);
+	float temp;
+	if (b < 0) temp = -0.5f * (b - sqrtDiscrim);
+	else       temp = -0.5f * (b + sqrtDiscrim);
+	x0 = temp / a;
+	x1 = c / temp;
+	if (x0 > x1) { const float t = x0; x0 = x1; x1 = t; }
+	return true;
+}
+// intersectCylPlane (cylinder.cpp:216-255): the ellipse an infinite cylinder cuts out of a plane
+KD_HD inline bool cylPlane(F3 planePt, F3 planeNrml, F3 cylPt, F3 cylD, float radius, F3 &center, F3 *axes, float *lengths) {
+	if (fabsf(f3dot(planeNrml, cylD)) < kEps)
+		return false;
+	F3 B, A = f3sub(cylD, f3mul(planeNrml, f3dot(cylD, planeNrml)));
+	const float length = sqrtf(A.x * A.x + A.y * A.y + A.z * A.z);
+	if (length != 0) {
+		const float recip = 1.0f / length;
+		A = F3{ A.x * recip, A.y * recip, A.z * recip };
+		B = f3cross(planeNrml, A);
+	} else {
+		// coordinateSystem (util.cpp:602-611)
+		if (fabsf(planeNrml.x) > fabsf(planeNrml.y)) {
+			const float invLen = 1.0f / sqrtf(planeNrml.x * planeNrml.x + planeNrml.z * planeNrml.z);
+			A = F3{ -planeNrml.z * invLen, 0.0f, planeNrml.x * invLen };
+		} else {
+			const float invLen = 1.0f / sqrtf(planeNrml.y * planeNrml.y + planeNrml.z * planeNrml.z);
+			A = F3{ 0.0f, -planeNrml.z * invLen, planeNrml.y * invLen };
+		}
+		B = f3cross(planeNrml, A);
+	}
+	const F3 delta = f3sub(planePt, cylPt), deltaProj = f3sub(delta, f3mul(cylD, f3dot(delta, cylD)));
+	const float aDotD = f3dot(A, cylD), bDotD = f3dot(B, cylD);
+	const float c0 = 1 - aDotD * aDotD, c1 = 1 - bDotD * bDotD;
+	const float c2 = 2 * f3dot(A, deltaProj), c3 = 2 * f3dot(B, deltaProj);
+	const float c4 = f3dot(delta, deltaProj) - radius * radius;
+	const float lambda = (c2 * c2 / (4 * c0) + c3 * c3 / (4 * c1) - c4) / (c0 * c1);
+	const float alpha0 = -c2 / (2 * c0), beta0 = -c3 / (2 * c1);
+	lengths[0] = sqrtf(c1 * lambda);
+	lengths[1] = sqrtf(c0 * lambda);
+	center = f3add(f3add(planePt, f3mul(A, alpha0)), f3mul(B, beta0));
+	axes[0] = A; axes[1] = B;
+	return true;
+}
+// intersectCylFace (cylinder.cpp:257-330); points whose coordinates are NaN (beta / alpha with alpha == 0, a negative lambda)
+// fail contains() and the [0, 1] tests as they do there
+KD_HD inline Box cylFace(int axis, F3 mn, F3 mx, F3 cylPt, F3 cylD, float radius) {
+	const int axis1 = (axis + 1) % 3, axis2 = (axis + 2) % 3;
+	F3 planeNrml{ 0.0f, 0.0f, 0.0f };
+	f3set(planeNrml, axis, 1.0f);
+	F3 ellipseCenter, ellipseAxes[2];
+	float ellipseLengths[2];
+	Box aabb; aabb.reset();
+	if (!cylPlane(mn, planeNrml, cylPt, cylD, radius, ellipseCenter, ellipseAxes, ellipseLengths))
+		return aabb;
+	for (int i = 0; i < 4; ++i) {
+		F3 p1, p2;
+		f3set(p1, axis, f3at(mn, axis)); f3set(p2, axis, f3at(mn, axis));
+		f3set(p1, axis1, ((i + 1) & 2) ? f3at(mn, axis1) : f3at(mx, axis1));
+		f3set(p1, axis2, ((i + 0) & 2) ? f3at(mn, axis2) : f3at(mx, axis2));
+		f3set(p2, axis1, ((i + 2) & 2) ? f3at(mn, axis1) : f3at(mx, axis1));
+		f3set(p2, axis2, ((i + 1) & 2) ? f3at(mn, axis2) : f3at(mx, axis2));
+		const float p1lx = f3dot(f3sub(p1, ellipseCenter), ellipseAxes[0]) / ellipseLengths[0];
+		const float p1ly = f3dot(f3sub(p1, ellipseCenter), ellipseAxes[1]) / ellipseLengths[1];
+		const float p2lx = f3dot(f3sub(p2, ellipseCenter), ellipseAxes[0]) / ellipseLengths[0];
+		const float p2ly = f3dot(f3sub(p2, ellipseCenter), ellipseAxes[1]) / ellipseLengths[1];
+		const float relx = p2lx - p1lx, rely = p2ly - p1ly;
+		const float A = relx * relx + rely * rely;
+		const float B = 2 * (p1lx * relx + p1ly * rely);
+		const float C = (p1lx * p1lx + p1ly * p1ly) - 1;
+		float x0, x1;
+		if (kdSolveQuadratic(A, B, C, x0, x1)) {
+			if (x0 >= 0 && x0 <= 1) { const F3 p = f3add(p1, f3mul(f3sub(p2, p1), x0)); const float q[3] = { p.x, p.y, p.z }; aabb.expand(q); }
+			if (x1 >= 0 && x1 <= 1) { const F3 p = f3add(p1, f3mul(f3sub(p2, p1), x1)); const float q[3] = { p.x, p.y, p.z }; aabb.expand(q); }
+		}
+	}
+	ellipseAxes[0] = f3mul(ellipseAxes[0], ellipseLengths[0]);
+	ellipseAxes[1] = f3mul(ellipseAxes[1], ellipseLengths[1]);
+	// the componentwise maxima of the ellipse
+	for (int i = 0; i < 2; ++i) {
+		const int j = (i == 0) ? axis1 : axis2;
+		const float alpha = f3at(ellipseAxes[0], j), beta = f3at(ellipseAxes[1], j);
+		const float ratio = beta / alpha, tmp = sqrtf(1 + ratio * ratio);
+		const float cosTheta = 1 / tmp, sinTheta = ratio / tmp;
+		const F3 p1 = f3add(f3add(ellipseCenter, f3mul(ellipseAxes[0], cosTheta)), f3mul(ellipseAxes[1], sinTheta));
+		const F3 p2 = f3sub(f3sub(ellipseCenter, f3mul(ellipseAxes[0], cosTheta)), f3mul(ellipseAxes[1], sinTheta));
+		const float q1[3] = { p1.x, p1.y, p1.z }, q2[3] = { p2.x, p2.y, p2.z }, lo[3] = { mn.x, mn.y, mn.z }, hi[3] = { mx.x, mx.y, mx.z };
+		bool in1 = true, in2 = true;      // AABB::contains (aabb.h:133-138)
+		for (int c = 0; c < 3; ++c) {
+			if (q1[c] < lo[c] || q1[c] > hi[c]) in1 = false;
+			if (q2[c] < lo[c] || q2[c] > hi[c]) in2 = false;
+		}
+		if (in1) aabb.expand(q1);
+		if (in2) aabb.expand(q2);
+	}
+	return aabb;
+}
+// getClippedAABB (cylinder.cpp:332-375): own = getAABB(), to = the cell; false when the result is not valid
+KD_HD inline bool cylinderClippedBox(const float *cyl, const Box &own, const Box &to, Box &out) {
+	Box base = own;
+	base.clip(to);
+	const F3 cylPt{ cyl[0], cyl[1], cyl[2] }, cylD{ cyl[3], cyl[4], cyl[5] };
+	const float radius = cyl[6];
+	const float *n = base.mn, *x = base.mx;
+	out.reset();
+	out.expand(cylFace(0, F3{ n[0], n[1], n[2] }, F3{ n[0], x[1], x[2] }, cylPt, cylD, radius));
+	out.expand(cylFace(0, F3{ x[0], n[1], n[2] }, F3{ x[0], x[1], x[2] }, cylPt, cylD, radius));
+	out.expand(cylFace(1, F3{ n[0], n[1], n[2] }, F3{ x[0], n[1], x[2] }, cylPt, cylD, radius));
+	out.expand(cylFace(1, F3{ n[0], x[1], n[2] }, F3{ x[0], x[1], x[2] }, cylPt, cylD, radius));
+	out.expand(cylFace(2, F3{ n[0], n[1], n[2] }, F3{ x[0], x[1], n[2] }, cylPt, cylD, radius));
+	out.expand(cylFace(2, F3{ n[0], n[1], x[2] }, F3{ x[0], x[1], x[2] }, cylPt, cylD, radius));
+	out.clip(to);
+	return out.valid();
+}
+
 // SurfaceAreaHeuristic (sahkdtree3.h:35-79)
 struct SAH {
 	float t0[3], t1[3];
@@ -132,7 +269,8 @@ struct Params {
 // The primitives by number.  `corners` says whether a primitive is a triangle and where its corners are; any other
 // shape has its own box in genBox [n][6] (shape->getAABB(), skdtree.h:203-213).  The host reads the indexed mesh, the
 // device exact phase nine floats per primitive (kdbuild_exact.hip); the boxes are the same expressions on both.
-template <class Corners> struct GeometryOf { Corners corners; const float *genBox; };
+// cyl [n][kCylRow]: the cylinder table, NULL without a cylinder; row i is read when its last float is non-zero (a cylinder)
+template <class Corners> struct GeometryOf { Corners corners; const float *genBox; const float *cyl; };
 // static: a copy per unit, which the compiler sees through as it did the one-unit builder's local Geometry::box.  As inline
 // members shared between units these were calls that may throw and write memory: the host binning loop ran 3-5 % slower
 template <class G> KD_HD static void primBox(const G &g, uint32_t i, Box &b) {
@@ -143,8 +281,12 @@ template <class G> KD_HD static void primBox(const G &g, uint32_t i, Box &b) {
 	b.reset(); b.expand(g.corners.corner(i, 0)); b.expand(g.corners.corner(i, 1)); b.expand(g.corners.corner(i, 2));
 }
 template <class G> KD_HD static bool primClipped(const G &g, uint32_t i, const Box &to, Box &b) {
-	if (!g.corners.triangle(i)) {            // Shape::getClippedAABB (shape.cpp:59-63): getAABB().clip(box)
-		primBox(g, i, b); b.clip(to);
+	if (!g.corners.triangle(i)) {
+		if (g.cyl && g.cyl[kCylRow * (size_t) i + 7] != 0.0f) {      // Cylinder::getClippedAABB
+			Box own; primBox(g, i, own);
+			return cylinderClippedBox(g.cyl + kCylRow * (size_t) i, own, to, b);
+		}
+		primBox(g, i, b); b.clip(to);         // Shape::getClippedAABB (shape.cpp:59-63): getAABB().clip(box)
 		return b.valid();
 	}
 	return clippedTriangleBoxHD(g.corners.corner(i, 0), g.corners.corner(i, 1), g.corners.corner(i, 2), to.mn, to.mx, b.mn, b.mx);

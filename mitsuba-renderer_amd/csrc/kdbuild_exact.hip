@@ -78,14 +78,17 @@ using XGeometry = GeometryOf<SoupCorners>;
 
 // transitionToNLogN (gkdtree.h:1668-1704): the instances of the jobs' primitives; keep[i] = 0 drops a primitive whose
 // clipped box is empty or has no area
-__global__ void k_x_init(const float *triPos, const float *genBox, const uint32_t *prims, const uint32_t *primNode, uint32_t n,
+// CYL: the instantiation that knows the cylinder table, launched for scenes that have one; the other one reads no table and
+// keeps the registers it had before there were cylinders
+template <bool CYL>
+__global__ void k_x_init(const float *triPos, const float *genBox, const float *cyl, const uint32_t *prims, const uint32_t *primNode, uint32_t n,
                          const XNodeG *nodes, int clip, XInst *out, uint32_t *keep) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	XInst x; x.prim = prims[i]; x.node = primNode[i];
 	const XNodeG &nd = nodes[x.node];
 	bool ok = true;
-	const XGeometry geo{ { triPos }, genBox };
+	const XGeometry geo{ { triPos }, genBox, CYL ? cyl : nullptr };
 	if (clip) ok = primClipped(geo, x.prim, nd.box, x.box) && x.box.area() != 0;
 	else primBox(geo, x.prim, x.box);
 	out[i] = x; keep[i] = ok ? 1u : 0u;
@@ -236,7 +239,8 @@ __global__ void k_x_decide(XNodeG *nodes, uint32_t nNodes, const unsigned long l
 
 // classification wrt. the chosen plane (gkdtree.h:2053-2103) and the boxes of the straddlers inside the children
 // (perfect splits, :2140-2219)
-__global__ void k_x_classify(const XInst *inst, uint32_t n, XNodeG *nodes, const float *triPos, const float *genBox, int clip,
+template <bool CYL>
+__global__ void k_x_classify(const XInst *inst, uint32_t n, XNodeG *nodes, const float *triPos, const float *genBox, const float *cyl, int clip,
                              uint32_t *goesL, uint32_t *goesR, uint32_t *isLeafInst, float *boxL, float *boxR) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
@@ -259,7 +263,7 @@ __global__ void k_x_classify(const XInst *inst, uint32_t n, XNodeG *nodes, const
 		if (both) {
 			L = R = 1;
 			if (clip) {
-				const XGeometry geo{ { triPos }, genBox };
+				const XGeometry geo{ { triPos }, genBox, CYL ? cyl : nullptr };
 				Box l = nd.box, r = nd.box, in;
 				l.mx[a] = split; r.mn[a] = split;
 				if (primClipped(geo, x.prim, l, in) && in.area() > 0) { for (int c = 0; c < 3; ++c) { boxL[6 * (size_t) i + c] = in.mn[c]; boxL[6 * (size_t) i + 3 + c] = in.mx[c]; } }
@@ -402,6 +406,34 @@ template <typename T> void growKeep(ThrowingBuf<T> &b, size_t used, size_t need,
 
 } // namespace
 
+// mtsgpu_cylinder_clip on the device: cylinderClippedBox (kdbuild.h) as k_x_init and k_x_classify call it, one cell per thread
+namespace {
+__global__ void k_x_cyl_clip(const float *cyl8, const float *own6, uint32_t n, const float *boxes, float *out, uint32_t *valid) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	Box own, to, b;
+	for (int a = 0; a < 3; ++a) { own.mn[a] = own6[a]; own.mx[a] = own6[3 + a]; to.mn[a] = boxes[6 * (size_t) i + a]; to.mx[a] = boxes[6 * (size_t) i + 3 + a]; }
+	valid[i] = cylinderClippedBox(cyl8, own, to, b) ? 1u : 0u;
+	for (int a = 0; a < 3; ++a) { out[6 * (size_t) i + a] = b.mn[a]; out[6 * (size_t) i + 3 + a] = b.mx[a]; }
+}
+}
+void cylinderClipDevice(const float *cyl8, const float *own6, uint32_t n, const float *boxes, float *out, uint32_t *valid) {
+	requireDevice("the cylinder clip hook");
+	if (!n) return;
+	const Stream st("cylinder clip hook");
+	ThrowingBuf<float> dIn, dBoxes, dOut;
+	ThrowingBuf<uint32_t> dValid;
+	dIn.reserve(kCylRow + 6); dBoxes.reserve(6 * (size_t) n); dOut.reserve(6 * (size_t) n); dValid.reserve(n);
+	KXHIP(hipMemcpyAsync(dIn.p, cyl8, kCylRow * sizeof(float), hipMemcpyHostToDevice, st));
+	KXHIP(hipMemcpyAsync(dIn.p + kCylRow, own6, 6 * sizeof(float), hipMemcpyHostToDevice, st));
+	KXHIP(hipMemcpyAsync(dBoxes.p, boxes, 6 * (size_t) n * sizeof(float), hipMemcpyHostToDevice, st));
+	hipLaunchKernelGGL(k_x_cyl_clip, dim3((n + 255u) / 256u), dim3(256), 0, st, dIn.p, dIn.p + kCylRow, n, dBoxes.p, dOut.p, dValid.p);
+	KXHIP(hipGetLastError());
+	KXHIP(hipMemcpyAsync(out, dOut.p, 6 * (size_t) n * sizeof(float), hipMemcpyDeviceToHost, st));
+	KXHIP(hipMemcpyAsync(valid, dValid.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+	KXHIP(hipStreamSynchronize(st));
+}
+
 void kd::exactOnDevice(const Params &p, const Geometry &g, uint32_t nPrims, std::vector<std::unique_ptr<Job>> &jobs) {
 	requireDevice("the device exact phase");
 	if (jobs.empty()) return;
@@ -417,7 +449,7 @@ void kd::exactOnDevice(const Params &p, const Geometry &g, uint32_t nPrims, std:
 	const int nThreads = std::max(1, std::min<int>(16, (int) std::thread::hardware_concurrency()));
 
 	// geometry: nine floats per triangle (NaN marks a non-triangle primitive, whose box is in genBox)
-	ThrowingBuf<float> dTri, dGen;
+	ThrowingBuf<float> dTri, dGen, dCyl;      // dCyl.p stays NULL without a cylinder
 	{
 		std::unique_ptr<float[]> tpBuf(new float[9 * (size_t) nPrims]);
 		float *tp = tpBuf.get();
@@ -434,6 +466,10 @@ void kd::exactOnDevice(const Params &p, const Geometry &g, uint32_t nPrims, std:
 		KXHIP(hipMemcpyAsync(dTri.p, tp, 9 * (size_t) nPrims * sizeof(float), hipMemcpyHostToDevice, st));
 		dGen.reserve(anyGen ? 6 * (size_t) nPrims : 6);
 		if (anyGen) KXHIP(hipMemcpyAsync(dGen.p, g.genBox, 6 * (size_t) nPrims * sizeof(float), hipMemcpyHostToDevice, st));
+		if (g.cyl) {
+			dCyl.reserve(kCylRow * (size_t) nPrims);
+			KXHIP(hipMemcpyAsync(dCyl.p, g.cyl, kCylRow * (size_t) nPrims * sizeof(float), hipMemcpyHostToDevice, st));
+		}
 		KXHIP(hipStreamSynchronize(st));
 	}
 
@@ -491,7 +527,7 @@ void kd::exactOnDevice(const Params &p, const Geometry &g, uint32_t nPrims, std:
 		KXHIP(hipMemcpyAsync(dU[0].p, hp.data(), nInit * 4, hipMemcpyHostToDevice, st));
 		KXHIP(hipMemcpyAsync(dU[1].p, hn.data(), nInit * 4, hipMemcpyHostToDevice, st));
 		if (nInit) {
-			hipLaunchKernelGGL(k_x_init, grid(nInit), dim3(B), 0, st, dTri.p, dGen.p, dU[0].p, dU[1].p, (uint32_t) nInit, dAll.p, prm.clip, dInstB.p, dU[2].p);
+			hipLaunchKernelGGL((dCyl.p ? k_x_init<true> : k_x_init<false>), grid(nInit), dim3(B), 0, st, dTri.p, dGen.p, dCyl.p, dU[0].p, dU[1].p, (uint32_t) nInit, dAll.p, prm.clip, dInstB.p, dU[2].p);
 			scan.sum(dU[2].p, dU[3].p, nInit, st);
 			hipLaunchKernelGGL(k_x_compact, grid(nInit), dim3(B), 0, st, dInstB.p, dU[2].p, dU[3].p, (uint32_t) nInit, dInstA.p);
 			hipLaunchKernelGGL(k_x_roots, grid(jobs.size()), dim3(B), 0, st, dAll.p, (uint32_t) jobs.size(), dU[3].p, dTotals.p);
@@ -542,7 +578,7 @@ void kd::exactOnDevice(const Params &p, const Geometry &g, uint32_t nPrims, std:
 		uint32_t *gL = dU[0].p, *gR = dU[1].p, *lf = dU[2].p, *sL = dU[3].p, *sR = dU[4].p, *sLf = dU[5].p;
 		uint32_t *splitFlag = dV[0].p, *sSplit = dV[1].p, *c2 = dV[2].p, *sC2 = dV[3].p;
 		if (nInst) {
-			hipLaunchKernelGGL(k_x_classify, grid(nInst), dim3(B), 0, st, dInstA.p, (uint32_t) nInst, nodes, dTri.p, dGen.p, prm.clip, gL, gR, lf, dBoxL.p, dBoxR.p);
+			hipLaunchKernelGGL((dCyl.p ? k_x_classify<true> : k_x_classify<false>), grid(nInst), dim3(B), 0, st, dInstA.p, (uint32_t) nInst, nodes, dTri.p, dGen.p, dCyl.p, prm.clip, gL, gR, lf, dBoxL.p, dBoxR.p);
 			scan.sum(gL, sL, nInst, st); scan.sum(gR, sR, nInst, st); scan.sum(lf, sLf, nInst, st);
 		}
 		hipLaunchKernelGGL(k_x_counts, grid(nA), dim3(B), 0, st, nodes, (uint32_t) nA, sL, sR, splitFlag, c2);

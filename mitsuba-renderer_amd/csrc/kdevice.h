@@ -118,4 +118,62 @@ __device__ __forceinline__ bool sphere_occludes(V3 center, float radius, V3 ro, 
 	return true;
 }
 
+// ===========================================================================
+// Cylinder shape (src/shapes/cylinder.cpp).  Its traversal record is four 16-byte rows in the leaf-record buffer behind the
+// records themselves (mtsgpu_upload_scene_cylinders): r0, r1, r2 = the rows of worldToObject (3x4), r3 = (radius, length, -, -).
+// ===========================================================================
+// the ray in object space (Transform::operator()(Ray), transform.h:219-235, with w == 1) and the quadratic of
+// Cylinder::rayIntersect (cylinder.cpp:82-100); lz, ldz = the z components of the local origin and direction
+__device__ __forceinline__ bool cylinder_roots(const float4 r0, const float4 r1, const float4 r2, float radius, V3 ro, V3 rd,
+                                               float &nearT, float &farT, float &lz, float &ldz) {
+	const float ox = r0.x * ro.x + r0.y * ro.y + r0.z * ro.z + r0.w;
+	const float oy = r1.x * ro.x + r1.y * ro.y + r1.z * ro.z + r1.w;
+	lz = r2.x * ro.x + r2.y * ro.y + r2.z * ro.z + r2.w;
+	const float dx = r0.x * rd.x + r0.y * rd.y + r0.z * rd.z;
+	const float dy = r1.x * rd.x + r1.y * rd.y + r1.z * rd.z;
+	ldz = r2.x * rd.x + r2.y * rd.y + r2.z * rd.z;
+	const float A = dx * dx + dy * dy;
+	const float B = 2 * (dx * ox + dy * oy);
+	const float C = ox * ox + oy * oy - radius * radius;
+	return solve_quadratic(A, B, C, nearT, farT);
+}
+// Cylinder::rayIntersect(ray, mint, maxt, t, tmp) (cylinder.cpp:82-118)
+__device__ __forceinline__ bool cylinder_intersect(const float4 r0, const float4 r1, const float4 r2, float radius, float len, V3 ro, V3 rd,
+                                                   float mint, float maxt, float &t) {
+	float nearT, farT, lz, ldz;
+	if (!cylinder_roots(r0, r1, r2, radius, ro, rd, nearT, farT, lz, ldz))
+		return false;
+	if (nearT > maxt || farT < mint)
+		return false;
+	const float zPosNear = lz + ldz * nearT;
+	const float zPosFar = lz + ldz * farT;
+	if (zPosNear >= 0 && zPosNear <= len && nearT >= mint) {
+		t = nearT;
+	} else if (zPosFar >= 0 && zPosFar <= len) {
+		if (farT > maxt)
+			return false;
+		t = farT;
+	} else {
+		return false;
+	}
+	return true;
+}
+// Cylinder::rayIntersect(ray, mint, maxt) (cylinder.cpp:120-152)
+__device__ __forceinline__ bool cylinder_occludes(const float4 r0, const float4 r1, const float4 r2, float radius, float len, V3 ro, V3 rd,
+                                                  float mint, float maxt) {
+	float nearT, farT, lz, ldz;
+	if (!cylinder_roots(r0, r1, r2, radius, ro, rd, nearT, farT, lz, ldz))
+		return false;
+	if (nearT > maxt || farT < mint)
+		return false;
+	const float zPosNear = lz + ldz * nearT;
+	const float zPosFar = lz + ldz * farT;
+	if (zPosNear >= 0 && zPosNear <= len && nearT >= mint)
+		return true;
+	else if (zPosFar >= 0 && zPosFar <= len && farT <= maxt)
+		return true;
+	else
+		return false;
+}
+
 } // namespace mg

@@ -84,6 +84,9 @@ enum : uint32_t { kReqPair = 1, kReqNode = 2, kReqLeaf = 3, kReqRay = 4, kReqHit
 enum { kStatClosest = 0, kStatShadow = 1, kStatOverflow = 2, kStatLaunches = 3, kStatBin0 = 4, kNumDevStats = kStatBin0 + kNumBins };
 
 // Scene in HBM (all pointers are device pointers); see DESIGN.md section 3
+// DScene::has_shapes: 0 = triangles only, kHasShapes = other shapes too, kHasCylinders = a cylinder among them (the issue's has_cylinders,
+// kept in the same word so that DScene and DTraceScene keep their layout)
+constexpr uint32_t kHasShapes = 1u, kHasCylinders = 2u;
 struct DScene {
 	const uint2    *nodes;        // 8 B: (left child index << 2 | axis, split) or (1 << 31 | first record, end record)
 	// TriAccel records in LEAF ORDER: entry e of the kd-tree index list holds the 48-byte
@@ -101,7 +104,8 @@ struct DScene {
 	// environment map (level 0 of the MIPMap, RGB) and its sampling density (envmap.cpp:95-110)
 	const float    *env_pixels, *env_pdf, *env_cdf;
 	uint32_t        env_width, env_height, env_pdf_width, env_pdf_height;
-	uint32_t        has_shapes;   // the scene has non-triangle shapes (lets the traversal skip their test with one scalar branch)
+	uint32_t        has_shapes;   // the scene has non-triangle shapes (lets the traversal skip their test with one scalar branch);
+	                              // 2 = a cylinder among them: the traversal launches its cylinder instantiations (trace.hip: CYL)
 	const uint32_t *shape_flags, *shape_tri_offset;
 	const uint32_t *bsdf_type;
 	const float    *bsdf_params;

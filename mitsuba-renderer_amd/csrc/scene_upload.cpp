@@ -63,8 +63,11 @@ bool gatherMeshRows(const uint32_t *triIdx, uint32_t t0, uint32_t t1, const floa
 
 extern "C" {
 
-// mtsgpu_upload_scene (vtx_dpdu = shape_has_tangents = NULL, withTangents = false) and mtsgpu_upload_scene_tangents
-static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_dpdu, const uint32_t *shape_has_tangents, bool withTangents) {
+// mtsgpu_upload_scene (vtx_dpdu = shape_has_tangents = NULL, withTangents = false), mtsgpu_upload_scene_tangents and
+// mtsgpu_upload_scene_cylinders (cylinders = the derived blocks [n_shapes][MTSGPU_CYLINDER_NDERIVED] or NULL, `me` = the call
+// that accepts them; NULL, nullptr in the other two, which refuse the shape type)
+static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_dpdu, const uint32_t *shape_has_tangents, bool withTangents,
+                       const float *cylinders = nullptr, bool acceptsCylinders = false) {
 	if (!c || !sc) return fail(c, MTSGPU_EINVAL, "null argument");
 	c->lastPass.valid = false;
 	if (sc->abi_version != MTSGPU_ABI_VERSION) return fail(c, MTSGPU_EINVAL, "scene ABI version %u != %d", sc->abi_version, MTSGPU_ABI_VERSION);
@@ -108,7 +111,10 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 	if ((sc->shape_type == nullptr) != (sc->shape_params == nullptr)) return fail(c, MTSGPU_EINVAL, "shape_type and shape_params must both be given or both be NULL");
 	auto shapeType = [&](uint32_t s) { return sc->shape_type ? sc->shape_type[s] : (uint32_t) MTSGPU_SHAPE_TRIMESH; };
 	for (uint32_t s = 0; s < sc->n_shapes; ++s) {
-		if (shapeType(s) > MTSGPU_SHAPE_SPHERE) return fail(c, MTSGPU_EINVAL, "shape %u: unknown shape type", s);
+		if (shapeType(s) == MTSGPU_SHAPE_CYLINDER) {
+			if (!acceptsCylinders) return fail(c, MTSGPU_EINVAL, "shape %u is a cylinder: its derived block travels beside the scene, upload it with mtsgpu_upload_scene_cylinders", s);
+			if (!cylinders) return fail(c, MTSGPU_EINVAL, "shape %u is a cylinder, but mtsgpu_upload_scene_cylinders was given no cylinder blocks", s);
+		} else if (shapeType(s) > MTSGPU_SHAPE_SPHERE) return fail(c, MTSGPU_EINVAL, "shape %u: unknown shape type", s);
 		if (sc->shape_tri_offset[s] > sc->shape_tri_offset[s + 1] || sc->shape_tri_offset[s + 1] > sc->n_tris) return fail(c, MTSGPU_EINVAL, "shape_tri_offset not monotone");
 		const bool mesh = shapeType(s) == MTSGPU_SHAPE_TRIMESH;
 		if (!mesh) {
@@ -116,7 +122,22 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 			if (sc->shape_tri_offset[s + 1] - sc->shape_tri_offset[s] != 1) return fail(c, MTSGPU_EINVAL, "shape %u: a non-mesh shape must own exactly one primitive", s);
 			const float *SP = sc->shape_params + (size_t) MTSGPU_SHAPE_NPARAMS * s;
 			for (int i = 0; i < MTSGPU_SHAPE_NPARAMS; ++i) if (!std::isfinite(SP[i])) return fail(c, MTSGPU_EINVAL, "shape %u: non-finite parameter", s);
-			if (SP[3] == 0.0f) return fail(c, MTSGPU_EINVAL, "shape %u: zero radius", s);
+			if (shapeType(s) == MTSGPU_SHAPE_CYLINDER) {
+				const std::string why = checkCylinderBlock(cylinders + (size_t) MTSGPU_CYLINDER_NDERIVED * s);
+				if (!why.empty()) return fail(c, MTSGPU_EINVAL, "shape %u: %s", s, why.c_str());
+				// what a cylinder's hit has been rendered and checked with: a plain Lambertian (constant, checkerboard, grid or bitmap
+				// reflectance).  Every other family is refused by name until it has its frames: the shading kernels of the other
+				// bins and of the mask, snow and cloth families are compiled without the cylinder's record (shade_bsdf.h: CYL)
+				// (without a BSDF its closest hits would go to the terminal bin, whose kernel does not build a cylinder's record either)
+				if (sc->shape_bsdf[s] < 0)
+					return fail(c, MTSGPU_EINVAL, "shape %u: a cylinder without a BSDF is not served yet: give it a plain lambertian", s);
+				if (sc->shape_bsdf[s] < (int32_t) sc->n_bsdfs && sc->bsdf_type[sc->shape_bsdf[s]] != (uint32_t) MTSGPU_BSDF_LAMBERTIAN)
+					return fail(c, MTSGPU_EINVAL, "shape %u: a cylinder takes a plain lambertian BSDF only; BSDF %d is of type %u%s, not served on a cylinder yet",
+					            s, sc->shape_bsdf[s], sc->bsdf_type[sc->shape_bsdf[s]] & 0xFFu, (sc->bsdf_type[sc->shape_bsdf[s]] & MTSGPU_BSDF_TWOSIDED) ? " under twosided" : "");
+				if (sc->shape_lum[s] >= 0)
+					return fail(c, MTSGPU_EINVAL, "shape %u: a cylinder cannot carry an area luminaire: Cylinder has no pdfArea, and Shape::pdfArea raises an error "
+					            "on the first BSDF-sampled hit (shape.cpp:174-178), so the reference cannot render it either", s);
+			} else if (SP[3] == 0.0f) return fail(c, MTSGPU_EINVAL, "shape %u: zero radius", s);
 		}
 		for (uint32_t t = sc->shape_tri_offset[s]; t < sc->shape_tri_offset[s + 1]; ++t) {
 			const uint32_t k = sc->triaccel[12 * (size_t) t];
@@ -271,7 +292,22 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 		// indirection on the device); non-occluders are shapes without a BSDF
 		// (Shape::isOccluder, shape.h:324)
 		const size_t LS = 4 * (size_t) kLeafStride;                 // dwords per record slot
-		std::vector<uint32_t> ta(LS * ((size_t) sc->n_indices + 1), 0u);
+		// behind the records: four 16-byte rows per cylinder, worldToObject 3x4 and (radius, length, -, -) (kdevice.h); a
+		// cylinder's record points at them with dword 4 = the index of the first row in units of 16 bytes
+		std::vector<uint32_t> cylRow(sc->n_shapes, 0u);
+		const size_t firstCylRow = (size_t) kLeafStride * ((size_t) sc->n_indices + 1);
+		size_t nCyl = 0;
+		for (uint32_t s = 0; s < sc->n_shapes; ++s)
+			if (shapeType(s) == MTSGPU_SHAPE_CYLINDER) cylRow[s] = (uint32_t) (firstCylRow + 4 * nCyl++);
+		if (firstCylRow + 4 * nCyl >= (1ull << 32)) return fail(c, MTSGPU_EINVAL, "too many leaf records");
+		std::vector<uint32_t> ta(LS * ((size_t) sc->n_indices + 1) + 16 * nCyl, 0u);
+		for (uint32_t s = 0; s < sc->n_shapes; ++s)
+			if (shapeType(s) == MTSGPU_SHAPE_CYLINDER) {
+				const float *D = cylinders + (size_t) MTSGPU_CYLINDER_NDERIVED * s;
+				uint32_t *rows = &ta[4 * (size_t) cylRow[s]];
+				std::memcpy(rows, D + 12, 48);
+				std::memcpy(rows + 12, D + 24, 8);
+			}
 		for (uint32_t e = 0; e < sc->n_indices; ++e) {
 			const uint32_t prim = sc->kd_indices[e];
 			uint32_t *dst = &ta[LS * (size_t) e];
@@ -290,6 +326,7 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 					const float *SP = sc->shape_params + (size_t) MTSGPU_SHAPE_NPARAMS * dst[10];
 					dst[1] = shapeType(dst[10]);
 					std::memcpy(dst + 4, SP, 16);
+					if (dst[1] == MTSGPU_SHAPE_CYLINDER) dst[4] = cylRow[dst[10]];
 				}
 			}
 		}
@@ -302,7 +339,8 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 				float *P = &triRec[TS * (size_t) t], *Nn = P + 12;
 				if (shapeType(s) != MTSGPU_SHAPE_TRIMESH) {
 					// non-mesh shape: centre + radius, flag bit 31 (the rest comes from shape_params)
-					const uint32_t flags = sc->shape_flags[s] | 0x80000000u;
+					// (bit 30: the shape is a cylinder, whose record fill_its builds from its own layout of shape_params)
+					const uint32_t flags = sc->shape_flags[s] | 0x80000000u | (shapeType(s) == MTSGPU_SHAPE_CYLINDER ? 0x40000000u : 0u);
 					std::memcpy(P, sc->shape_params + (size_t) MTSGPU_SHAPE_NPARAMS * s, 16);
 					std::memcpy(P + 10, &s, 4); std::memcpy(P + 11, &flags, 4);
 					continue;
@@ -334,6 +372,16 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 			std::copy(sc->shape_type, sc->shape_type + sc->n_shapes, st.begin());
 			std::copy(sc->shape_params, sc->shape_params + (size_t) MTSGPU_SHAPE_NPARAMS * sc->n_shapes, sp.begin());
 		}
+		// a cylinder's device row, what the shading reads (shade_bsdf.h): [0..11] worldToObject 3x4, [12..20] the 3x3 of
+		// objectToWorld, [21] length, [22] radius, [23] 1 / area
+		for (uint32_t s = 0; s < sc->n_shapes; ++s)
+			if (shapeType(s) == MTSGPU_SHAPE_CYLINDER) {
+				const float *D = cylinders + (size_t) MTSGPU_CYLINDER_NDERIVED * s;
+				float *P = &sp[(size_t) MTSGPU_SHAPE_NPARAMS * s];
+				std::memcpy(P, D + 12, 48);
+				for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) P[12 + 3 * i + j] = D[4 * i + j];
+				P[21] = D[25]; P[22] = D[24]; P[23] = D[26];
+			}
 		rc |= upload(c, &d.shape_type, st.data(), st.size());
 		rc |= upload(c, &d.shape_params, sp.data(), sp.size());
 	}
@@ -369,7 +417,8 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 	c->dtan = DTangents{ reinterpret_cast<const float4 *>(dDpdu), dHasTan };
 	d.lum_sel_sum = sc->lum_sel_sum; d.background_lum = sc->background_lum;
 	d.has_shapes = 0;
-	for (uint32_t s = 0; s < sc->n_shapes; ++s) if (shapeType(s) != MTSGPU_SHAPE_TRIMESH) d.has_shapes = 1;
+	for (uint32_t s = 0; s < sc->n_shapes; ++s) if (shapeType(s) != MTSGPU_SHAPE_TRIMESH) d.has_shapes = kHasShapes;
+	for (uint32_t s = 0; s < sc->n_shapes; ++s) if (shapeType(s) == MTSGPU_SHAPE_CYLINDER) d.has_shapes = kHasCylinders;      // the CYL kernels of trace.hip
 	d.n_lums = sc->n_lums; d.n_nodes = sc->n_nodes; d.n_tris = sc->n_tris; d.n_shapes = sc->n_shapes;
 	for (int a = 0; a < 3; ++a) { d.aabb_min[a] = sc->aabb_min[a]; d.aabb_max[a] = sc->aabb_max[a]; }
 	c->dsc = d; c->nTris = sc->n_tris;
@@ -400,6 +449,12 @@ static int uploadScene(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_d
 }
 
 int mtsgpu_upload_scene(mtsgpu_ctx *c, const mtsgpu_scene *sc) { return uploadScene(c, sc, nullptr, nullptr, false); }
+
+int mtsgpu_upload_scene_cylinders(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_dpdu, const uint32_t *shape_has_tangents, const float *cylinders) {
+	if ((vtx_dpdu == nullptr) != (shape_has_tangents == nullptr))
+		return fail(c, MTSGPU_EINVAL, "vtx_dpdu and shape_has_tangents must both be given or both be NULL");
+	return uploadScene(c, sc, vtx_dpdu, shape_has_tangents, true, cylinders, true);
+}
 
 int mtsgpu_upload_scene_tangents(mtsgpu_ctx *c, const mtsgpu_scene *sc, const float *vtx_dpdu, const uint32_t *shape_has_tangents) {
 	if ((vtx_dpdu == nullptr) != (shape_has_tangents == nullptr))
@@ -571,6 +626,10 @@ static int setUvTextures(mtsgpu_ctx *c, const float *vtx_uv, const uint32_t *sha
 		for (size_t i = 0; i < 2 * (size_t) nBsdfs; ++i) anySlot |= bsdf_slot_texture[i] >= 0;
 	}
 	bool anyMask = false, anyMaskTex = false;
+	if (bsdf_mask && c->dsc.has_shapes == kHasCylinders)
+		for (uint32_t b = 0; b < nBsdfs; ++b)
+			if (bsdf_mask[b].kind != (uint32_t) MTSGPU_MASK_NONE)
+				return fail(c, MTSGPU_EINVAL, "BSDF %u: the mask BSDF is not served in a scene with a cylinder yet (the mask kernels do not build a cylinder's record)", b);
 	if (bsdf_mask) {
 		const std::string why = checkBsdfMasks(nBsdfs, h.bsdfType.data(), h.bsdfParams.data(), bsdf_mask, n_textures);
 		if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
@@ -695,6 +754,8 @@ int mtsgpu_set_snow_bsdfs(mtsgpu_ctx *c, const mtsgpu_bsdf_snow *table) {
 	c->dsnw = DSnows{ nullptr };
 	c->hostSnowKind.clear();
 	if (!table) return 0;
+	if (c->dsc.has_shapes == kHasCylinders)
+		return fail(c, MTSGPU_EINVAL, "the snow BRDFs are not served in a scene with a cylinder yet (the snow kernels do not build a cylinder's record)");
 	const mtsgpu_ctx::HostScene &h = c->host;
 	const uint32_t nBsdfs = (uint32_t) h.bsdfType.size();
 	const std::string why = checkBsdfSnow(nBsdfs, h.bsdfType.data(), h.bsdfParams.data(), table,
@@ -731,6 +792,8 @@ int mtsgpu_set_cloth_bsdfs(mtsgpu_ctx *c, uint32_t n_weaves, const mtsgpu_weave 
 	c->dclo = DCloths{ nullptr, nullptr, nullptr, nullptr };
 	c->hostClothWeave.clear();
 	if (!bsdf_weave) return 0;
+	if (c->dsc.has_shapes == kHasCylinders)
+		return fail(c, MTSGPU_EINVAL, "the cloth BRDF is not served in a scene with a cylinder yet (the cloth kernels do not build a cylinder's record)");
 	if (n_weaves && !weaves) return fail(c, MTSGPU_EINVAL, "n_weaves without weaves");
 	if (n_weaves > (1u << 20)) return fail(c, MTSGPU_EINVAL, "at most 2^20 weaves");
 	const mtsgpu_ctx::HostScene &h = c->host;

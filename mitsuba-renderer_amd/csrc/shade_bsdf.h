@@ -15,10 +15,36 @@ struct Its {
 
 // fillIntersectionRecord<true> (include/mitsuba/render/skdtree.h:352-432)
 // t0, t1, t2: the first three chunks of the primitive's gather record (sc.tri_pos), fetched by the caller
+// CYL: the form that knows the cylinder's record.  Only the kernels a cylinder's hit can reach have it (shade_path: the Lambertian
+// bin of the families without mask, snow and cloth; the upload and those calls refuse everything else on a cylinder) and the
+// read-out hooks; every other kernel is compiled without the branch and keeps the registers it had
+template <bool CYL = true>
 __device__ __forceinline__ void fill_its(const DScene &sc, V3 rayO, V3 rayD, float t, uint32_t prim, float u, float v,
                                          const float4 t0, const float4 t1, const float4 t2, Its &its) {
 	V3 sS, sT;
-	if (__float_as_uint(t2.w) & 0x80000000u) {
+	if (CYL && (__float_as_uint(t2.w) & 0xC0000000u) == 0xC0000000u) {
+		// Cylinder::fillIntersectionRecord (src/shapes/cylinder.cpp:154-176): its.p = ray(t); CP = the cylinder's row of
+		// shape_params: [0..11] worldToObject 3x4, [12..20] the 3x3 of objectToWorld, [21] length
+		its.shape = __float_as_uint(t2.z);
+		const float *CP = sc.shape_params + 24 * (size_t) its.shape;
+		const float *O2W = CP + 12;
+		its.p = V3(rayO.x + t * rayD.x, rayO.y + t * rayD.y, rayO.z + t * rayD.z);
+		const float lx = CP[0] * its.p.x + CP[1] * its.p.y + CP[2] * its.p.z + CP[3];
+		const float ly = CP[4] * its.p.x + CP[5] * its.p.y + CP[6] * its.p.z + CP[7];
+		const V3 du(-ly * (2 * kPi), lx * (2 * kPi), 0 * (2 * kPi));
+		const V3 dv(0.0f, 0.0f, CP[21]);
+		const V3 dpdu(O2W[0] * du.x + O2W[1] * du.y + O2W[2] * du.z, O2W[3] * du.x + O2W[4] * du.y + O2W[5] * du.z,
+		              O2W[6] * du.x + O2W[7] * du.y + O2W[8] * du.z);
+		const V3 dpdv(O2W[0] * dv.x + O2W[1] * dv.y + O2W[2] * dv.z, O2W[3] * dv.x + O2W[4] * dv.y + O2W[5] * dv.z,
+		              O2W[6] * dv.x + O2W[7] * dv.y + O2W[8] * dv.z);
+		// the normal: cross(dpdu, dpdv) of the LOCAL vectors, pushed through objectToWorld as a Vector, then normalised (:169)
+		const V3 cr = cross(du, dv);
+		const V3 n = normalize(V3(O2W[0] * cr.x + O2W[1] * cr.y + O2W[2] * cr.z, O2W[3] * cr.x + O2W[4] * cr.y + O2W[5] * cr.z,
+		                          O2W[6] * cr.x + O2W[7] * cr.y + O2W[8] * cr.z));
+		sS = normalize(dpdu);
+		sT = normalize(dpdv);
+		its.geoN = n; its.shN = n;
+	} else if (__float_as_uint(t2.w) & 0x80000000u) {
 		// Sphere::fillIntersectionRecord (src/shapes/sphere.cpp:136-178): its.p = ray(t), frame from dpdu / dpdv
 		its.shape = __float_as_uint(t2.z);
 		const float *SP = sc.shape_params + 24 * (size_t) its.shape;
@@ -80,9 +106,10 @@ __device__ __forceinline__ void fill_its(const DScene &sc, V3 rayO, V3 rayD, flo
 // vertex tangents of the primitive (DTangents::tri_dpdu), n the normalised interpolated normal fill_its has left in its.shN,
 // s = normalize(dpdu - n * dot(n, dpdu)), t = cross(n, s) -- and its.wi in that frame.  Every other shape (spheres, meshes
 // without tangents) keeps what fill_its wrote.  The shading kernels and the read-out hook (k_shading_frame_eval) both call this.
+template <bool CYL = true>
 __device__ __forceinline__ void fill_its_tan(const DScene &sc, const DTangents &tan, V3 rayO, V3 rayD, float t, uint32_t prim, float u, float v,
                                              const float4 t0, const float4 t1, const float4 t2, Its &its) {
-	fill_its(sc, rayO, rayD, t, prim, u, v, t0, t1, t2, its);
+	fill_its<CYL>(sc, rayO, rayD, t, prim, u, v, t0, t1, t2, its);
 	if (!tan.shape_has_tan[its.shape]) return;
 	const float4 *TD = tan.tri_dpdu + kTriDpduStride * (size_t) prim;
 	const float4 d0 = TD[0], d1 = TD[1], d2 = TD[2];
@@ -120,9 +147,20 @@ __device__ __forceinline__ void bsdf_block_with_color(const float *P, uint32_t s
 // with b = ((1 - u) - v, u, v) as (t0 * b.x + t1 * b.y) + t2 * b.z per component; a mesh without texcoords has zero rows and
 // gets (0, 0), the reference's value.  Sphere (sphere.cpp:136-145): spherical coordinates of the hit point p in object space,
 // `local` formed as fill_its forms it.
+template <bool CYL = true>
 __device__ __forceinline__ void its_uv(const DScene &sc, const float4 *tri_uv, uint32_t prim, uint32_t shape, float u, float v, V3 p,
                                        float &uvx, float &uvy) {
-	if (sc.shape_type[shape] == 1u) {
+	if (CYL && sc.shape_type[shape] == 2u) {
+		// Cylinder (cylinder.cpp:158-163): uv = (local.z / length, phi / (2 * M_PI)), a division
+		const float *CP = sc.shape_params + 24 * (size_t) shape;
+		const float lx = CP[0] * p.x + CP[1] * p.y + CP[2] * p.z + CP[3];
+		const float ly = CP[4] * p.x + CP[5] * p.y + CP[6] * p.z + CP[7];
+		const float lz = CP[8] * p.x + CP[9] * p.y + CP[10] * p.z + CP[11];
+		float phi = datan2(ly, lx);
+		if (phi < 0) phi += 2 * kPi;
+		uvx = lz / CP[21];
+		uvy = phi / (2 * kPi);
+	} else if (sc.shape_type[shape] == 1u) {
 		const float *SP = sc.shape_params + 24 * (size_t) shape;
 		const float *W2O = SP + 14;
 		const V3 center(SP[0], SP[1], SP[2]);

@@ -90,11 +90,13 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 		// this shading hit something, so in the tail below `depth` is one ahead until the place of its depth++ (the camera ray's
 		// record holds depth 1 either way)
 		const bool settled = !ROUNDS && cfg.miss_settled && !direct;
+		// the kernels a cylinder's hit can reach (fill_its: CYL)
+		constexpr bool kCyl = BT == 0 && !MSK && !SNW && !CLO;
 		Its its;
 		if (valid) {
 			// (a scene that is here for its masks alone has no tangent table)
-			if (TAN && !(MSK && tan.shape_has_tan == nullptr)) fill_its_tan(sc, tan, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
-			else fill_its(sc, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
+			if (TAN && !(MSK && tan.shape_has_tan == nullptr)) fill_its_tan<kCyl>(sc, tan, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
+			else fill_its<kCyl>(sc, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
 		}
 		const int shapeLum = valid ? sc.shape_lum[its.shape] : -1;
 
@@ -189,7 +191,7 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				weaveIdx = clo.bsdf_weave[bsdfIdx];
 				if (weaveIdx >= 0) {
 					float clothU = 0, clothV = 0;
-					its_uv(sc, tex.tri_uv, h.w, its.shape, __uint_as_float(h.y), __uint_as_float(h.z), its.p, clothU, clothV);
+					its_uv<false>(sc, tex.tri_uv, h.w, its.shape, __uint_as_float(h.y), __uint_as_float(h.z), its.p, clothU, clothV);
 					clothHit = cloth_prepare(clo, weaveIdx, clothU, clothV);
 				}
 			}
@@ -206,7 +208,7 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				// (a scene that is here for its snow alone has no mask table)
 				if (MSK && !(SNW && msk.bsdf_mask == nullptr)) m = msk.bsdf_mask[bsdfIdx];
 				if (k0 >= 0 || k1 >= 0 || (MSK && m.kind == kMaskTexture))
-					its_uv(sc, tex.tri_uv, h.w, its.shape, __uint_as_float(h.y), __uint_as_float(h.z), its.p, uvx, uvy);
+					its_uv<kCyl>(sc, tex.tri_uv, h.w, its.shape, __uint_as_float(h.y), __uint_as_float(h.z), its.p, uvx, uvy);
 				if (MSK && m.kind == kMaskConstant) maskP = luminance(V3(m.opacity[0], m.opacity[1], m.opacity[2]));
 				else if (MSK && m.kind == kMaskTexture) maskP = luminance(tex_eval(tex.textures[m.texture], tex.texels, uvx, uvy));
 				// one slot after the other, so that only one value is alive next to the block

@@ -66,7 +66,11 @@ __device__ __forceinline__ const uint4 *leaf_tail(const DTraceScene &sc, uint32_
 // through the kernel with the mailbox.  A sphere (k == 3, A.y != 0) takes part like a triangle: accepted with t = ts, u = v = 0
 // at retirement, its shape in dword 10 like a triangle's.
 constexpr uint32_t kTiedBit = 0x80000000u;     // leaf entries are < 2^31 (bit 31 of a leaf node's first word is its leaf flag)
-template <int MODE, bool COUNT, bool BIN, bool PARKED, bool LEAN>
+// CYL: the instantiations that know the cylinder (A.y == 2: Cylinder::rayIntersect, kdevice.h), launched for the scenes that have
+// one (DScene::has_shapes == 2) and for no other: a scene without a cylinder runs the kernels it ran before there were any.
+// A cylinder takes part like a sphere: accepted with its t, u = v = 0, its shape in dword 10; B.x of its record = the index of
+// its four rows in sc.leaf_ta.
+template <int MODE, bool COUNT, bool BIN, bool PARKED, bool LEAN, bool CYL>
 __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &ps, const DQueues &q, const TracePlan &plan,
                                            const uint32_t *queue, uint32_t n, const uint32_t first, const uint32_t stride,
                                            uint32_t (*s_stack)[kTraceBlock], uint32_t (*s_mbox)[kTraceBlock], const uint4 *s_top) {
@@ -424,18 +428,37 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 							// a non-triangle shape (skdtree.h:287-296 / :328-332); A.y = shape type, B = centre + radius
 							const uint4 B = *leaf_tail(sc, e, 0);
 							if (COUNT) { g_tail++; rec_add(kReqLeaf, kLeafStride * e + 1u); }
-							const V3 ctr(__uint_as_float(B.x), __uint_as_float(B.y), __uint_as_float(B.z));
-							const float rad = __uint_as_float(B.w);
-							if (MODE != 0) {
-								if (sphere_occludes(ctr, rad, V3(ox, oy, oz), V3(dx, dy, dz), mint, maxt)) hitShadow = true;
+							if (CYL && A.y == 2u) {
+								const float4 *R = reinterpret_cast<const float4 *>(sc.leaf_ta + B.x);
+								const float4 r0 = R[0], r1 = R[1], r2 = R[2], r3 = R[3];
+								if (COUNT) { g_tail += 4u; for (uint32_t row = 0; row < 4u; ++row) rec_add(kReqLeaf, B.x + row); }
+								if (MODE != 0) {
+									if (cylinder_occludes(r0, r1, r2, r3.x, r3.y, V3(ox, oy, oz), V3(dx, dy, dz), mint, maxt)) hitShadow = true;
+								} else {
+									float ts;
+									if (cylinder_intersect(r0, r1, r2, r3.x, r3.y, V3(ox, oy, oz), V3(dx, dy, dz), mint, maxt, ts)) {
+										if (LEAN) accept_lean(ts, e, prim);
+										maxt = ts;
+										if (!LEAN) {
+											best_t = ts; best_u = 0.0f; best_v = 0.0f; best_prim = prim;
+											best_shape = leaf_tail(sc, e, 1)->z;
+										}
+									}
+								}
 							} else {
-								float ts;
-								if (sphere_intersect(ctr, rad, V3(ox, oy, oz), V3(dx, dy, dz), mint, maxt, ts)) {
-									if (LEAN) accept_lean(ts, e, prim);
-									maxt = ts;
-									if (!LEAN) {
-										best_t = ts; best_u = 0.0f; best_v = 0.0f; best_prim = prim;
-										best_shape = leaf_tail(sc, e, 1)->z;
+								const V3 ctr(__uint_as_float(B.x), __uint_as_float(B.y), __uint_as_float(B.z));
+								const float rad = __uint_as_float(B.w);
+								if (MODE != 0) {
+									if (sphere_occludes(ctr, rad, V3(ox, oy, oz), V3(dx, dy, dz), mint, maxt)) hitShadow = true;
+								} else {
+									float ts;
+									if (sphere_intersect(ctr, rad, V3(ox, oy, oz), V3(dx, dy, dz), mint, maxt, ts)) {
+										if (LEAN) accept_lean(ts, e, prim);
+										maxt = ts;
+										if (!LEAN) {
+											best_t = ts; best_u = 0.0f; best_v = 0.0f; best_prim = prim;
+											best_shape = leaf_tail(sc, e, 1)->z;
+										}
 									}
 								}
 							}
@@ -528,7 +551,7 @@ __device__ __forceinline__ void trace_body(const DTraceScene &sc, const DPaths &
 	}
 }
 
-template <int MODE, bool COUNT, bool BIN, bool PARKED = false, bool LEAN = false>
+template <int MODE, bool COUNT, bool BIN, bool PARKED = false, bool LEAN = false, bool CYL = false>
 __global__ __launch_bounds__(kTraceBlock, trace_waves_per_simd(MODE, LEAN)) void k_trace(DTraceScene sc, DPaths ps, DQueues q,
                                                           const uint32_t *queue, uint32_t n_host, const uint32_t *n_dev) {
 	__shared__ uint32_t s_stack[kStackLDS][kTraceBlock];
@@ -550,7 +573,7 @@ __global__ __launch_bounds__(kTraceBlock, trace_waves_per_simd(MODE, LEAN)) void
 		for (uint32_t t = threadIdx.x; t < kTopPairs; t += kTraceBlock) s_top[t] = reinterpret_cast<const uint4 *>(sc.nodes)[t];
 		__syncthreads();
 	}
-	trace_body<MODE, COUNT, BIN, PARKED, LEAN>(sc, ps, q, plan, queue, n, first, stride, s_stack, s_mbox, s_top);
+	trace_body<MODE, COUNT, BIN, PARKED, LEAN, CYL>(sc, ps, q, plan, queue, n, first, stride, s_stack, s_mbox, s_top);
 }
 
 // Device-driven bounces: the per-bin views k_shade needs, from the shard counters the closest-hit launch left in `cur`
@@ -578,8 +601,8 @@ __global__ __launch_bounds__(256) void k_prep(const uint32_t *cur, uint32_t *nex
 	}
 }
 
-template <int MODE, bool COUNT, bool BIN, bool PARKED = false, bool LEAN = false>
-static void launch_trace_t(hipStream_t s, const DScene &sc, const DPaths &ps, const DQueues &q, const uint32_t *queue, uint32_t n,
+template <int MODE, bool COUNT, bool BIN, bool PARKED, bool LEAN, bool CYL>
+static void launch_trace_c(hipStream_t s, const DScene &sc, const DPaths &ps, const DQueues &q, const uint32_t *queue, uint32_t n,
                            const uint32_t *n_dev) {
 	// persistent grid: enough workgroups to fill every CU, never more than there are rays (trace_plan); when only the
 	// device knows the count, the grid is sized for the upper bound n and the surplus workgroups exit at once
@@ -592,7 +615,15 @@ static void launch_trace_t(hipStream_t s, const DScene &sc, const DPaths &ps, co
 		blocks = std::min<unsigned>(blocks_for(n, minBatch * (kTraceBlock / 64)), q.n_cus * perCu);
 	}
 	if (!blocks) return;
-	hipLaunchKernelGGL((k_trace<MODE, COUNT, BIN, PARKED, LEAN>), dim3(blocks), dim3(kTraceBlock), 0, s, trace_scene(sc), ps, q, queue, n, n_dev);
+	hipLaunchKernelGGL((k_trace<MODE, COUNT, BIN, PARKED, LEAN, CYL>), dim3(blocks), dim3(kTraceBlock), 0, s, trace_scene(sc), ps, q, queue, n, n_dev);
+}
+
+// the instantiation of the scene: with the cylinder test when it has a cylinder (has_shapes == 2, scene_upload.cpp)
+template <int MODE, bool COUNT, bool BIN, bool PARKED = false, bool LEAN = false>
+static void launch_trace_t(hipStream_t s, const DScene &sc, const DPaths &ps, const DQueues &q, const uint32_t *queue, uint32_t n,
+                           const uint32_t *n_dev) {
+	if (sc.has_shapes == kHasCylinders) launch_trace_c<MODE, COUNT, BIN, PARKED, LEAN, true>(s, sc, ps, q, queue, n, n_dev);
+	else launch_trace_c<MODE, COUNT, BIN, PARKED, LEAN, false>(s, sc, ps, q, queue, n, n_dev);
 }
 
 void launch_trace(hipStream_t s, int mode, bool count, bool bin, const DScene &sc, const DPaths &ps,

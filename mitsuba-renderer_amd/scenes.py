@@ -312,6 +312,27 @@ class SphereDesc(MeshDesc):
         self.sphere = (tuple(float(F(v)) for v in center), float(F(radius)), bool(inverted))
 
 
+class CylinderDesc(MeshDesc):
+    """<shape type="cylinder"> (src/shapes/cylinder.cpp:34-64) with `p1`, `p2` and `radius`, or with a `toWorld` from the unit
+    cylinder (4 x 4, last row 0 0 0 1): one kd-tree primitive.  No area luminaire: the reference cannot render one either."""
+
+    def __init__(self, p1=None, p2=None, radius=None, to_world=None, bsdf=-1, lum=-1, name="cylinder"):
+        MeshDesc.__init__(self, np.zeros((0, 3)), np.zeros((0, 3), dtype=np.uint32), bsdf, lum, True, None, name)
+        self.shape_type = abi.SHAPE_CYLINDER
+        if to_world is not None:
+            if p1 is not None or p2 is not None or radius is not None:
+                raise ValueError("a cylinder takes p1, p2 and radius, or to_world")
+            self.cylinder = (abi.CYLINDER_TOWORLD, (0.0,) * 3, (0.0,) * 3, 0.0, tuple(float(v) for v in np.asarray(to_world, dtype=np.float32).reshape(16)))
+        else:
+            if p1 is None or p2 is None or radius is None:
+                raise ValueError("a cylinder takes p1, p2 and radius, or to_world")
+            self.cylinder = (abi.CYLINDER_POINTS, tuple(float(F(v)) for v in p1), tuple(float(F(v)) for v in p2), float(F(radius)), (0.0,) * 16)
+
+    def to_struct(self):
+        form, p1, p2, radius, tw = self.cylinder
+        return abi.Cylinder(form, (C.c_float * 3)(*p1), (C.c_float * 3)(*p2), radius, (C.c_float * 16)(*tw))
+
+
 class SceneDescription:
     """meshes + BSDF blocks + luminaires + camera (+ integrator defaults for the config)"""
 
@@ -638,6 +659,11 @@ class SceneDescription:
 
     def add_sphere(self, *a, **k):
         self.meshes.append(SphereDesc(*a, **k))
+        return self.meshes[-1]
+
+    def add_cylinder(self, p1=None, p2=None, radius=None, to_world=None, bsdf=-1, lum=-1, name="cylinder"):
+        """add_cylinder(p1, p2, radius, bsdf=...) or add_cylinder(to_world=..., bsdf=...)"""
+        self.meshes.append(CylinderDesc(p1, p2, radius, to_world, bsdf, lum, name))
         return self.meshes[-1]
 
     @property

@@ -1,5 +1,6 @@
 // api.cpp -- the C ABI of libmtsgpu (include/mtsgpu.h): the context, its configuration setters and its film, and the
-// wrappers of the host-side loaders.  The scene goes to HBM in scene_upload.cpp, render.cpp drives the wavefront stages per
+// wrappers of the host-side loaders.  The scene goes to HBM in scene_upload.cpp (scene_attach.cpp: what comes and goes between
+// two uploads; scene_layout.cpp: what both check and lay out, without a context), render.cpp drives the wavefront stages per
 // bounce, readout.cpp holds the test and measurement hooks.
 // There is no CPU fallback: every compute entry point needs a gfx950 device.
 #include "ctx.h"

@@ -1,5 +1,6 @@
 // ctx.h -- the context behind the C ABI (include/mtsgpu.h) and the helpers its translation units share: api.cpp (context,
-// setters, film), scene_upload.cpp, render.cpp (the wavefront engine), readout.cpp (test and measurement hooks), group.cpp.
+// setters, film), scene_upload.cpp, scene_attach.cpp, render.cpp (the wavefront engine), readout.cpp (test and measurement hooks),
+// group.cpp.  scene_layout.cpp, the pure half of the upload calls, is declared in host.h and does not include this file.
 // Device memory of a context has one owner per buffer: a DevBuf (grow-only, freed by its destructor) or one of the *Allocs
 // lists; ~mtsgpu_ctx releases the lists, the pinned words, the events and the streams, so mtsgpu_destroy names no buffer.
 #pragma once
@@ -51,12 +52,51 @@ constexpr size_t kCounterSetBytes = (size_t) kNumCounters * kCounterStride * siz
 
 using EventPool = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
 inline void freeAll(std::vector<void *> &v) { for (void *p : v) (void) hipFree(p); v.clear(); }
+
+// One record per attachment family: the device arrays it owns apart from the scene's (they come and go between two uploads),
+// the view its kernels take (all NULL while the family is off) and host copies of the tables in force (empty = none), by which
+// the other families' calls refuse what this one holds (claimRefusal, host.h).  clear() is a setter's free and an upload's reset.
+struct ColorFamily {                     // mtsgpu_set_vertex_colors
+	std::vector<void *> allocs;
+	DColors d{ nullptr, nullptr };
+	std::vector<uint32_t> slots;         // bsdf_color_slots
+	void clear() { freeAll(allocs); d = DColors{ nullptr, nullptr }; slots.clear(); }
+};
+struct TextureFamily {                   // mtsgpu_set_uv_textures, _bitmap_textures, _masked_textures: the masks are owned with the textures
+	std::vector<void *> allocs;
+	DTextures d{ nullptr, nullptr, nullptr, nullptr };
+	DMasks msk{ nullptr };
+	std::vector<int32_t> slotTex;        // bsdf_slot_texture
+	std::vector<uint32_t> maskKind;
+	std::vector<uint32_t> shapeHasUv;    // the shapes that have texcoords and the extremes of their texcoords (uMin, uMax, vMin, vMax
+	std::vector<double> uvRange;         // per shape), which the cloth call checks its casts on
+	void clear() {
+		freeAll(allocs); d = DTextures{ nullptr, nullptr, nullptr, nullptr }; msk = DMasks{ nullptr };
+		slotTex.clear(); maskKind.clear(); shapeHasUv.clear(); uvRange.clear();
+	}
+};
+struct SnowFamily {                      // mtsgpu_set_snow_bsdfs
+	std::vector<void *> allocs;
+	DSnows d{ nullptr };
+	std::vector<uint32_t> kind;
+	void clear() { freeAll(allocs); d = DSnows{ nullptr }; kind.clear(); }
+};
+struct ClothFamily {                     // mtsgpu_set_cloth_bsdfs
+	std::vector<void *> allocs;
+	DCloths d{ nullptr, nullptr, nullptr, nullptr };
+	std::vector<int32_t> weave;          // bsdf_weave
+	void clear() { freeAll(allocs); d = DCloths{ nullptr, nullptr, nullptr, nullptr }; weave.clear(); }
+};
+struct TangentFamily {                   // mtsgpu_upload_scene_tangents: the arrays are the scene's (sceneAllocs) and go with it
+	DTangents d{ nullptr, nullptr };
+	void clear() { d = DTangents{ nullptr, nullptr }; }
+};
 }
 
 struct mtsgpu_ctx {
 	// with `device` current and idle (mtsgpu_destroy): everything no DevBuf member owns.  A caller's stream or film is not ours.
 	~mtsgpu_ctx() {
-		for (auto *list : { &sceneAllocs, &colorAllocs, &texAllocs, &snowAllocs, &clothAllocs, &pathAllocs }) mg::freeAll(*list);
+		for (auto *list : { &sceneAllocs, &colors.allocs, &tex.allocs, &snow.allocs, &cloth.allocs, &pathAllocs }) mg::freeAll(*list);
 		if (hostCounters) (void) hipHostFree(hostCounters);
 		for (auto *pool : { &traceEvents, &shadeEvents })
 			for (auto &e : *pool) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
@@ -81,43 +121,23 @@ struct mtsgpu_ctx {
 	mg::DScene dsc{};
 	std::vector<void *> sceneAllocs;
 	uint32_t nTris = 0;
-	// What mtsgpu_set_vertex_colors needs of the uploaded scene once the caller's arrays may be gone: host copies, taken by
-	// mtsgpu_upload_scene.  colorAllocs: DColors::tri_col and bsdf_color_slots, owned apart from sceneAllocs because they
-	// come and go between two uploads.
-	struct HostScene {
-		uint32_t nVerts = 0;
-		std::vector<uint32_t> triIdx, shapeTriOffset, shapeType, bsdfType, lumType;
-		std::vector<int32_t> shapeBsdf;
-		std::vector<float> bsdfParams;
-		std::vector<uint32_t> shapeNormals, shapeTangents;      // per shape: has vertex normals / uploaded tangents (0 / 1)
-	} host;
-	std::vector<void *> colorAllocs;
-	mg::DColors dcol{ nullptr, nullptr };   // what the vertex-colour kernels take (NULL, NULL without colours)
-	// mtsgpu_set_uv_textures: DTextures' arrays, owned like the colours', and host copies of the two slot tables in force
-	// (empty = none), so that each of the two calls can refuse a slot the other one has taken
-	std::vector<void *> texAllocs;
-	mg::DTextures dtex{ nullptr, nullptr, nullptr, nullptr };
-	// mtsgpu_set_uv_masked_textures: DMasks' table, owned with the textures (texAllocs); NULL while no BSDF has a mask
-	mg::DMasks dmsk{ nullptr };
-	// mtsgpu_upload_scene_tangents: DTangents' arrays, owned with the scene (sceneAllocs); NULL, NULL without a tangent mesh
-	mg::DTangents dtan{ nullptr, nullptr };
-	// mtsgpu_set_snow_bsdfs: DSnows' table, owned like the colours' (snowAllocs), and a host copy of its kinds (empty = no
-	// table), so that the colour, texture and mask calls can refuse a slot or a mask on a snow entry; and the mask kinds in force
-	// (empty = none), so that this call can refuse a snow record on a masked entry
-	std::vector<void *> snowAllocs;
-	mg::DSnows dsnw{ nullptr };
-	std::vector<uint32_t> hostSnowKind, hostMaskKind;
-	// mtsgpu_set_cloth_bsdfs: DCloths' pool, owned like the snow table (clothAllocs), and a host copy of bsdf_weave (empty = no
-	// table), so that the colour, texture, mask and snow calls can refuse what a cloth entry does not take; and, from the texture
-	// call, the shapes that have texcoords with the extremes of their texcoords (uMin, uMax, vMin, vMax per shape; empty = no
-	// texture call supplied any), which the cloth call checks its casts on
-	std::vector<void *> clothAllocs;
-	mg::DCloths dclo{ nullptr, nullptr, nullptr, nullptr };
-	std::vector<int32_t> hostClothWeave;
-	std::vector<double> hostUvRange;
-	std::vector<uint32_t> hostShapeHasUv;
-	std::vector<uint32_t> hostColorSlots;
-	std::vector<int32_t> hostSlotTex;
+	mg::HostScene host;                     // what the setters need of it once the caller's arrays may be gone
+	// what comes and goes between two uploads, one record per family (below)
+	mg::ColorFamily colors;
+	mg::TextureFamily tex;
+	mg::SnowFamily snow;
+	mg::ClothFamily cloth;
+	mg::TangentFamily tan;
+	// a new scene starts without any of them
+	void clearAttachments() { colors.clear(); tex.clear(); snow.clear(); cloth.clear(); tan.clear(); }
+	// the tables in force, as the pure checks of host.h take them
+	mg::InForce inForce() const {
+		auto p = [](const auto &v) { return v.empty() ? nullptr : v.data(); };
+		mg::InForce f;
+		f.colorSlots = p(colors.slots); f.slotTex = p(tex.slotTex); f.maskKind = p(tex.maskKind); f.snowKind = p(snow.kind);
+		f.clothWeave = p(cloth.weave); f.shapeHasUv = p(tex.shapeHasUv); f.uvRange = p(tex.uvRange);
+		return f;
+	}
 
 	// configuration
 	bool haveCamera = false;
@@ -226,11 +246,6 @@ uint32_t effectiveSpp(const mtsgpu_ctx *c);
 int checkReady(mtsgpu_ctx *c);
 int ensureFilm(mtsgpu_ctx *c);
 int ensureFilmStats(mtsgpu_ctx *c);
-
-// scene_upload.cpp
-std::string checkUvTexture(const mtsgpu_uv_texture &t, bool bitmaps = false);
-std::string checkBitmap(const mtsgpu_bitmap &b, uint64_t *total);
-void packBitmapTexels(const mtsgpu_bitmap &b, float *dst);
 
 // render.cpp
 void applyTuning(mtsgpu_ctx *c);

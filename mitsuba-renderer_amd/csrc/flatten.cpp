@@ -595,13 +595,6 @@ Xf scale(float x, float y, float z) {                                           
 // ---------------------------------------------------------------------------
 // Cylinder (src/shapes/cylinder.cpp): the constructors, getAABB
 // ---------------------------------------------------------------------------
-std::string checkCylinderBlock(const float *D) {
-	for (int i = 0; i < MTSGPU_CYLINDER_NDERIVED; ++i)
-		if (!std::isfinite(D[i])) return "non-finite cylinder parameter";
-	if (!(D[24] > 0.0f) || !(D[25] > 0.0f)) return "a cylinder needs radius > 0 and length > 0 (Assert, cylinder.cpp:63)";
-	return std::string();
-}
-
 std::string cylinderConfigure(const mtsgpu_cylinder &in, float *D) {
 	Xf o2w;
 	float radius, len;

@@ -7,6 +7,7 @@
 #include "../../include/mtsgpu_cylinder.h"
 #include "devmath.h"
 #include "kdtree.h"
+#include "kernels.h"
 #include <cmath>
 #include <memory>
 #include <stdexcept>
@@ -48,6 +49,68 @@ inline int bsdfColorSlotCount(uint32_t type) {
 	if (t >= MTSGPU_BSDF_NTYPES) return 0;
 	return (kBsdfColorSlotOffset[t][0] >= 0) + (kBsdfColorSlotOffset[t][1] >= 0);
 }
+// The attachment families that can claim a BSDF entry between two uploads, and the tables in force: host copies of what each
+// family's setter accepted last, NULL while the family is off.  colorSlots [n_bsdfs] (mtsgpu_set_vertex_colors), slotTex
+// [n_bsdfs][2] and maskKind [n_bsdfs] (the texture calls), snowKind [n_bsdfs], clothWeave [n_bsdfs]; and, from the texture
+// call, shapeHasUv [n_shapes] with the extremes uvRange [n_shapes][4] = uMin, uMax, vMin, vMax of every shape's texcoords
+enum Family : uint32_t { kFamColors = 1u, kFamTextures = 2u, kFamMasks = 4u, kFamSnow = 8u, kFamCloth = 16u, kFamAll = 31u };
+struct InForce {
+	const uint32_t *colorSlots = nullptr;
+	const int32_t *slotTex = nullptr;
+	const uint32_t *maskKind = nullptr, *snowKind = nullptr;
+	const int32_t *clothWeave = nullptr;
+	const uint32_t *shapeHasUv = nullptr;
+	const double *uvRange = nullptr;
+};
+// the slots of entry b that a slot table [n_bsdfs][2] (or NULL) gives a texture, as bits
+inline uint32_t textureSlotsClaimed(const int32_t *slotTex, uint32_t b) {
+	return slotTex ? (slotTex[2 * (size_t) b] >= 0 ? 1u : 0u) | (slotTex[2 * (size_t) b + 1] >= 0 ? 2u : 0u) : 0u;
+}
+// May family `f` claim BSDF entry b, given what is in force?  The one place of the pairwise rules: a texture slot takes vertex
+// colours or a uv texture, not both; a snow or cloth entry has no texture slot, no mask, and is one of the two.  want: the
+// slots claimed (bit s; colours, textures) or non-zero (masks, snow, cloth); holders: the families asked, in the order colours,
+// textures, masks, snow, cloth (the setters report in their own order and ask for them one at a time where that differs).
+// Returns the refusal in the words of the claiming call, or an empty string.
+inline std::string claimRefusal(Family f, uint32_t b, uint32_t want, const InForce &in, uint32_t holders = kFamAll) {
+	if (!want) return std::string();
+	const std::string who = "BSDF " + std::to_string(b) + ": ";
+	const uint32_t colors = (holders & kFamColors) && in.colorSlots ? in.colorSlots[b] : 0u;
+	const uint32_t tex = (holders & kFamTextures) ? textureSlotsClaimed(in.slotTex, b) : 0u;
+	const bool mask = (holders & kFamMasks) && in.maskKind && in.maskKind[b] != (uint32_t) MTSGPU_MASK_NONE;
+	const bool snow = (holders & kFamSnow) && in.snowKind && in.snowKind[b] != (uint32_t) MTSGPU_SNOW_NONE;
+	const bool cloth = (holders & kFamCloth) && in.clothWeave && in.clothWeave[b] >= 0;
+	auto slot = [](uint32_t bits) { return std::to_string((bits & 1u) ? 0 : 1); };
+	switch (f) {
+	case kFamColors:
+		if (want & tex) return who + "slot " + slot(want & tex) + " takes vertex colours and has a uv texture as well";
+		if (snow) return who + "the entry takes vertex colours and has a snow record, whose BRDF has no texture slot";
+		if (cloth) return who + "the entry takes vertex colours and has a weave, whose BRDF has no texture slot";
+		break;
+	case kFamTextures:
+		if (want & colors) return who + "slot " + slot(want & colors) + " has a uv texture and takes vertex colours as well";
+		if (snow) return who + "the entry has a uv texture and a snow record, whose BRDF has no texture slot";
+		if (cloth) return who + "the entry has a uv texture and a weave, whose BRDF has no texture slot";
+		break;
+	case kFamMasks:
+		if (snow) return who + "the entry has a mask and a snow record: a mask around a snow BRDF is not supported";
+		if (cloth) return who + "the entry has a mask and a weave: a mask around a cloth BRDF is not supported";
+		break;
+	case kFamSnow:
+		if (colors) return who + "a snow BRDF has no texture slot, and the entry takes vertex colours";
+		if (tex) return who + "a snow BRDF has no texture slot, and the entry has a uv texture";
+		if (mask) return who + "a mask around a snow BRDF is not supported";
+		if (cloth) return who + "the entry has a weave and a snow record";
+		break;
+	case kFamCloth:
+		if (colors) return who + "a cloth BRDF has no texture slot, and the entry takes vertex colours";
+		if (tex) return who + "a cloth BRDF has no texture slot, and the entry has a uv texture";
+		if (mask) return who + "a mask around a cloth BRDF is not supported";
+		if (snow) return who + "the entry has a snow record and a weave";
+		break;
+	default: break;
+	}
+	return std::string();
+}
 // What mtsgpu_set_vertex_colors requires of the slot masks against a checked BSDF table: no bit beyond the slots of the
 // type, none on a composite's child.  Returns the reason, or an empty string.
 inline std::string checkBsdfColorSlots(uint32_t n_bsdfs, const uint32_t *type, const float *params, const uint32_t *slots) {
@@ -69,10 +132,10 @@ inline std::string checkBsdfColorSlots(uint32_t n_bsdfs, const uint32_t *type, c
 }
 
 // What mtsgpu_set_uv_textures requires of the slot table [n_bsdfs][2] (a texture index, or -1) against a checked BSDF table
-// and the colour masks in force (NULL = none): indices inside the texture list, no slot beyond those of the type, none that
+// and the colour masks in force: indices inside the texture list, no slot beyond those of the type, none that
 // is coloured as well, none on a composite's child.  Returns the reason, or an empty string.
 inline std::string checkBsdfSlotTextures(uint32_t n_bsdfs, const uint32_t *type, const float *params, const int32_t *slotTex, uint32_t n_textures,
-                                         const uint32_t *colorSlots) {
+                                         const InForce &in) {
 	auto msg = [](uint32_t b, const std::string &what) { return "BSDF " + std::to_string(b) + ": " + what; };
 	for (uint32_t b = 0; b < n_bsdfs; ++b) {
 		const int n = bsdfColorSlotCount(type[b]);
@@ -83,8 +146,8 @@ inline std::string checkBsdfSlotTextures(uint32_t n_bsdfs, const uint32_t *type,
 			if (k < 0) continue;
 			if (s >= n)
 				return msg(b, "uv texture in slot " + std::to_string(s) + ", beyond the " + std::to_string(n) + " texture slot(s) of its type");
-			if (colorSlots && ((colorSlots[b] >> s) & 1u))
-				return msg(b, "slot " + std::to_string(s) + " has a uv texture and takes vertex colours as well");
+			const std::string held = claimRefusal(kFamTextures, b, 1u << s, in, kFamColors);
+			if (!held.empty()) return held;
 		}
 	}
 	for (uint32_t b = 0; b < n_bsdfs; ++b) {
@@ -200,20 +263,15 @@ inline std::string checkSnowEntry(const mtsgpu_bsdf_snow &e, uint32_t type) {
 	return std::string();
 }
 
-// ... and of the table [n_bsdfs] against a checked BSDF table: every record as above, none on a composite's child.  colorSlots
-// [n_bsdfs], slotTex [2 n_bsdfs] and maskKind [n_bsdfs] are the tables in force or NULL: a snow entry has no coloured slot, no
-// textured slot and no mask.
-inline std::string checkBsdfSnow(uint32_t n_bsdfs, const uint32_t *type, const float *params, const mtsgpu_bsdf_snow *snow,
-                                 const uint32_t *colorSlots, const int32_t *slotTex, const uint32_t *maskKind) {
+// ... and of the table [n_bsdfs] against a checked BSDF table and the tables in force: every record as above, none on an entry
+// with a coloured slot, a textured slot or a mask, none on a composite's child.
+inline std::string checkBsdfSnow(uint32_t n_bsdfs, const uint32_t *type, const float *params, const mtsgpu_bsdf_snow *snow, const InForce &in) {
 	auto msg = [](uint32_t b, const std::string &what) { return "BSDF " + std::to_string(b) + ": " + what; };
 	for (uint32_t b = 0; b < n_bsdfs; ++b) {
 		const std::string why = checkSnowEntry(snow[b], type[b]);
 		if (!why.empty()) return msg(b, why);
-		if (snow[b].kind == (uint32_t) MTSGPU_SNOW_NONE) continue;
-		if (colorSlots && colorSlots[b]) return msg(b, "a snow BRDF has no texture slot, and the entry takes vertex colours");
-		if (slotTex && (slotTex[2 * (size_t) b] >= 0 || slotTex[2 * (size_t) b + 1] >= 0))
-			return msg(b, "a snow BRDF has no texture slot, and the entry has a uv texture");
-		if (maskKind && maskKind[b] != (uint32_t) MTSGPU_MASK_NONE) return msg(b, "a mask around a snow BRDF is not supported");
+		const std::string held = claimRefusal(kFamSnow, b, snow[b].kind != (uint32_t) MTSGPU_SNOW_NONE, in, kFamColors | kFamTextures | kFamMasks);
+		if (!held.empty()) return held;
 	}
 	for (uint32_t b = 0; b < n_bsdfs; ++b) {
 		if ((type[b] & 0xFFu) != MTSGPU_BSDF_COMPOSITE) continue;
@@ -427,7 +485,7 @@ void flattenScene(const mtsgpu_scene_desc &d, const mtsgpu_kd_params *kp, FlatSc
                   const uint32_t *bsdfAnisotropic = nullptr, const mtsgpu_cylinder *cylinders = nullptr);
 // mtsgpu_cylinder_configure: both constructors of cylinder.cpp:34-64; the reason it refuses, or an empty string
 std::string cylinderConfigure(const mtsgpu_cylinder &in, float *derived);
-// What the upload requires of a derived block; the reason, or an empty string
+// What the upload requires of a derived block; the reason, or an empty string (scene_layout.cpp)
 std::string checkCylinderBlock(const float *derived);
 // Cylinder::getAABB (cylinder.cpp:187-208) of a derived block: out6 = min, max
 void cylinderAabb(const float *derived, float *out6);
@@ -455,5 +513,78 @@ void makeCamera(const float origin[3], const float target[3], const float up[3],
                 mtsgpu_camera &out);
 void makeCameraOrtho(const float origin[3], const float target[3], const float up[3], float scaleX, float scaleY,
                      int width, int height, mtsgpu_camera &out);
+
+// --- scene_layout.cpp: the pure half of the upload calls (no context, no HIP call): what they check and what they lay out ---
+// the arguments that travel beside the scene: mtsgpu_upload_scene passes none, mtsgpu_upload_scene_tangents the first three,
+// mtsgpu_upload_scene_cylinders all (cylinders = the derived blocks [n_shapes][MTSGPU_CYLINDER_NDERIVED] or NULL)
+struct UploadExtras {
+	const float *vtxDpdu = nullptr;
+	const uint32_t *shapeHasTangents = nullptr;
+	bool withTangents = false;
+	const float *cylinders = nullptr;
+	bool acceptsCylinders = false;
+};
+// Everything the kernels index with, checked before anything is laid out or freed (an out-of-range index would fault the GPU);
+// no array is read through an index that has not been checked.  depthLimit: the deepest branch the traversal stack holds
+// (trace_stack_levels() - 2); skyDerived [MTSGPU_SKY_NDERIVED] receives SkyLuminaire::configure() of a background sky.
+// Returns the reason, or an empty string.
+std::string checkScene(const mtsgpu_scene &sc, const UploadExtras &x, uint32_t depthLimit, float *skyDerived);
+// What the upload derives from a checked scene, in the order it is uploaded (DScene, DTangents)
+struct SceneLayout {
+	std::vector<uint32_t> nodes;         // the kd-tree in device order, 2 words per slot
+	std::vector<uint32_t> leafTa;        // TriAccel records in leaf order, then the cylinders' rows
+	std::vector<float> triRec;           // per-primitive position / normal records
+	std::vector<uint32_t> shapeBin, shapeType;      // [n_shapes + 1]
+	std::vector<float> shapeParams;      // [n_shapes + 1][MTSGPU_SHAPE_NPARAMS], a cylinder's row as the shading reads it
+	std::vector<float> triDpdu;          // the gather array of the tangents, empty without a tangent mesh
+	std::vector<uint32_t> hasTan;        // ... and its flags [n_shapes + 1]
+	uint32_t hasShapes = 0, binMask = 0; // DScene::has_shapes; the material queues that can ever be non-empty
+};
+// topSlots: trace_top_nodes().  Returns a size refusal, or an empty string.
+std::string layoutScene(const mtsgpu_scene &sc, const UploadExtras &x, uint32_t topSlots, SceneLayout &out);
+
+// What the setters need of the uploaded scene once the caller's arrays may be gone: host copies, taken by the upload
+struct HostScene {
+	uint32_t nVerts = 0, hasShapes = 0;      // hasShapes: DScene::has_shapes
+	std::vector<uint32_t> triIdx, shapeTriOffset, shapeType, bsdfType, lumType;      // triIdx: [n_tris][3]
+	std::vector<int32_t> shapeBsdf;
+	std::vector<float> bsdfParams;
+	std::vector<uint32_t> shapeNormals, shapeTangents;      // per shape: has vertex normals / uploaded tangents (0 / 1)
+};
+void keepHostScene(const mtsgpu_scene &sc, const UploadExtras &x, const SceneLayout &lay, HostScene &out);
+// The rows of one mesh in a per-primitive gather array: for each of its primitives [t0, t1) the attribute of the three
+// vertices (`comps` floats per vertex: 4 floats apart for tangents and colours, 2 for texcoords), in rows of 4 * stride
+// floats.  A non-finite component is refused: false, and *bad names the vertex.
+bool gatherMeshRows(const uint32_t *triIdx, uint32_t t0, uint32_t t1, const float *vtx, int comps, size_t stride, float *rows, uint32_t *bad);
+std::string checkUvTexture(const mtsgpu_uv_texture &t, bool bitmaps = false);
+std::string checkBitmap(const mtsgpu_bitmap &b, uint64_t *total);
+void packBitmapTexels(const mtsgpu_bitmap &b, float *dst);
+// the arguments of the three texture calls (withBitmaps = false: kind MTSGPU_TEX_BITMAP is unknown; bsdf_mask: the masked call's)
+struct TextureArgs {
+	const float *vtx_uv = nullptr; const uint32_t *shape_has_uv = nullptr;
+	uint32_t n_textures = 0; const mtsgpu_uv_texture *textures = nullptr; const int32_t *bsdf_slot_texture = nullptr;
+	uint32_t n_bitmaps = 0; const mtsgpu_bitmap *bitmaps = nullptr; const int32_t *texture_bitmap = nullptr;
+	bool withBitmaps = false;
+	const mtsgpu_bsdf_mask *bsdf_mask = nullptr;
+};
+// ... and what they upload and keep (keep = false: the call switches the family off and keeps nothing)
+struct TexturePlan {
+	bool keep = false, anySlot = false, anyMask = false, anyMaskTex = false, anyBitmap = false;
+	std::vector<float> triUv;            // the gather array of the texcoords
+	std::vector<DTexture> desc;          // the descriptors, a bitmap's with its place in the pool (empty when neither a slot nor a mask reads one)
+	std::vector<float> pool;             // the bitmaps one behind the other, 16 bytes per texel (only when a kept texture shows one)
+	std::vector<uint32_t> shapeHasUv;    // what mtsgpu_set_cloth_bsdfs checks its casts on: the flags and the extremes of every
+	std::vector<double> uvRange;         // shape's texcoords (both empty without vtx_uv)
+};
+// the refusals of a texture call after its free, in its order, then the plan; the reason, or an empty string
+std::string planTextures(const HostScene &h, const InForce &in, const TextureArgs &a, TexturePlan &out);
+struct ClothPlan {
+	bool keep = false;
+	std::vector<DWeave> weaves;
+	std::vector<uint32_t> pattern;
+	std::vector<DYarn> yarns;
+};
+// likewise mtsgpu_set_cloth_bsdfs after its free
+std::string planCloth(const HostScene &h, const InForce &in, uint32_t n_weaves, const mtsgpu_weave *weaves, const int32_t *bsdf_weave, ClothPlan &out);
 
 } // namespace mg

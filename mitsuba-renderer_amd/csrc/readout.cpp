@@ -299,7 +299,7 @@ int mtsgpu_bsdf_eval_colored(mtsgpu_ctx *c, uint32_t bsdf_type, const float *par
 
 int mtsgpu_vertex_color_eval(mtsgpu_ctx *c, uint32_t n, const uint32_t *prim, const float *uv, float *out) {
 	if (!c || !prim || !uv || !out) return fail(c, MTSGPU_EINVAL, "null argument");
-	if (!c->haveScene || !c->dcol.tri_col) return fail(c, MTSGPU_ESTATE, "no vertex colours are set (mtsgpu_set_vertex_colors)");
+	if (!c->haveScene || !c->colors.d.tri_col) return fail(c, MTSGPU_ESTATE, "no vertex colours are set (mtsgpu_set_vertex_colors)");
 	if (int rc = checkRecordCount(c, n)) return rc;
 	if (int rc = checkPrimitives(c, n, prim)) return rc;
 	if (n == 0) return 0;
@@ -307,7 +307,7 @@ int mtsgpu_vertex_color_eval(mtsgpu_ctx *c, uint32_t n, const uint32_t *prim, co
 	const uint32_t *dP = s.put(prim, n);
 	const float *dUV = s.put(uv, (size_t) n * 2);
 	float *dOut = s.alloc<float>((size_t) n * 3);
-	if (s.ok()) launch_vertex_color_eval(c->stream, c->dcol.tri_col, n, dP, dUV, dOut);
+	if (s.ok()) launch_vertex_color_eval(c->stream, c->colors.d.tri_col, n, dP, dUV, dOut);
 	s.get(out, dOut, (size_t) n * 3);
 	return s.finish("vertex-colour read-out");
 }
@@ -433,7 +433,7 @@ int mtsgpu_uv_texture_eval(mtsgpu_ctx *c, const mtsgpu_uv_texture *tex, uint32_t
 	const uint32_t *dP = s.put(prim, n);
 	const float *dRec = s.put(rec, (size_t) n * 3);
 	float *dOut = s.alloc<float>((size_t) n * 5);
-	const float4 *triUv = c->dtex.tri_uv;
+	const float4 *triUv = c->tex.d.tri_uv;
 	if (!triUv) triUv = s.zeros<float4>(kTriUvStride * ((size_t) c->nTris + 1));      // no texcoords set: every mesh reads zero rows
 	if (s.ok()) {
 		DTexture t;
@@ -464,7 +464,7 @@ int mtsgpu_bitmap_texture_eval(mtsgpu_ctx *c, const mtsgpu_uv_texture *tex, cons
 	const float *dRec = s.put(rec, (size_t) n * 3);
 	const float *dTexels = s.put(pool.data(), pool.size());
 	float *dOut = s.alloc<float>((size_t) n * 5);
-	const float4 *triUv = c->dtex.tri_uv;
+	const float4 *triUv = c->tex.d.tri_uv;
 	if (!triUv) triUv = s.zeros<float4>(kTriUvStride * ((size_t) c->nTris + 1));      // no texcoords set: every mesh reads zero rows
 	if (s.ok()) {
 		DTexture t;
@@ -487,7 +487,7 @@ int mtsgpu_shading_frame_eval(mtsgpu_ctx *c, uint32_t n, const uint32_t *prim, c
 	const uint32_t *dP = s.put(prim, n);
 	const float *dRec = s.put(rec, (size_t) n * 3);
 	float *dOut = s.alloc<float>((size_t) n * 9);
-	DTangents tan = c->dtan;
+	DTangents tan = c->tan.d;
 	// no tangents uploaded: every shape reads a zero flag, and tri_dpdu is never touched
 	if (!tan.shape_has_tan) tan.shape_has_tan = s.zeros<uint32_t>(c->host.shapeBsdf.size() + 1);
 	if (s.ok()) launch_shading_frame_eval(c->stream, c->dsc, tan, n, dP, dRec, dOut);

@@ -17,7 +17,7 @@
  *   BSDFs       lambertian, dielectric, roughmetal, microfacet, mirror, phong, roughglass, difftrans, ward (anisotropic on
  *               spheres and on meshes with texture coordinates, whose vertex tangents travel along), twosided(any of them), composite(up to 7 of the non-delta ones, each with or without twosided);
  *               constant reflectances only (textures need uv partials and a MIPMap lookup per hit: out of scope)
- *   luminaires  area (on meshes and spheres), constant, point, spot (no projection texture), directional, collimated, envmap
+ *   luminaires  area (on meshes and spheres), constant, point, spot (with a checkerboard, grid or ldrtexture projection texture; a filtered bitmap needs power-of-two sides), directional, collimated, envmap
  *   cameras     perspective (pinhole and thin lens), orthographic
  *   samplers    independent, ldsampler, stratified (keyed forms), halton, hammersley
  *   films       any (the result goes back as ImageBlocks); reconstruction filter = the film's own TabulatedFilter
@@ -216,6 +216,27 @@ struct FlatScene {
 			&uvTextures[0], ptr(bsdfSlotTexture), (uint32_t) bitmaps.size(), &bitmaps[0], &textureBitmap[0]);
 	}
 
+	/* the projection textures of the spot luminaires (spot.cpp:95-101): one descriptor, filter flag and -- for an `ldrtexture` --
+	 * decoded bitmap per textured spot, and per luminaire its texture (-1 = none): what mtsgpu_group_set_spot_textures takes */
+	std::vector<mtsgpu_uv_texture> spotTextures;
+	std::vector<uint32_t> spotBilinear, spotWrap, spotWidth, spotHeight;
+	std::vector<int32_t> spotTextureBitmap, lumTexture;
+	std::vector<std::vector<float> > spotTexels;
+	/* after upload() and every BSDF-side call (the library refuses a textured spot beside masks, snow and cloth, by name) */
+	int setSpotTextures(mtsgpu_group *group) const {
+		if (spotTextures.empty()) return MTSGPU_OK;
+		std::vector<mtsgpu_bitmap> bitmaps(spotTexels.size());
+		for (size_t k = 0; k < spotTexels.size(); ++k) {
+			bitmaps[k].width = spotWidth[k]; bitmaps[k].height = spotHeight[k];
+			bitmaps[k].wrap_mode = spotWrap[k]; bitmaps[k].reserved = 0;
+			bitmaps[k].texels = &spotTexels[k][0];
+		}
+		std::vector<int32_t> perLum(lumTexture);      /* (filled up to the last textured spot: the luminaires after it have none) */
+		perLum.resize(lumType.size(), -1);
+		return mtsgpu_group_set_spot_textures(group, (uint32_t) spotTextures.size(), ptr(spotTextures), (uint32_t) bitmaps.size(), ptr(bitmaps),
+			ptr(spotTextureBitmap), ptr(spotBilinear), ptr(perLum));
+	}
+
 	/* after upload(): hands the colours over when a mesh has some or a BSDF slot asks for them (then the
 	 * library refuses a coloured slot on a shape without colours, where the reference would read an its.color nobody wrote) */
 	int setVertexColors(mtsgpu_group *group) const {
@@ -274,7 +295,27 @@ struct FlatScene {
 			} else if (cls == "SpotLuminaire") {
 				lumType.push_back(MTSGPU_LUM_SPOT);
 				ref<MemoryStream> st = serializedDetached(lum);                     /* spot.cpp:63-70, configure() :56-62 */
-				if (!mtsgpu_stream::parseSpot<Float>(st->getData(), st->getSize(), P, &err)) SLog(EError, "gpupath: %s", err.c_str());
+				mtsgpu_stream::SpotTexture tex;
+				if (!mtsgpu_stream::parseSpotTextured<Float>(st->getData(), st->getSize(), P, &tex, &err)) SLog(EError, "gpupath: %s", err.c_str());
+				if (tex.present) {
+					lumTexture.resize(lumType.size(), -1);
+					lumTexture.back() = (int32_t) spotTextures.size();
+					spotTextures.push_back(tex.tex);
+					spotBilinear.push_back(tex.bilinear);
+					spotTextureBitmap.push_back(-1);
+					if (tex.isBitmap) {      /* the encoded file through Mitsuba's decoder and mtsgpu_ldr_texels, as decodeLdrTexture does it */
+						ref<MemoryStream> file = new MemoryStream(tex.ldr.size);
+						file->write(st->getData() + tex.ldr.offset, tex.ldr.size);
+						file->setPos(0);
+						ref<Bitmap> bitmap = new Bitmap(static_cast<Bitmap::EFileFormat>(tex.ldr.format), file);
+						const uint32_t bw = (uint32_t) bitmap->getWidth(), bh = (uint32_t) bitmap->getHeight();
+						std::vector<float> texels(3 * (size_t) bw * bh);
+						if (bw == 0 || bh == 0 || mtsgpu_ldr_texels(bitmap->getBitsPerPixel(), bw, bh, bitmap->getData(), tex.ldr.gamma, &texels[0]) != MTSGPU_OK)
+							SLog(EError, "gpupath: texture \"%s\": %s", tex.ldr.filename.c_str(), (bw == 0 || bh == 0) ? "empty bitmap" : mtsgpu_last_error(NULL));
+						spotTextureBitmap.back() = (int32_t) spotTexels.size();
+						spotTexels.push_back(texels); spotWidth.push_back(bw); spotHeight.push_back(bh); spotWrap.push_back(tex.ldr.wrapMode);
+					}
+				}
 			} else if (cls == "CollimatedBeamLuminaire") {
 				lumType.push_back(MTSGPU_LUM_COLLIMATED);
 				ref<MemoryStream> st = serializedDetached(lum);                     /* collimated.cpp:47-51 */
@@ -610,6 +651,7 @@ struct GPURenderDriver {
 			check(flat.setUvTextures(group));
 			check(flat.setSnowBsdfs(group));
 			check(flat.setClothBsdfs(group));
+			check(flat.setSpotTextures(group));
 		}
 
 		/* --- camera: raster space of the FULL film, crop window as offset + size (perspective.cpp:43-71, film.cpp:33-41) --- */

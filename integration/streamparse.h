@@ -20,6 +20,7 @@
 #include <mtsgpu_snow.h>
 #include <mtsgpu_cloth.h>
 #include <mtsgpu_cylinder.h>
+#include <mtsgpu_spot.h>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -651,6 +652,91 @@ template <typename FloatT> inline bool parseSpot(const uint8_t *data, size_t siz
 	copy3x3(P + 10, w2l.fwd);
 	P[19] = (float) beamWidth;
 	if (!r.ok()) { if (err) *err = r.error(); return false; }
+	return true;
+}
+
+/* The projection texture of a spot luminaire, as parseSpotTextured found it.  present = false: a ConstantSpectrumTexture, which
+ * falloffCurve never evaluates whatever its value (spot.cpp:95: only another class is looked up; the constant enters getPower
+ * alone, which is not on this path) -- the luminaire is the plain spot.  Otherwise tex is the descriptor mtsgpu_set_spot_textures
+ * takes and bilinear its filter flag; for an LDRTexture (isBitmap) ldr says where the encoded file lies, ldr.texture = 0. */
+struct SpotTexture {
+	bool present, isBitmap;
+	mtsgpu_uv_texture tex;
+	uint32_t bilinear;
+	LdrTexture ldr;
+};
+/* SpotLuminaire with any texture this path serves (spot.cpp:63-70): parseSpot's block, and the nested texture instance read the
+ * way the BSDF slots read theirs -- Checkerboard, GridTexture (Texture2D::serialize, brightColor, darkColor, the grid's lineWidth)
+ * and LDRTexture with its encoded-file span (ldrtexture.cpp:210-228).  A luminaire lookup has no uv partials (spot.cpp:97), so
+ * LDRTexture::getValue is MIPMap::triangle(0, u, v) for every filter type: none (2) is the nearest texel, ewa (0) and trilinear (1)
+ * the bilinear lookup on level 0; all three are accepted here and translated to the flag.  ExrTexture, VertexColors and every
+ * other class are refused by name. */
+template <typename FloatT> inline bool parseSpotTextured(const uint8_t *data, size_t size, float *P, SpotTexture *tex, std::string *err) {
+	ByteReader<FloatT> r(data, size);
+	openDetached(r, "SpotLuminaire");
+	const Xform<FloatT> w2l = readLuminaireBase(r);
+	SpotTexture t;
+	t.present = t.isBitmap = false; t.bilinear = 0;
+	memset(&t.tex, 0, sizeof(t.tex));
+	t.ldr.texture = 0; t.ldr.gamma = 0; t.ldr.format = 0; t.ldr.filterType = 2; t.ldr.wrapMode = 0; t.ldr.maxAnisotropy = 0; t.ldr.offset = 0; t.ldr.size = 0;
+	{
+		if (r.readUInt() == 0 && r.ok()) r.fail("the texture of the SpotLuminaire is missing");
+		const std::string cls = r.readString();
+		r.readUInt();                                                        /* Texture::serialize: its parent (the luminaire: a known id, or none) */
+		if (!r.ok()) {
+		} else if (cls == "ConstantSpectrumTexture") {
+			float c[3]; r.readSpectrum(c);
+		} else if (cls == "Checkerboard" || cls == "GridTexture") {
+			t.present = true;
+			t.tex.kind = cls == "GridTexture" ? MTSGPU_TEX_GRID : MTSGPU_TEX_CHECKERBOARD;
+			t.tex.uoffset = (float) r.readFloat(); t.tex.voffset = (float) r.readFloat();              /* Point2 m_uvOffset */
+			t.tex.uscale = (float) r.readFloat(); t.tex.vscale = (float) r.readFloat();                /* Vector2 m_uvScale */
+			r.readSpectrum(t.tex.bright); r.readSpectrum(t.tex.dark);
+			if (t.tex.kind == MTSGPU_TEX_GRID) t.tex.line_width = (float) r.readFloat();
+		} else if (cls == "LDRTexture") {
+			t.present = t.isBitmap = true;
+			t.tex.kind = MTSGPU_TEX_BITMAP;
+			t.tex.uoffset = (float) r.readFloat(); t.tex.voffset = (float) r.readFloat();
+			t.tex.uscale = (float) r.readFloat(); t.tex.vscale = (float) r.readFloat();
+			t.ldr.filename = r.readString();
+			t.ldr.gamma = (float) r.readFloat();
+			t.ldr.format = r.readInt();
+			t.ldr.filterType = r.readInt();
+			const uint32_t wrap = r.readUInt();
+			t.ldr.maxAnisotropy = (float) r.readFloat();
+			t.ldr.size = r.readUInt();
+			t.ldr.offset = r.pos();
+			static const uint32_t wrapOf[4] = { MTSGPU_WRAP_REPEAT, MTSGPU_WRAP_BLACK, MTSGPU_WRAP_WHITE, MTSGPU_WRAP_CLAMP };
+			if (!r.ok()) {
+			} else if (t.ldr.filterType < 0 || t.ldr.filterType > 2) {
+				r.fail("the texture of the SpotLuminaire is an LDRTexture with unknown filter type " + std::to_string((long long) t.ldr.filterType));
+			} else if (wrap > 3) {
+				r.fail("the texture of the SpotLuminaire is an LDRTexture with unknown wrap mode " + std::to_string((unsigned long long) wrap));
+			} else if (t.ldr.size > r.size() - t.ldr.offset) {
+				r.fail("the texture of the SpotLuminaire is an LDRTexture whose encoded file (" + std::to_string((unsigned long long) t.ldr.size) + " bytes) is truncated");
+			} else {
+				t.ldr.wrapMode = wrapOf[wrap];
+				t.bilinear = t.ldr.filterType == 2 ? 0u : 1u;                   /* MIPMap::ENone = 2; EEWA = 0, ETrilinear = 1 */
+				r.setPos(t.ldr.offset + t.ldr.size);
+			}
+		} else {
+			r.fail("the texture of the SpotLuminaire is a " + cls + ": projection textures are a Checkerboard, a GridTexture or an LDRTexture on this path"
+			       + (cls == "ExrTexture" || cls == "VertexColors" ? " (this class is out of scope)" : ""));
+		}
+	}
+	r.readSpectrum(P);
+	const FloatT beamWidth = r.readFloat(), cutoffAngle = r.readFloat();
+	/* m_luminaireToWorld(Point(0, 0, 0)) (transform.h:133-149): the translation column, divided by w unless it is 1 */
+	FloatT x = w2l.inv.m[0][3], y = w2l.inv.m[1][3], z = w2l.inv.m[2][3];
+	const FloatT w = w2l.inv.m[3][3];
+	if (w != (FloatT) 1) { const FloatT rc = (FloatT) 1 / w; x *= rc; y *= rc; z *= rc; }
+	P[3] = (float) x; P[4] = (float) y; P[5] = (float) z;
+	P[6] = (float) std::cos(beamWidth); P[7] = (float) std::cos(cutoffAngle);
+	P[8] = (float) cutoffAngle; P[9] = (float) ((FloatT) 1 / (cutoffAngle - beamWidth));
+	copy3x3(P + 10, w2l.fwd);
+	P[19] = (float) beamWidth;
+	if (!r.ok()) { if (err) *err = r.error(); return false; }
+	if (tex) *tex = t;
 	return true;
 }
 

@@ -57,6 +57,8 @@ CLOTH_EXPORTS = ["mtsgpu_set_cloth_bsdfs", "mtsgpu_group_set_cloth_bsdfs", "mtsg
 
 
 # the cylinder shape's entry points: the extension declared in include/mtsgpu_cylinder.h
+# the projection textures of the spot luminaire: the extension declared in include/mtsgpu_spot.h
+SPOT_EXPORTS = ["mtsgpu_set_spot_textures", "mtsgpu_group_set_spot_textures", "mtsgpu_spot_textures_check", "mtsgpu_spot_eval"]
 CYLINDER_EXPORTS = ["mtsgpu_cylinder_configure", "mtsgpu_flatten_cylinders", "mtsgpu_flat_scene_cylinders", "mtsgpu_upload_scene_cylinders",
                     "mtsgpu_group_upload_scene_cylinders", "mtsgpu_cylinder_aabb", "mtsgpu_cylinder_clip"]
 
@@ -282,6 +284,10 @@ def lib():
     L.mtsgpu_devmath.argtypes = [C.c_int, C.c_uint32, f32p, f32p, f32p]
     L.mtsgpu_flatten_tangents_flagged.argtypes = L.mtsgpu_flatten_tangents.argtypes[:3] + [u32p] + L.mtsgpu_flatten_tangents.argtypes[3:]
     L.mtsgpu_ldr_texels.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_float, f32p]
+    L.mtsgpu_set_spot_textures.argtypes = [vp, C.c_uint32, texp, C.c_uint32, bmpp, abi.i32p, u32p, abi.i32p]
+    L.mtsgpu_group_set_spot_textures.argtypes = [vp, C.c_uint32, texp, C.c_uint32, bmpp, abi.i32p, u32p, abi.i32p]
+    L.mtsgpu_spot_textures_check.argtypes = [C.c_uint32, u32p, f32p, C.c_uint32, texp, C.c_uint32, bmpp, abi.i32p, u32p, abi.i32p, C.c_uint32, f32p]
+    L.mtsgpu_spot_eval.argtypes = [vp, f32p, texp, bmpp, C.c_uint32, C.c_uint32, f32p, f32p]
     _lib = L
     return L
 
@@ -379,6 +385,28 @@ def bitmap_array(bitmaps):
     """a ctypes array of mtsgpu_bitmap from scenes.BitmapTexture objects (or abi.Bitmap values)"""
     items = [b if isinstance(b, abi.Bitmap) else b.bitmap() for b in bitmaps]
     return (abi.Bitmap * max(len(items), 1))(*items) if items else (abi.Bitmap * 1)()
+
+
+def spot_textures_check(lum_type, lum_params, textures, texture_bilinear, lum_texture, in_force=0, bitmaps=None, texture_bitmap=None):
+    """mtsgpu_spot_textures_check: what mtsgpu_set_spot_textures requires, without a context.  textures: scenes texture objects (or
+    abi.UvTexture values with `bitmaps` / `texture_bitmap` given); in_force: bit 0 a mask, 1 a snow table, 2 a cloth table.
+    Returns uv_factor [n_lums]; raises MtsGpuError with the refusal"""
+    lt = np.ascontiguousarray(lum_type, dtype=np.uint32).reshape(-1)
+    lp = np.ascontiguousarray(lum_params, dtype=np.float32).reshape(-1, abi.LUM_NPARAMS)
+    textures = list(textures) if textures is not None else None
+    if textures is not None and bitmaps is None:
+        bitmaps, texture_bitmap = bitmap_table(textures)
+    tb = None if texture_bitmap is None else np.ascontiguousarray(texture_bitmap, dtype=np.int32)
+    fl = None if texture_bilinear is None else np.ascontiguousarray(texture_bilinear, dtype=np.uint32)
+    lx = None if lum_texture is None else np.ascontiguousarray(lum_texture, dtype=np.int32)
+    out = np.zeros(max(len(lt), 1), dtype=np.float32)
+    rc = lib().mtsgpu_spot_textures_check(len(lt), abi.ptr(lt, abi.u32p), abi.ptr(lp, abi.f32p), len(textures or []),
+                                          uv_texture_array(textures) if textures else None, len(bitmaps or []),
+                                          bitmap_array(bitmaps) if bitmaps else None, abi.ptr(tb, abi.i32p), abi.ptr(fl, abi.u32p),
+                                          abi.ptr(lx, abi.i32p), int(in_force), abi.ptr(out, abi.f32p))
+    if rc != 0:
+        raise MtsGpuError("spot_textures_check: %s" % lib().mtsgpu_last_error(None).decode())
+    return out[:len(lt)]
 
 
 def bitmap_table(textures):
@@ -520,9 +548,24 @@ class Scene:
         # the snow records of the BSDFs (none: the scene never calls mtsgpu_set_snow_bsdfs)
         self.bsdf_snow = bsdf_snow_array(description.snow_table(snow_configure)) if getattr(description, "bsdf_snow", None) else None
 
+        # the projection textures of the spot luminaires (none: the scene never calls mtsgpu_set_spot_textures)
+        self.spot = None
+        if getattr(description, "spot_textures", None):
+            st, flags, lum = description.spot_texture_table()
+            sb, stb = bitmap_table(st)
+            self.spot = (st, uv_texture_array(st), sb, bitmap_array(sb), stb, flags, lum)
+
     @property
     def sc(self):
         return self.ptr.contents
+
+    def spot_texture_args(self):
+        """what mtsgpu_set_spot_textures takes for this scene: (n_textures, textures, n_bitmaps, bitmaps, texture_bitmap,
+        texture_bilinear, lum_texture), or None when no spot luminaire of the scene has a projection texture"""
+        if self.spot is None:
+            return None
+        st, ta, sb, ba, stb, flags, lum = self.spot
+        return (len(st), ta, len(sb), ba if sb else None, abi.ptr(stb, abi.i32p) if sb else None, abi.ptr(flags, abi.u32p), abi.ptr(lum, abi.i32p))
 
     def cylinder_blocks(self):
         """the derived blocks mtsgpu_upload_scene_cylinders takes behind the scene, [n_shapes][28], or None without a cylinder"""
@@ -742,6 +785,9 @@ class MIPathTracer:
                 self._chk(lib().mtsgpu_set_uv_textures(self._ctx, *scene.uv_only_args()), "set_uv_textures")
             self._chk(lib().mtsgpu_set_cloth_bsdfs(self._ctx, len(scene.description.weaves), scene.cloth[0], abi.ptr(scene.cloth[2], abi.i32p)),
                       "set_cloth_bsdfs")
+        sx = scene.spot_texture_args() if isinstance(scene, Scene) else None
+        if sx is not None:
+            self._chk(lib().mtsgpu_set_spot_textures(self._ctx, *sx), "set_spot_textures")
         self.camera = camera
         self._chk(lib().mtsgpu_set_camera(self._ctx, C.byref(camera.c if hasattr(camera, "c") else camera)), "set_camera")
         kind = {"independent": abi.SAMPLER_INDEPENDENT_KEYED, "ldsampler": abi.SAMPLER_LD_KEYED, "halton": abi.SAMPLER_HALTON,
@@ -1117,6 +1163,32 @@ class MIPathTracer:
                                         abi.ptr(out, abi.f32p)), "lum_eval")
         return out
 
+    def set_spot_textures(self, textures=None, texture_bilinear=None, lum_texture=None):
+        """mtsgpu_set_spot_textures on the uploaded scene: scenes texture objects, one filter flag per texture and one texture index
+        (or -1) per luminaire; all None switches the projection textures off"""
+        if textures is None and lum_texture is None:
+            self._chk(lib().mtsgpu_set_spot_textures(self._ctx, 0, None, 0, None, None, None, None), "set_spot_textures")
+            return
+        textures = list(textures or [])
+        sb, stb = bitmap_table(textures)
+        fl = None if texture_bilinear is None else np.ascontiguousarray(texture_bilinear, dtype=np.uint32)
+        lx = np.ascontiguousarray(lum_texture, dtype=np.int32)
+        self._chk(lib().mtsgpu_set_spot_textures(self._ctx, len(textures), uv_texture_array(textures) if textures else None, len(sb),
+                                                 bitmap_array(sb) if sb else None, abi.ptr(stb, abi.i32p) if sb else None,
+                                                 abi.ptr(fl, abi.u32p), abi.ptr(lx, abi.i32p)), "set_spot_textures")
+
+    def spot_eval(self, block, texture, points, bilinear=False):
+        """SpotLuminaire::sample with the projection texture `texture` on the device (mtsgpu_spot_eval) for the spot whose parameter
+        block is `block` and points [n][3] -> [n][8] = lRec.d, uv, lRec.value"""
+        b = np.ascontiguousarray(block, dtype=np.float32).reshape(abi.LUM_NPARAMS)
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((len(p), 8), dtype=np.float32)
+        t = uv_texture_array([texture])
+        bm = bitmap_array([texture]) if getattr(texture, "kind", None) == abi.TEX_BITMAP else None
+        self._chk(lib().mtsgpu_spot_eval(self._ctx, abi.ptr(b, abi.f32p), t, bm, 1 if bilinear else 0, len(p), abi.ptr(p, abi.f32p),
+                                         abi.ptr(out, abi.f32p)), "spot_eval")
+        return out
+
     def scene_lum_eval(self, op, queries):
         """the luminaires of the uploaded scene on the device (mtsgpu_scene_lum_eval) for query records [n][16]: op 0
         sampleLuminaire(p, s) without the occlusion test, op 1 pdfLuminaire(p, lRec.p, lRec.n, lRec.d, index), op 2 the
@@ -1221,6 +1293,9 @@ class DeviceGroup:
                 self._chk(lib().mtsgpu_group_set_uv_textures(self._g, *scene.uv_only_args()), "set_uv_textures")
             self._chk(lib().mtsgpu_group_set_cloth_bsdfs(self._g, len(scene.description.weaves), scene.cloth[0], abi.ptr(scene.cloth[2], abi.i32p)),
                       "set_cloth_bsdfs")
+        sx = scene.spot_texture_args() if isinstance(scene, Scene) else None
+        if sx is not None:
+            self._chk(lib().mtsgpu_group_set_spot_textures(self._g, *sx), "set_spot_textures")
         self.camera = camera
         self._chk(lib().mtsgpu_group_set_camera(self._g, C.byref(camera.c)), "set_camera")
         kind = {"independent": abi.SAMPLER_INDEPENDENT_KEYED, "ldsampler": abi.SAMPLER_LD_KEYED, "halton": abi.SAMPLER_HALTON,

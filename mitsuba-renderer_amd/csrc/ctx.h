@@ -87,6 +87,11 @@ struct ClothFamily {                     // mtsgpu_set_cloth_bsdfs
 	std::vector<int32_t> weave;          // bsdf_weave
 	void clear() { freeAll(allocs); d = DCloths{ nullptr, nullptr, nullptr, nullptr }; weave.clear(); }
 };
+struct SpotFamily {                      // mtsgpu_set_spot_textures
+	std::vector<void *> allocs;
+	DSpots d{ nullptr, nullptr, nullptr, nullptr };
+	void clear() { freeAll(allocs); d = DSpots{ nullptr, nullptr, nullptr, nullptr }; }
+};
 struct TangentFamily {                   // mtsgpu_upload_scene_tangents: the arrays are the scene's (sceneAllocs) and go with it
 	DTangents d{ nullptr, nullptr };
 	void clear() { d = DTangents{ nullptr, nullptr }; }
@@ -96,7 +101,7 @@ struct TangentFamily {                   // mtsgpu_upload_scene_tangents: the ar
 struct mtsgpu_ctx {
 	// with `device` current and idle (mtsgpu_destroy): everything no DevBuf member owns.  A caller's stream or film is not ours.
 	~mtsgpu_ctx() {
-		for (auto *list : { &sceneAllocs, &colors.allocs, &tex.allocs, &snow.allocs, &cloth.allocs, &pathAllocs }) mg::freeAll(*list);
+		for (auto *list : { &sceneAllocs, &colors.allocs, &tex.allocs, &snow.allocs, &cloth.allocs, &spots.allocs, &pathAllocs }) mg::freeAll(*list);
 		if (hostCounters) (void) hipHostFree(hostCounters);
 		for (auto *pool : { &traceEvents, &shadeEvents })
 			for (auto &e : *pool) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
@@ -128,14 +133,16 @@ struct mtsgpu_ctx {
 	mg::SnowFamily snow;
 	mg::ClothFamily cloth;
 	mg::TangentFamily tan;
+	mg::SpotFamily spots;
 	// a new scene starts without any of them
-	void clearAttachments() { colors.clear(); tex.clear(); snow.clear(); cloth.clear(); tan.clear(); }
+	void clearAttachments() { colors.clear(); tex.clear(); snow.clear(); cloth.clear(); tan.clear(); spots.clear(); }
 	// the tables in force, as the pure checks of host.h take them
 	mg::InForce inForce() const {
 		auto p = [](const auto &v) { return v.empty() ? nullptr : v.data(); };
 		mg::InForce f;
 		f.colorSlots = p(colors.slots); f.slotTex = p(tex.slotTex); f.maskKind = p(tex.maskKind); f.snowKind = p(snow.kind);
 		f.clothWeave = p(cloth.weave); f.shapeHasUv = p(tex.shapeHasUv); f.uvRange = p(tex.uvRange);
+		f.spotTextures = spots.d.lum_texture != nullptr;
 		return f;
 	}
 

@@ -483,6 +483,14 @@ int mtsgpu_group_set_cloth_bsdfs(mtsgpu_group *g, uint32_t n_weaves, const mtsgp
 	               [](mtsgpu_ctx *c) { return mtsgpu_set_cloth_bsdfs(c, 0, nullptr, nullptr); });
 }
 
+int mtsgpu_group_set_spot_textures(mtsgpu_group *g, uint32_t n_textures, const mtsgpu_uv_texture *textures, uint32_t n_bitmaps, const mtsgpu_bitmap *bitmaps,
+                                   const int32_t *texture_bitmap, const uint32_t *texture_bilinear, const int32_t *lum_texture) {
+	if (!g) return gfail(nullptr, MTSGPU_EINVAL, "null group");
+	return forEach(g, "set_spot_textures", [&](mtsgpu_ctx *c) {
+		return mtsgpu_set_spot_textures(c, n_textures, textures, n_bitmaps, bitmaps, texture_bitmap, texture_bilinear, lum_texture); },
+	               [](mtsgpu_ctx *c) { return mtsgpu_set_spot_textures(c, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr); });
+}
+
 int mtsgpu_hbm_triad(int device, size_t bytes, int iters, double *gbs) {
 	if (!gbs || bytes < 4096 || iters <= 0) return gfail(nullptr, MTSGPU_EINVAL, "bad triad arguments");
 	*gbs = 0;

@@ -5,6 +5,7 @@
 #include "../../include/mtsgpu_snow.h"
 #include "../../include/mtsgpu_cloth.h"
 #include "../../include/mtsgpu_cylinder.h"
+#include "../../include/mtsgpu_spot.h"
 #include "devmath.h"
 #include "kdtree.h"
 #include "kernels.h"
@@ -61,7 +62,14 @@ struct InForce {
 	const int32_t *clothWeave = nullptr;
 	const uint32_t *shapeHasUv = nullptr;
 	const double *uvRange = nullptr;
+	bool spotTextures = false;           // mtsgpu_set_spot_textures has given a luminaire a texture: masks, snow and cloth stay out
 };
+// The refusal of a mask, snow or cloth call (`what`) in a context that has a textured spot, and of the spot call in a context that
+// has one of the three: the kernels of a textured spot carry colours, uv textures and tangents only.  Whichever call comes second refuses
+inline std::string spotBesideRefusal(const char *what) {
+	return std::string(what) + " is not served in a context with a textured spot luminaire (the spot kernels do not carry it); "
+	       "switch the projection textures off with mtsgpu_set_spot_textures(ctx, 0, NULL, 0, NULL, NULL, NULL, NULL)";
+}
 // the slots of entry b that a slot table [n_bsdfs][2] (or NULL) gives a texture, as bits
 inline uint32_t textureSlotsClaimed(const int32_t *slotTex, uint32_t b) {
 	return slotTex ? (slotTex[2 * (size_t) b] >= 0 ? 1u : 0u) | (slotTex[2 * (size_t) b + 1] >= 0 ? 2u : 0u) : 0u;
@@ -548,7 +556,7 @@ struct HostScene {
 	uint32_t nVerts = 0, hasShapes = 0;      // hasShapes: DScene::has_shapes
 	std::vector<uint32_t> triIdx, shapeTriOffset, shapeType, bsdfType, lumType;      // triIdx: [n_tris][3]
 	std::vector<int32_t> shapeBsdf;
-	std::vector<float> bsdfParams;
+	std::vector<float> bsdfParams, lumParams;     // lumParams: [n_lums][MTSGPU_LUM_NPARAMS]
 	std::vector<uint32_t> shapeNormals, shapeTangents;      // per shape: has vertex normals / uploaded tangents (0 / 1)
 };
 void keepHostScene(const mtsgpu_scene &sc, const UploadExtras &x, const SceneLayout &lay, HostScene &out);
@@ -578,6 +586,26 @@ struct TexturePlan {
 };
 // the refusals of a texture call after its free, in its order, then the plan; the reason, or an empty string
 std::string planTextures(const HostScene &h, const InForce &in, const TextureArgs &a, TexturePlan &out);
+// the arguments of mtsgpu_set_spot_textures
+struct SpotArgs {
+	uint32_t n_textures = 0; const mtsgpu_uv_texture *textures = nullptr;
+	uint32_t n_bitmaps = 0; const mtsgpu_bitmap *bitmaps = nullptr; const int32_t *texture_bitmap = nullptr;
+	const uint32_t *texture_bilinear = nullptr;
+	const int32_t *lum_texture = nullptr;
+};
+// ... and what it uploads (keep = false: the call switches the family off and keeps nothing)
+struct SpotPlan {
+	bool keep = false;
+	std::vector<DTexture> desc;          // a bitmap's with its place in the pool and its filter flag (DSpots)
+	std::vector<float> pool;             // the bitmaps one behind the other, 16 bytes per texel
+	std::vector<float> uvFactor;         // [n_lums]: tan(cutoffAngle) of a luminaire with a texture, 0 otherwise
+};
+// SpotLuminaire::configure()'s m_uvFactor = std::tan(m_cutoffAngle) (spot.cpp:59) in binary32, the tangent of DESIGN.md section 5
+inline float spotUvFactor(float cutoffAngle) { return dtan(cutoffAngle); }
+// the refusals of mtsgpu_set_spot_textures after its free, in its order, then the plan; the reason, or an empty string.
+// lumType [nLums], lumParams [nLums][MTSGPU_LUM_NPARAMS]; haveMask / haveSnow / haveCloth: what is in force in the context
+std::string planSpots(uint32_t nLums, const uint32_t *lumType, const float *lumParams, const SpotArgs &a, bool haveMask, bool haveSnow,
+                      bool haveCloth, SpotPlan &out);
 struct ClothPlan {
 	bool keep = false;
 	std::vector<DWeave> weaves;

@@ -237,6 +237,19 @@ struct DCloths {
 	const DYarn    *yarns;
 	const int32_t  *bsdf_weave;
 };
+// The projection textures of the spot luminaires (mtsgpu_set_spot_textures, mtsgpu_spot.h), all NULL without one.  An argument of
+// kernels of their own (k_shade_spt) only, which serve colours, uv textures and tangents as the tangent kernels do.
+// textures[n_textures]: the descriptors; word reserved[0] of a bitmap's is its filter flag (kSpotBilinear: MIPMap::triangle(0, ., .)
+// on level 0, otherwise the nearest texel).  texels: the pool of these bitmaps, laid out like DTextures::texels.
+// lum_texture[n_lums]: the texture of each luminaire, -1 = none; non-NULL only while some luminaire has one, and the shading
+// launches pick the spot kernels by it.  lum_uv_factor[n_lums]: SpotLuminaire::m_uvFactor = tan(cutoffAngle) of those luminaires
+struct DSpots {
+	const DTexture *textures;
+	const float4   *texels;
+	const int32_t  *lum_texture;
+	const float    *lum_uv_factor;
+};
+constexpr uint32_t kSpotBilinear = 1u;
 // what a texture slot of a BSDF takes at a hit (bsdf_block_with_slots)
 enum : int { kSlotBlock = 0, kSlotColor = 1, kSlotTexture = 2 };
 
@@ -504,7 +517,13 @@ void launch_shading_frame_eval(hipStream_t s, const DScene &sc, const DTangents 
 void launch_sky_eval(hipStream_t s, const float *block, int op, uint32_t n, const float *queries, float *out);
 // the luminaires of the uploaded scene (mtsgpu_scene_lum_eval): sample_luminaire (op 0), pdf_luminaire (1), background_le (2)
 // for n query records [n][16]; out [n][16]
-void launch_scene_lum_eval(hipStream_t s, const DScene &sc, int op, uint32_t n, const float *queries, float *out);
+// spt.lum_texture != NULL: the instantiation of sample_luminaire that the frames of a scene with a textured spot run
+void launch_scene_lum_eval(hipStream_t s, const DScene &sc, int op, uint32_t n, const float *queries, float *out,
+                           const DSpots &spt = DSpots{ nullptr, nullptr, nullptr, nullptr });
+// mtsgpu_spot_eval: SpotLuminaire::sample with a projection texture for n points p [n][3]; block = the luminaire's parameters in
+// device memory; out [n][8] = lRec.d, uv, lRec.value
+void launch_spot_eval(hipStream_t s, const float *block, const DTexture &tex, const float4 *texels, float uv_factor, uint32_t n,
+                      const float *p, float *out);
 void launch_generate(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                      const uint32_t *pixel_list, uint32_t n_slots, const uint32_t *explicit_samples,
                      uint32_t n_paths, uint32_t *queue);
@@ -529,7 +548,8 @@ void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, co
                   const uint32_t *bin_ids = nullptr, const DColors &col = DColors{ nullptr, nullptr },
                   const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr },
                   const DMasks &msk = DMasks{ nullptr }, const DSnows &snw = DSnows{ nullptr },
-                  const DCloths &clo = DCloths{ nullptr, nullptr, nullptr, nullptr });
+                  const DCloths &clo = DCloths{ nullptr, nullptr, nullptr, nullptr },
+                  const DSpots &spt = DSpots{ nullptr, nullptr, nullptr, nullptr });
 // device-driven bounces, path integrator / one-sample direct integrator: all bins of bin_mask in one launch; views_dev as
 // above, n_bound bounds the sum of the bin sizes
 void launch_shade_all(hipStream_t s, const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q,

@@ -547,6 +547,34 @@ int mtsgpu_lum_eval(mtsgpu_ctx *c, uint32_t lum_type, const float *block, int op
 	return s.finish("luminaire read-out");
 }
 
+int mtsgpu_spot_eval(mtsgpu_ctx *c, const float *block, const mtsgpu_uv_texture *tex, const mtsgpu_bitmap *bitmap, uint32_t bilinear, uint32_t n,
+                     const float *p, float *out) {
+	if (!c || !block || !tex || !p || !out) return fail(c, MTSGPU_EINVAL, "null argument");
+	const bool isBitmap = tex->kind == (uint32_t) MTSGPU_TEX_BITMAP;
+	if (isBitmap != (bitmap != nullptr)) return fail(c, MTSGPU_EINVAL, "a bitmap goes with a texture of kind MTSGPU_TEX_BITMAP and with no other");
+	// the block as the flattener completes it (SpotLuminaire::configure, spot.cpp:56-60), checked as the call on a scene checks it
+	float host[MTSGPU_LUM_NPARAMS];
+	std::memcpy(host, block, sizeof host);
+	host[6] = std::cos(host[19]); host[7] = std::cos(host[8]); host[9] = 1.0f / (host[8] - host[19]);
+	const uint32_t lumType = MTSGPU_LUM_SPOT, flag = bilinear;
+	const int32_t zero = 0;
+	SpotPlan plan;
+	const SpotArgs a{ 1u, tex, isBitmap ? 1u : 0u, bitmap, &zero, &flag, &zero };
+	const std::string why = planSpots(1u, &lumType, host, a, false, false, false, plan);
+	if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+	if (int rc = checkRecordCount(c, n)) return rc;
+	if (n == 0) return 0;
+	Scratch s(c);
+	const float *dB = s.put(host, (size_t) MTSGPU_LUM_NPARAMS);
+	const float *dP = s.put(p, (size_t) n * 3);
+	const float *dTexels = plan.pool.empty() ? nullptr : s.put(plan.pool.data(), plan.pool.size());
+	float *dOut = s.alloc<float>((size_t) n * 8);
+	if (s.ok()) s.check(hipStreamSynchronize(c->stream));       // `host` and the plan live on this stack
+	if (s.ok()) launch_spot_eval(c->stream, dB, plan.desc[0], reinterpret_cast<const float4 *>(dTexels), plan.uvFactor[0], n, dP, dOut);
+	s.get(out, dOut, (size_t) n * 8);
+	return s.finish("spot read-out");
+}
+
 int mtsgpu_scene_lum_eval(mtsgpu_ctx *c, int op, uint32_t n, const float *queries, float *out) {
 	if (!c || !queries || !out) return fail(c, MTSGPU_EINVAL, "null argument");
 	if (!c->haveScene) return fail(c, MTSGPU_ESTATE, "mtsgpu_scene_lum_eval before mtsgpu_upload_scene");
@@ -567,7 +595,7 @@ int mtsgpu_scene_lum_eval(mtsgpu_ctx *c, int op, uint32_t n, const float *querie
 	Scratch s(c);
 	const float *dQ = s.put(queries, (size_t) n * 16);
 	float *dOut = s.alloc<float>((size_t) n * 16);
-	if (s.ok()) launch_scene_lum_eval(c->stream, c->dsc, op, n, dQ, dOut);
+	if (s.ok()) launch_scene_lum_eval(c->stream, c->dsc, op, n, dQ, dOut, c->spots.d);
 	s.get(out, dOut, (size_t) n * 16);
 	return s.finish("scene luminaire read-out");
 }

@@ -322,7 +322,7 @@ struct Shader {
 	// Bin b: over the view the host read back, or (viewsDev) over the one k_prep wrote, with a grid for `bound` paths.
 	// ids: the queue to shade instead of the bin's (the ray queue, for the material-independent tail)
 	void bin(int b, const BinView &view, const BinView *viewsDev = nullptr, uint32_t bound = 0, const uint32_t *ids = nullptr) const {
-		launch_shade(s, b, c->dsc, c->paths, cfg, c->q, view, viewsDev, bound, ids, c->colors.d, c->tex.d, c->tan.d, c->tex.msk, c->snow.d, c->cloth.d);
+		launch_shade(s, b, c->dsc, c->paths, cfg, c->q, view, viewsDev, bound, ids, c->colors.d, c->tex.d, c->tan.d, c->tex.msk, c->snow.d, c->cloth.d, c->spots.d);
 	}
 	// the first nBins bins of a bounce whose sizes the host has read
 	void bins(const BinView *views, int nBins = kNumBins) const { for (int b = 0; b < nBins; ++b) bin(b, views[b]); }
@@ -330,7 +330,8 @@ struct Shader {
 	// other bin the scene can fill (the composite, which the fused kernel leaves out; every bin without it)
 	void binsOnDevice(uint32_t bound) const {
 		uint32_t each = c->binMask;
-		if (cfg.dr_mode == 0 && fused) {
+		// (a scene with a textured spot: every bin on its own, through the spot kernels; there is no fused form of them)
+		if (cfg.dr_mode == 0 && fused && !c->spots.d.lum_texture) {
 			// a scene with a snow or a cloth BRDF: the Lambertian's bin has kernels of its own (k_shade_snw, k_shade_clo) and is launched
 			// like the composite's
 			const uint32_t all = (c->snow.d.bsdf_snow || c->cloth.d.bsdf_weave) ? kShadeAllBins & ~1u : kShadeAllBins;

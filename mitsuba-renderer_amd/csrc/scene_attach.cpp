@@ -1,5 +1,5 @@
 // scene_attach.cpp -- what comes and goes between two uploads (ctx.h: one record per family): vertex colours, uv textures with
-// bitmaps and masks, snow records, cloth weaves.  Every setter has one shape: the shared prologue, the family's clear(), the pure
+// bitmaps and masks, snow records, cloth weaves, the projection textures of spot luminaires.  Every setter has one shape: the shared prologue, the family's clear(), the pure
 // checks and plan (host.h: claimRefusal, planTextures, planCloth; scene_layout.cpp), then upload and commit.  A refused call
 // leaves its family switched off.
 #include "ctx.h"
@@ -106,6 +106,9 @@ static int setUvTextures(mtsgpu_ctx *c, const TextureArgs &a, const char *me) {
 	});
 	if (rc0) return rc0;
 	c->tex.clear();
+	if (c->inForce().spotTextures && a.bsdf_mask)
+		for (uint32_t b = 0; b < (uint32_t) c->host.bsdfType.size(); ++b)
+			if (a.bsdf_mask[b].kind != (uint32_t) MTSGPU_MASK_NONE) return fail(c, MTSGPU_EINVAL, "BSDF %u: %s", b, spotBesideRefusal("the mask BSDF").c_str());
 	TexturePlan p;
 	const std::string why = planTextures(c->host, c->inForce(), a, p);
 	if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
@@ -153,6 +156,9 @@ int mtsgpu_set_snow_bsdfs(mtsgpu_ctx *c, const mtsgpu_bsdf_snow *table) {
 	if (int rc = beginAttach(c, "mtsgpu_set_snow_bsdfs")) return rc;
 	c->snow.clear();
 	if (!table) return 0;
+	if (c->inForce().spotTextures)
+		for (uint32_t b = 0; b < (uint32_t) c->host.bsdfType.size(); ++b)
+			if (table[b].kind != (uint32_t) MTSGPU_SNOW_NONE) return fail(c, MTSGPU_EINVAL, "BSDF %u: %s", b, spotBesideRefusal("a snow BRDF").c_str());
 	if (c->host.hasShapes == kHasCylinders)
 		return fail(c, MTSGPU_EINVAL, "the snow BRDFs are not served in a scene with a cylinder yet (the snow kernels do not build a cylinder's record)");
 	const HostScene &h = c->host;
@@ -175,6 +181,9 @@ int mtsgpu_set_snow_bsdfs(mtsgpu_ctx *c, const mtsgpu_bsdf_snow *table) {
 int mtsgpu_set_cloth_bsdfs(mtsgpu_ctx *c, uint32_t n_weaves, const mtsgpu_weave *weaves, const int32_t *bsdf_weave) {
 	if (int rc = beginAttach(c, "mtsgpu_set_cloth_bsdfs")) return rc;
 	c->cloth.clear();
+	if (bsdf_weave && c->inForce().spotTextures)
+		for (uint32_t b = 0; b < (uint32_t) c->host.bsdfType.size(); ++b)
+			if (bsdf_weave[b] >= 0) return fail(c, MTSGPU_EINVAL, "BSDF %u: %s", b, spotBesideRefusal("the cloth BRDF").c_str());
 	ClothPlan p;
 	const std::string why = planCloth(c->host, c->inForce(), n_weaves, weaves, bsdf_weave, p);
 	if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
@@ -189,6 +198,42 @@ int mtsgpu_set_cloth_bsdfs(mtsgpu_ctx *c, uint32_t n_weaves, const mtsgpu_weave 
 	if (rc) { c->cloth.clear(); return rc; }
 	c->cloth.d = DCloths{ dW, dP, dY, dB };
 	c->cloth.weave.assign(bsdf_weave, bsdf_weave + nBsdfs);
+	return 0;
+}
+
+int mtsgpu_set_spot_textures(mtsgpu_ctx *c, uint32_t n_textures, const mtsgpu_uv_texture *textures, uint32_t n_bitmaps, const mtsgpu_bitmap *bitmaps,
+                             const int32_t *texture_bitmap, const uint32_t *texture_bilinear, const int32_t *lum_texture) {
+	if (int rc = beginAttach(c, "mtsgpu_set_spot_textures")) return rc;
+	c->spots.clear();
+	const HostScene &h = c->host;
+	const InForce in = c->inForce();
+	const uint32_t nLums = (uint32_t) h.lumType.size();
+	SpotPlan p;
+	const SpotArgs a{ n_textures, textures, n_bitmaps, bitmaps, texture_bitmap, texture_bilinear, lum_texture };
+	const std::string why = planSpots(nLums, h.lumType.data(), h.lumParams.data(), a, in.maskKind != nullptr, in.snowKind != nullptr, in.clothWeave != nullptr, p);
+	if (!why.empty()) return fail(c, MTSGPU_EINVAL, "%s", why.c_str());
+	if (!p.keep) return 0;
+	std::vector<void *> *owner = &c->spots.allocs;
+	const DTexture *dTex = nullptr; const float *dTexels = nullptr, *dFactor = nullptr; const int32_t *dLum = nullptr;
+	int rc = upload(c, &dTex, p.desc.data(), p.desc.size(), owner);
+	if (!rc && !p.pool.empty()) rc = upload(c, &dTexels, p.pool.data(), p.pool.size(), owner);
+	if (!rc) rc = upload(c, &dLum, lum_texture, nLums, owner);
+	if (!rc) rc = upload(c, &dFactor, p.uvFactor.data(), nLums, owner);
+	if (rc) { c->spots.clear(); return rc; }
+	c->spots.d = DSpots{ dTex, reinterpret_cast<const float4 *>(dTexels), dLum, dFactor };
+	return 0;
+}
+
+int mtsgpu_spot_textures_check(uint32_t n_lums, const uint32_t *lum_type, const float *lum_params, uint32_t n_textures, const mtsgpu_uv_texture *textures,
+                               uint32_t n_bitmaps, const mtsgpu_bitmap *bitmaps, const int32_t *texture_bitmap, const uint32_t *texture_bilinear,
+                               const int32_t *lum_texture, uint32_t in_force, float *uv_factor) {
+	if (n_lums && (!lum_type || !lum_params)) return fail(nullptr, MTSGPU_EINVAL, "null argument");
+	if (in_force > 7u) return fail(nullptr, MTSGPU_EINVAL, "unknown in_force bits %u", in_force);
+	SpotPlan p;
+	const SpotArgs a{ n_textures, textures, n_bitmaps, bitmaps, texture_bitmap, texture_bilinear, lum_texture };
+	const std::string why = planSpots(n_lums, lum_type, lum_params, a, (in_force & 1u) != 0, (in_force & 2u) != 0, (in_force & 4u) != 0, p);
+	if (!why.empty()) return fail(nullptr, MTSGPU_EINVAL, "%s", why.c_str());
+	for (uint32_t l = 0; uv_factor && l < n_lums; ++l) uv_factor[l] = p.keep ? p.uvFactor[l] : 0.0f;
 	return 0;
 }
 

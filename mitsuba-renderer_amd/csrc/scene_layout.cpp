@@ -341,6 +341,7 @@ void keepHostScene(const mtsgpu_scene &sc, const UploadExtras &x, const SceneLay
 	h.bsdfParams.assign(sc.bsdf_params, sc.bsdf_params + (size_t) MTSGPU_BSDF_NPARAMS * sc.n_bsdfs);
 	h.shapeBsdf.assign(sc.shape_bsdf, sc.shape_bsdf + sc.n_shapes);
 	h.lumType.assign(sc.lum_type, sc.lum_type + sc.n_lums);
+	h.lumParams.assign(sc.lum_params, sc.lum_params + (size_t) MTSGPU_LUM_NPARAMS * sc.n_lums);
 	h.shapeNormals.assign(sc.n_shapes, 0u);
 	h.shapeTangents.assign(sc.n_shapes, 0u);
 	for (uint32_t s = 0; s < sc.n_shapes; ++s) {
@@ -533,6 +534,87 @@ std::string planTextures(const HostScene &h, const InForce &in, const TextureArg
 					r[0] = std::min(r[0], u); r[1] = std::max(r[1], u); r[2] = std::min(r[2], w); r[3] = std::max(r[3], w);
 				}
 		}
+	}
+	return std::string();
+}
+
+std::string planSpots(uint32_t nLums, const uint32_t *lumType, const float *lumParams, const SpotArgs &a, bool haveMask, bool haveSnow,
+                      bool haveCloth, SpotPlan &out) {
+	out = SpotPlan();
+	if (!a.textures && !a.bitmaps && !a.texture_bitmap && !a.texture_bilinear && !a.lum_texture) return std::string();
+	if (!a.lum_texture) return "textures without lum_texture";
+	if (a.n_textures && !a.textures) return "n_textures without textures";
+	if (a.n_textures > (1u << 20)) return "at most 2^20 textures";
+	if (a.n_bitmaps && !a.bitmaps) return "n_bitmaps without bitmaps";
+	if (a.n_bitmaps > (1u << 20)) return "at most 2^20 bitmaps";
+	for (uint32_t k = 0; k < a.n_textures; ++k) {
+		const std::string why = checkUvTexture(a.textures[k], true);
+		if (!why.empty()) return "texture " + std::to_string(k) + ": " + why;
+		if (a.texture_bilinear && a.texture_bilinear[k] > 1u)
+			return "texture " + std::to_string(k) + ": unknown filter flag " + std::to_string(a.texture_bilinear[k]) + " (0 = nearest, 1 = bilinear)";
+	}
+	std::vector<uint32_t> first(a.n_bitmaps, 0u);
+	uint64_t nTexels = 0;
+	for (uint32_t b = 0; b < a.n_bitmaps; ++b) {
+		first[b] = (uint32_t) nTexels;
+		const std::string why = checkBitmap(a.bitmaps[b], &nTexels);
+		if (!why.empty()) return "bitmap " + std::to_string(b) + ": " + why;
+	}
+	std::vector<DTexture> &desc = out.desc;
+	desc.resize(a.n_textures);
+	bool anyBitmap = false;
+	const double lim = 2147483648.0 - 65536.0;
+	for (uint32_t k = 0; k < a.n_textures; ++k) {
+		const mtsgpu_uv_texture &t = a.textures[k];
+		std::memcpy(&desc[k], &t, sizeof(DTexture));
+		double size = 2.0;
+		if (t.kind == (uint32_t) MTSGPU_TEX_BITMAP) {
+			const int32_t b = a.texture_bitmap ? a.texture_bitmap[k] : -1;
+			if (b < 0 || (uint32_t) b >= a.n_bitmaps)
+				return "texture " + std::to_string(k) + ": bitmap index " + std::to_string(b) + " out of range (" + std::to_string(a.n_bitmaps) + " bitmaps)";
+			const mtsgpu_bitmap &bm = a.bitmaps[b];
+			const bool bilinear = a.texture_bilinear && a.texture_bilinear[k] == 1u;
+			if (bilinear && ((bm.width & (bm.width - 1u)) != 0u || (bm.height & (bm.height - 1u)) != 0u))
+				return "texture " + std::to_string(k) + ": a filtered (trilinear / ewa) bitmap of " + std::to_string(bm.width) + " x " + std::to_string(bm.height)
+				       + " texels: the reference resamples a size that is not a power of two with a Lanczos kernel first (mipmap.cpp:34-88), not done here";
+			desc[k].width = bm.width; desc[k].height = bm.height; desc[k].wrap = bm.wrap_mode; desc[k].first = first[b];
+			desc[k].reserved[0] = bilinear ? kSpotBilinear : 0u; desc[k].reserved[1] = desc[k].reserved[2] = 0u;
+			size = std::max(2.0, (double) std::max(bm.width, bm.height));
+			anyBitmap = true;
+		}
+		// uv lies in [0, 1] up to rounding: |uv'| <= |scale| + |offset|, and the margin of 1 covers the rounding, the half-texel
+		// shift and the second tap of the bilinear lookup
+		if (!((std::fabs((double) t.uscale) + std::fabs((double) t.uoffset) + 1.0) * size < lim)
+		    || !((std::fabs((double) t.vscale) + std::fabs((double) t.voffset) + 1.0) * size < lim))
+			return "texture " + std::to_string(k) + " can map uv outside the range of the (int) cast ((|scale| + |offset| + 1) * max(2, width, height) >= 2^31 - 2^16)";
+	}
+	bool any = false;
+	out.uvFactor.assign(nLums, 0.0f);
+	for (uint32_t l = 0; l < nLums; ++l) {
+		const int32_t k = a.lum_texture[l];
+		const std::string who = "luminaire " + std::to_string(l) + ": ";
+		if (k < -1 || k >= (int64_t) a.n_textures) return who + "texture index " + std::to_string(k) + " out of range (" + std::to_string(a.n_textures) + " textures)";
+		if (k < 0) continue;
+		if (lumType[l] != (uint32_t) MTSGPU_LUM_SPOT) return who + "a projection texture on a luminaire that is not a spot (type " + std::to_string(lumType[l]) + ")";
+		const float *P = lumParams + (size_t) MTSGPU_LUM_NPARAMS * l;
+		// ([9], invTransitionWidth, is infinite where beamWidth = cutoffAngle, as in the reference, and then never read)
+		for (int i = 0; i < 20; ++i) if (i != 9 && !std::isfinite(P[i])) return who + "non-finite spot parameter";
+		// below 90 degrees localDir.z > cosCutoff > 0 where uv is formed
+		if (!(P[8] < 0.5f * kPi) || !(std::cos((double) P[8]) > 0.0) || !(P[7] > 0.0f))
+			return who + "a textured spot needs cutoffAngle < 90 degrees (from there on the division that forms uv and the casts of the lookup have no bound)";
+		const float f = spotUvFactor(P[8]);
+		if (!std::isfinite(f) || !(f > 0.0f)) return who + "uvFactor = tan(cutoffAngle) is not finite and positive";
+		out.uvFactor[l] = f;
+		any = true;
+	}
+	if (!any) { out = SpotPlan(); return std::string(); }      // nothing to keep: the context launches what it launches without the call
+	if (haveMask) return spotBesideRefusal("the mask BSDF");
+	if (haveSnow) return spotBesideRefusal("a snow BRDF");
+	if (haveCloth) return spotBesideRefusal("the cloth BRDF");
+	out.keep = true;
+	if (anyBitmap) {
+		out.pool.resize(4 * (size_t) nTexels);
+		for (uint32_t b = 0; b < a.n_bitmaps; ++b) packBitmapTexels(a.bitmaps[b], &out.pool[4 * (size_t) first[b]]);
 	}
 	return std::string();
 }

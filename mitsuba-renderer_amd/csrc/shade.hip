@@ -1,5 +1,5 @@
 // shade.hip -- K3+K5: launch_shade / launch_shade_all pick the kernel family of the scene.  The device code is shade_bsdf.h and
-// shade_path.h; each family's kernels are instantiated in a unit of their own (shade_plain / _vcol / _tex / _tan / _mask / _snow / _cloth.hip).
+// shade_path.h; each family's kernels are instantiated in a unit of their own (shade_plain / _vcol / _tex / _tan / _mask / _snow / _cloth / _spot.hip).
 #include "kdevice.h"
 #include "shade_launch.h"
 
@@ -13,12 +13,15 @@ namespace mg {
 // bins 0..8 only -- a composite's children and the terminal bin take no colours)
 void launch_shade(hipStream_t s, int bin, const DScene &sc, const DPaths &ps, const DConfig &cfg,
                   const DQueues &q, const BinView &view, const BinView *views_dev, uint32_t n_bound, const uint32_t *bin_ids, const DColors &col,
-                  const DTextures &tex, const DTangents &tan, const DMasks &msk, const DSnows &snw, const DCloths &clo) {
+                  const DTextures &tex, const DTangents &tan, const DMasks &msk, const DSnows &snw, const DCloths &clo, const DSpots &spt) {
 	const uint32_t n = views_dev ? n_bound : view.prefix[kBinShards];
 	if (!n) return;
 	if (!bin_ids) bin_ids = q.bin(bin);
 	const ShadeBinLaunch a{ s, dim3(blocks_for(n, kShadeBlock)), dim3(kShadeBlock), sc, ps, cfg, q, view, views_dev, bin_ids };
-	if (bin == 0 && clo.bsdf_weave != nullptr) launch_shade_clo(a, col, tex, tan, msk, snw, clo);
+	// a textured spot (DSpots::lum_texture; bins 0..9, first: the host refuses masks, snow and cloth beside one, and the spot kernels
+	// serve tangents, textures and colours as well)
+	if (bin >= 0 && bin <= 9 && spt.lum_texture != nullptr) launch_shade_spt(a, bin, col, tex, tan, spt);
+	else if (bin == 0 && clo.bsdf_weave != nullptr) launch_shade_clo(a, col, tex, tan, msk, snw, clo);
 	else if (bin == 0 && snw.bsdf_snow != nullptr) launch_shade_snw(a, col, tex, tan, msk, snw);
 	else if (bin >= 0 && bin < 9 && msk.bsdf_mask != nullptr) launch_shade_msk(a, bin, col, tex, tan, msk);
 	else if (bin >= 0 && bin <= 9 && tan.tri_dpdu != nullptr) launch_shade_tan(a, bin, col, tex, tan);

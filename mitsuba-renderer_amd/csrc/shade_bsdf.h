@@ -203,6 +203,45 @@ __device__ __forceinline__ V3 bitmap_eval(const DTexture &t, const float4 *texel
 	const float4 v = texels[(size_t) t.first + (size_t) xPos + (size_t) w * (size_t) yPos];
 	return V3(v.x, v.y, v.z);
 }
+// MIPMap::triangle(0, x, y) of a filtered bitmap (mipmap.cpp:232-242), what LDRTexture::getValue(uv) is for filterType trilinear
+// and ewa (ldrtexture.cpp:230-232): the bilinear lookup on level 0.  Four getTexel taps, each with the `x <= 0` column quirk and
+// the wrap mode of bitmap_eval, summed left to right per channel.  env_triangle is this function for the envmap (repeat only).
+__device__ __forceinline__ V3 bitmap_triangle(const DTexture &t, const float4 *texels, float x, float y) {
+	const int w = (int) t.width, h = (int) t.height;
+	x = x * w - 0.5f;
+	y = y * h - 0.5f;
+	const int xPos = (int) floorf(x), yPos = (int) floorf(y);
+	const float dx = x - xPos, dy = y - yPos;
+	V3 acc(0, 0, 0);
+	#pragma unroll
+	for (int k = 0; k < 4; ++k) {
+		// T00 (1-dx)(1-dy) + T01 (1-dx) dy + T10 dx (1-dy) + T11 dx dy, Txy = getTexel(0, xPos + x, yPos + y)
+		int tx = xPos + (k >> 1), ty = yPos + (k & 1);
+		V3 texel;
+		bool constant = false;
+		if (tx <= 0 || ty < 0 || tx >= w || ty >= h) {
+			if (t.wrap == kWrapRepeat) {
+				tx = tx - (tx / w) * w; if (tx < 0) tx += w;
+				ty = ty - (ty / h) * h; if (ty < 0) ty += h;
+			} else if (t.wrap == kWrapClamp) {
+				tx = tx < 0 ? 0 : tx > w - 1 ? w - 1 : tx;
+				ty = ty < 0 ? 0 : ty > h - 1 ? h - 1 : ty;
+			} else {
+				const float c = t.wrap == kWrapBlack ? 0.0f : 1.0f;
+				texel = V3(c, c, c);
+				constant = true;
+			}
+		}
+		if (!constant) {
+			const float4 v = texels[(size_t) t.first + (size_t) tx + (size_t) w * (size_t) ty];
+			texel = V3(v.x, v.y, v.z);
+		}
+		const float a = (k < 2) ? (1.0f - dx) : dx, b = (k & 1) ? dy : (1.0f - dy);
+		const V3 term(texel.x * a * b, texel.y * a * b, texel.z * a * b);
+		acc = (k == 0) ? term : V3(acc.x + term.x, acc.y + term.y, acc.z + term.z);
+	}
+	return acc;
+}
 // Texture2D::getValue(its) (texture.cpp:73-82) of a checkerboard (checkerboard.cpp:48-56), a grid texture
 // (gridtexture.cpp:51-64) or an unfiltered bitmap (ldrtexture.cpp:230-232) at its.uv = (uvx, uvy).  The casts truncate towards
 // zero as the reference's (int) does; the host has checked that they stay inside the int range for every texcoord of the scene
@@ -389,11 +428,36 @@ __device__ __forceinline__ V3 background_le(const DScene &sc, V3 rayD) {
 	return (sc.lum_type[sc.background_lum] == 5u) ? env_le(sc, LP, normalize(rayD)) : V3(LP[0], LP[1], LP[2]);
 }
 
+// SpotLuminaire::falloffCurve with a projection texture (spot.cpp:87-108) for the unit direction d from the luminaire: LP = its
+// parameter block, t = the texture (DSpots), uvFactor = tan(cutoffAngle).  The host has checked cutoffAngle < 90 degrees, so
+// localDir.z > cosCutoff > 0 where the division happens, and that the casts of the lookup stay inside the int range.  The
+// texture's value multiplies the intensity before the falloff factor does.  uvx, uvy: its.uv (0 outside the cone), for the hook
+__device__ __forceinline__ V3 spot_falloff_textured(const float *LP, const DTexture &t, const float4 *texels, float uvFactor, V3 d,
+                                                    float &uvx, float &uvy) {
+	V3 result(LP[0], LP[1], LP[2]);
+	const V3 localDir(LP[10] * d.x + LP[11] * d.y + LP[12] * d.z, LP[13] * d.x + LP[14] * d.y + LP[15] * d.z,
+	                  LP[16] * d.x + LP[17] * d.y + LP[18] * d.z);
+	const float cosTheta = localDir.z;
+	uvx = uvy = 0.0f;
+	if (cosTheta <= LP[7]) return V3(0, 0, 0);
+	uvx = 0.5f + 0.5f * localDir.x / (localDir.z * uvFactor);
+	uvy = 0.5f + 0.5f * localDir.y / (localDir.z * uvFactor);
+	// Texture2D::getValue(its) without uv partials = getValue(uv') (texture.cpp:73-82); an ldrtexture's is MIPMap::triangle(0, ., .)
+	V3 value;
+	if (t.kind == kTexBitmap && t.reserved[0] == kSpotBilinear) value = bitmap_triangle(t, texels, uvx * t.uscale + t.uoffset, uvy * t.vscale + t.voffset);
+	else value = tex_eval(t, texels, uvx, uvy);
+	result = result * value;
+	if (cosTheta >= LP[6]) return result;
+	return result * ((LP[8] - dacos(cosTheta)) * LP[9]);
+}
+
 // Scene::sampleLuminaire without the visibility test (scene.cpp:396-415):
 // returns true when a shadow ray has to be traced; value is already divided by pdf.
 // SKY: the instantiation for scenes whose background luminaire is a sky (the only one that carries its code)
-template <bool SKY>
-__device__ __forceinline__ bool sample_luminaire(const DScene &sc, V3 p, float s0, float s1, LRec &lRec) {
+// SPT: the instantiation for scenes in which a spot luminaire has a projection texture (DSpots::lum_texture != NULL), likewise
+template <bool SKY, bool SPT = false>
+__device__ __forceinline__ bool sample_luminaire(const DScene &sc, V3 p, float s0, float s1, LRec &lRec,
+                                                 const DSpots &spt = DSpots{ nullptr, nullptr, nullptr, nullptr }) {
 	float sx = s0, sy = s1;
 	const int l = dpdf_sample_reuse(sc.lum_sel_cdf, sc.n_lums, sx);
 	const float lumPdf = sc.lum_sel_pdf[l];
@@ -489,7 +553,10 @@ __device__ __forceinline__ bool sample_luminaire(const DScene &sc, V3 p, float s
 		lRec.n = V3(0, 0, 0);
 		lRec.pdf = 1.0f;
 		V3 result(LP[0], LP[1], LP[2]);
-		if (sc.lum_type[l] == 4u) {
+		if (SPT && sc.lum_type[l] == 4u && spt.lum_texture[l] >= 0) {
+			float uvx, uvy;
+			result = spot_falloff_textured(LP, spt.textures[spt.lum_texture[l]], spt.texels, spt.lum_uv_factor[l], lRec.d, uvx, uvy);
+		} else if (sc.lum_type[l] == 4u) {
 			// falloffCurve (spot.cpp:84-103), constant texture; cosTheta = m_worldToLuminaire(d).z
 			const float cosTheta = LP[16] * lRec.d.x + LP[17] * lRec.d.y + LP[18] * lRec.d.z;
 			if (cosTheta <= LP[7]) result = V3(0, 0, 0);

@@ -318,6 +318,45 @@ __global__ void k_scene_lum_eval(DScene sc, int op, uint32_t n, const float *que
 	for (int k = 0; k < 16; ++k) out[16 * (size_t) i + k] = o[k];
 }
 
+// the same for a scene with a textured spot (DSpots::lum_texture != NULL): op 0 runs sample_luminaire<SKY, true>, the
+// instantiation the k_shade_spt kernels run; the other two operations do not depend on the table
+__global__ void k_scene_lum_eval_spt(DScene sc, DSpots spt, int op, uint32_t n, const float *queries, float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float *q = queries + 16 * (size_t) i;
+	float o[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	if (op == 0) {
+		LRec r;
+		r.p = r.n = r.d = r.value = V3(0.0f, 0.0f, 0.0f); r.pdf = 0.0f; r.lum = -1;
+		const V3 p(q[0], q[1], q[2]);
+		const bool found = sc.sky ? sample_luminaire<true, true>(sc, p, q[3], q[4], r, spt) : sample_luminaire<false, true>(sc, p, q[3], q[4], r, spt);
+		o[0] = found ? 1.0f : 0.0f; o[1] = (float) r.lum;
+		o[2] = r.p.x; o[3] = r.p.y; o[4] = r.p.z;
+		o[5] = r.n.x; o[6] = r.n.y; o[7] = r.n.z;
+		o[8] = r.d.x; o[9] = r.d.y; o[10] = r.d.z;
+		o[11] = r.pdf;
+		o[12] = r.value.x; o[13] = r.value.y; o[14] = r.value.z;
+	} else if (sc.sky) scene_lum_eval_one<true>(sc, op, q, o);
+	else scene_lum_eval_one<false>(sc, op, q, o);
+	#pragma unroll
+	for (int k = 0; k < 16; ++k) out[16 * (size_t) i + k] = o[k];
+}
+
+// mtsgpu_spot_eval: SpotLuminaire::sample (spot.cpp:116-124) with a projection texture, as the spot branch of sample_luminaire runs
+// it, for n points; block = the parameter block in device memory
+__global__ void k_spot_eval(const float *block, DTexture tex, const float4 *texels, float uv_factor, uint32_t n, const float *p, float *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float *LP = block;
+	const V3 lumToP = V3(p[3 * (size_t) i], p[3 * (size_t) i + 1], p[3 * (size_t) i + 2]) - V3(LP[3], LP[4], LP[5]);
+	const float invDist = 1.0f / length(lumToP);
+	const V3 d = lumToP * invDist;
+	float uvx, uvy;
+	const V3 value = spot_falloff_textured(LP, tex, texels, uv_factor, d, uvx, uvy) * (invDist * invDist);
+	float *o = out + 8 * (size_t) i;
+	o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = uvx; o[4] = uvy; o[5] = value.x; o[6] = value.y; o[7] = value.z;
+}
+
 void launch_bsdf_eval(hipStream_t s, uint32_t type, const float *params, int op, uint32_t n, const float *queries, float *out) {
 	BsdfParams p;
 	for (int k = 0; k < kBsdfNParams; ++k) p.v[k] = params[k];
@@ -333,7 +372,13 @@ void launch_sky_eval(hipStream_t s, const float *block, int op, uint32_t n, cons
 	if (n) hipLaunchKernelGGL(k_sky_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, block, op, n, queries, out);
 }
 
-void launch_scene_lum_eval(hipStream_t s, const DScene &sc, int op, uint32_t n, const float *queries, float *out) {
+void launch_spot_eval(hipStream_t s, const float *block, const DTexture &tex, const float4 *texels, float uv_factor, uint32_t n,
+                      const float *p, float *out) {
+	if (n) hipLaunchKernelGGL(k_spot_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, block, tex, texels, uv_factor, n, p, out);
+}
+
+void launch_scene_lum_eval(hipStream_t s, const DScene &sc, int op, uint32_t n, const float *queries, float *out, const DSpots &spt) {
+	if (n && spt.lum_texture) { hipLaunchKernelGGL(k_scene_lum_eval_spt, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, spt, op, n, queries, out); return; }
 	if (n) hipLaunchKernelGGL(k_scene_lum_eval, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, op, n, queries, out);
 }
 

@@ -1,12 +1,12 @@
 // shade_launch.h -- private to the shading units: what launch_shade / launch_shade_all (shade.hip) call in the unit of each
-// kernel family (shade_plain / _vcol / _tex / _tan / _mask / _snow / _cloth.hip), and the one ROUNDS x SKY ladder those units launch through.
+// kernel family (shade_plain / _vcol / _tex / _tan / _mask / _snow / _cloth / _spot.hip), and the one ROUNDS x SKY ladder those units launch through.
 #pragma once
 #include <type_traits>
 #include "kernels.h"
 
 namespace mg {
 
-// the arguments every k_shade* takes, with the launch they go to: a family appends its own (DColors, DTextures, DTangents, DMasks, DSnows, DCloths)
+// the arguments every k_shade* takes, with the launch they go to: a family appends its own (DColors, DTextures, DTangents, DMasks, DSnows, DCloths, DSpots)
 struct ShadeBinLaunch {
 	hipStream_t s; dim3 g, b;
 	const DScene &sc; const DPaths &ps; const DConfig &cfg; const DQueues &q;
@@ -30,6 +30,8 @@ void launch_shade_msk(const ShadeBinLaunch &a, int bin, const DColors &col, cons
 void launch_shade_snw(const ShadeBinLaunch &a, const DColors &col, const DTextures &tex, const DTangents &tan, const DMasks &msk, const DSnows &snw);
 void launch_shade_clo(const ShadeBinLaunch &a, const DColors &col, const DTextures &tex, const DTangents &tan, const DMasks &msk, const DSnows &snw,
                       const DCloths &clo);
+// spt: bins 0..9, the superset family of a scene with a textured spot (colours, textures and tangents may each be absent)
+void launch_shade_spt(const ShadeBinLaunch &a, int bin, const DColors &col, const DTextures &tex, const DTangents &tan, const DSpots &spt);
 // All material queues of a bounce in one launch, per family
 void launch_shade_all_plain(const ShadeAllLaunch &a);
 void launch_shade_all_vcol(const ShadeAllLaunch &a, const DColors &col);

@@ -1,6 +1,6 @@
-// shade_path.h -- K3+K5: one iteration of MIPathTracer::Li per material queue, and the kernel templates of the seven families
+// shade_path.h -- K3+K5: one iteration of MIPathTracer::Li per material queue, and the kernel templates of the eight families
 // (k_shade*, k_shade_all*).  Each family is instantiated by the unit that launches it: shade_plain / _vcol / _tex / _tan / _mask / _snow /
-// _cloth.hip.
+// _cloth / _spot.hip.
 #pragma once
 #include "shade_bsdf.h"
 #include "shade_cloth.h"
@@ -57,15 +57,18 @@ __device__ __forceinline__ uint32_t shade_row_index(uint32_t lane, uint32_t k) {
 // BsdfMasked with the opacity's luminance at the hit, and the tangent table may be NULL as well.
 // SNW: the instantiation of bin 0 for scenes with a snow BRDF (DSnows::bsdf_snow != NULL), on top of MSK: a hit whose BSDF has a
 // snow record is evaluated through BsdfSnow2, every other one as in the mask kernel, and the mask table may be NULL as well.
+// SPT: the instantiation for scenes in which a spot luminaire has a projection texture (DSpots::lum_texture != NULL), on top of
+// TAN and beside MSK: the luminaire sampling evaluates the texture (sample_luminaire<SKY, true>), and the tangent table may be NULL.
 // CLO: the instantiation of bin 0 for scenes with a woven-cloth BRDF (DCloths::bsdf_weave != NULL), on top of SNW: a hit whose
 // BSDF has a weave is evaluated through BsdfCloth2 at its.uv, every other one as in the snow kernel, and the snow table may be NULL.
-template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false, bool SNW = false, bool CLO = false>
+template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false, bool SNW = false, bool CLO = false, bool SPT = false>
 __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, const DConfig &cfg, const uint32_t id,
                                            const float4 ro, const float4 rd, const uint4 h, const float4 T4, const float4 L4,
                                            const ShadeRow row, bool &continues, bool &wantShadow, V3 &neeV, V3 &shO, V3 &shD, const DColors &col,
                                            const DTextures &tex, const DTangents &tan = DTangents{ nullptr, nullptr },
                                            const DMasks &msk = DMasks{ nullptr }, const DSnows &snw = DSnows{ nullptr },
-                                           const DCloths &clo = DCloths{ nullptr, nullptr, nullptr, nullptr }) {
+                                           const DCloths &clo = DCloths{ nullptr, nullptr, nullptr, nullptr },
+                                           const DSpots &spt = DSpots{ nullptr, nullptr, nullptr, nullptr }) {
 	{
 		// rounds of MIDirectIntegrator (DConfig::dr_mode): later BSDF samples start again from the camera hit
 		const int mode = ROUNDS ? cfg.dr_mode : 0;
@@ -94,8 +97,8 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 		constexpr bool kCyl = BT == 0 && !MSK && !SNW && !CLO;
 		Its its;
 		if (valid) {
-			// (a scene that is here for its masks alone has no tangent table)
-			if (TAN && !(MSK && tan.shape_has_tan == nullptr)) fill_its_tan<kCyl>(sc, tan, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
+			// (a scene that is here for its masks or its textured spot alone has no tangent table)
+			if (TAN && !((MSK || SPT) && tan.shape_has_tan == nullptr)) fill_its_tan<kCyl>(sc, tan, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
 			else fill_its<kCyl>(sc, rayO, rayD, __uint_as_float(h.x), h.w, __uint_as_float(h.y), __uint_as_float(h.z), row[0], row[1], row[3], its);
 		}
 		const int shapeLum = valid ? sc.shape_lum[its.shape] : -1;
@@ -257,7 +260,7 @@ __device__ __forceinline__ void shade_path(const DScene &sc, const DPaths &ps, c
 				if (ROUNDS && direct && cfg.n_lum > 1) sampler_array2d(cfg, smp, misc_zw.y, 0, (uint32_t) cfg.dr_index, s0, s1);   // direct.cpp:122-123
 				else sampler_next2d(cfg, smp, s0, s1);
 				LRec lRec;
-				if ((!direct || cfg.n_lum > 0) && sample_luminaire<SKY>(sc, its.p, s0, s1, lRec)) {
+				if ((!direct || cfg.n_lum > 0) && sample_luminaire<SKY, SPT>(sc, its.p, s0, s1, lRec, spt)) {
 					const V3 wo = -lRec.d;
 					const V3 woL(dot(wo, its.shS), dot(wo, its.shT), dot(wo, its.shN));
 					V3 bsdfVal = ((CLO && weaveIdx >= 0) ? cloth_f(clo, weaveIdx, clothHit, twoSided, its.wi, woL)
@@ -342,12 +345,13 @@ struct ShadeShared {
 };
 // One workgroup of k_shade: the paths block * kShadeBlock .. of the material queue whose segment sizes are `prefix`
 // (prefix[kBinShards] entries in kBinShards segments of bin_ids)
-template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false, bool SNW = false, bool CLO = false>
+template <int BT, bool ROUNDS, bool SKY, int VCOL, bool TAN = false, bool MSK = false, bool SNW = false, bool CLO = false, bool SPT = false>
 __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, const DConfig &cfg, const DQueues &q, const uint32_t *prefix,
                                             const uint32_t *bin_ids, const uint32_t block, ShadeShared &sh, const DColors &col,
                                             const DTextures &tex = DTextures{ nullptr, nullptr, nullptr, nullptr }, const DTangents &tan = DTangents{ nullptr, nullptr },
                                             const DMasks &msk = DMasks{ nullptr }, const DSnows &snw = DSnows{ nullptr },
-                                            const DCloths &clo = DCloths{ nullptr, nullptr, nullptr, nullptr }) {
+                                            const DCloths &clo = DCloths{ nullptr, nullptr, nullptr, nullptr },
+                                            const DSpots &spt = DSpots{ nullptr, nullptr, nullptr, nullptr }) {
 	uint32_t (&s_cnt)[2][kShadeBlock / 64] = sh.cnt;
 	uint32_t (&s_base)[2] = sh.base;
 	float4 (&s_rows)[kShadeBlock / 64][64 * kRowStride] = sh.rows;
@@ -433,7 +437,7 @@ __device__ __forceinline__ void shade_block(const DScene &sc, const DPaths &ps, 
 	}
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	if (active)
-		shade_path<BT, ROUNDS, SKY, VCOL, TAN, MSK, SNW, CLO>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col, tex, tan, msk, snw, clo);
+		shade_path<BT, ROUNDS, SKY, VCOL, TAN, MSK, SNW, CLO, SPT>(sc, ps, cfg, id, ro, rd, h, T4, L4, row, continues, wantShadow, neeV, shO, shD, col, tex, tan, msk, snw, clo, spt);
 	// the pending direct-light term is parked in the record with the write-back below (the line is written whole anyway):
 	// the any-hit kernel clears the slot if the shadow ray is occluded, the record's next reader adds what is still there
 	if (q.nee_parked && wantShadow) row[2] = make_float4(neeV.x, neeV.y, neeV.z, __uint_as_float(kNeeTag));
@@ -544,6 +548,19 @@ __global__ MG_SHADE_BOUNDS void k_shade_clo(DScene sc, DPaths ps, DConfig cfg, D
 	static_assert(BT == 0, "a weave sits on a Lambertian entry");
 	__shared__ ShadeShared sh;
 	shade_block<BT, ROUNDS, SKY, kSlotTexture, true, true, true, true>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col, tex, tan, msk, snw, clo);
+}
+// and for scenes in which a spot luminaire has a projection texture (DSpots), built on the tangent kernels: the only ones that take
+// the spot tables, their last argument.  Bins 0..9 (the terminal bin samples no luminaire).  One superset family: any of the
+// colour, texture-slot and tangent tables may be NULL here.  Masks, snow and cloth are refused beside a textured spot.
+// Device-driven bounces launch these kernels bin by bin instead of the fused one
+template <int BT, bool ROUNDS, bool SKY>
+__global__ MG_SHADE_BOUNDS void k_shade_spt(DScene sc, DPaths ps, DConfig cfg, DQueues q, BinView view_host,
+                                                           const BinView *views_dev, const uint32_t *bin_ids, DColors col, DTextures tex, DTangents tan,
+                                                           DSpots spt) {
+	static_assert(BT < kNumBsdfTypes, "the terminal bin samples no luminaire");
+	__shared__ ShadeShared sh;
+	shade_block<BT, ROUNDS, SKY, kSlotTexture, true, false, false, false, true>(sc, ps, cfg, q, views_dev ? views_dev[BT].prefix : view_host.prefix, bin_ids, blockIdx.x, sh, col, tex, tan,
+	                                                                            DMasks{ nullptr }, DSnows{ nullptr }, DCloths{ nullptr, nullptr, nullptr, nullptr }, spt);
 }
 
 // All material queues of a bounce in ONE launch (device-driven bounces): the workgroups are dealt to the bins in bin order,

@@ -569,8 +569,10 @@ class SceneDescription:
         self.lum_params[l][3:6] = d / np.sqrt((d * d).sum(), dtype=np.float32)
         return l
 
-    def spot_light(self, position, target, intensity, cutoff_deg=20.0, beam_deg=None):
-        """SpotLuminaire with toWorld = lookAt(position, target, up) (src/luminaires/spot.cpp:33-62)"""
+    def spot_light(self, position, target, intensity, cutoff_deg=20.0, beam_deg=None, texture=None, bilinear=False):
+        """SpotLuminaire with toWorld = lookAt(position, target, up) (src/luminaires/spot.cpp:33-62).  texture: its projection
+        texture (:95-101), a Checkerboard, GridTexture or BitmapTexture object; bilinear: a BitmapTexture is looked up as
+        filterType trilinear / ewa are without uv partials, MIPMap::triangle(0, ., .), instead of the nearest texel (none)"""
         l = self.add_lum(abi.LUM_SPOT, [intensity] * 3 if np.isscalar(intensity) else intensity)
         P = self.lum_params[l]
         pos, tgt = np.asarray(position, dtype=np.float32), np.asarray(target, dtype=np.float32)
@@ -583,7 +585,24 @@ class SceneDescription:
         P[8] = F(cutoff_deg) * (F(np.pi) / F(180.0))         # degToRad
         P[19] = F(beam) * (F(np.pi) / F(180.0))
         P[10:13] = right; P[13:16] = new_up; P[16:19] = d    # world -> luminaire rotation (rows)
+        if texture is not None:
+            if not isinstance(texture, _UvTexture):
+                raise TypeError("spot_light: texture is a Checkerboard, GridTexture or BitmapTexture")
+            if not hasattr(self, "spot_textures"):
+                self.spot_textures = {}
+            self.spot_textures[l] = (texture, bool(bilinear))
         return l
+
+    def spot_texture_table(self):
+        """(textures, texture_bilinear [n_textures] uint32, lum_texture [n_lums] int32) of the spot luminaires with a projection
+        texture: what mtsgpu_set_spot_textures takes, one texture entry per textured luminaire"""
+        st = getattr(self, "spot_textures", {})
+        textures, flags = [], []
+        lum = np.full(len(self.lum_type), -1, dtype=np.int32)
+        for l in sorted(st):
+            lum[l] = len(textures)
+            textures.append(st[l][0]); flags.append(1 if st[l][1] else 0)
+        return textures, np.asarray(flags, dtype=np.uint32), lum
 
     def collimated_beam(self, position, target, intensity, radius=0.01):
         """<luminaire type="collimated"> with toWorld = lookAt(position, target) (src/luminaires/collimated.cpp)"""

@@ -1,6 +1,6 @@
 """Scenes and case files of tests/upload_harness: the scene list whose device layout tests/golden/upload_layout.json pins, and
-the flat binary file the harness reads -- everything MIPathTracer.preprocess hands to the upload call and to the four setters
-for a scene, taken from a mts.Scene on the CPU.  Test infrastructure.
+the flat binary file the harness reads -- everything preprocess() hands to the upload call and to the setters for a scene,
+taken from a mts.Scene on the CPU.  Which calls a case has is read off Scene.upload_plan().  Test infrastructure.
 
 The file: for every section, in any order, u32 length of the name, the name, u64 byte count, the bytes.  A section that is
 absent is a NULL pointer of the call.  "hdr" holds the counts (HDR); the rest are the arrays under the names of the C ABI."""
@@ -56,51 +56,49 @@ def case_of(mts, scene, depth_limit, top_slots):
         out["shape_type"], out["shape_params"] = a["shape_type"], a["shape_params"]
     if sc.env_pixels:
         out["env_pixels"], out["env_pdf"], out["env_cdf"] = a["env_pixels"], a["env_pdf"], a["env_cdf"]
-    # the extras of the upload call MIPathTracer.preprocess picks
+    # which calls the scene takes, in which order, is the plan's to say; the arrays are read from the scene
+    plan = scene.upload_plan()
+    calls = [c for c, _ in plan]
     ta, cb = scene.tangent_args(), scene.cylinder_blocks()
-    if cb is not None:
+    if calls[0] == "upload_scene_cylinders":
         hdr.update(with_tangents=1, accepts_cylinders=1)
         out["cylinders"] = cb
-    if ta is not None:
+    if calls[0] == "upload_scene_tangents":
         hdr.update(with_tangents=1)
-        if ta[0] is not None:
-            out["vtx_dpdu"], out["shape_has_tangents"] = ta
-    # ... and the arguments of the setters it calls
+    if ta is not None and ta[0] is not None:
+        out["vtx_dpdu"], out["shape_has_tangents"] = ta
     col, has = scene.vertex_colors()
-    if scene.vertex_color_args() is not None:
+    if "set_vertex_colors" in calls:
         if col is not None:
             out["vtx_col"], out["shape_has_colors"] = col, has
         if scene.bsdf_color_slots is not None:
             out["bsdf_color_slots"] = scene.bsdf_color_slots
     uv, has = scene.vertex_texcoords()
-    um, ub, ut = scene.uv_masked_texture_args(), scene.uv_bitmap_texture_args(), scene.uv_texture_args()
-    nt, nb = len(getattr(scene.description, "textures", [])), len(scene._bitmap_objects)
-    if um is not None or ub is not None or ut is not None:
+    tex, args = next(((c, a) for c, a in plan if c in ("set_uv_masked_textures", "set_uv_bitmap_textures", "set_uv_textures")), (None, None))
+    if tex == "set_uv_textures" and args[3] is None:
+        # no texture call has handed the texcoords over: one without textures, after the snow call
+        out["tex_call"] = np.ones(1, dtype=np.uint32)
+        out["vtx_uv"], out["shape_has_uv"] = (uv, has) if uv is not None else scene._uv_zero
+    elif tex is not None:
+        masked, nb = tex == "set_uv_masked_textures", len(scene._bitmap_objects)
         out["tex_call"] = np.zeros(1, dtype=np.uint32)
         if uv is not None:
             out["vtx_uv"], out["shape_has_uv"] = uv, has
-        hdr.update(n_textures=nt if um is not None else len(scene.textures), with_bitmaps=int(um is not None or ub is not None))
-        if um is None or nt:
-            out["textures"] = _struct_bytes(scene.textures, hdr["n_textures"])
+        hdr.update(n_textures=args[2], with_bitmaps=int(tex != "set_uv_textures"))
+        if not masked or args[2]:
+            out["textures"] = _struct_bytes(scene.textures, args[2])
         if scene.bsdf_slot_texture is not None:
             out["bsdf_slot_texture"] = scene.bsdf_slot_texture
-        if nb and (um is not None or ub is not None):
+        if nb and tex != "set_uv_textures":
             hdr.update(n_bitmaps=nb)
             out["bitmaps"] = np.asarray([[b.width, b.height, b.wrap, 0] for b in scene._bitmap_objects], dtype=np.uint32)
             out["bitmap_texels"] = np.concatenate([np.ascontiguousarray(b.texels, dtype=np.float32).ravel() for b in scene._bitmap_objects])
             out["texture_bitmap"] = scene.texture_bitmap
-        if um is not None:
+        if masked:
             out["bsdf_mask"] = _struct_bytes(scene.bsdf_mask, sc.n_bsdfs)
-    if scene.bsdf_snow is not None:
+    if "set_snow_bsdfs" in calls:
         out["bsdf_snow"] = _struct_bytes(scene.bsdf_snow, sc.n_bsdfs)
-    if scene.cloth is not None:
-        if "tex_call" not in out:       # no texture call has handed the texcoords over: one without textures
-            out["tex_call"] = np.ones(1, dtype=np.uint32)       # 1: after the snow call
-            if uv is not None:
-                out["vtx_uv"], out["shape_has_uv"] = uv, has
-            else:
-                out["vtx_uv"] = np.zeros((max(int(sc.n_verts), 1), 2), dtype=np.float32)
-                out["shape_has_uv"] = np.zeros(max(int(sc.n_shapes), 1), dtype=np.uint32)
+    if "set_cloth_bsdfs" in calls:
         W = scene.description.weaves
         hdr.update(n_weaves=len(W))
         out.update(weave_sections(A, W))
